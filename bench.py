@@ -3,6 +3,8 @@
 
     python bench.py --gpus N --steps K --warmup W            (N=1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --full                               (every leg listed below as well)
+    python bench.py ... --dump-outputs DIR                   (what the last timed step computed, as DIR/<name>.npy)
 
 One "step" = one pass of the hot path (K1 polygon->bbox and K2 all-pairs IoU flag in ONE fused launch,
 dyd_bbox_iou_fused_dev — the launch the product's replace -> IoU step functions issue) over one batch of synthetic rows
@@ -12,6 +14,7 @@ GPU (configs[2]'s table: <=32 boxes/image, 3..12 points/polygon, 1.24 G points =
 
 Prints ONE JSON line (rank 0) with the driver's contract plus
   roofline       dominant kernel (the fused K1+K2 kernel) — algorithmic bytes / HIP-event time vs 8 TB/s HBM peak
+A plain run stops there: set-up, warm-up, the K timed steps, the dump, the line.  With --full the line also carries
   cpu_baseline   the CPU port of the reference path (oracle/steps.py) timed on this box's host cores (rank 0, N=1 only)
   host_inclusive SURVEY §8d region 2: DataFrame in -> frames out through the product's step function
                  (replace_and_filter_frame: scan + H2D + fused launch + D2H + emit) and its ratio to cpu_baseline;
@@ -22,7 +25,12 @@ Prints ONE JSON line (rank 0) with the driver's contract plus
   dense          configs[4] scaled (1M rows x 256 boxes, 44 GB): the same launch, its own roofline object
 and the sharded dedup / reference filter of configs[3] with its collectives timed on their own: sharded_exchange (weak: rows per GPU
 fixed, at N > 1 or --workload c4) and sharded_exchange_strong (a fixed 100 M-row table cut into N shards, at every N incl. 1); at N > 1
-also fused_strong: the fused launch on every rank's shard of that fixed table (configs[3] itself at N = 8).
+also fused_strong: the fused launch on every rank's shard of that fixed table (configs[3] itself at N = 8).  Without --full those
+objects are null.
+
+--dump-outputs DIR (rank 0) writes what the caller of the timed launch receives after the last timed step — box4 [B,4] f64,
+arg4 [B,4] i32, high [N] u8 — as a fixed, seeded sample of rows and boxes plus exact per-block sums over all of them, float32 /
+float64, 44 MB at most (dump_outputs).  The inputs depend on the arguments only, so two builds compare output for output.
 """
 from __future__ import annotations
 
@@ -49,6 +57,69 @@ WORKLOADS = {
     "c5": (1_000_000, 256, "configs[4] scaled: dense-box stress, 256 boxes/img, polygons of 3..12 points"),
 }
 GEN_CHUNK = 2_000_000
+# --dump-outputs: sampled rows / boxes (fixed seed) and the block length of the exact sums over all of them
+DUMP_SEED, DUMP_ROWS, DUMP_BOXES, DUMP_BLOCK = 20_241, 1 << 21, 1 << 18, 1 << 16
+
+
+def draw_table(rows, bpr, seed_base, dev):
+    """the synthetic batch of one rank, drawn on the device in chunks (seed_base + chunk index): xy [P,2] f64, pt_off [B+1] i32,
+    box_off [N+1] i32, label [B] i32, all resident in HBM"""
+    import torch
+    from deal_yolo_daya_amd import synth
+
+    chunk = GEN_CHUNK if bpr is None else 100_000
+    xy_p, npts_p, nbox_p, lab_p = [], [], [], []
+    for ci, start in enumerate(range(0, rows, chunk)):
+        d = synth.generate_device(min(chunk, rows - start), seed_base + ci, dev, boxes_per_row=bpr)
+        xy_p.append(d["xy"])
+        npts_p.append(torch.diff(d["pt_off"]))
+        nbox_p.append(torch.diff(d["box_off"]))
+        lab_p.append(d["label"])
+        del d
+    xy = torch.cat(xy_p); del xy_p
+    npts = torch.cat(npts_p); nbox = torch.cat(nbox_p); label = torch.cat(lab_p)
+    del npts_p, nbox_p, lab_p
+    P, B, N = int(xy.shape[0]), int(npts.shape[0]), int(nbox.shape[0])
+    if P >= 2 ** 31:
+        raise SystemExit("points per GPU exceed int32 offsets; lower --rows")
+    pt_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+    pt_off[1:] = torch.cumsum(npts, 0, dtype=torch.int64).to(torch.int32)
+    box_off = torch.zeros(N + 1, dtype=torch.int32, device=dev)
+    box_off[1:] = torch.cumsum(nbox, 0, dtype=torch.int64).to(torch.int32)
+    return {"xy": xy, "pt_off": pt_off, "box_off": box_off, "label": label}
+
+
+def dump_outputs(path, out_box, out_arg, out_high):
+    """DIR/<name>.npy of the fused launch's outputs (box4 [B,4] f64, arg4 [B,4] i32, high [N] u8, device tensors): the same
+    seeded rows and boxes for the same table whatever the build, and int64 sums over blocks of DUMP_BLOCK consecutive rows / boxes
+    that cover every one of them (exact, so any build that computes the same values writes the same files).  -> bytes written"""
+    import torch
+
+    N, B = int(out_high.shape[0]), int(out_box.shape[0])
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.sort(rng.choice(N, min(N, DUMP_ROWS), replace=False))
+    boxes = np.sort(rng.choice(B, min(B, DUMP_BOXES), replace=False))
+    ri = torch.from_numpy(rows).to(out_high.device)
+    bi = torch.from_numpy(boxes).to(out_high.device)
+
+    def block_sums(v):
+        padded = torch.zeros(-(-v.numel() // DUMP_BLOCK) * DUMP_BLOCK, dtype=torch.int64, device=v.device)
+        padded[:v.numel()] = v
+        return padded.view(-1, DUMP_BLOCK).sum(1).cpu().numpy().astype(np.float64)
+
+    arrays = {
+        "high_sample": out_high[ri].cpu().numpy().astype(np.float32),               # 1 = the row is HIGH
+        "high_sample_rows": rows.astype(np.float64),
+        "box_sample": out_box[bi].cpu().numpy(),                                      # x_min, y_min, x_max, y_max
+        "arg_sample": out_arg[bi].cpu().numpy().astype(np.float64),                   # each extreme's point within its polygon
+        "box_sample_ids": boxes.astype(np.float64),
+        "high_count_per_block": block_sums(out_high),
+        "arg_sum_per_block": block_sums(out_arg.sum(1, dtype=torch.int64)),
+    }
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    return sum(a.nbytes for a in arrays.values())
 
 
 def cpu_baseline(sizes):
@@ -437,6 +508,11 @@ def main():
                          "a low shader clock while the inputs are generated, and a handful of launches do not bring it up")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3")
     ap.add_argument("--rows", type=int, default=None, help="rows per GPU (overrides the workload's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (cpu_baseline, host_inclusive, full_pipeline, dense, sharded_exchange*, "
+                         "fused_strong), as the options below set them; a plain run times the K steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--cpu-sample", type=int, default=100000, help="largest CPU-baseline sample (0 = skip); 10000 rows are timed as well")
     ap.add_argument("--host-rows", type=int, default=1_000_000, help="rows of the host-inclusive DataFrame run (0 = skip)")
     ap.add_argument("--pipeline", type=int, default=1, help="1 = also time configs[2]'s full pipeline per stage (c3, N=1)")
@@ -451,6 +527,8 @@ def main():
     ap.add_argument("--strong-steps", type=int, default=20)
     ap.add_argument("--fused-variant", type=int, default=-1, help="A/B only: force a kernel variant of the fused launch (dyd_set_option)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -496,26 +574,10 @@ def main():
     def resident(rows, bpr, steps, warmup, ramp_ms, seed_base):
         """the synthetic batch for this rank, drawn on the device in chunks and resident in HBM; W warm-up steps, then EXACTLY
         `steps` timed steps of the fused launch, HIP events around each on the launch stream"""
-        chunk = GEN_CHUNK if bpr is None else 100_000
-        xy_p, npts_p, nbox_p, lab_p = [], [], [], []
-        for ci, start in enumerate(range(0, rows, chunk)):
-            d = synth.generate_device(min(chunk, rows - start), seed_base + ci, dev, boxes_per_row=bpr)
-            xy_p.append(d["xy"])
-            npts_p.append(torch.diff(d["pt_off"]))
-            nbox_p.append(torch.diff(d["box_off"]))
-            lab_p.append(d["label"])
-            del d
-        xy = torch.cat(xy_p); del xy_p
-        npts = torch.cat(npts_p); nbox = torch.cat(nbox_p); label = torch.cat(lab_p)
-        del npts_p, nbox_p, lab_p
-        P, B, N = int(xy.shape[0]), int(npts.shape[0]), int(nbox.shape[0])
-        if P >= 2 ** 31:
-            raise SystemExit("points per GPU exceed int32 offsets; lower --rows")
-        pt_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-        pt_off[1:] = torch.cumsum(npts, 0, dtype=torch.int64).to(torch.int32)
-        box_off = torch.zeros(N + 1, dtype=torch.int32, device=dev)
-        box_off[1:] = torch.cumsum(nbox, 0, dtype=torch.int64).to(torch.int32)
-        del npts, nbox
+        t = draw_table(rows, bpr, seed_base, dev)
+        xy, pt_off, box_off, label = t["xy"], t["pt_off"], t["box_off"], t["label"]
+        del t
+        P, B, N = int(xy.shape[0]), int(pt_off.shape[0]) - 1, int(box_off.shape[0]) - 1
         out_box = torch.empty((B, 4), dtype=torch.float64, device=dev)
         out_arg = torch.empty((B, 4), dtype=torch.int32, device=dev)
         out_high = torch.empty(N, dtype=torch.uint8, device=dev)
@@ -590,8 +652,10 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     high_rows = main_res["high_rows"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *main_res["keep"][3:])
     exchange, exchange_strong = None, None
-    if args.exchange:                                                # every rank takes part; rank 0 reports
+    if args.full and args.exchange:                                  # every rank takes part; rank 0 reports
         if world == 1 and not dist.is_initialized():                  # one GPU: a group of one, over RCCL like the real thing
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
             os.environ.setdefault("MASTER_PORT", "29531")
@@ -603,7 +667,7 @@ def main():
             exchange_strong = sharded_dedup(args.strong_rows // world, rank, world, dev, reps=2, scaling="strong")
 
     fused_strong = None
-    if world > 1 and args.strong_rows > 0 and args.workload == "c3":
+    if args.full and world > 1 and args.strong_rows > 0 and args.workload == "c3":
         # configs[3] as a FIXED table: --strong-rows rows (100 M) cut into `world` contiguous shards, the same fused launch on each rank's
         # shard (12.5 M rows per GPU at N = 8: configs[3] itself); max over ranks; together with sharded_exchange_strong the strong-scaling
         # series of the whole configuration.  Skipped where a shard would not fit: 2.9 KB per row resident, and about twice that while
@@ -646,6 +710,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": ms_step,
             "higher_is_better": True,
             "scaling": "weak",
@@ -665,7 +730,7 @@ def main():
         line["sharded_exchange"] = exchange
         line["sharded_exchange_strong"] = exchange_strong
         line["fused_strong"] = fused_strong
-        if world == 1:
+        if world == 1 and args.full:
             if args.pipeline and args.workload == "c3":
                 line["full_pipeline"] = full_pipeline({"N": N, "B": B, "P": P, "label": label, "fused": fused}, dev, L, ck, sp)
             del label, fused

@@ -28,7 +28,7 @@ def test_ranks_on_one_card(world):
     env = dict(os.environ, DYD_BENCH_DEVICE="0", DYD_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
-           "--rows", str(rows), "--ramp-ms", "10", "--strong-rows", "400000"]
+           "--rows", str(rows), "--ramp-ms", "10", "--strong-rows", "400000", "--full"]
     out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -65,7 +65,7 @@ def test_one_rank_runs_the_exchange_over_rccl():
     (all_gather_into_tensor of 16-byte keys, all_reduce of bytes) at configs[3]'s per-GPU size"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT=str(_free_port()))
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--workload", "c4", "--steps", "2", "--warmup", "1", "--ramp-ms", "10",
-           "--cpu-sample", "0", "--host-rows", "0", "--pipeline", "0", "--dense", "0", "--strong-rows", "20000000"]
+           "--cpu-sample", "0", "--host-rows", "0", "--pipeline", "0", "--dense", "0", "--strong-rows", "20000000", "--full"]
     out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

@@ -3,11 +3,12 @@
 # tools/collect_profiles.py <tag> turns it into the committed summaries under profiles/.
 #   usage on the GPU box:  bash tools/gpu_profile.sh        (BENCH_ARGS="--workload c2" for another workload)
 set -u
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-timeout -k 10 500 python bench.py ${BENCH_ARGS:-} > $OUT/bench.log 2> $OUT/bench.err; rc=$?
+timeout -k 10 500 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.log 2> $OUT/bench.err; rc=$?
 echo "bench rc=$rc"; tail -n 1 $OUT/bench.log | cut -c1-600
 if [ $rc -ge 124 ]; then exit $rc; fi
 cd /tmp
@@ -16,7 +17,7 @@ cd /tmp
 # duration away from the 10M-row launches the roofline is quoted on; everything on the device stays (ramp, warm-up, the K timed
 # steps and the full-pipeline stages: every k12_wave_kernel call is a 10M-row launch)
 rm -rf $OUT/prof_bench $OUT/pmc_*
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 $GRAFT_REPO_ROOT/bench.py --host-rows 0 --cpu-sample 0 --strong-rows 0 ${BENCH_ARGS:-} > $OUT/rocprof_bench.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 "$REPO/bench.py" --full --host-rows 0 --cpu-sample 0 --strong-rows 0 ${BENCH_ARGS:-} > $OUT/rocprof_bench.log 2>&1
 echo "rocprof stats rc=$?"
 # counters: their own runs, kernel trace off, one TCC counter per pass (FETCH_SIZE and WRITE_SIZE do not fit together); the
 # device-resident part of the command only (the host-side legs launch the same kernels on other table sizes)
