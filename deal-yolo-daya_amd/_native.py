@@ -58,6 +58,15 @@ SIGNATURES = {
     "dyd_bbox_minmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "dyd_bbox_minmax_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dyd_iou_any_ge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    "dyd_suppress_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "dyd_suppress_boxes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_double, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "dyd_json_scan_box_objects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    "dyd_json_scan_box_objects_v": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    "dyd_scan_box_object": (C.c_void_p, [C.c_void_p]),
+    "dyd_scan_box_name": (C.c_void_p, [C.c_void_p]),
+    "dyd_json_emit_dropping": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_void_p)]),
     "dyd_iou_any_ge_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "dyd_bbox_iou_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
@@ -291,6 +300,26 @@ def iou_any_ge(box4: np.ndarray, row_off: np.ndarray, min_boxes: int, thr: float
     check(lib().dyd_iou_any_ge(_ptr(box4), _ptr(row_off), n, int(min_boxes), float(thr), _ptr(high),
                                _ptr(mx) if want_max else None), "dyd_iou_any_ge")
     return (high, mx) if want_max else high
+
+
+def suppress_boxes(box4: np.ndarray, row_off: np.ndarray, thr: float, name=None):
+    """K9 over host arrays: (keep [B] u8, partner [B] i32).  A box is dropped when an earlier kept box of its row (of equal
+    name id when ``name`` is given) reaches IoU >= thr with it; partner = in-row index of the first such box, else -1."""
+    box4 = np.ascontiguousarray(box4, dtype=np.float64).reshape(-1)
+    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
+    n = len(row_off) - 1
+    if n < 0 or row_off[0] != 0 or 4 * int(row_off[-1]) != box4.size:
+        raise ValueError("row_off must start at 0 and end at the number of boxes")
+    nb = int(row_off[-1])
+    if name is not None:
+        name = np.ascontiguousarray(name, dtype=np.int32)
+        if name.size != nb:
+            raise ValueError("name must hold one id per box")
+    keep = np.ones(nb, np.uint8)
+    partner = np.full(nb, -1, np.int32)
+    check(lib().dyd_suppress_boxes(_ptr(box4), _ptr(row_off), n, _ptr(name) if name is not None else None, float(thr),
+                                   _ptr(keep), _ptr(partner)), "dyd_suppress_boxes")
+    return keep, partner
 
 
 def bbox_iou_fused(xy: np.ndarray, pt_off: np.ndarray, box_off: np.ndarray, min_boxes: int, thr: float,

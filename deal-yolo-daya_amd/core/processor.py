@@ -922,6 +922,193 @@ def filter_by_box_count_and_iou(
     other.to_csv(other_csv, index=False, encoding="utf-8-sig")
 
 
+# =============================================================================== a4'  duplicate-box suppression
+# The IoU step moves a whole image to high_iou_*.csv when two of its boxes overlap with IoU >= thr.  These functions apply the
+# usual fix instead — drop the redundant box, keep the image: NMS without scores, the earlier box in annotation order wins.
+# Boxes are those of the IoU step (extract_boxes :341-366), the arithmetic is calculate_iou(earlier, later) (:328-339); a box
+# is dropped when an earlier KEPT box (of the same name when by_label) reaches thr with it.  Native scan -> K9 -> native emit
+# for regular cells, flatten.suppress_cell for the cells the scanner leaves to Python.  A cell that loses nothing keeps its
+# text (the same str object); a changed cell is re-spelled as json.dumps(doc, ensure_ascii=False).
+def _suppress_decide(scan, cell_at, thr, by_label, be, totals):
+    """one scanned chunk -> ({cell: new text}, [(cell, object, kept_object, iou)] in (cell, object) order)"""
+    row_off = scan.row_off
+    nb = int(row_off[-1]) if len(row_off) else 0
+    irregular = np.flatnonzero(scan.status == _nj.IRREGULAR).tolist()
+    totals["boxes"] += nb
+    totals["python_cells"] += len(irregular)
+    texts, recs, redo = {}, [], []
+    if nb:
+        keep, partner = be.suppress_boxes(scan.box4, row_off, thr, name=scan.box_name if by_label else None)
+        dropped = np.flatnonzero(np.asarray(keep) == 0)
+        if len(dropped):
+            cell_of = np.searchsorted(row_off, dropped, side="right") - 1
+            kept_box = row_off[cell_of] + np.asarray(partner)[dropped]
+            box4 = scan.box4.tolist()
+            obj = scan.box_object
+            for b, c, kb in zip(dropped.tolist(), cell_of.tolist(), kept_box.tolist()):
+                recs.append((c, int(obj[b]), int(obj[kb]), _fl.pair_iou(_corners(box4[kb]), _corners(box4[b]))))
+            changed, strs = scan.emit_dropping(np.asarray(keep) == 0)
+            texts = dict(zip(np.flatnonzero(changed == 1).tolist(), strs))
+            redo = np.flatnonzero(changed == 2).tolist()
+    for i in redo:                                         # decided above, re-spelled by CPython
+        texts[i] = _fl.suppress_cell(cell_at(i), thr, by_label)[0]
+    for i in irregular:                                    # may raise (string coordinates ...), like meet_conditions
+        text, rem = _fl.suppress_cell(cell_at(i), thr, by_label)
+        if rem:
+            texts[i] = text
+            recs += [(i, k, kk, iou) for k, kk, iou in rem]
+    if irregular:
+        recs.sort(key=lambda r: (r[0], r[1]))
+    return texts, recs
+
+
+def _corners(b):
+    """extract_boxes :359-362 on the scanned (p1x, p1y, p2x, p2y)"""
+    return min(b[0], b[2]), min(b[1], b[3]), max(b[0], b[2]), max(b[1], b[3])
+
+
+def _suppress_backend(backend):
+    be = _backend(backend)
+    if not hasattr(be, "suppress_boxes"):
+        raise TypeError("backend lacks ['suppress_boxes']")
+    return be
+
+
+def _suppress_stats(stats, totals, n_rows, texts_count, recs_count):
+    if stats is not None:
+        stats.update({"rows": n_rows, "boxes": totals["boxes"], "python_cells": totals["python_cells"],
+                      "rows_changed": texts_count, "boxes_removed": recs_count})
+
+
+def suppress_duplicate_boxes_cells(cells, iou_threshold: float = 0.98, by_label: bool = False, backend=None,
+                                   stats: Optional[dict] = None) -> tuple:
+    """Per bbox-JSON cell: drop every box that an earlier kept box of the same cell overlaps with IoU >= iou_threshold (of
+    the same name when by_label) -> (cells with only the changed ones replaced, [(cell, object, kept_object, iou)])."""
+    be = _suppress_backend(backend)
+    out = list(cells)
+    totals = {"boxes": 0, "python_cells": 0}
+    removed, changed = [], 0
+    for start in range(0, len(out), _NATIVE_CHUNK_CELLS):
+        chunk = out[start:start + _NATIVE_CHUNK_CELLS]
+        scan = _nj.scan_box_objects(chunk)
+        try:
+            texts, recs = _suppress_decide(scan, chunk.__getitem__, float(iou_threshold), bool(by_label), be, totals)
+        finally:
+            scan.close()
+        for i, t in texts.items():
+            out[start + i] = t
+        changed += len(texts)
+        removed += [(start + c, k, kk, iou) for c, k, kk, iou in recs]
+    _suppress_stats(stats, totals, len(out), changed, len(removed))
+    return out, removed
+
+
+def _removed_frame(recs, sources) -> pd.DataFrame:
+    cols = {}
+    if sources is not None:
+        cols["source"] = pd.Series([sources[r[0]] for r in recs], dtype=object)
+    cols["row"] = np.asarray([r[0] for r in recs], np.int64)
+    cols["object"] = np.asarray([r[1] for r in recs], np.int64)
+    cols["kept_object"] = np.asarray([r[2] for r in recs], np.int64)
+    cols["iou"] = np.asarray([r[3] for r in recs], np.float64)
+    return pd.DataFrame(cols)
+
+
+def suppress_duplicate_boxes_frame(df: pd.DataFrame, iou_threshold: float = 0.98, by_label: bool = False, backend=None,
+                                   stats: Optional[dict] = None):
+    """-> (copy of df in which only BBOX_COL differs, removed boxes: [source,] row (position in df), object, kept_object, iou)"""
+    cells, recs = suppress_duplicate_boxes_cells(df[BBOX_COL].tolist(), iou_threshold, by_label, backend, stats)
+    out = df.copy()
+    if recs:
+        out[BBOX_COL] = pd.Series(cells, index=out.index, dtype=object)
+    sources = df["source"].tolist() if "source" in df.columns else None
+    return out, _removed_frame(recs, sources)
+
+
+def _splice_column(col, texts: dict):
+    """fastcsv.Utf8Column with the cells of `texts` replaced (their bytes spliced into a new flat buffer)"""
+    if not texts:
+        return col
+    idx = sorted(texts)
+    data = col.data
+    off = np.asarray(col.off, np.int64)
+    parts, prev = [], 0
+    lens = np.diff(off)
+    for i in idx:
+        b = texts[i].encode("utf-8")
+        parts.append(data[prev:off[i]].tobytes())
+        parts.append(b)
+        prev = int(off[i + 1])
+        lens[i] = len(b)
+    parts.append(data[prev:off[-1]].tobytes())
+    blob = b"".join(parts)
+    new_off = np.zeros(len(off), np.int64)
+    np.cumsum(lens, out=new_off[1:])
+    new_data = np.frombuffer(blob, np.uint8) if blob else np.zeros(1, np.uint8)
+    return _fc.Utf8Column(new_data, new_off, col.na, blob)
+
+
+def _suppress_csv_fast(input_csv_path, output_csv_path, iou_threshold, by_label, backend):
+    """-> (n_rows, texts count, recs, sources) or NotImplemented (nothing written then)"""
+    try:
+        table = _fc.read_split(str(input_csv_path), [ANNOTATION_COL, BBOX_COL])
+    except (OSError, ValueError, pd.errors.ParserError, UnicodeDecodeError):
+        return NotImplemented
+    if table is None or BBOX_COL not in table.heavy:
+        return NotImplemented
+    be = _suppress_backend(backend)
+    col = table.heavy[BBOX_COL]
+    totals = {"boxes": 0, "python_cells": 0}
+    scan = _nj.scan_box_objects_buffers(col.data, col.off, col.na)
+    try:
+        texts, recs = _suppress_decide(scan, col.cell, float(iou_threshold), bool(by_label), be, totals)
+    finally:
+        scan.close()
+    new_col = _splice_column(col, texts)
+    columns = [new_col if nm == BBOX_COL else (table.heavy[nm] if nm in table.heavy else table.light[nm]) for nm in table.names]
+    Path(output_csv_path).parent.mkdir(parents=True, exist_ok=True)
+    if not _fc.write_table(str(output_csv_path), table.names, columns, table.n_rows):
+        return NotImplemented
+    sources = table.light["source"].tolist() if "source" in table.light.columns else None
+    return table.n_rows, len(texts), recs, sources
+
+
+def suppress_duplicate_boxes_csv(input_csv_path, output_csv_path="deduped_boxes.csv", removed_csv=None,
+                                 iou_threshold: float = 0.98, by_label: bool = False, backend=None):
+    """CSV -> CSV twin of suppress_duplicate_boxes_frame, in the IoU step's conventions: read as utf-8-sig; a read failure
+    prints 读取失败：... and a missing column 错误：缺少必要列 ..., both returning None.  The output holds the input's rows with
+    BBOX_COL rewritten; `removed_csv` (optional) lists the dropped boxes.  -> {"rows", "rows_changed", "boxes_removed",
+    "output", "removed_output"}"""
+    res = NotImplemented
+    if _fc.enabled() and os.path.isfile(str(input_csv_path)):
+        res = _suppress_csv_fast(input_csv_path, output_csv_path, iou_threshold, by_label, backend)
+    if res is NotImplemented:
+        LAST_IO_PATH["suppress"] = "pandas"
+        try:
+            df = pd.read_csv(input_csv_path, encoding="utf-8-sig")
+        except Exception as e:
+            print(f"读取失败：{e}")
+            return None
+        if BBOX_COL not in df.columns:
+            print(f"错误：缺少必要列 {BBOX_COL}")
+            return None
+        be = _suppress_backend(backend)
+        stats = {}
+        out, removed = suppress_duplicate_boxes_frame(df, iou_threshold, by_label, be, stats)
+        Path(output_csv_path).parent.mkdir(parents=True, exist_ok=True)
+        out.to_csv(output_csv_path, index=False, encoding="utf-8-sig")
+        n_rows, n_changed = len(df), stats["rows_changed"]
+    else:
+        LAST_IO_PATH["suppress"] = "native"
+        n_rows, n_changed, recs, sources = res
+        removed = _removed_frame(recs, sources)
+    if removed_csv is not None:
+        Path(removed_csv).parent.mkdir(parents=True, exist_ok=True)
+        removed.to_csv(removed_csv, index=False, encoding="utf-8-sig")
+    return {"rows": n_rows, "rows_changed": n_changed, "boxes_removed": len(removed), "output": output_csv_path,
+            "removed_output": removed_csv}
+
+
 # =============================================================================== a3 + a4  replace -> IoU in one pass
 # The processing page runs the two steps back to back on the same rows (reference ui/pages/processing.py:580-598), and the
 # replace step's output box IS the two-point ptList the IoU step reads back (:260 -> :354-362).  The functions below do both

@@ -817,8 +817,16 @@ BoxResult ptlist_box(Parser &ps, double v[4], bool &is_box) {
     return BR_OK;
 }
 
-// p at the '{' of an "objects" element
-BoxResult object_box(Parser &ps, double v[4], bool &is_box) {
+// what the suppression scan also records per box: the object's "name" (kind_of of its value, -1 = no "name" key) and its span
+struct ObjName {
+    int kind = -1;
+    Span tok{nullptr, nullptr};
+};
+
+// p at the '{' of an "objects" element.  META (suppression scan) also records the object's "name"; without it the walker is
+// the IoU step's as it always was.
+template <bool META>
+BoxResult object_box_t(Parser &ps, double v[4], bool &is_box, ObjName *nm) {
     is_box = false;
     ++ps.p;
     KeySet ks;
@@ -830,7 +838,12 @@ BoxResult object_box(Parser &ps, double v[4], bool &is_box) {
         ks.add(ps, k);
         ps.ws();
         ++ps.p;
-        if (Parser::span_is(k, "polygon")) {
+        if (META && Parser::span_is(k, "name")) {
+            nm->kind = kind_of(ps.peek());
+            const char *b = ps.p;
+            ps.value(nullptr);
+            nm->tok = Span{b, ps.p};
+        } else if (Parser::span_is(k, "polygon")) {
             const Kind pk = kind_of(ps.peek());
             if (pk != K_OBJECT) return BR_STOP;  // None / list / str / number .get -> AttributeError
             ++ps.p;
@@ -864,10 +877,25 @@ BoxResult object_box(Parser &ps, double v[4], bool &is_box) {
     }
 }
 
+// per-box extras of the suppression scan: index of the box's object in "objects" and a cell-local name id
+// (equal ids <=> equal decoded names; -1 = no "name" or null)
+struct BoxMetaSink {
+    std::vector<int32_t> obj, name;
+    std::vector<std::string> seen;   // the cell's distinct names, canonically re-spelled
+    std::string tmp;
+    void emit_name(Span tok) {       // tok: the string token with its quotes
+        Parser q{tok.b, tok.e};
+        q.emit_string(tmp, q.string_token());
+    }
+};
+
 // returns false when the cell must go to the Python path
-bool boxes_of_cell(Span cell, std::vector<double> &box4, int32_t &count) {
+template <bool META>
+bool boxes_of_cell_t(Span cell, std::vector<double> &box4, int32_t &count, BoxMetaSink *meta) {
     count = 0;
     const size_t mark = box4.size();
+    const size_t mmark = META ? meta->obj.size() : 0;
+    if (META) meta->seen.clear();
     Parser ps{cell.b, cell.e};
     try {  // validate the whole document first: an undecodable cell yields no boxes at all
         ps.value(nullptr);
@@ -891,17 +919,39 @@ bool boxes_of_cell(Span cell, std::vector<double> &box4, int32_t &count) {
             if (Parser::span_is(k, "objects")) {
                 const Kind kd = kind_of(ps.peek());
                 if (kd == K_NULL || kd == K_NUMBER || kd == K_TRUE || kd == K_FALSE) return true;  // iteration raises -> []
-                if (kd != K_ARRAY) { box4.resize(mark); count = 0; return false; }  // dict / str iterate: Python path
+                if (kd != K_ARRAY) { box4.resize(mark); count = 0; if (META) meta->obj.resize(mmark), meta->name.resize(mmark); return false; }  // dict / str iterate: Python path
                 ++ps.p;
                 if (ps.peek() == ']') return true;
-                while (true) {
+                for (int32_t k_obj = 0;; ++k_obj) {
                     if (ps.peek() == '{') {
                         double v[4];
                         bool is_box = false;
-                        const BoxResult r = object_box(ps, v, is_box);
+                        ObjName nm;
+                        const BoxResult r = object_box_t<META>(ps, v, is_box, &nm);
                         if (r == BR_STOP) return true;  // keep the prefix collected so far
-                        if (r == BR_IRREGULAR) { box4.resize(mark); count = 0; return false; }
-                        if (is_box) { box4.insert(box4.end(), v, v + 4); ++count; }
+                        if (r == BR_IRREGULAR || (META && is_box && nm.kind != -1 && nm.kind != K_NULL && nm.kind != K_STRING)) {
+                            box4.resize(mark);
+                            count = 0;
+                            if (META) { meta->obj.resize(mmark); meta->name.resize(mmark); }
+                            return false;
+                        }
+                        if (is_box) {
+                            box4.insert(box4.end(), v, v + 4);
+                            ++count;
+                            if (META) {
+                                int32_t id = -1;
+                                if (nm.kind == K_STRING) {
+                                    meta->tmp.clear();
+                                    meta->emit_name(nm.tok);
+                                    id = (int32_t)meta->seen.size();
+                                    for (size_t q = 0; q < meta->seen.size(); ++q)
+                                        if (meta->seen[q] == meta->tmp) { id = (int32_t)q; break; }
+                                    if (id == (int32_t)meta->seen.size()) meta->seen.push_back(meta->tmp);
+                                }
+                                meta->obj.push_back(k_obj);
+                                meta->name.push_back(id);
+                            }
+                        }
                     } else {
                         ps.value(nullptr);
                     }
@@ -916,9 +966,12 @@ bool boxes_of_cell(Span cell, std::vector<double> &box4, int32_t &count) {
     } catch (Fail f) {
         box4.resize(mark);
         count = 0;
+        if (META) { meta->obj.resize(mmark); meta->name.resize(mmark); }
         return false;
     }
 }
+
+bool boxes_of_cell(Span cell, std::vector<double> &box4, int32_t &count) { return boxes_of_cell_t<false>(cell, box4, count, nullptr); }
 
 template <class F>
 void parallel_cells(int64_t n, int n_threads, F fn) {
@@ -999,6 +1052,7 @@ struct dyd_scan {
     std::vector<double> w_val, h_val;
     std::vector<uint8_t> sel;           // labelled scan: box carries the row's label
     std::vector<uint8_t> iou_host;      // polygon scan: the cell's IoU flag needs CPython's exact int arithmetic (see dyd_scan_iou_host)
+    std::vector<int32_t> box_obj, box_name;   // suppression scan: per box its index in "objects" and its cell-local name id
     // emit output
     std::string text;
     std::vector<int64_t> text_off;
@@ -1658,6 +1712,188 @@ int dyd_json_scan_boxes(const uint8_t *text, const int64_t *cell_off, const uint
         return DYD_ERR_OOM;
     }
     *out = h;
+    return DYD_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// duplicate-box suppression (core/processor.py: suppress_duplicate_boxes_*): the IoU step's box walk plus, per box, the index of
+// its object and a name id; then the documents of the cells that lose objects, re-spelled as json.dumps(ensure_ascii=False)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+int scan_box_objects_src(const CellSrc &src, const uint8_t *missing, int64_t n_cells, int n_threads, dyd_scan **out) {
+    dyd_scan *h = new (std::nothrow) dyd_scan();
+    if (!h) return DYD_ERR_OOM;
+    h->n_cells = n_cells;
+    h->src = src;
+    try {
+        h->status.assign((size_t)n_cells, CELL_OK);
+        std::vector<int32_t> counts((size_t)n_cells, 0);
+        struct Part { std::vector<double> b; BoxMetaSink m; int64_t lo = 0, hi = 0; };
+        std::vector<Part> parts(64);
+        if (n_threads <= 0 || n_threads > 64) n_threads = default_threads();
+        const bool ok = parallel_cells_safe(n_cells, n_threads, [&](int t, int64_t lo, int64_t hi) {
+            Part &pt = parts[(size_t)t];
+            pt.lo = lo; pt.hi = hi;
+            for (int64_t i = lo; i < hi; ++i) {
+                if (missing && missing[i]) continue;  // NaN / non-str cell: unchanged
+                int32_t c = 0;
+                if (!boxes_of_cell_t<true>(src.get(i), pt.b, c, &pt.m)) {
+                    h->status[(size_t)i] = CELL_IRREGULAR;
+                    c = 0;
+                }
+                counts[(size_t)i] = c;
+            }
+        });
+        if (!ok) { delete h; return DYD_ERR_OOM; }
+        std::sort(parts.begin(), parts.end(), [](const Part &a, const Part &b) { return a.lo < b.lo; });
+        size_t tot = 0;
+        for (auto &pt : parts) tot += pt.b.size();
+        if (tot / 4 >= (size_t)1 << 31) { delete h; return DYD_ERR_RANGE; }
+        h->xy.reserve(tot);
+        h->box_obj.reserve(tot / 4);
+        h->box_name.reserve(tot / 4);
+        for (auto &pt : parts) {
+            h->xy.insert(h->xy.end(), pt.b.begin(), pt.b.end());
+            h->box_obj.insert(h->box_obj.end(), pt.m.obj.begin(), pt.m.obj.end());
+            h->box_name.insert(h->box_name.end(), pt.m.name.begin(), pt.m.name.end());
+        }
+        h->cell_box_off.resize((size_t)n_cells + 1);
+        h->cell_box_off[0] = 0;
+        for (int64_t i = 0; i < n_cells; ++i) h->cell_box_off[(size_t)i + 1] = h->cell_box_off[(size_t)i] + counts[(size_t)i];
+        h->pt_off.assign(1, 0);
+    } catch (const std::bad_alloc &) {
+        delete h;
+        return DYD_ERR_OOM;
+    }
+    *out = h;
+    return DYD_OK;
+}
+
+// the whole document of one cell with the objects whose drop_obj[k] is set left out ("objects" is a list: the cell had boxes)
+void emit_dropping_cell(Span cell, const std::vector<uint8_t> &drop_obj, std::string &out) {
+    Parser ps{cell.b, cell.e};
+    ps.ws();
+    if (ps.p >= ps.end || *ps.p != '{') ps.irregular();
+    ++ps.p;
+    out += '{';
+    bool first = true;
+    if (ps.peek() == '}') { ++ps.p; out += '}'; return; }
+    while (true) {
+        ps.ws();
+        const Span k = ps.string_token();
+        if (!first) out += ", ";
+        first = false;
+        ps.emit_string(out, k);
+        out += ": ";
+        ps.ws();
+        if (ps.p >= ps.end || *ps.p != ':') ps.bad();
+        ++ps.p;
+        if (Parser::span_is(k, "objects") && ps.peek() == '[') {
+            ++ps.p;
+            out += '[';
+            bool efirst = true;
+            if (ps.peek() == ']') {
+                ++ps.p;
+            } else {
+                for (size_t ko = 0;; ++ko) {
+                    const bool drop = ko < drop_obj.size() && drop_obj[ko];
+                    if (!drop && !efirst) out += ", ";
+                    if (!drop) efirst = false;
+                    ps.value(drop ? nullptr : &out);
+                    const char d = ps.peek();
+                    if (d == ',') { ++ps.p; continue; }
+                    if (d == ']') { ++ps.p; break; }
+                    ps.bad();
+                }
+            }
+            out += ']';
+        } else {
+            ps.value(&out);
+        }
+        const char d = ps.peek();
+        if (d == ',') { ++ps.p; continue; }
+        if (d == '}') { ++ps.p; break; }
+        ps.bad();
+    }
+    out += '}';
+}
+
+}  // namespace
+
+extern "C" {
+
+int dyd_json_scan_box_objects(const uint8_t *text, const int64_t *cell_off, const uint8_t *missing, int64_t n_cells, int n_threads,
+                              dyd_scan **out) {
+    if (!out || n_cells < 0 || (n_cells > 0 && (!cell_off || !text))) return DYD_ERR_INVALID;
+    CellSrc src;
+    src.text = text; src.off = cell_off;
+    return scan_box_objects_src(src, missing, n_cells, n_threads, out);
+}
+
+int dyd_json_scan_box_objects_v(const uint8_t *const *cell_ptr, const int64_t *cell_len, const uint8_t *missing, int64_t n_cells,
+                                int n_threads, dyd_scan **out) {
+    if (!out || n_cells < 0 || (n_cells > 0 && (!cell_ptr || !cell_len))) return DYD_ERR_INVALID;
+    CellSrc src;
+    src.ptr = cell_ptr; src.len = cell_len;
+    return scan_box_objects_src(src, missing, n_cells, n_threads, out);
+}
+
+const int32_t *dyd_scan_box_object(const dyd_scan *h) { return (h && !h->box_obj.empty()) ? h->box_obj.data() : nullptr; }
+const int32_t *dyd_scan_box_name(const dyd_scan *h) { return (h && !h->box_name.empty()) ? h->box_name.data() : nullptr; }
+
+int dyd_json_emit_dropping(dyd_scan *h, const uint8_t *drop_per_box, int n_threads, uint8_t *out_changed, const uint8_t **out_text,
+                           const int64_t **out_off) {
+    if (!h || !out_changed || !out_text || !out_off) return DYD_ERR_INVALID;
+    const int64_t n = h->n_cells;
+    const int64_t nb = h->cell_box_off.empty() ? 0 : h->cell_box_off[(size_t)n];
+    if (nb > 0 && (!drop_per_box || (int64_t)h->box_obj.size() != nb)) return DYD_ERR_INVALID;
+    try {
+        std::vector<std::string> texts(64);
+        std::vector<int64_t> lens((size_t)n, 0);
+        struct Range { int64_t lo = 0, hi = 0; };
+        std::vector<Range> ranges(64);
+        if (n_threads <= 0 || n_threads > 64) n_threads = default_threads();
+        const bool ok = parallel_cells_safe(n, n_threads, [&](int t, int64_t lo, int64_t hi) {
+            ranges[(size_t)t] = Range{lo, hi};
+            std::string &buf = texts[(size_t)t];
+            std::vector<uint8_t> drop_obj;
+            for (int64_t i = lo; i < hi; ++i) {
+                out_changed[i] = 0;
+                const int32_t b0 = h->cell_box_off[(size_t)i], b1 = h->cell_box_off[(size_t)i + 1];
+                bool any = false;
+                for (int32_t b = b0; b < b1; ++b) any |= drop_per_box[b] != 0;
+                if (!any) continue;
+                drop_obj.assign((size_t)h->box_obj[(size_t)b1 - 1] + 1, 0);
+                for (int32_t b = b0; b < b1; ++b)
+                    if (drop_per_box[b]) drop_obj[(size_t)h->box_obj[(size_t)b]] = 1;
+                const size_t mark = buf.size();
+                try {
+                    emit_dropping_cell(h->src.get(i), drop_obj, buf);
+                    out_changed[i] = 1;
+                } catch (Fail) {
+                    buf.resize(mark);
+                    out_changed[i] = 2;   // the Python path re-spells this cell
+                }
+                lens[(size_t)i] = (int64_t)(buf.size() - mark);
+            }
+        });
+        if (!ok) return DYD_ERR_OOM;
+        h->text_off.assign((size_t)n + 1, 0);
+        for (int64_t i = 0; i < n; ++i) h->text_off[(size_t)i + 1] = h->text_off[(size_t)i] + lens[(size_t)i];
+        h->text.clear();
+        h->text.reserve((size_t)h->text_off[(size_t)n]);
+        std::vector<size_t> order;
+        for (size_t t = 0; t < ranges.size(); ++t) if (ranges[t].hi > ranges[t].lo) order.push_back(t);
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return ranges[a].lo < ranges[b].lo; });
+        for (size_t t : order) h->text += texts[t];
+    } catch (const std::bad_alloc &) {
+        return DYD_ERR_OOM;
+    }
+    *out_text = reinterpret_cast<const uint8_t *>(h->text.data());
+    *out_off = h->text_off.data();
     return DYD_OK;
 }
 

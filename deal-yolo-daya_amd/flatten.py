@@ -218,6 +218,63 @@ def host_row_is_high(boxes, min_boxes, thr) -> bool:
     return False
 
 
+
+def pair_iou(p, q):
+    """calculate_iou (:328-339) of (earlier, later) corner tuples in CPython arithmetic: exact ints, IEEE doubles,
+    first-wins max / min — so a NaN corner behaves as in the reference and strings raise where it raises."""
+    ix1 = max(p[0], q[0])
+    iy1 = max(p[1], q[1])
+    ix2 = min(p[2], q[2])
+    iy2 = min(p[3], q[3])
+    inter = max(0, ix2 - ix1) * max(0, iy2 - iy1)
+    if inter == 0:
+        return 0.0
+    union = (p[2] - p[0]) * (p[3] - p[1]) + (q[2] - q[0]) * (q[3] - q[1]) - inter
+    return inter / union if union != 0 else 0.0
+
+
+def suppress_cell(cell, thr, by_label):
+    """Duplicate-box suppression of one cell on the host, for the cells the native scanner leaves to Python (huge ints,
+    string coordinates, repeated keys, odd names ...): -> (cell or its re-spelled document, [(object, kept_object, iou)]).
+
+    The boxes are extract_boxes' (:341-366, prefix on exception) with the index of their object and their name; a box is
+    dropped when an earlier kept box (of the same name when ``by_label``) reaches pair_iou >= thr with it.  Exceptions of
+    pair_iou propagate, as in meet_conditions.  A cell that loses nothing is returned as the same object."""
+    if not isinstance(cell, str):
+        return cell, []
+    boxes = []
+    try:
+        doc = json.loads(cell)
+        for k, obj in enumerate(doc.get("objects", [])):
+            if not isinstance(obj, dict):
+                continue
+            pts = obj.get("polygon", {}).get("ptList", [])
+            if len(pts) != 2:
+                continue
+            a, b = pts
+            if not (isinstance(a, dict) and isinstance(b, dict) and "x" in a and "y" in a and "x" in b and "y" in b):
+                continue
+            boxes.append((k, (min(a["x"], b["x"]), min(a["y"], b["y"]), max(a["x"], b["x"]), max(a["y"], b["y"])),
+                          obj.get("name")))
+    except Exception:                                   # noqa: BLE001 (:364-365) keep the prefix
+        pass
+    kept, removed = [], []
+    for k, box, name in boxes:
+        for kk, kbox, kname in kept:
+            if not by_label or kname == name:
+                iou = pair_iou(kbox, box)
+                if iou >= thr:
+                    removed.append((k, kk, iou))
+                    break
+        else:
+            kept.append((k, box, name))
+    if not removed:
+        return cell, []
+    drop = {k for k, _, _ in removed}
+    doc["objects"] = [o for k, o in enumerate(doc["objects"]) if k not in drop]
+    return json.dumps(doc, ensure_ascii=False), removed
+
+
 # ------------------------------------------------------------------------------------------
 # a1 / a2  key column -> flat bytes + offsets for K3
 # ------------------------------------------------------------------------------------------

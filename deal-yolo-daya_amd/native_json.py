@@ -361,6 +361,65 @@ def scan_boxes(cells, n_threads: int = 0) -> BoxScan:
     return BoxScan(h, len(off) - 1, keep)
 
 
+# ------------------------------------------------------------------------------------------ duplicate-box suppression
+class BoxObjectScan(BoxScan):
+    """Result of scan_box_objects: the IoU step's boxes plus, per box, the index of its object in "objects" (``box_object``)
+    and a cell-local name id (``box_name``: equal ids <=> equal names, -1 = no name or null)."""
+
+    def __init__(self, handle, n_cells, keep):
+        super().__init__(handle, n_cells, keep)
+        L = _native.load_library()
+        nb = int(self.cell_box_off[-1]) if n_cells else 0
+        self.n_boxes = nb
+        self.box_object = _view(L.dyd_scan_box_object(handle), np.int32, nb).copy()
+        self.box_name = _view(L.dyd_scan_box_name(handle), np.int32, nb).copy()
+
+    def emit_dropping(self, drop: np.ndarray, n_threads: int = 0) -> tuple:
+        """-> (changed u8 [n_cells]: 0 unchanged, 1 re-spelled here, 2 left to the caller; str per changed == 1 cell, in order)"""
+        L = _native.load_library()
+        drop = np.ascontiguousarray(drop, dtype=np.uint8)
+        if drop.size != len(self.box_object):
+            raise ValueError("drop must hold one flag per box")
+        changed = np.zeros(self.n_cells, np.uint8)
+        tp, op = C.c_void_p(), C.c_void_p()
+        _native.check(L.dyd_json_emit_dropping(self._h, drop.ctypes.data if drop.size else None, n_threads,
+                                               changed.ctypes.data if self.n_cells else None, C.byref(tp), C.byref(op)),
+                      "dyd_json_emit_dropping")
+        idx = np.flatnonzero(changed == 1)
+        if not len(idx):
+            return changed, np.empty(0, object)
+        off = _view(op.value, np.int64, self.n_cells + 1)
+        sub = np.append(off[idx], off[idx[-1] + 1])           # unchanged cells have no text: the changed ones are contiguous
+        text = _view(tp.value, np.uint8, max(int(off[-1]), 1))
+        return changed, strings_from_buffers(text, sub, None, n_threads)
+
+
+def scan_box_objects_buffers(data, off, missing, n_threads: int = 0, keep=None) -> BoxObjectScan:
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    missing = np.ascontiguousarray(missing, dtype=np.uint8)
+    L = _native.load_library()
+    h = C.c_void_p()
+    _native.check(L.dyd_json_scan_box_objects(data.ctypes.data, off.ctypes.data, missing.ctypes.data, len(off) - 1,
+                                              n_threads, C.byref(h)), "dyd_json_scan_box_objects")
+    return BoxObjectScan(h, len(off) - 1, (keep, data, off, missing))
+
+
+def scan_box_objects(cells, n_threads: int = 0) -> BoxObjectScan:
+    """cells -> BoxObjectScan.  With the CPython helper the scanner reads the str objects' own UTF-8 buffers (no copy)."""
+    from . import pycells
+
+    L = _native.load_library()
+    h = C.c_void_p()
+    if pycells.available():
+        v = pycells.CellViews(cells.to_numpy() if hasattr(cells, "to_numpy") else cells)
+        _native.check(L.dyd_json_scan_box_objects_v(v.ptr.ctypes.data, v.len.ctypes.data, v.missing.ctypes.data, len(v),
+                                                    n_threads, C.byref(h)), "dyd_json_scan_box_objects_v")
+        return BoxObjectScan(h, len(v), v)
+    data, off, missing, keep = cells_to_buffers(cells)
+    return scan_box_objects_buffers(data, off, missing, n_threads, keep)
+
+
 # ------------------------------------------------------------------------------------------ split step
 SP_OK, SP_EMPTY, SP_UNDECODABLE, SP_NOT_A_LIST, SP_NO_OBJECTS, SP_IRREGULAR = 0, 1, 2, 3, 4, 5
 EV_NO_NAME, EV_UNDEFINED, EV_NOTHING_CLASSIFIED = 1, 2, 3

@@ -106,6 +106,23 @@ int dyd_iou_any_ge_dev(const double *box4, const int32_t *row_off, int64_t n_row
                        int32_t min_boxes, double thr, uint8_t *out_high,
                        double *out_max_iou_or_null, void *stream);
 
+/* ---- K9: greedy duplicate-box suppression inside each image row -------------------
+ * For box j of a row: dropped iff some earlier box of the row that is itself kept has
+ * calculate_iou(earlier, j) >= thr (processor.py:328-339 arithmetic, corners normalised as
+ * in extract_boxes :359-362); with name_or_null only boxes of equal name id compare.
+ * box4       : per box the two ptList points as stored (p1x, p1y, p2x, p2y)   [4*B]
+ * row_off    : box offsets per image row                                     [n_rows+1]
+ * name_or_null: optional name id per box (boxes compare iff the ids are equal)  [B]
+ * out_keep   : 1 = kept, 0 = dropped                                         [B]
+ * out_partner: in-row index of the first kept box that hit this one, or -1   [B] */
+int dyd_suppress_boxes(const double *box4, const int32_t *row_off, int64_t n_rows,
+                       const int32_t *name_or_null, double thr, uint8_t *out_keep,
+                       int32_t *out_partner);
+/* device pointers; n_boxes = row_off[n_rows] (required: it sizes the list of rows above 64 boxes) */
+int dyd_suppress_boxes_dev(const double *box4, const int32_t *row_off, int64_t n_rows, int64_t n_boxes,
+                           const int32_t *name_or_null, double thr, uint8_t *out_keep,
+                           int32_t *out_partner, void *stream);
+
 /* ---- K1+K2 fused: poly -> bbox -> IoU flag in one pass ---------------------------
  * One launch that produces K1's outputs and K2's flag for rows whose boxes all come
  * from K1 (processing.py:580-598 runs the two steps back to back on the same rows).
@@ -273,6 +290,22 @@ int dyd_json_emit_polygons(dyd_scan *scan, const uint8_t *text, const int64_t *c
                            const int64_t **out_off);
 int dyd_json_scan_boxes(const uint8_t *text, const int64_t *cell_off, const uint8_t *missing,
                         int64_t n_cells, int n_threads, dyd_scan **out);
+/* Duplicate-box suppression: dyd_json_scan_boxes' walk (same boxes, prefix-on-exception rule and status) plus, per box,
+ * dyd_scan_box_object = index of its object in "objects" and dyd_scan_box_name = a name id local to the cell (equal ids <=>
+ * equal decoded names; -1 = no "name" or null).  A box whose "name" is neither a string nor null makes the cell irregular.
+ * The _v form takes one (pointer, length) per cell; the pointers must stay valid until dyd_scan_free. */
+int dyd_json_scan_box_objects(const uint8_t *text, const int64_t *cell_off, const uint8_t *missing,
+                              int64_t n_cells, int n_threads, dyd_scan **out);
+int dyd_json_scan_box_objects_v(const uint8_t *const *cell_ptr, const int64_t *cell_len, const uint8_t *missing,
+                                int64_t n_cells, int n_threads, dyd_scan **out);
+const int32_t *dyd_scan_box_object(const dyd_scan *scan);   /* [n_boxes] */
+const int32_t *dyd_scan_box_name(const dyd_scan *scan);     /* [n_boxes] */
+/* After dyd_json_scan_box_objects: for every cell with at least one drop_per_box[b] set, the whole document as
+ * json.dumps(..., ensure_ascii=False) writes it with those boxes' objects left out.  out_changed[i] (caller's, [n_cells]):
+ * 0 unchanged (empty text), 1 text written, 2 the cell could not be re-spelled natively (the caller decides it).  The text
+ * and its offsets [n_cells+1] are owned by the handle. */
+int dyd_json_emit_dropping(dyd_scan *scan, const uint8_t *drop_per_box, int n_threads, uint8_t *out_changed,
+                           const uint8_t **out_text, const int64_t **out_off);
 int64_t dyd_scan_n_boxes(const dyd_scan *scan);
 int64_t dyd_scan_n_points(const dyd_scan *scan);
 const double *dyd_scan_xy(const dyd_scan *scan);              /* points [2*P] (polygons) or box4 [4*B] (boxes) */

@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmarks on one MI355X (device-resident inputs, HIP-event timing,
 interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant.
 
-    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]
+    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression against K2 alone)
 """
 import argparse
 import json
@@ -131,6 +131,30 @@ def main():
         med, mn = timeit(lambda: ck(L.dyd_iou_any_ge_dev(out_box.data_ptr(), box_off.data_ptr(), N, B, 2, 0.98,
                                                           out_high.data_ptr(), mx.data_ptr(), sp), "k2max"))
         report("k2_iou_want_max", k2_bytes + 8 * N, med, mn, gpairs_per_s=round(pairs / med / 1e6, 2))
+
+    if "k9" in only:
+        # K9 (duplicate-box suppression) against K2 alone on the same device buffers, interleaved rounds
+        ck(L.dyd_bbox_minmax_dev(xy.data_ptr(), pt_off.data_ptr(), B, P, out_box.data_ptr(), out_arg.data_ptr(), sp), "k1")
+        keep = torch.empty(B, dtype=torch.uint8, device=dev)
+        partner = torch.empty(B, dtype=torch.int32, device=dev)
+        names = labels.to(torch.int32).contiguous()
+        legs = {"k2 auto (dyd_iou_any_ge_dev)": (32 * B + 4 * (N + 1) + N, lambda: ck(L.dyd_iou_any_ge_dev(
+                    out_box.data_ptr(), box_off.data_ptr(), N, B, 2, 0.98, out_high.data_ptr(), None, sp), "k2")),
+                "k9_suppress": (32 * B + 4 * (N + 1) + 5 * B, lambda: ck(L.dyd_suppress_boxes_dev(
+                    out_box.data_ptr(), box_off.data_ptr(), N, B, None, 0.98, keep.data_ptr(), partner.data_ptr(), sp), "k9")),
+                "k9_suppress by_label": (36 * B + 4 * (N + 1) + 5 * B, lambda: ck(L.dyd_suppress_boxes_dev(
+                    out_box.data_ptr(), box_off.data_ptr(), N, B, names.data_ptr(), 0.98, keep.data_ptr(), partner.data_ptr(),
+                    sp), "k9"))}
+        res = {}
+        for rnd in range(2):
+            for nm, (_, fn) in legs.items():
+                res.setdefault(nm, []).append(timeit(fn))
+        for nm, (nbytes, _) in legs.items():
+            med = float(np.median([r[0] for r in res[nm]])); mn = min(r[1] for r in res[nm])
+            report(nm, nbytes, med, mn, rows_per_s=round(N / med * 1e3))
+        legs["k9_suppress"][1]()
+        torch.cuda.synchronize()
+        print(json.dumps({"kernel": "k9_suppress", "dropped": int((keep == 0).sum().item())}), flush=True)
 
     if "k12" in only:
         k12_bytes = 16 * P + 4 * (B + 1) + 48 * B + 4 * (N + 1) + N
