@@ -67,6 +67,14 @@ SIGNATURES = {
     "dyd_scan_box_name": (C.c_void_p, [C.c_void_p]),
     "dyd_json_emit_dropping": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_void_p)]),
+    "dyd_box_audit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dyd_box_audit_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "dyd_json_scan_named_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    "dyd_json_scan_named_boxes_v": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    "dyd_scan_names": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "dyd_iou_any_ge_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "dyd_bbox_iou_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
@@ -320,6 +328,39 @@ def suppress_boxes(box4: np.ndarray, row_off: np.ndarray, thr: float, name=None)
     check(lib().dyd_suppress_boxes(_ptr(box4), _ptr(row_off), n, _ptr(name) if name is not None else None, float(thr),
                                    _ptr(keep), _ptr(partner)), "dyd_suppress_boxes")
     return keep, partner
+
+
+AUDIT_BPI = 257      # boxes_per_image bins: 0..255 boxes, then >= 256
+
+
+def box_audit(box4: np.ndarray, row_off: np.ndarray, cls: np.ndarray, width: np.ndarray, height: np.ndarray,
+              size_status: np.ndarray, n_classes: int, nbins: int):
+    """K10 over host arrays -> (flag [B] u8, row_counts [N,6] i32, class_counts [C,9] i64, hist_wh [C,nb,nb] i64,
+    hist_xy [C,nb,nb] i64, boxes_per_image [257] i64).  See include/dyd.h for the columns and the flag bits."""
+    box4 = np.ascontiguousarray(box4, dtype=np.float64).reshape(-1)
+    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
+    n = len(row_off) - 1
+    if n < 0 or row_off[0] != 0 or 4 * int(row_off[-1]) != box4.size:
+        raise ValueError("row_off must start at 0 and end at the number of boxes")
+    nbins, n_classes = int(nbins), int(n_classes)
+    if not 1 <= nbins <= 64:
+        raise ValueError(f"nbins must lie in 1..64, got {nbins}")
+    nb = int(row_off[-1])
+    cls = np.ascontiguousarray(cls, dtype=np.int32)
+    width = np.ascontiguousarray(width, dtype=np.float64)
+    height = np.ascontiguousarray(height, dtype=np.float64)
+    size_status = np.ascontiguousarray(size_status, dtype=np.uint8)
+    if cls.size != nb or width.size != n or height.size != n or size_status.size != n:
+        raise ValueError("cls must hold one id per box; width, height and size_status one value per row")
+    flag = np.zeros(nb, np.uint8)
+    rows = np.zeros((n, 6), np.int32)
+    cc = np.zeros((n_classes, 9), np.int64)
+    wh = np.zeros((n_classes, nbins, nbins), np.int64)
+    xy = np.zeros((n_classes, nbins, nbins), np.int64)
+    bpi = np.zeros(AUDIT_BPI, np.int64)
+    check(lib().dyd_box_audit(_ptr(box4), _ptr(row_off), n, _ptr(cls), _ptr(width), _ptr(height), _ptr(size_status), n_classes,
+                              nbins, _ptr(flag), _ptr(rows), _ptr(cc), _ptr(wh), _ptr(xy), _ptr(bpi)), "dyd_box_audit")
+    return flag, rows, cc, wh, xy, bpi
 
 
 def bbox_iou_fused(xy: np.ndarray, pt_off: np.ndarray, box_off: np.ndarray, min_boxes: int, thr: float,

@@ -2057,6 +2057,313 @@ def yolo_label_texts(cells, label_values, class_ids, widths, heights, backend=No
     return texts, reasons
 
 
+# =============================================================================== f5  box audit
+# A dataset health report before any label file is written: per class, how many of its boxes the YOLO step will write, skip or
+# write with a coordinate outside [0, 1], with size / position histograms and a list of the boxes that break.  Boxes are the YOLO
+# step's (utils._extract_boxes_with_labels, reference utils.py:681-710) with the index of their object; the arithmetic is that
+# of :1046-1058 on float(v) in IEEE f64 (beyond 2^53 the YOLO step's exact int arithmetic can differ: accepted).  Native scan
+# (csrc/host_json.cpp; flatten.audit_cell_boxes for irregular cells) -> K10 (csrc/k10_audit.hip) -> frames.
+AUDIT_STATUS = ("ok", "missing", "invalid")                        # row size status (codes 0, 1, 2)
+AUDIT_CATEGORIES = ("no_size", "bad_coords", "degenerate", "writable")
+_AUDIT_CLASS_COLS = ("no_size", "bad_coords", "degenerate", "writable", "out_of_image", "small", "medium", "large", "images")
+_AUDIT_ROW_COLS = ("unmatchable", "no_size", "bad_coords", "degenerate", "writable", "out_of_image")
+_NUMBER_TYPES = (int, float, np.integer, np.floating)               # bool is an int, as in Python arithmetic
+
+
+class BoxAudit:
+    """Result of audit_boxes_*: classes (sorted as str), per_class / per_row / problems frames, hist_wh and hist_xy
+    (int64 [C, nbins, nbins], [c, bin(w / W), bin(h / H)] and [c, bin(xc), bin(yc)] over writable boxes), boxes_per_image
+    (int64 [257], the last bin takes >= 256 boxes) and totals."""
+
+    def __init__(self, classes, per_class, hist_wh, hist_xy, boxes_per_image, per_row, problems, totals):
+        self.classes = classes
+        self.per_class = per_class
+        self.hist_wh = hist_wh
+        self.hist_xy = hist_xy
+        self.boxes_per_image = boxes_per_image
+        self.per_row = per_row
+        self.problems = problems
+        self.totals = totals
+
+    def __repr__(self):
+        return f"BoxAudit({len(self.classes)} classes, {self.totals})"
+
+
+def _audit_number(v) -> float:
+    """float(v) of an int / float (bool included); NaN for anything else and inf when float() overflows: both are bad_coords"""
+    if not isinstance(v, _NUMBER_TYPES):
+        return float("nan")
+    try:
+        return float(v)
+    except OverflowError:
+        return float("inf")
+
+
+def _audit_size_py(w, h) -> tuple:
+    """(status code, W, H) of one row: missing when `not w or not h` (:1023-1025), invalid unless both are finite
+    numbers > 0"""
+    try:
+        if not w or not h:
+            return 1, 0.0, 0.0
+    except Exception:                                   # noqa: BLE001  pd.NA, arrays ...: no usable size
+        return 2, 0.0, 0.0
+    fw, fh = _audit_number(w), _audit_number(h)
+    if not (np.isfinite(fw) and np.isfinite(fh) and fw > 0 and fh > 0):
+        return 2, 0.0, 0.0
+    return 0, fw, fh
+
+
+def _audit_sizes(widths, heights, n: int) -> tuple:
+    """-> (status u8, W f64, H f64) per row; numpy when both columns are numeric, Python per row otherwise"""
+    if widths is None or heights is None:                # no size columns: row.get gives None
+        return np.ones(n, np.uint8), np.zeros(n), np.zeros(n)
+    kinds = ("integer", "floating", "mixed-integer-float")
+    if n and pd.api.types.infer_dtype(widths, skipna=False) in kinds and pd.api.types.infer_dtype(heights, skipna=False) in kinds:
+        try:
+            w, h = np.asarray(widths, np.float64), np.asarray(heights, np.float64)
+        except OverflowError:
+            w = None
+        if w is not None:
+            missing = (w == 0) | (h == 0)                # NaN is truthy: it gets past `not w`
+            ok = ~missing & np.isfinite(w) & np.isfinite(h) & (w > 0) & (h > 0)
+            status = np.where(missing, 1, np.where(ok, 0, 2)).astype(np.uint8)
+            return status, np.where(ok, w, 0.0), np.where(ok, h, 0.0)
+    res = [_audit_size_py(a, b) for a, b in zip(widths, heights)]
+    status = np.fromiter((r[0] for r in res), np.uint8, count=n)
+    return status, np.fromiter((r[1] for r in res), np.float64, count=n), np.fromiter((r[2] for r in res), np.float64, count=n)
+
+
+def _audit_backend(backend):
+    be = _backend(backend)
+    if not hasattr(be, "box_audit"):
+        raise TypeError("backend lacks ['box_audit']")
+    return be
+
+
+class _AuditTotals:
+    """class-keyed sums over the chunks, classes in first-seen order until the end"""
+
+    def __init__(self, nbins):
+        self.nbins = nbins
+        self.index = {}
+        self.cc = np.zeros((0, len(_AUDIT_CLASS_COLS)), np.int64)
+        self.wh = np.zeros((0, nbins, nbins), np.int64)
+        self.xy = np.zeros((0, nbins, nbins), np.int64)
+        self.bpi = np.zeros(257, np.int64)
+        self.rows, self.n_boxes, self.status, self.problems = [], [], [], []
+        self.python_cells = 0
+
+    def add_classes(self, names, cc, wh, xy):
+        g = np.asarray([self.index.setdefault(nm, len(self.index)) for nm in names], np.int64)
+        grow = len(self.index) - len(self.cc)
+        if grow:
+            nb = self.nbins
+            self.cc = np.concatenate([self.cc, np.zeros((grow, self.cc.shape[1]), np.int64)])
+            self.wh = np.concatenate([self.wh, np.zeros((grow, nb, nb), np.int64)])
+            self.xy = np.concatenate([self.xy, np.zeros((grow, nb, nb), np.int64)])
+        if len(g):
+            self.cc[g] += cc
+            self.wh[g] += wh
+            self.xy[g] += xy
+
+
+def _audit_chunk(cells, status, W, H, be, acc: _AuditTotals, start: int):
+    """one chunk of rows: scan (native, CPython for irregular cells) -> K10 -> class-keyed sums, per-row counts, problems"""
+    n = len(cells)
+    try:
+        scan = _nj.scan_named_boxes(cells) if _nj.enabled() else None
+    except UnicodeEncodeError:                           # a lone surrogate: every cell of the chunk through CPython
+        scan = None
+    if scan is not None:
+        try:
+            nat_off = scan.cell_box_off.astype(np.int64)
+            counts = np.diff(nat_off)
+            irregular = np.flatnonzero(scan.status == _nj.IRREGULAR).tolist()
+            names = list(scan.names)
+            box4, obj, cls = scan.box4, scan.box_object, scan.box_class
+        finally:
+            scan.close()
+    else:
+        nat_off = np.zeros(n + 1, np.int64)
+        counts = np.zeros(n, np.int64)
+        irregular = list(range(n))
+        names, box4, obj, cls = [], np.zeros((0, 4)), np.zeros(0, np.int32), np.zeros(0, np.int32)
+    acc.python_cells += len(irregular)
+    py = {}
+    for i in irregular:
+        boxes = _fl.audit_cell_boxes(cells[i])
+        if boxes:
+            py[i] = boxes
+            counts[i] = len(boxes)
+    row_off = np.zeros(n + 1, np.int64)
+    np.cumsum(counts, out=row_off[1:])
+    if py:                                               # splice the CPython boxes in at their rows
+        nat_counts = np.diff(nat_off)
+        dest = np.repeat(row_off[:-1] - nat_off[:-1], nat_counts) + np.arange(len(obj), dtype=np.int64)
+        nb = int(row_off[-1])
+        b4, ob, cl = np.empty((nb, 4)), np.empty(nb, np.int32), np.empty(nb, np.int32)
+        b4[dest], ob[dest], cl[dest] = box4, obj, cls
+        ids = {nm: k for k, nm in enumerate(names)}
+        for i, boxes in py.items():
+            p = int(row_off[i])
+            for k, (o, nm, *xy) in enumerate(boxes):
+                b4[p + k] = [_audit_number(v) for v in xy]
+                ob[p + k] = o
+                cl[p + k] = ids.setdefault(nm, len(ids)) if isinstance(nm, str) else -1
+        names = list(ids)
+        box4, obj, cls = b4, ob, cl
+    if row_off[-1] >= (1 << 31):
+        raise ValueError("a chunk holds 2^31 boxes or more")
+    flag, rows, cc, wh, xy, bpi = be.box_audit(box4, row_off.astype(np.int32), cls, W, H, status, len(names), acc.nbins)
+    acc.add_classes(names, np.asarray(cc, np.int64), np.asarray(wh, np.int64), np.asarray(xy, np.int64))
+    acc.bpi += np.asarray(bpi, np.int64)
+    acc.rows.append(np.asarray(rows, np.int64).reshape(n, len(_AUDIT_ROW_COLS)))
+    acc.n_boxes.append(counts)
+    acc.status.append(status)
+    flag = np.asarray(flag, np.uint8)
+    cat = flag & 3
+    bad = np.flatnonzero(((flag & 0x80) == 0) & ((cat == 1) | (cat == 2) | ((flag & 4) != 0)))
+    if len(bad):
+        issue = np.where(cat[bad] == 1, "bad_coords", np.where(cat[bad] == 2, "degenerate", "out_of_image")).astype(object)
+        name_arr = np.asarray(names, object)
+        acc.problems.append((start + np.searchsorted(row_off, bad, side="right") - 1, obj[bad].astype(np.int64),
+                             name_arr[cls[bad]], issue, np.asarray(box4, np.float64).reshape(-1, 4)[bad]))
+
+
+def audit_boxes_cells(cells, widths, heights, nbins: int = 16, backend=None, stats: Optional[dict] = None,
+                      sources=None) -> BoxAudit:
+    """Box audit of the annotation cells of a table (see the section comment; widths / heights are the row's image size as the
+    YOLO step reads it, None for a table without the columns).  -> BoxAudit.  ``sources`` (optional) adds a source column to
+    per_row and problems."""
+    if isinstance(nbins, bool) or not isinstance(nbins, (int, np.integer)) or not 1 <= int(nbins) <= 64:
+        raise ValueError(f"nbins must be an int in 1..64, got {nbins!r}")
+    nbins = int(nbins)
+    be = _audit_backend(backend)
+    cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
+    n = len(cells)
+    if (widths is None) != (heights is None) or (widths is not None and (len(widths) != n or len(heights) != n)):
+        raise ValueError("widths and heights must both be given with one value per cell, or both be None")
+    status, W, H = _audit_sizes(widths, heights, n)
+    acc = _AuditTotals(nbins)
+    for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
+        s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
+        _audit_chunk(cells[s0:s1], status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0)
+    return _audit_result(acc, n, status, sources, stats)
+
+
+def _audit_result(acc: _AuditTotals, n: int, status, sources, stats) -> BoxAudit:
+    classes = sorted(acc.index)
+    perm = np.asarray([acc.index[c] for c in classes], np.int64)
+    cc, wh, xy = acc.cc[perm], acc.wh[perm], acc.xy[perm]
+    cols = dict(zip(_AUDIT_CLASS_COLS, cc.T)) if len(classes) else {k: np.zeros(0, np.int64) for k in _AUDIT_CLASS_COLS}
+    per_class = pd.DataFrame({"class": pd.Series(classes, dtype=object),
+                              "boxes": cols["no_size"] + cols["bad_coords"] + cols["degenerate"] + cols["writable"],
+                              "images": cols["images"],
+                              **{k: cols[k] for k in _AUDIT_CLASS_COLS[:-1]}})
+    rows = np.concatenate(acc.rows) if acc.rows else np.zeros((0, len(_AUDIT_ROW_COLS)), np.int64)
+    n_boxes = np.concatenate(acc.n_boxes) if acc.n_boxes else np.zeros(0, np.int64)
+    pr = {"row": np.arange(n, dtype=np.int64)}
+    if sources is not None:
+        pr["source"] = np.asarray(sources, object)
+    pr["size_status"] = pd.Categorical.from_codes(np.asarray(status, np.int8), AUDIT_STATUS)
+    pr["n_boxes"] = n_boxes
+    pr.update({k: rows[:, j] for j, k in enumerate(_AUDIT_ROW_COLS)})
+    per_row = pd.DataFrame(pr)
+    pc = {}
+    if acc.problems:
+        r, o, nm, issue, b = (np.concatenate([p[k] for p in acc.problems]) for k in range(5))
+    else:
+        r, o, nm, issue, b = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, object), np.zeros(0, object),
+                              np.zeros((0, 4)))
+    if sources is not None:
+        pc["source"] = np.asarray(sources, object)[r] if len(r) else np.zeros(0, object)
+    pc.update({"row": r, "object": o, "name": nm, "issue": issue, "x1": b[:, 0], "y1": b[:, 1], "x2": b[:, 2], "y2": b[:, 3]})
+    problems = pd.DataFrame(pc)                          # rows ascend; within a row the boxes keep their object order
+    status = np.asarray(status)
+    totals = {"rows": n, "rows_ok": int((status == 0).sum()), "rows_missing": int((status == 1).sum()),
+              "rows_invalid": int((status == 2).sum()), "boxes": int(n_boxes.sum()),
+              "unmatchable_name_boxes": int(rows[:, 0].sum()), "python_cells": acc.python_cells, "nbins": acc.nbins}
+    if stats is not None:
+        stats.update(totals)
+    return BoxAudit(classes, per_class, wh, xy, acc.bpi.copy(), per_row, problems, totals)
+
+
+def audit_boxes_frame(df: pd.DataFrame, json_col: str = BBOX_COL, width_col: str = "width", height_col: str = "height",
+                      nbins: int = 16, backend=None, stats: Optional[dict] = None) -> BoxAudit:
+    """Box audit of a processed table (after the IoU filter or the label replace, before the split).  A frame without the
+    size columns has every row `missing`.  per_row["row"] / problems["row"] are positions in df."""
+    has_size = width_col in df.columns and height_col in df.columns
+    return audit_boxes_cells(df[json_col].to_numpy(), df[width_col].to_numpy() if has_size else None,
+                             df[height_col].to_numpy() if has_size else None, nbins, backend, stats,
+                             df["source"].to_numpy() if "source" in df.columns else None)
+
+
+def _audit_csv_fast(input_csv_path, json_col, nbins, backend):
+    """-> BoxAudit, or NotImplemented (the pandas route decides then)"""
+    try:
+        table = _fc.read_split(str(input_csv_path), [json_col])
+    except (OSError, ValueError, pd.errors.ParserError, UnicodeDecodeError):
+        return NotImplemented
+    if table is None or json_col not in table.heavy:
+        return NotImplemented
+    be = _audit_backend(backend)
+    col = table.heavy[json_col]
+    light = table.light
+    n = table.n_rows
+    has_size = "width" in light.columns and "height" in light.columns
+    status, W, H = _audit_sizes(light["width"].to_numpy() if has_size else None,
+                                light["height"].to_numpy() if has_size else None, n)
+    acc = _AuditTotals(nbins)
+    for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
+        s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
+        _audit_chunk(_fc_cells(col, s0, s1), status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0)
+    return _audit_result(acc, n, status, light["source"].to_numpy() if "source" in light.columns else None, None)
+
+
+def _fc_cells(col, s0, s1):
+    """rows [s0, s1) of a fastcsv.Utf8Column as an object array of str (None where the field is empty)"""
+    off = np.asarray(col.off[s0:s1 + 1], np.int64)
+    return _nj.strings_from_buffers(col.data[off[0]:max(int(off[-1]), int(off[0]) + 1)], off - off[0],
+                                    np.asarray(col.na[s0:s1]))
+
+
+def _write_audit(audit: BoxAudit, output_dir) -> dict:
+    out = Path(output_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    paths = {"classes": str(out / "box_audit_classes.csv"), "problems": str(out / "box_audit_problems.csv"),
+             "hist": str(out / "box_audit_hist.npz")}
+    audit.per_class.to_csv(paths["classes"], index=False, encoding="utf-8-sig")
+    audit.problems.to_csv(paths["problems"], index=False, encoding="utf-8-sig")
+    np.savez(paths["hist"], classes=np.asarray(audit.classes, dtype=str), hist_wh=audit.hist_wh, hist_xy=audit.hist_xy,
+             boxes_per_image=audit.boxes_per_image)
+    return paths
+
+
+def audit_boxes_csv(input_csv_path, output_dir, json_col: str = BBOX_COL, nbins: int = 16, backend=None):
+    """CSV -> box_audit_classes.csv, box_audit_problems.csv and box_audit_hist.npz (classes, hist_wh, hist_xy,
+    boxes_per_image) under output_dir, in the IoU step's conventions: read as utf-8-sig; a read failure prints 读取失败：...
+    and a missing column 错误：缺少必要列 ..., both returning None.  -> dict(totals, paths=...)"""
+    if isinstance(nbins, bool) or not isinstance(nbins, (int, np.integer)) or not 1 <= int(nbins) <= 64:
+        raise ValueError(f"nbins must be an int in 1..64, got {nbins!r}")
+    audit = NotImplemented
+    if _fc.enabled() and os.path.isfile(str(input_csv_path)):
+        audit = _audit_csv_fast(input_csv_path, json_col, int(nbins), backend)
+    if audit is NotImplemented:
+        LAST_IO_PATH["audit"] = "pandas"
+        try:
+            df = pd.read_csv(input_csv_path, encoding="utf-8-sig")
+        except Exception as e:
+            print(f"读取失败：{e}")
+            return None
+        if json_col not in df.columns:
+            print(f"错误：缺少必要列 {json_col}")
+            return None
+        audit = audit_boxes_frame(df, json_col, nbins=int(nbins), backend=backend)
+    else:
+        LAST_IO_PATH["audit"] = "native"
+    return {**audit.totals, "paths": _write_audit(audit, output_dir)}
+
+
 def generate_yolo_datasets_from_excels(
         category_excels: list,
         output_dir: str,

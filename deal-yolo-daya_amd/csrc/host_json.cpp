@@ -1053,6 +1053,9 @@ struct dyd_scan {
     std::vector<uint8_t> sel;           // labelled scan: box carries the row's label
     std::vector<uint8_t> iou_host;      // polygon scan: the cell's IoU flag needs CPython's exact int arithmetic (see dyd_scan_iou_host)
     std::vector<int32_t> box_obj, box_name;   // suppression scan: per box its index in "objects" and its cell-local name id
+    std::vector<std::string> names;           // named-box scan: the decoded name of each table-wide id ...
+    std::string name_text;                    // ... concatenated, with offsets
+    std::vector<int64_t> name_off;
     // emit output
     std::string text;
     std::vector<int64_t> text_off;
@@ -2831,8 +2834,11 @@ double coord_value(Parser &ps, Span tok) {
     return n.v;
 }
 
-// regular cells only; anything the reference treats through an exception or a non-list container throws Fail{2}
-void labelled_cell(Span cell, std::string_view label, std::vector<double> &box4, std::vector<uint8_t> &sel, int32_t &count) {
+// regular cells only; anything the reference treats through an exception or a non-list container throws Fail{2}.
+// Every box goes to sk.box(object index, decoded name, {min x, min y, max x, max y}): the YOLO step compares the name with the
+// row's label (LabelSink), the box audit numbers the names (NameSink).
+template <class Sink>
+void named_boxes_cell(Span cell, Sink &sk, int32_t &count) {
     count = 0;
     Parser ps{cell.b, cell.e};
     ps.ws();
@@ -2857,7 +2863,7 @@ void labelled_cell(Span cell, std::string_view label, std::vector<double> &box4,
             if (ps.peek() == ']') {
                 ++ps.p;
             } else {
-                while (true) {
+                for (int32_t k_obj = 0;; ++k_obj) {
                     if (ps.peek() != '{') {
                         ps.value(nullptr);                      // non-dict objects are skipped (:689)
                     } else {
@@ -2956,8 +2962,7 @@ void labelled_cell(Span cell, std::string_view label, std::vector<double> &box4,
                         }
                         if (has_name && truthy && has_box) {
                             const double v[4] = {xs.lo, ys.lo, xs.hi, ys.hi};
-                            box4.insert(box4.end(), v, v + 4);
-                            sel.push_back(std::string_view(name) == label ? 1 : 0);
+                            sk.box(k_obj, name, v);
                             ++count;
                         }
                     }
@@ -2977,9 +2982,145 @@ void labelled_cell(Span cell, std::string_view label, std::vector<double> &box4,
     if (ps.p != ps.end) ps.bad();
 }
 
+struct LabelSink {
+    std::string_view label;
+    std::vector<double> &box4;
+    std::vector<uint8_t> &sel;
+    void box(int32_t, const std::string &name, const double v[4]) {
+        box4.insert(box4.end(), v, v + 4);
+        sel.push_back(std::string_view(name) == label ? 1 : 0);
+    }
+};
+
+void labelled_cell(Span cell, std::string_view label, std::vector<double> &box4, std::vector<uint8_t> &sel, int32_t &count) {
+    LabelSink sk{label, box4, sel};
+    named_boxes_cell(cell, sk, count);
+}
+
+// box audit: per box its object index and a class id local to the thread's part (first occurrence in the part's cell order)
+struct NameSink {
+    std::vector<double> box4;
+    std::vector<int32_t> obj, name;
+    std::vector<std::string> names;
+    std::unordered_map<std::string, int32_t> ids;
+    void box(int32_t k_obj, const std::string &nm, const double v[4]) {
+        box4.insert(box4.end(), v, v + 4);
+        obj.push_back(k_obj);
+        auto it = ids.find(nm);
+        if (it == ids.end()) {
+            it = ids.emplace(nm, (int32_t)names.size()).first;
+            names.push_back(nm);
+        }
+        name.push_back(it->second);
+    }
+    void truncate(size_t nbox) {   // drop what a cell that turned out irregular emitted (its names may stay numbered: unused)
+        box4.resize(4 * nbox);
+        obj.resize(nbox);
+        name.resize(nbox);
+    }
+};
+
+int scan_named_boxes_src(const CellSrc &src, const uint8_t *missing, int64_t n_cells, int n_threads, dyd_scan **out) {
+    dyd_scan *h = new (std::nothrow) dyd_scan();
+    if (!h) return DYD_ERR_OOM;
+    h->n_cells = n_cells;
+    h->src = src;
+    try {
+        h->status.assign((size_t)n_cells, CELL_OK);
+        std::vector<int32_t> counts((size_t)n_cells, 0);
+        struct Part { NameSink sk; int64_t lo = 0, hi = 0; };
+        std::vector<Part> parts(64);
+        if (n_threads <= 0 || n_threads > 64) n_threads = default_threads();
+        const bool ok = parallel_cells_safe(n_cells, n_threads, [&](int t, int64_t lo, int64_t hi) {
+            Part &pt = parts[(size_t)t];
+            pt.lo = lo; pt.hi = hi;
+            for (int64_t i = lo; i < hi; ++i) {
+                if (missing && missing[i]) { h->status[(size_t)i] = CELL_MISSING; continue; }
+                const size_t mark = pt.sk.obj.size();
+                int32_t c = 0;
+                try {
+                    named_boxes_cell(src.get(i), pt.sk, c);
+                } catch (Fail f) {
+                    pt.sk.truncate(mark);
+                    c = 0;
+                    h->status[(size_t)i] = (f.code == 1) ? CELL_UNDECODABLE : CELL_IRREGULAR;
+                }
+                counts[(size_t)i] = c;
+            }
+        });
+        if (!ok) { delete h; return DYD_ERR_OOM; }
+        std::sort(parts.begin(), parts.end(), [](const Part &a, const Part &b) { return a.lo < b.lo; });
+        size_t tot = 0;
+        for (auto &pt : parts) tot += pt.sk.obj.size();
+        if (tot >= (size_t)1 << 31) { delete h; return DYD_ERR_RANGE; }
+        h->xy.reserve(4 * tot);
+        h->box_obj.reserve(tot);
+        h->box_name.reserve(tot);
+        // table-wide ids: the parts in cell order, each part's boxes in order -> numbered by first occurrence in the table
+        std::unordered_map<std::string, int32_t> global;
+        std::vector<int32_t> remap;
+        for (auto &pt : parts) {
+            h->xy.insert(h->xy.end(), pt.sk.box4.begin(), pt.sk.box4.end());
+            h->box_obj.insert(h->box_obj.end(), pt.sk.obj.begin(), pt.sk.obj.end());
+            remap.assign(pt.sk.names.size(), -1);
+            for (int32_t id : pt.sk.name) {
+                int32_t &g = remap[(size_t)id];
+                if (g < 0) {
+                    auto it = global.find(pt.sk.names[(size_t)id]);
+                    if (it == global.end()) {
+                        it = global.emplace(pt.sk.names[(size_t)id], (int32_t)h->names.size()).first;
+                        h->names.push_back(pt.sk.names[(size_t)id]);
+                    }
+                    g = it->second;
+                }
+                h->box_name.push_back(g);
+            }
+            pt.sk = NameSink();
+        }
+        h->name_off.assign(1, 0);
+        h->name_text.clear();
+        for (const auto &nm : h->names) {
+            h->name_text += nm;
+            h->name_off.push_back((int64_t)h->name_text.size());
+        }
+        h->cell_box_off.resize((size_t)n_cells + 1);
+        h->cell_box_off[0] = 0;
+        for (int64_t i = 0; i < n_cells; ++i) h->cell_box_off[(size_t)i + 1] = h->cell_box_off[(size_t)i] + counts[(size_t)i];
+        h->pt_off.assign(1, 0);
+    } catch (const std::bad_alloc &) {
+        delete h;
+        return DYD_ERR_OOM;
+    }
+    *out = h;
+    return DYD_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int dyd_json_scan_named_boxes(const uint8_t *text, const int64_t *cell_off, const uint8_t *missing, int64_t n_cells, int n_threads,
+                              dyd_scan **out) {
+    if (!out || n_cells < 0 || (n_cells > 0 && (!cell_off || !text))) return DYD_ERR_INVALID;
+    CellSrc src;
+    src.text = text; src.off = cell_off;
+    return scan_named_boxes_src(src, missing, n_cells, n_threads, out);
+}
+
+int dyd_json_scan_named_boxes_v(const uint8_t *const *cell_ptr, const int64_t *cell_len, const uint8_t *missing, int64_t n_cells,
+                                int n_threads, dyd_scan **out) {
+    if (!out || n_cells < 0 || (n_cells > 0 && (!cell_ptr || !cell_len))) return DYD_ERR_INVALID;
+    CellSrc src;
+    src.ptr = cell_ptr; src.len = cell_len;
+    return scan_named_boxes_src(src, missing, n_cells, n_threads, out);
+}
+
+int64_t dyd_scan_names(const dyd_scan *h, const uint8_t **text, const int64_t **off) {
+    if (!h || !text || !off) return DYD_ERR_INVALID;
+    *text = reinterpret_cast<const uint8_t *>(h->name_text.data());
+    *off = h->name_off.empty() ? nullptr : h->name_off.data();
+    return (int64_t)h->names.size();
+}
 
 // Labelled boxes for the YOLO step: per cell the (min x, min y, max x, max y) of every named object with a
 // non-empty ptList (utils.py:681-710) and whether its name equals the row's label value (processor.py:1006).

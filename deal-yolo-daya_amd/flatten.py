@@ -275,6 +275,34 @@ def suppress_cell(cell, thr, by_label):
     return json.dumps(doc, ensure_ascii=False), removed
 
 
+def audit_cell_boxes(cell) -> list:
+    """The box audit's boxes of one cell on the host, for the cells the native scanner leaves to Python (numbers, true or
+    containers as "name", string or huge-int coordinates, repeated keys ...): utils._extract_boxes_with_labels' walk
+    (reference utils.py:681-710: named objects with a non-empty ptList, first-wins min / max, the prefix kept on any
+    exception) -> [(index of the object in "objects", name, min x, min y, max x, max y)]."""
+    collected = []
+    if not isinstance(cell, str):
+        return collected
+    try:
+        for k, obj in enumerate(json.loads(cell).get("objects", [])):
+            if not isinstance(obj, dict):
+                continue
+            name = obj.get("name")
+            if not name:
+                continue
+            points = obj.get("polygon", {}).get("ptList", [])
+            if not points:
+                continue
+            dict_points = [pt for pt in points if isinstance(pt, dict)]
+            xs = [pt.get("x") for pt in dict_points if "x" in pt]
+            ys = [pt.get("y") for pt in dict_points if "y" in pt]
+            if xs and ys:
+                collected.append((k, name, min(xs), min(ys), max(xs), max(ys)))
+    except Exception:                                   # noqa: BLE001 (utils.py:708-709) keep the prefix
+        pass
+    return collected
+
+
 # ------------------------------------------------------------------------------------------
 # a1 / a2  key column -> flat bytes + offsets for K3
 # ------------------------------------------------------------------------------------------

@@ -420,6 +420,58 @@ def scan_box_objects(cells, n_threads: int = 0) -> BoxObjectScan:
     return scan_box_objects_buffers(data, off, missing, n_threads, keep)
 
 
+# ------------------------------------------------------------------------------------------ box audit
+class NamedBoxScan(_Scan):
+    """Result of scan_named_boxes: the YOLO step's boxes (utils._extract_boxes_with_labels) of the regular cells as box4
+    (min x, min y, max x, max y), per box the index of its object in "objects" (``box_object``) and a table-wide class id
+    (``box_class``, numbered by first occurrence in cell order), and ``names`` = the decoded name of each id.  Arrays are
+    copies: they outlive the handle."""
+
+    def __init__(self, handle, n_cells, keep):
+        super().__init__(handle, n_cells, keep)
+        L = _native.load_library()
+        nb = int(self.cell_box_off[-1]) if n_cells else 0
+        self.n_boxes = nb
+        self.box4 = _view(L.dyd_scan_xy(handle), np.float64, 4 * nb).reshape(-1, 4).copy()
+        self.box_object = _view(L.dyd_scan_box_object(handle), np.int32, nb).copy()
+        self.box_class = _view(L.dyd_scan_box_name(handle), np.int32, nb).copy()
+        tp, op = C.c_void_p(), C.c_void_p()
+        k = int(L.dyd_scan_names(handle, C.byref(tp), C.byref(op)))
+        if k:
+            off = _view(op.value, np.int64, k + 1)
+            text = bytes(_view(tp.value, np.uint8, int(off[-1])) if off[-1] else b"")
+            self.names = [text[off[i]:off[i + 1]].decode("utf-8") for i in range(k)]
+        else:
+            self.names = []
+
+
+def scan_named_boxes_buffers(data, off, missing, n_threads: int = 0, keep=None) -> NamedBoxScan:
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    missing = np.ascontiguousarray(missing, dtype=np.uint8)
+    L = _native.load_library()
+    h = C.c_void_p()
+    _native.check(L.dyd_json_scan_named_boxes(data.ctypes.data, off.ctypes.data, missing.ctypes.data, len(off) - 1,
+                                              n_threads, C.byref(h)), "dyd_json_scan_named_boxes")
+    return NamedBoxScan(h, len(off) - 1, (keep, data, off, missing))
+
+
+def scan_named_boxes(cells, n_threads: int = 0) -> NamedBoxScan:
+    """cells -> NamedBoxScan.  With the CPython helper the scanner reads the str objects' own UTF-8 buffers (no copy).
+    Raises UnicodeEncodeError for a cell holding a lone surrogate when the cells have to be encoded."""
+    from . import pycells
+
+    L = _native.load_library()
+    h = C.c_void_p()
+    if pycells.available():
+        v = pycells.CellViews(cells.to_numpy() if hasattr(cells, "to_numpy") else cells)
+        _native.check(L.dyd_json_scan_named_boxes_v(v.ptr.ctypes.data, v.len.ctypes.data, v.missing.ctypes.data, len(v),
+                                                    n_threads, C.byref(h)), "dyd_json_scan_named_boxes_v")
+        return NamedBoxScan(h, len(v), v)
+    data, off, missing, keep = cells_to_buffers(cells)
+    return scan_named_boxes_buffers(data, off, missing, n_threads, keep)
+
+
 # ------------------------------------------------------------------------------------------ split step
 SP_OK, SP_EMPTY, SP_UNDECODABLE, SP_NOT_A_LIST, SP_NO_OBJECTS, SP_IRREGULAR = 0, 1, 2, 3, 4, 5
 EV_NO_NAME, EV_UNDEFINED, EV_NOTHING_CLASSIFIED = 1, 2, 3

@@ -123,6 +123,46 @@ int dyd_suppress_boxes_dev(const double *box4, const int32_t *row_off, int64_t n
                            const int32_t *name_or_null, double thr, uint8_t *out_keep,
                            int32_t *out_partner, void *stream);
 
+/* ---- K10: box audit — per-class box statistics of the YOLO step's boxes -------------
+ * Per box (the labelled boxes of utils.py:681-710 with min/max corners, and the row's
+ * width / height as processor.py:1013-1014 reads them): one category, tested in order
+ *   0 no_size     the row's size_status is not 0 (1: `not w or not h`, :1023-1025; 2: not a
+ *                 finite positive number)
+ *   1 bad_coords  a corner is not finite (the caller encodes non-numbers as NaN)
+ *   2 degenerate  bw = max(x2 - x1, 0.0) <= 0 or bh = max(y2 - y1, 0.0) <= 0 (:1052-1053)
+ *   3 writable    everything else: out_of_image = x1 < 0 or y1 < 0 or x2 > W or y2 > H;
+ *                 area bw * bh: small < 1024 <= medium < 9216 <= large; the line of :1056-1058
+ *                 binned as bin(v) = min(max(floor(v * nbins), 0), nbins - 1) (in double) of
+ *                 xc = (x1 + x2) / 2 / W, yc = (y1 + y2) / 2 / H, wn = bw / W, hn = bh / H.
+ * Arithmetic in IEEE f64 without contraction.  A box whose class id is -1 (its name is no
+ * str: it never equals a row label, :1006) gets only the unmatchable flag and row count.
+ * box4       : per box (x1, y1, x2, y2) f64, 16-byte aligned                    [4*B]
+ * row_off    : box offsets per image row                                       [n_rows+1]
+ * cls        : class id per box, -1 or 0..n_classes-1 (_dev: others count as -1) [B]
+ * width, height, size_status: per row f64, f64, u8 (0 ok, 1 missing, 2 invalid)  [n_rows]
+ * n_classes >= 0, nbins in 1..64
+ * out_flag   : bits 0-1 category, bit 2 out_of_image, bits 3-4 area bucket
+ *              (0 small, 1 medium, 2 large; writable only), 0x80 = class id -1   [B]
+ * out_row_counts: per row unmatchable, no_size, bad_coords, degenerate, writable,
+ *              out_of_image                                                    [6*n_rows] i32
+ * out_class_counts: per class no_size, bad_coords, degenerate, writable,
+ *              out_of_image, small, medium, large, images (rows holding a box
+ *              of the class)                                                   [9*n_classes] i64
+ * out_hist_wh, out_hist_xy: [c][bin(wn)][bin(hn)], [c][bin(xc)][bin(yc)] over
+ *              writable boxes                                      [n_classes*nbins*nbins] i64
+ * out_boxes_per_image: rows with k boxes (all boxes), k = 256 takes >= 256       [257] i64 */
+int dyd_box_audit(const double *box4, const int32_t *row_off, int64_t n_rows, const int32_t *cls,
+                  const double *width, const double *height, const uint8_t *size_status,
+                  int32_t n_classes, int32_t nbins, uint8_t *out_flag, int32_t *out_row_counts,
+                  int64_t *out_class_counts, int64_t *out_hist_wh, int64_t *out_hist_xy,
+                  int64_t *out_boxes_per_image);
+/* device pointers; n_boxes = row_off[n_rows]; every output is written (the sums are zeroed first) */
+int dyd_box_audit_dev(const double *box4, const int32_t *row_off, int64_t n_rows, int64_t n_boxes,
+                      const int32_t *cls, const double *width, const double *height,
+                      const uint8_t *size_status, int32_t n_classes, int32_t nbins, uint8_t *out_flag,
+                      int32_t *out_row_counts, int64_t *out_class_counts, int64_t *out_hist_wh,
+                      int64_t *out_hist_xy, int64_t *out_boxes_per_image, void *stream);
+
 /* ---- K1+K2 fused: poly -> bbox -> IoU flag in one pass ---------------------------
  * One launch that produces K1's outputs and K2's flag for rows whose boxes all come
  * from K1 (processing.py:580-598 runs the two steps back to back on the same rows).
@@ -332,6 +372,16 @@ int dyd_json_scan_polygons_v(const uint8_t *const *cell_ptr, const int64_t *cell
 int dyd_json_scan_labelled(const uint8_t *text, const int64_t *cell_off, const uint8_t *missing, int64_t n_cells,
                            const uint8_t *label_text, const int64_t *label_off, int n_threads, dyd_scan **out);
 const uint8_t *dyd_scan_sel(const dyd_scan *scan);             /* [n_boxes] (labelled scan only) */
+/* Box audit: the labelled scan's walk (same boxes, same irregular cells) without a row label; per box
+ * dyd_scan_box_object = index of its object in "objects" and dyd_scan_box_name = a table-wide class id, numbered
+ * by first occurrence in cell order whatever the thread count.  The decoded names (UTF-8) of the ids are
+ * dyd_scan_names: n_names, then bytes and offsets [n_names+1] owned by the handle.  Numbers, true and containers
+ * as "name" make the cell irregular; the _v form takes one (pointer, length) per cell. */
+int dyd_json_scan_named_boxes(const uint8_t *text, const int64_t *cell_off, const uint8_t *missing,
+                              int64_t n_cells, int n_threads, dyd_scan **out);
+int dyd_json_scan_named_boxes_v(const uint8_t *const *cell_ptr, const int64_t *cell_len, const uint8_t *missing,
+                                int64_t n_cells, int n_threads, dyd_scan **out);
+int64_t dyd_scan_names(const dyd_scan *scan, const uint8_t **text, const int64_t **off);
 /* The replace step and the IoU step in ONE native pass (processor.py:262-281 then :341-376; ui/pages/processing.py:580-598 runs them
  * back to back): cells as flat text + offsets, or as one (pointer, length) pair per cell (text == cell_off == NULL).  Every worker
  * thread holds one staging slot (dyd_stage_acquire) and takes its share of the cells through scan -> dyd_bbox_iou_fused_staged -> emit

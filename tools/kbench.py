@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmarks on one MI355X (device-resident inputs, HIP-event timing,
 interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant.
 
-    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression against K2 alone)
+    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, each against K2 alone)
 """
 import argparse
 import json
@@ -155,6 +155,50 @@ def main():
         legs["k9_suppress"][1]()
         torch.cuda.synchronize()
         print(json.dumps({"kernel": "k9_suppress", "dropped": int((keep == 0).sum().item())}), flush=True)
+
+    if "k10" in only:
+        # K10 (box audit) against K2 alone on the same device buffers, interleaved rounds: 20 classes at nb = 16 (LDS histograms)
+        # and nb = 64 (global), 5,000 classes at nb = 16 (global class counters and histograms)
+        ck(L.dyd_bbox_minmax_dev(xy.data_ptr(), pt_off.data_ptr(), B, P, out_box.data_ptr(), out_arg.data_ptr(), sp), "k1")
+        g = torch.Generator(device=dev).manual_seed(10)
+        cls20 = (labels.to(torch.int64) % 20).to(torch.int32).contiguous()
+        cls5k = torch.randint(0, 5000, (B,), generator=g, device=dev, dtype=torch.int32)
+        wdt = torch.full((N,), 1280.0, dtype=torch.float64, device=dev)
+        hgt = torch.full((N,), 720.0, dtype=torch.float64, device=dev)
+        st = torch.zeros(N, dtype=torch.uint8, device=dev)
+        flag = torch.empty(B, dtype=torch.uint8, device=dev)
+        rowc = torch.empty((N, 6), dtype=torch.int32, device=dev)
+        bpi = torch.empty(257, dtype=torch.int64, device=dev)
+        outs = {}
+
+        def k10(cls, nc, nb):
+            if (nc, nb) not in outs:
+                outs[(nc, nb)] = (torch.empty((nc, 9), dtype=torch.int64, device=dev),
+                                  torch.empty(nc * nb * nb, dtype=torch.int64, device=dev),
+                                  torch.empty(nc * nb * nb, dtype=torch.int64, device=dev))
+            cc, wh, hxy = outs[(nc, nb)]
+            return lambda: ck(L.dyd_box_audit_dev(out_box.data_ptr(), box_off.data_ptr(), N, B, cls.data_ptr(), wdt.data_ptr(),
+                                                  hgt.data_ptr(), st.data_ptr(), nc, nb, flag.data_ptr(), rowc.data_ptr(),
+                                                  cc.data_ptr(), wh.data_ptr(), hxy.data_ptr(), bpi.data_ptr(), sp), "k10")
+
+        audit_bytes = 32 * B + 4 * B + B + 4 * (N + 1) + 17 * N + 24 * N
+        legs = {"k2 auto (dyd_iou_any_ge_dev)": (32 * B + 4 * (N + 1) + N, lambda: ck(L.dyd_iou_any_ge_dev(
+                    out_box.data_ptr(), box_off.data_ptr(), N, B, 2, 0.98, out_high.data_ptr(), None, sp), "k2")),
+                "k10_audit c20 nb16": (audit_bytes, k10(cls20, 20, 16)),
+                "k10_audit c20 nb64": (audit_bytes, k10(cls20, 20, 64)),
+                "k10_audit c5000 nb16": (audit_bytes, k10(cls5k, 5000, 16))}
+        res = {}
+        for rnd in range(2):
+            for nm, (_, fn) in legs.items():
+                res.setdefault(nm, []).append(timeit(fn))
+        for nm, (nbytes, _) in legs.items():
+            med = float(np.median([r[0] for r in res[nm]])); mn = min(r[1] for r in res[nm])
+            report(nm, nbytes, med, mn, rows_per_s=round(N / med * 1e3))
+        legs["k10_audit c20 nb16"][1]()
+        torch.cuda.synchronize()
+        cc = outs[(20, 16)][0]
+        print(json.dumps({"kernel": "k10_audit", "writable": int(cc[:, 3].sum().item()), "boxes": int(cc[:, :4].sum().item()),
+                          "images": int(cc[:, 8].sum().item())}), flush=True)
 
     if "k12" in only:
         k12_bytes = 16 * P + 4 * (B + 1) + 48 * B + 4 * (N + 1) + N
