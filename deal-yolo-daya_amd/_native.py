@@ -72,6 +72,13 @@ SIGNATURES = {
     "dyd_box_audit_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
+    "dyd_repair_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                   C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dyd_repair_boxes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "dyd_json_emit_repaired": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_void_p)]),
     "dyd_json_scan_named_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "dyd_json_scan_named_boxes_v": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "dyd_scan_names": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
@@ -361,6 +368,40 @@ def box_audit(box4: np.ndarray, row_off: np.ndarray, cls: np.ndarray, width: np.
     check(lib().dyd_box_audit(_ptr(box4), _ptr(row_off), n, _ptr(cls), _ptr(width), _ptr(height), _ptr(size_status), n_classes,
                               nbins, _ptr(flag), _ptr(rows), _ptr(cc), _ptr(wh), _ptr(xy), _ptr(bpi)), "dyd_box_audit")
     return flag, rows, cc, wh, xy, bpi
+
+
+REPAIR_ACTIONS = 8   # action codes of K11: keep, clip, no_size, bad_coords, degenerate, outside, low_visibility, small
+
+
+def repair_boxes(box4: np.ndarray, row_off: np.ndarray, cls: np.ndarray, width: np.ndarray, height: np.ndarray,
+                 size_status: np.ndarray, n_classes: int, min_visibility: float = 0.0, min_size: float = 0.0):
+    """K11 over host arrays -> (action [B] u8, box4 [B,4] f64, row_counts [N,8] i32, class_counts [C,8] i64).  See
+    include/dyd.h for the action codes and the rules."""
+    box4 = np.ascontiguousarray(box4, dtype=np.float64).reshape(-1)
+    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
+    n = len(row_off) - 1
+    if n < 0 or row_off[0] != 0 or 4 * int(row_off[-1]) != box4.size:
+        raise ValueError("row_off must start at 0 and end at the number of boxes")
+    min_visibility, min_size, n_classes = float(min_visibility), float(min_size), int(n_classes)
+    if not 0.0 <= min_visibility <= 1.0:
+        raise ValueError(f"min_visibility must lie in [0, 1], got {min_visibility}")
+    if not (np.isfinite(min_size) and min_size >= 0.0):
+        raise ValueError(f"min_size must be finite and >= 0, got {min_size}")
+    nb = int(row_off[-1])
+    cls = np.ascontiguousarray(cls, dtype=np.int32)
+    width = np.ascontiguousarray(width, dtype=np.float64)
+    height = np.ascontiguousarray(height, dtype=np.float64)
+    size_status = np.ascontiguousarray(size_status, dtype=np.uint8)
+    if cls.size != nb or width.size != n or height.size != n or size_status.size != n:
+        raise ValueError("cls must hold one id per box; width, height and size_status one value per row")
+    action = np.zeros(nb, np.uint8)
+    out_box = np.zeros((nb, 4), np.float64)
+    rows = np.zeros((n, REPAIR_ACTIONS), np.int32)
+    cc = np.zeros((n_classes, REPAIR_ACTIONS), np.int64)
+    check(lib().dyd_repair_boxes(_ptr(box4), _ptr(row_off), n, _ptr(cls), _ptr(width), _ptr(height), _ptr(size_status),
+                                 n_classes, min_visibility, min_size, _ptr(action), _ptr(out_box), _ptr(rows), _ptr(cc)),
+          "dyd_repair_boxes")
+    return action, out_box, rows, cc
 
 
 def bbox_iou_fused(xy: np.ndarray, pt_off: np.ndarray, box_off: np.ndarray, min_boxes: int, thr: float,

@@ -2364,6 +2364,289 @@ def audit_boxes_csv(input_csv_path, output_dir, json_col: str = BBOX_COL, nbins:
     return {**audit.totals, "paths": _write_audit(audit, output_dir)}
 
 
+# =============================================================================== f6  box repair
+# The fix the audit points at, applied before any label file is written: clip each box that leaves the image to the image, drop
+# the boxes no trainer can use, report per class what was done.  Boxes are the audit's (the walk of utils._extract_boxes_with_labels,
+# reference utils.py:681-710, with the index of their object) with the row's size as _audit_sizes gives it; K11
+# (csrc/k11_repair.hip, rules in include/dyd.h and DESIGN §5k) decides every box, in IEEE f64.  A cell is re-spelled only when a
+# box of it is removed or clipped: json.dumps(doc, ensure_ascii=False) with the removed objects left out and each clipped
+# object's polygon.ptList replaced by [{"x": x1', "y": y1'}, {"x": x2', "y": y2'}] (the replace step's shape, reference
+# processor.py:260).  Every other cell is returned as the same object.  Native scan -> K11 -> native emit
+# (NamedBoxScan.emit_repaired); the cells the scanner leaves to CPython are scanned by flatten.audit_cell_boxes, spliced into
+# the same K11 launch and re-spelled by flatten.repair_cell.
+REPAIR_ACTIONS = ("keep", "clip", "no_size", "bad_coords", "degenerate", "outside", "low_visibility", "small")   # K11 codes 0..7
+_REPAIR_CHANGE_COLS = ("row", "object", "name", "action", "x1", "y1", "x2", "y2", "nx1", "ny1", "nx2", "ny2")
+
+
+def _repair_backend(backend):
+    be = _backend(backend)
+    if not hasattr(be, "repair_boxes"):
+        raise TypeError("backend lacks ['repair_boxes']")
+    return be
+
+
+def _repair_params(min_visibility, min_size) -> tuple:
+    """-> (min_visibility, min_size) as floats; ValueError unless min_visibility lies in [0, 1] and min_size is finite >= 0"""
+    vals = []
+    for nm, v in (("min_visibility", min_visibility), ("min_size", min_size)):
+        if isinstance(v, bool) or not isinstance(v, _NUMBER_TYPES):
+            raise ValueError(f"{nm} must be a number, got {v!r}")
+        vals.append(float(v))
+    if not 0.0 <= vals[0] <= 1.0:
+        raise ValueError(f"min_visibility must lie in [0, 1], got {min_visibility!r}")
+    if not (np.isfinite(vals[1]) and vals[1] >= 0.0):
+        raise ValueError(f"min_size must be finite and >= 0, got {min_size!r}")
+    return vals[0], vals[1]
+
+
+class _RepairTotals:
+    """class-keyed action counts over the chunks, changes per chunk, totals"""
+
+    def __init__(self):
+        self.index = {}
+        self.cc = np.zeros((0, len(REPAIR_ACTIONS)), np.int64)
+        self.changes = []
+        self.rows_changed = self.boxes = self.clipped = self.removed = self.python_cells = 0
+
+    def add_classes(self, names, cc):
+        g = np.asarray([self.index.setdefault(nm, len(self.index)) for nm in names], np.int64)
+        grow = len(self.index) - len(self.cc)
+        if grow:
+            self.cc = np.concatenate([self.cc, np.zeros((grow, self.cc.shape[1]), np.int64)])
+        if len(g):
+            self.cc[g] += cc
+
+
+def _repair_chunk(cells, status, W, H, be, acc: _RepairTotals, start: int, min_vis: float, min_size: float) -> tuple:
+    """one chunk of rows: scan (native, CPython for irregular cells) -> K11 -> emit -> (rows in the chunk, their new texts)
+    as int64 and object arrays; the class counts and the changed boxes go to acc"""
+    n = len(cells)
+    try:
+        scan = _nj.scan_named_boxes(cells) if _nj.enabled() else None
+    except UnicodeEncodeError:                           # a lone surrogate: every cell of the chunk through CPython
+        scan = None
+    try:
+        if scan is not None:
+            nat_off = scan.cell_box_off.astype(np.int64)
+            counts = np.diff(nat_off)
+            irregular = np.flatnonzero(scan.status == _nj.IRREGULAR).tolist()
+            names = list(scan.names)
+            box4, obj, cls = scan.box4, scan.box_object, scan.box_class
+        else:
+            nat_off = np.zeros(n + 1, np.int64)
+            counts = np.zeros(n, np.int64)
+            irregular = list(range(n))
+            names, box4, obj, cls = [], np.zeros((0, 4)), np.zeros(0, np.int32), np.zeros(0, np.int32)
+        acc.python_cells += len(irregular)
+        py = {}
+        for i in irregular:
+            boxes = _fl.audit_cell_boxes(cells[i])
+            if boxes:
+                py[i] = boxes
+                counts[i] = len(boxes)
+        row_off = np.zeros(n + 1, np.int64)
+        np.cumsum(counts, out=row_off[1:])
+        nb = int(row_off[-1])
+        if nb >= (1 << 31):
+            raise ValueError("a chunk holds 2^31 boxes or more")
+        odd_names = {}                                   # box -> its name when that is no str (class id -1)
+        dest = None
+        if py:                                           # splice the CPython boxes in at their rows
+            nat_counts = np.diff(nat_off)
+            dest = np.repeat(row_off[:-1] - nat_off[:-1], nat_counts) + np.arange(len(obj), dtype=np.int64)
+            b4, ob, cl = np.empty((nb, 4)), np.empty(nb, np.int32), np.empty(nb, np.int32)
+            b4[dest], ob[dest], cl[dest] = box4, obj, cls
+            ids = {nm: k for k, nm in enumerate(names)}
+            for i, boxes in py.items():
+                p = int(row_off[i])
+                for k, (o, nm, *xy) in enumerate(boxes):
+                    b4[p + k] = [_audit_number(v) for v in xy]
+                    ob[p + k] = o
+                    if isinstance(nm, str):
+                        cl[p + k] = ids.setdefault(nm, len(ids))
+                    else:
+                        cl[p + k] = -1
+                        odd_names[p + k] = nm
+            names = list(ids)
+            box4, obj, cls = b4, ob, cl
+        action, obox, _rows, cc = be.repair_boxes(box4, row_off.astype(np.int32), cls, W, H, status, len(names), min_vis,
+                                                  min_size)
+        acc.add_classes(names, np.asarray(cc, np.int64).reshape(len(names), len(REPAIR_ACTIONS)))
+        code = np.asarray(action, np.uint8) & 7
+        obox = np.asarray(obox, np.float64).reshape(-1, 4)
+        idx, strs, redo = np.zeros(0, np.int64), np.zeros(0, object), []
+        if scan is not None and scan.n_boxes and ((code == 1) | (code >= 3)).any():
+            nat = slice(None) if dest is None else dest
+            changed, strs = scan.emit_repaired(code[nat], obox[nat])
+            idx = np.flatnonzero(changed == 1)
+            redo = np.flatnonzero(changed == 2).tolist()
+    finally:
+        if scan is not None:
+            scan.close()
+    touched = (code == 1) | (code >= 3)
+    py_idx, py_strs = [], []
+    for i in redo + sorted(py):                          # decided by K11 above, re-spelled by CPython
+        b0, b1 = int(row_off[i]), int(row_off[i + 1])
+        if touched[b0:b1].any():
+            py_idx.append(i)
+            py_strs.append(_fl.repair_cell(cells[i], {int(obj[b]): (tuple(obox[b]) if code[b] == 1 else None)
+                                                      for b in range(b0, b1) if touched[b]}))
+    if py_idx:
+        idx = np.concatenate([idx, np.asarray(py_idx, np.int64)])
+        strs = np.concatenate([np.asarray(strs, object), np.fromiter(py_strs, object, len(py_strs))])
+    acc.boxes += nb
+    acc.rows_changed += len(idx)
+    sel = np.flatnonzero(touched)
+    if len(sel):
+        sc = code[sel]
+        acc.clipped += int((sc == 1).sum())
+        acc.removed += int((sc != 1).sum())
+        name_arr = np.asarray(names + [None], object)    # class id -1 -> the trailing None, then the odd names
+        nm = name_arr[np.asarray(cls, np.int64)[sel]]
+        if odd_names:
+            pos = np.searchsorted(sel, np.fromiter(odd_names, np.int64, len(odd_names)))
+            for p, b in zip(pos.tolist(), odd_names):
+                if p < len(sel) and sel[p] == b:
+                    nm[p] = odd_names[b]
+        new = np.where((sc == 1)[:, None], obox[sel], np.nan)
+        acc.changes.append((start + np.searchsorted(row_off, sel, side="right") - 1, np.asarray(obj, np.int64)[sel], nm,
+                            np.asarray(REPAIR_ACTIONS, object)[sc], np.asarray(box4, np.float64).reshape(-1, 4)[sel], new))
+    return idx, strs
+
+
+def _repair_result(acc: _RepairTotals, n: int, status, sources) -> tuple:
+    """-> (changes frame, per_class frame, totals)"""
+    if acc.changes:
+        r, o, nm, act, b, nb4 = (np.concatenate([c[k] for c in acc.changes]) for k in range(6))
+    else:
+        r, o, nm, act, b, nb4 = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, object), np.zeros(0, object),
+                                 np.zeros((0, 4)), np.zeros((0, 4)))
+    ch = {}
+    if sources is not None:
+        ch["source"] = np.asarray(sources, object)[r] if len(r) else np.zeros(0, object)
+    ch.update({"row": r, "object": o, "name": nm, "action": act, "x1": b[:, 0], "y1": b[:, 1], "x2": b[:, 2], "y2": b[:, 3],
+               "nx1": nb4[:, 0], "ny1": nb4[:, 1], "nx2": nb4[:, 2], "ny2": nb4[:, 3]})
+    changes = pd.DataFrame(ch)                           # rows ascend; within a row the boxes keep their object order
+    classes = sorted(acc.index)
+    cc = acc.cc[np.asarray([acc.index[c] for c in classes], np.int64)] if classes else np.zeros((0, len(REPAIR_ACTIONS)), np.int64)
+    per_class = pd.DataFrame({"class": pd.Series(classes, dtype=object), "boxes": cc.sum(axis=1),
+                              **{k: cc[:, j] for j, k in enumerate(REPAIR_ACTIONS)}})
+    totals = {"rows": n, "rows_changed": acc.rows_changed, "boxes": acc.boxes, "boxes_clipped": acc.clipped,
+              "boxes_removed": acc.removed, "rows_no_size": int((np.asarray(status) != 0).sum()),
+              "python_cells": acc.python_cells}
+    return changes, per_class, totals
+
+
+def repair_boxes_cells(cells, widths, heights, min_visibility: float = 0.0, min_size: float = 0.0, backend=None,
+                       stats: Optional[dict] = None, sources=None) -> tuple:
+    """Box repair of the annotation cells of a table (see the section comment; widths / heights are the row's image size as the
+    YOLO step reads it, None for a table without the columns).  -> (cells with only the changed ones replaced, changes frame,
+    per_class frame).  ``changes``: [source,] row, object, name, action, x1, y1, x2, y2, nx1, ny1, nx2, ny2 per clipped or
+    removed box (n* = the clipped corners, NaN for a removed box); ``per_class``: class, boxes and one count per action."""
+    out, changes, per_class = _repair_cells_array(cells, widths, heights, min_visibility, min_size, backend, stats, sources)
+    return out.tolist(), changes, per_class
+
+
+def _repair_cells_array(cells, widths, heights, min_visibility, min_size, backend, stats, sources) -> tuple:
+    """repair_boxes_cells with the cells as an object array"""
+    min_vis, min_size = _repair_params(min_visibility, min_size)
+    be = _repair_backend(backend)
+    cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
+    n = len(cells)
+    if (widths is None) != (heights is None) or (widths is not None and (len(widths) != n or len(heights) != n)):
+        raise ValueError("widths and heights must both be given with one value per cell, or both be None")
+    status, W, H = _audit_sizes(widths, heights, n)
+    out = np.fromiter(cells, object, n)                  # the same objects; only the changed rows are replaced
+    acc = _RepairTotals()
+    for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
+        s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
+        idx, strs = _repair_chunk(cells[s0:s1], status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, min_vis, min_size)
+        out[s0 + idx] = strs
+    changes, per_class, totals = _repair_result(acc, n, status, sources)
+    if stats is not None:
+        stats.update(totals)
+    return out, changes, per_class
+
+
+def repair_boxes_frame(df: pd.DataFrame, json_col: str = BBOX_COL, width_col: str = "width", height_col: str = "height",
+                       min_visibility: float = 0.0, min_size: float = 0.0, backend=None, stats: Optional[dict] = None) -> tuple:
+    """Box repair of a processed table (after the IoU filter / suppression, before the label replace and the split) ->
+    (copy of df in which only json_col differs, changes, per_class).  A frame without the size columns has every row
+    `no_size`: nothing changes.  changes["row"] is the position in df."""
+    has_size = width_col in df.columns and height_col in df.columns
+    cells, changes, per_class = _repair_cells_array(df[json_col].to_numpy(), df[width_col].to_numpy() if has_size else None,
+                                                    df[height_col].to_numpy() if has_size else None, min_visibility, min_size,
+                                                    backend, stats, df["source"].to_numpy() if "source" in df.columns else None)
+    out = df.copy()
+    if len(changes):
+        out[json_col] = pd.Series(cells, index=out.index, dtype=object)
+    return out, changes, per_class
+
+
+def _repair_csv_fast(input_csv_path, output_csv_path, json_col, min_vis, min_size, backend):
+    """-> (changes, per_class, totals), or NotImplemented (nothing written then; the pandas route decides)"""
+    try:
+        table = _fc.read_split(str(input_csv_path), [json_col])
+    except (OSError, ValueError, pd.errors.ParserError, UnicodeDecodeError):
+        return NotImplemented
+    if table is None or json_col not in table.heavy:
+        return NotImplemented
+    be = _repair_backend(backend)
+    col = table.heavy[json_col]
+    light = table.light
+    n = table.n_rows
+    has_size = "width" in light.columns and "height" in light.columns
+    status, W, H = _audit_sizes(light["width"].to_numpy() if has_size else None,
+                                light["height"].to_numpy() if has_size else None, n)
+    acc = _RepairTotals()
+    texts = {}
+    for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
+        s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
+        idx, strs = _repair_chunk(_fc_cells(col, s0, s1), status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, min_vis, min_size)
+        texts.update(zip((s0 + idx).tolist(), strs))
+    new_col = _splice_column(col, texts)
+    columns = [new_col if nm == json_col else (table.heavy[nm] if nm in table.heavy else light[nm]) for nm in table.names]
+    Path(output_csv_path).parent.mkdir(parents=True, exist_ok=True)
+    if not _fc.write_table(str(output_csv_path), table.names, columns, n):
+        return NotImplemented
+    return _repair_result(acc, n, status, light["source"].to_numpy() if "source" in light.columns else None)
+
+
+def repair_boxes_csv(input_csv_path, output_csv_path="repaired_boxes.csv", changes_csv=None, classes_csv=None,
+                     json_col: str = BBOX_COL, min_visibility: float = 0.0, min_size: float = 0.0, backend=None):
+    """CSV -> CSV twin of repair_boxes_frame, in the IoU step's conventions: read as utf-8-sig; a read failure prints
+    读取失败：... and a missing column 错误：缺少必要列 ..., both returning None.  The output holds the input's rows with json_col
+    rewritten; `changes_csv` / `classes_csv` (optional) receive the two frames.  -> {"rows", "rows_changed", "boxes",
+    "boxes_clipped", "boxes_removed", "rows_no_size", "python_cells", "output", "changes_output", "classes_output"}"""
+    min_vis, min_size = _repair_params(min_visibility, min_size)
+    res = NotImplemented
+    if _fc.enabled() and os.path.isfile(str(input_csv_path)):
+        res = _repair_csv_fast(input_csv_path, output_csv_path, json_col, min_vis, min_size, backend)
+    if res is NotImplemented:
+        LAST_IO_PATH["repair"] = "pandas"
+        try:
+            df = pd.read_csv(input_csv_path, encoding="utf-8-sig")
+        except Exception as e:
+            print(f"读取失败：{e}")
+            return None
+        if json_col not in df.columns:
+            print(f"错误：缺少必要列 {json_col}")
+            return None
+        totals = {}
+        out, changes, per_class = repair_boxes_frame(df, json_col, min_visibility=min_vis, min_size=min_size,
+                                                     backend=backend, stats=totals)
+        Path(output_csv_path).parent.mkdir(parents=True, exist_ok=True)
+        out.to_csv(output_csv_path, index=False, encoding="utf-8-sig")
+    else:
+        LAST_IO_PATH["repair"] = "native"
+        changes, per_class, totals = res
+    for path, frame in ((changes_csv, changes), (classes_csv, per_class)):
+        if path is not None:
+            Path(path).parent.mkdir(parents=True, exist_ok=True)
+            frame.to_csv(path, index=False, encoding="utf-8-sig")
+    return {**totals, "output": output_csv_path, "changes_output": changes_csv, "classes_output": classes_csv}
+
+
 def generate_yolo_datasets_from_excels(
         category_excels: list,
         output_dir: str,

@@ -1775,6 +1775,52 @@ int scan_box_objects_src(const CellSrc &src, const uint8_t *missing, int64_t n_c
     return DYD_OK;
 }
 
+// The changed cells' documents, re-spelled side by side: cell_fn(i, buf, scratch) appends cell i's text and returns true, or
+// returns false (unchanged, nothing written); a Fail it throws leaves the cell to the caller (out_changed 2).  The texts of the
+// threads' ranges are joined in cell order.
+template <class F>
+int emit_changed_cells(dyd_scan *h, int n_threads, uint8_t *out_changed, const uint8_t **out_text, const int64_t **out_off, F cell_fn) {
+    const int64_t n = h->n_cells;
+    try {
+        std::vector<std::string> texts(64);
+        std::vector<int64_t> lens((size_t)n, 0);
+        struct Range { int64_t lo = 0, hi = 0; };
+        std::vector<Range> ranges(64);
+        if (n_threads <= 0 || n_threads > 64) n_threads = default_threads();
+        const bool ok = parallel_cells_safe(n, n_threads, [&](int t, int64_t lo, int64_t hi) {
+            ranges[(size_t)t] = Range{lo, hi};
+            std::string &buf = texts[(size_t)t];
+            std::vector<uint8_t> scratch;
+            for (int64_t i = lo; i < hi; ++i) {
+                out_changed[i] = 0;
+                const size_t mark = buf.size();
+                try {
+                    if (!cell_fn(i, buf, scratch)) continue;
+                    out_changed[i] = 1;
+                } catch (Fail) {
+                    buf.resize(mark);
+                    out_changed[i] = 2;   // the Python path re-spells this cell
+                }
+                lens[(size_t)i] = (int64_t)(buf.size() - mark);
+            }
+        });
+        if (!ok) return DYD_ERR_OOM;
+        h->text_off.assign((size_t)n + 1, 0);
+        for (int64_t i = 0; i < n; ++i) h->text_off[(size_t)i + 1] = h->text_off[(size_t)i] + lens[(size_t)i];
+        h->text.clear();
+        h->text.reserve((size_t)h->text_off[(size_t)n]);
+        std::vector<size_t> order;
+        for (size_t t = 0; t < ranges.size(); ++t) if (ranges[t].hi > ranges[t].lo) order.push_back(t);
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return ranges[a].lo < ranges[b].lo; });
+        for (size_t t : order) h->text += texts[t];
+    } catch (const std::bad_alloc &) {
+        return DYD_ERR_OOM;
+    }
+    *out_text = reinterpret_cast<const uint8_t *>(h->text.data());
+    *out_off = h->text_off.data();
+    return DYD_OK;
+}
+
 // the whole document of one cell with the objects whose drop_obj[k] is set left out ("objects" is a list: the cell had boxes)
 void emit_dropping_cell(Span cell, const std::vector<uint8_t> &drop_obj, std::string &out) {
     Parser ps{cell.b, cell.e};
@@ -1824,6 +1870,142 @@ void emit_dropping_cell(Span cell, const std::vector<uint8_t> &drop_obj, std::st
     out += '}';
 }
 
+// box repair: K11's action code (bits 0-2) -> what happens to the box's object
+enum RepairMode : uint8_t { REPAIR_KEEP = 0, REPAIR_CLIP = 1, REPAIR_DROP = 2 };
+inline RepairMode repair_mode(uint8_t action) {
+    const int a = action & 7;
+    return a == 1 ? REPAIR_CLIP : a >= 3 ? REPAIR_DROP : REPAIR_KEEP;
+}
+
+// one "objects" element (p at '{') with polygon.ptList replaced by the clipped box's two corners, in key order
+void emit_clipped_object(Parser &ps, const double *box, std::string &out) {
+    ++ps.p;
+    out += '{';
+    KeySet ks;
+    bool first = true;
+    if (ps.peek() == '}') { ++ps.p; out += '}'; return; }
+    while (true) {
+        ps.ws();
+        const Span k = ps.string_token();
+        ks.add(ps, k);
+        if (!first) out += ", ";
+        first = false;
+        ps.emit_string(out, k);
+        out += ": ";
+        ps.ws();
+        if (ps.p >= ps.end || *ps.p != ':') ps.bad();
+        ++ps.p;
+        if (Parser::span_is(k, "polygon") && ps.peek() == '{') {
+            ++ps.p;
+            out += '{';
+            KeySet pks;
+            bool pfirst = true;
+            if (ps.peek() == '}') {
+                ++ps.p;
+            } else {
+                while (true) {
+                    ps.ws();
+                    const Span pk = ps.string_token();
+                    pks.add(ps, pk);
+                    if (!pfirst) out += ", ";
+                    pfirst = false;
+                    ps.emit_string(out, pk);
+                    out += ": ";
+                    ps.ws();
+                    if (ps.p >= ps.end || *ps.p != ':') ps.bad();
+                    ++ps.p;
+                    if (Parser::span_is(pk, "ptList")) {
+                        ps.value(nullptr);
+                        out += "[{\"x\": ";
+                        append_py_float(out, box[0]);
+                        out += ", \"y\": ";
+                        append_py_float(out, box[1]);
+                        out += "}, {\"x\": ";
+                        append_py_float(out, box[2]);
+                        out += ", \"y\": ";
+                        append_py_float(out, box[3]);
+                        out += "}]";
+                    } else {
+                        ps.value(&out);
+                    }
+                    const char d = ps.peek();
+                    if (d == ',') { ++ps.p; continue; }
+                    if (d == '}') { ++ps.p; break; }
+                    ps.bad();
+                }
+            }
+            out += '}';
+        } else {
+            ps.value(&out);
+        }
+        const char d = ps.peek();
+        if (d == ',') { ++ps.p; continue; }
+        if (d == '}') { ++ps.p; break; }
+        ps.bad();
+    }
+    out += '}';
+}
+
+// the whole document of one cell with the REPAIR_DROP objects left out and the REPAIR_CLIP objects' ptList replaced by clip[k]
+void emit_repaired_cell(Span cell, const std::vector<uint8_t> &mode, const std::vector<const double *> &clip, std::string &out) {
+    Parser ps{cell.b, cell.e};
+    ps.ws();
+    if (ps.p >= ps.end || *ps.p != '{') ps.irregular();
+    ++ps.p;
+    out += '{';
+    KeySet ks;
+    bool first = true;
+    if (ps.peek() == '}') { ++ps.p; out += '}'; return; }
+    while (true) {
+        ps.ws();
+        const Span k = ps.string_token();
+        ks.add(ps, k);
+        if (!first) out += ", ";
+        first = false;
+        ps.emit_string(out, k);
+        out += ": ";
+        ps.ws();
+        if (ps.p >= ps.end || *ps.p != ':') ps.bad();
+        ++ps.p;
+        if (Parser::span_is(k, "objects") && ps.peek() == '[') {
+            ++ps.p;
+            out += '[';
+            bool efirst = true;
+            if (ps.peek() == ']') {
+                ++ps.p;
+            } else {
+                for (size_t ko = 0;; ++ko) {
+                    const uint8_t m = ko < mode.size() ? mode[ko] : (uint8_t)REPAIR_KEEP;
+                    if (m != REPAIR_DROP) {
+                        if (!efirst) out += ", ";
+                        efirst = false;
+                    }
+                    if (m == REPAIR_CLIP) {
+                        if (ps.peek() != '{') ps.irregular();
+                        emit_clipped_object(ps, clip[ko], out);
+                    } else {
+                        ps.value(m == REPAIR_DROP ? nullptr : &out);
+                    }
+                    const char d = ps.peek();
+                    if (d == ',') { ++ps.p; continue; }
+                    if (d == ']') { ++ps.p; break; }
+                    ps.bad();
+                }
+            }
+            out += ']';
+        } else {
+            ps.value(&out);
+        }
+        const char d = ps.peek();
+        if (d == ',') { ++ps.p; continue; }
+        if (d == '}') { ++ps.p; break; }
+        ps.bad();
+    }
+    ps.ws();
+    if (ps.p != ps.end) ps.bad();
+    out += '}';
+}
+
 }  // namespace
 
 extern "C" {
@@ -1850,54 +2032,43 @@ const int32_t *dyd_scan_box_name(const dyd_scan *h) { return (h && !h->box_name.
 int dyd_json_emit_dropping(dyd_scan *h, const uint8_t *drop_per_box, int n_threads, uint8_t *out_changed, const uint8_t **out_text,
                            const int64_t **out_off) {
     if (!h || !out_changed || !out_text || !out_off) return DYD_ERR_INVALID;
-    const int64_t n = h->n_cells;
-    const int64_t nb = h->cell_box_off.empty() ? 0 : h->cell_box_off[(size_t)n];
+    const int64_t nb = h->cell_box_off.empty() ? 0 : h->cell_box_off[(size_t)h->n_cells];
     if (nb > 0 && (!drop_per_box || (int64_t)h->box_obj.size() != nb)) return DYD_ERR_INVALID;
-    try {
-        std::vector<std::string> texts(64);
-        std::vector<int64_t> lens((size_t)n, 0);
-        struct Range { int64_t lo = 0, hi = 0; };
-        std::vector<Range> ranges(64);
-        if (n_threads <= 0 || n_threads > 64) n_threads = default_threads();
-        const bool ok = parallel_cells_safe(n, n_threads, [&](int t, int64_t lo, int64_t hi) {
-            ranges[(size_t)t] = Range{lo, hi};
-            std::string &buf = texts[(size_t)t];
-            std::vector<uint8_t> drop_obj;
-            for (int64_t i = lo; i < hi; ++i) {
-                out_changed[i] = 0;
-                const int32_t b0 = h->cell_box_off[(size_t)i], b1 = h->cell_box_off[(size_t)i + 1];
-                bool any = false;
-                for (int32_t b = b0; b < b1; ++b) any |= drop_per_box[b] != 0;
-                if (!any) continue;
-                drop_obj.assign((size_t)h->box_obj[(size_t)b1 - 1] + 1, 0);
-                for (int32_t b = b0; b < b1; ++b)
-                    if (drop_per_box[b]) drop_obj[(size_t)h->box_obj[(size_t)b]] = 1;
-                const size_t mark = buf.size();
-                try {
-                    emit_dropping_cell(h->src.get(i), drop_obj, buf);
-                    out_changed[i] = 1;
-                } catch (Fail) {
-                    buf.resize(mark);
-                    out_changed[i] = 2;   // the Python path re-spells this cell
-                }
-                lens[(size_t)i] = (int64_t)(buf.size() - mark);
-            }
-        });
-        if (!ok) return DYD_ERR_OOM;
-        h->text_off.assign((size_t)n + 1, 0);
-        for (int64_t i = 0; i < n; ++i) h->text_off[(size_t)i + 1] = h->text_off[(size_t)i] + lens[(size_t)i];
-        h->text.clear();
-        h->text.reserve((size_t)h->text_off[(size_t)n]);
-        std::vector<size_t> order;
-        for (size_t t = 0; t < ranges.size(); ++t) if (ranges[t].hi > ranges[t].lo) order.push_back(t);
-        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return ranges[a].lo < ranges[b].lo; });
-        for (size_t t : order) h->text += texts[t];
-    } catch (const std::bad_alloc &) {
-        return DYD_ERR_OOM;
-    }
-    *out_text = reinterpret_cast<const uint8_t *>(h->text.data());
-    *out_off = h->text_off.data();
-    return DYD_OK;
+    return emit_changed_cells(h, n_threads, out_changed, out_text, out_off,
+                              [&](int64_t i, std::string &buf, std::vector<uint8_t> &drop_obj) {
+        const int32_t b0 = h->cell_box_off[(size_t)i], b1 = h->cell_box_off[(size_t)i + 1];
+        bool any = false;
+        for (int32_t b = b0; b < b1; ++b) any |= drop_per_box[b] != 0;
+        if (!any) return false;
+        drop_obj.assign((size_t)h->box_obj[(size_t)b1 - 1] + 1, 0);
+        for (int32_t b = b0; b < b1; ++b)
+            if (drop_per_box[b]) drop_obj[(size_t)h->box_obj[(size_t)b]] = 1;
+        emit_dropping_cell(h->src.get(i), drop_obj, buf);
+        return true;
+    });
+}
+
+int dyd_json_emit_repaired(dyd_scan *h, const uint8_t *action_per_box, const double *box4, int n_threads, uint8_t *out_changed,
+                           const uint8_t **out_text, const int64_t **out_off) {
+    if (!h || !out_changed || !out_text || !out_off) return DYD_ERR_INVALID;
+    const int64_t nb = h->cell_box_off.empty() ? 0 : h->cell_box_off[(size_t)h->n_cells];
+    if (nb > 0 && (!action_per_box || !box4 || (int64_t)h->box_obj.size() != nb)) return DYD_ERR_INVALID;
+    return emit_changed_cells(h, n_threads, out_changed, out_text, out_off,
+                              [&](int64_t i, std::string &buf, std::vector<uint8_t> &mode) {
+        const int32_t b0 = h->cell_box_off[(size_t)i], b1 = h->cell_box_off[(size_t)i + 1];
+        bool any = false;
+        for (int32_t b = b0; b < b1; ++b) any |= repair_mode(action_per_box[b]) != REPAIR_KEEP;
+        if (!any) return false;
+        mode.assign((size_t)h->box_obj[(size_t)b1 - 1] + 1, REPAIR_KEEP);
+        std::vector<const double *> clip(mode.size(), nullptr);
+        for (int32_t b = b0; b < b1; ++b) {
+            const size_t k = (size_t)h->box_obj[(size_t)b];
+            mode[k] = repair_mode(action_per_box[b]);
+            clip[k] = box4 + 4 * (int64_t)b;
+        }
+        emit_repaired_cell(h->src.get(i), mode, clip, buf);
+        return true;
+    });
 }
 
 }  // extern "C"

@@ -303,6 +303,21 @@ def audit_cell_boxes(cell) -> list:
     return collected
 
 
+def repair_cell(cell, decisions) -> str:
+    """One cell re-spelled by the box repair step from decisions already made (K11): ``decisions`` maps the index of an object
+    in "objects" to None (the object is left out) or to the clipped corners (x1', y1', x2', y2'), which replace its
+    polygon.ptList by the replace step's two-point shape (reference processor.py:260) with float values.  Every other object
+    stays as json.loads read it.  -> json.dumps(doc, ensure_ascii=False)"""
+    doc = json.loads(cell)
+    objs = doc["objects"]
+    for k, box in decisions.items():
+        if box is not None:
+            x1, y1, x2, y2 = (float(v) for v in box)
+            objs[k]["polygon"]["ptList"] = [{"x": x1, "y": y1}, {"x": x2, "y": y2}]
+    doc["objects"] = [o for k, o in enumerate(objs) if k not in decisions or decisions[k] is not None]
+    return json.dumps(doc, ensure_ascii=False)
+
+
 # ------------------------------------------------------------------------------------------
 # a1 / a2  key column -> flat bytes + offsets for K3
 # ------------------------------------------------------------------------------------------

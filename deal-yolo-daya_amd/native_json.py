@@ -444,6 +444,29 @@ class NamedBoxScan(_Scan):
         else:
             self.names = []
 
+    def emit_repaired(self, action: np.ndarray, box4: np.ndarray, n_threads: int = 0) -> tuple:
+        """K11's decisions -> (changed u8 [n_cells]: 0 unchanged, 1 re-spelled here, 2 left to the caller; str per changed == 1
+        cell, in order).  action [n_boxes] holds K11's codes (bits 0-2): 3..7 leave the box's object out, 1 replaces its
+        polygon.ptList by the two corners of box4 [n_boxes, 4]."""
+        L = _native.load_library()
+        action = np.ascontiguousarray(action, dtype=np.uint8)
+        box4 = np.ascontiguousarray(box4, dtype=np.float64)
+        if action.size != self.n_boxes or box4.size != 4 * self.n_boxes:
+            raise ValueError("action and box4 must hold one entry per box")
+        changed = np.zeros(self.n_cells, np.uint8)
+        tp, op = C.c_void_p(), C.c_void_p()
+        _native.check(L.dyd_json_emit_repaired(self._h, action.ctypes.data if action.size else None,
+                                               box4.ctypes.data if box4.size else None, n_threads,
+                                               changed.ctypes.data if self.n_cells else None, C.byref(tp), C.byref(op)),
+                      "dyd_json_emit_repaired")
+        idx = np.flatnonzero(changed == 1)
+        if not len(idx):
+            return changed, np.empty(0, object)
+        off = _view(op.value, np.int64, self.n_cells + 1)
+        sub = np.append(off[idx], off[idx[-1] + 1])           # unchanged cells have no text: the changed ones are contiguous
+        text = _view(tp.value, np.uint8, max(int(off[-1]), 1))
+        return changed, strings_from_buffers(text, sub, None, n_threads)
+
 
 def scan_named_boxes_buffers(data, off, missing, n_threads: int = 0, keep=None) -> NamedBoxScan:
     data = np.ascontiguousarray(data, dtype=np.uint8)

@@ -163,6 +163,40 @@ int dyd_box_audit_dev(const double *box4, const int32_t *row_off, int64_t n_rows
                       int32_t *out_row_counts, int64_t *out_class_counts, int64_t *out_hist_wh,
                       int64_t *out_hist_xy, int64_t *out_boxes_per_image, void *stream);
 
+/* ---- K11: box repair — clip boxes to the image, drop the unusable ones ---------------
+ * The box audit's boxes and inputs (K10).  Per box one action, the rules tested in order in
+ * IEEE f64 without contraction:
+ *   2 no_size         the row's size_status is not 0                      (box untouched)
+ *   3 bad_coords      a corner is not finite                              (object removed)
+ *   4 degenerate      max(x2 - x1, 0.0) <= 0 or max(y2 - y1, 0.0) <= 0     (object removed)
+ *     then x1' = 0.0 if x1 < 0 else x1, y1' likewise, x2' = W if x2 > W else x2, y2' = H if
+ *     y2 > H else y2, bw' = max(x2' - x1', 0.0), bh' likewise, clipped = x1 < 0 or y1 < 0 or
+ *     x2 > W or y2 > H (K10's out_of_image)
+ *   5 outside         bw' <= 0 or bh' <= 0                                (object removed)
+ *   6 low_visibility  bw' * bh' < min_visibility * (bw * bh), bw = x2 - x1 (object removed)
+ *   7 small           bw' < min_size or bh' < min_size                    (object removed)
+ *   1 clip            clipped                                 (ptList -> (x1', y1'), (x2', y2'))
+ *   0 keep            otherwise                                           (box untouched)
+ * Geometry applies to every box; a box whose class id is -1 (its name is no str) is counted
+ * per row only.
+ * box4, row_off, cls, width, height, size_status: as dyd_box_audit
+ * min_visibility in [0, 1], min_size finite and >= 0 (pixels)
+ * out_action : bits 0-2 action code, 0x80 = class id -1                         [B] u8
+ * out_box4   : per box the corners it is written with: (x1', y1', x2', y2') for
+ *              code 1, the input corners otherwise; 16-byte aligned            [4*B] f64
+ * out_row_counts: per row, per action code, over all boxes                   [8*n_rows] i32
+ * out_class_counts: per class, per action code, over class ids >= 0         [8*n_classes] i64 */
+int dyd_repair_boxes(const double *box4, const int32_t *row_off, int64_t n_rows, const int32_t *cls,
+                     const double *width, const double *height, const uint8_t *size_status,
+                     int32_t n_classes, double min_visibility, double min_size, uint8_t *out_action,
+                     double *out_box4, int32_t *out_row_counts, int64_t *out_class_counts);
+/* device pointers; n_boxes = row_off[n_rows]; every output is written (the sums are zeroed first) */
+int dyd_repair_boxes_dev(const double *box4, const int32_t *row_off, int64_t n_rows, int64_t n_boxes,
+                         const int32_t *cls, const double *width, const double *height,
+                         const uint8_t *size_status, int32_t n_classes, double min_visibility,
+                         double min_size, uint8_t *out_action, double *out_box4,
+                         int32_t *out_row_counts, int64_t *out_class_counts, void *stream);
+
 /* ---- K1+K2 fused: poly -> bbox -> IoU flag in one pass ---------------------------
  * One launch that produces K1's outputs and K2's flag for rows whose boxes all come
  * from K1 (processing.py:580-598 runs the two steps back to back on the same rows).
@@ -382,6 +416,13 @@ int dyd_json_scan_named_boxes(const uint8_t *text, const int64_t *cell_off, cons
 int dyd_json_scan_named_boxes_v(const uint8_t *const *cell_ptr, const int64_t *cell_len, const uint8_t *missing,
                                 int64_t n_cells, int n_threads, dyd_scan **out);
 int64_t dyd_scan_names(const dyd_scan *scan, const uint8_t **text, const int64_t **off);
+/* Box repair, after dyd_json_scan_named_boxes(_v): for every cell with a box whose action (bits 0-2 of
+ * action_per_box, K11's codes) is 1 or 3..7, the whole document as json.dumps(..., ensure_ascii=False) writes it
+ * with the objects of codes 3..7 left out and, for code 1, the object's polygon.ptList replaced by
+ * [{"x": x1', "y": y1'}, {"x": x2', "y": y2'}] from box4 [4*n_boxes] (float repr).  out_changed, text and
+ * offsets as dyd_json_emit_dropping. */
+int dyd_json_emit_repaired(dyd_scan *scan, const uint8_t *action_per_box, const double *box4, int n_threads,
+                           uint8_t *out_changed, const uint8_t **out_text, const int64_t **out_off);
 /* The replace step and the IoU step in ONE native pass (processor.py:262-281 then :341-376; ui/pages/processing.py:580-598 runs them
  * back to back): cells as flat text + offsets, or as one (pointer, length) pair per cell (text == cell_off == NULL).  Every worker
  * thread holds one staging slot (dyd_stage_acquire) and takes its share of the cells through scan -> dyd_bbox_iou_fused_staged -> emit

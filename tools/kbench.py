@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmarks on one MI355X (device-resident inputs, HIP-event timing,
 interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant.
 
-    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, each against K2 alone)
+    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone)
 """
 import argparse
 import json
@@ -199,6 +199,59 @@ def main():
         cc = outs[(20, 16)][0]
         print(json.dumps({"kernel": "k10_audit", "writable": int(cc[:, 3].sum().item()), "boxes": int(cc[:, :4].sum().item()),
                           "images": int(cc[:, 8].sum().item())}), flush=True)
+
+    if "k11" in only:
+        # K11 (box repair) against K2 alone and K10 (c20 nb16) on the same device buffers, interleaved rounds: 20 classes (LDS
+        # class counters) with the default and with strict parameters, 5,000 classes (global class counters)
+        ck(L.dyd_bbox_minmax_dev(xy.data_ptr(), pt_off.data_ptr(), B, P, out_box.data_ptr(), out_arg.data_ptr(), sp), "k1")
+        g = torch.Generator(device=dev).manual_seed(11)
+        cls20 = (labels.to(torch.int64) % 20).to(torch.int32).contiguous()
+        cls5k = torch.randint(0, 5000, (B,), generator=g, device=dev, dtype=torch.int32)
+        wdt = torch.full((N,), 1280.0, dtype=torch.float64, device=dev)
+        hgt = torch.full((N,), 720.0, dtype=torch.float64, device=dev)
+        st = torch.zeros(N, dtype=torch.uint8, device=dev)
+        act = torch.empty(B, dtype=torch.uint8, device=dev)
+        rbox = torch.empty((B, 4), dtype=torch.float64, device=dev)
+        rrows = torch.empty((N, 8), dtype=torch.int32, device=dev)
+        rcc = {20: torch.empty((20, 8), dtype=torch.int64, device=dev), 5000: torch.empty((5000, 8), dtype=torch.int64, device=dev)}
+        flag = torch.empty(B, dtype=torch.uint8, device=dev)
+        arows = torch.empty((N, 6), dtype=torch.int32, device=dev)
+        acc_ = torch.empty((20, 9), dtype=torch.int64, device=dev)
+        awh = torch.empty(20 * 16 * 16, dtype=torch.int64, device=dev)
+        axy = torch.empty(20 * 16 * 16, dtype=torch.int64, device=dev)
+        bpi = torch.empty(257, dtype=torch.int64, device=dev)
+
+        def k11(cls, nc, mv, ms):
+            return lambda: ck(L.dyd_repair_boxes_dev(out_box.data_ptr(), box_off.data_ptr(), N, B, cls.data_ptr(), wdt.data_ptr(),
+                                                     hgt.data_ptr(), st.data_ptr(), nc, mv, ms, act.data_ptr(), rbox.data_ptr(),
+                                                     rrows.data_ptr(), rcc[nc].data_ptr(), sp), "k11")
+
+        # bytes K11 needs: per box 32 in + 4 class + 1 action + 32 out; per row offset, W, H, status and 8 i32 counts
+        repair_bytes = (32 + 4 + 1 + 32) * B + 4 * (N + 1) + (8 + 8 + 1 + 32) * N
+        audit_bytes = 32 * B + 4 * B + B + 4 * (N + 1) + 17 * N + 24 * N
+        legs = {"k2 auto (dyd_iou_any_ge_dev)": (32 * B + 4 * (N + 1) + N, lambda: ck(L.dyd_iou_any_ge_dev(
+                    out_box.data_ptr(), box_off.data_ptr(), N, B, 2, 0.98, out_high.data_ptr(), None, sp), "k2")),
+                "k10_audit c20 nb16": (audit_bytes, lambda: ck(L.dyd_box_audit_dev(
+                    out_box.data_ptr(), box_off.data_ptr(), N, B, cls20.data_ptr(), wdt.data_ptr(), hgt.data_ptr(), st.data_ptr(),
+                    20, 16, flag.data_ptr(), arows.data_ptr(), acc_.data_ptr(), awh.data_ptr(), axy.data_ptr(), bpi.data_ptr(),
+                    sp), "k10")),
+                "k11_repair c20": (repair_bytes, k11(cls20, 20, 0.0, 0.0)),
+                "k11_repair c20 mv0.5 ms4": (repair_bytes, k11(cls20, 20, 0.5, 4.0)),
+                "k11_repair c5000": (repair_bytes, k11(cls5k, 5000, 0.0, 0.0))}
+        res = {}
+        for rnd in range(2):
+            for nm, (_, fn) in legs.items():
+                res.setdefault(nm, []).append(timeit(fn))
+        for nm, (nbytes, _) in legs.items():
+            med = float(np.median([r[0] for r in res[nm]])); mn = min(r[1] for r in res[nm])
+            report(nm, nbytes, med, mn, rows_per_s=round(N / med * 1e3))
+        legs["k11_repair c20"][1]()
+        torch.cuda.synchronize()
+        cc = rcc[20]
+        print(json.dumps({"kernel": "k11_repair", "boxes": int(cc.sum().item()),
+                          **{a: int(cc[:, k].sum().item()) for k, a in enumerate(
+                              ("keep", "clip", "no_size", "bad_coords", "degenerate", "outside", "low_visibility", "small"))}}),
+              flush=True)
 
     if "k12" in only:
         k12_bytes = 16 * P + 4 * (B + 1) + 48 * B + 4 * (N + 1) + N
