@@ -340,18 +340,14 @@ def suppress_boxes(box4: np.ndarray, row_off: np.ndarray, thr: float, name=None)
 AUDIT_BPI = 257      # boxes_per_image bins: 0..255 boxes, then >= 256
 
 
-def box_audit(box4: np.ndarray, row_off: np.ndarray, cls: np.ndarray, width: np.ndarray, height: np.ndarray,
-              size_status: np.ndarray, n_classes: int, nbins: int):
-    """K10 over host arrays -> (flag [B] u8, row_counts [N,6] i32, class_counts [C,9] i64, hist_wh [C,nb,nb] i64,
-    hist_xy [C,nb,nb] i64, boxes_per_image [257] i64).  See include/dyd.h for the columns and the flag bits."""
+def _box_table(box4, row_off, cls, width, height, size_status) -> tuple:
+    """the box table of K10 / K11 as contiguous arrays of the kernels' dtypes, its sizes checked -> (box4, row_off, cls, width,
+    height, size_status, n_rows, n_boxes)"""
     box4 = np.ascontiguousarray(box4, dtype=np.float64).reshape(-1)
     row_off = np.ascontiguousarray(row_off, dtype=np.int32)
     n = len(row_off) - 1
     if n < 0 or row_off[0] != 0 or 4 * int(row_off[-1]) != box4.size:
         raise ValueError("row_off must start at 0 and end at the number of boxes")
-    nbins, n_classes = int(nbins), int(n_classes)
-    if not 1 <= nbins <= 64:
-        raise ValueError(f"nbins must lie in 1..64, got {nbins}")
     nb = int(row_off[-1])
     cls = np.ascontiguousarray(cls, dtype=np.int32)
     width = np.ascontiguousarray(width, dtype=np.float64)
@@ -359,6 +355,17 @@ def box_audit(box4: np.ndarray, row_off: np.ndarray, cls: np.ndarray, width: np.
     size_status = np.ascontiguousarray(size_status, dtype=np.uint8)
     if cls.size != nb or width.size != n or height.size != n or size_status.size != n:
         raise ValueError("cls must hold one id per box; width, height and size_status one value per row")
+    return box4, row_off, cls, width, height, size_status, n, nb
+
+
+def box_audit(box4: np.ndarray, row_off: np.ndarray, cls: np.ndarray, width: np.ndarray, height: np.ndarray,
+              size_status: np.ndarray, n_classes: int, nbins: int):
+    """K10 over host arrays -> (flag [B] u8, row_counts [N,6] i32, class_counts [C,9] i64, hist_wh [C,nb,nb] i64,
+    hist_xy [C,nb,nb] i64, boxes_per_image [257] i64).  See include/dyd.h for the columns and the flag bits."""
+    box4, row_off, cls, width, height, size_status, n, nb = _box_table(box4, row_off, cls, width, height, size_status)
+    nbins, n_classes = int(nbins), int(n_classes)
+    if not 1 <= nbins <= 64:
+        raise ValueError(f"nbins must lie in 1..64, got {nbins}")
     flag = np.zeros(nb, np.uint8)
     rows = np.zeros((n, 6), np.int32)
     cc = np.zeros((n_classes, 9), np.int64)
@@ -377,23 +384,12 @@ def repair_boxes(box4: np.ndarray, row_off: np.ndarray, cls: np.ndarray, width: 
                  size_status: np.ndarray, n_classes: int, min_visibility: float = 0.0, min_size: float = 0.0):
     """K11 over host arrays -> (action [B] u8, box4 [B,4] f64, row_counts [N,8] i32, class_counts [C,8] i64).  See
     include/dyd.h for the action codes and the rules."""
-    box4 = np.ascontiguousarray(box4, dtype=np.float64).reshape(-1)
-    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
-    n = len(row_off) - 1
-    if n < 0 or row_off[0] != 0 or 4 * int(row_off[-1]) != box4.size:
-        raise ValueError("row_off must start at 0 and end at the number of boxes")
+    box4, row_off, cls, width, height, size_status, n, nb = _box_table(box4, row_off, cls, width, height, size_status)
     min_visibility, min_size, n_classes = float(min_visibility), float(min_size), int(n_classes)
     if not 0.0 <= min_visibility <= 1.0:
         raise ValueError(f"min_visibility must lie in [0, 1], got {min_visibility}")
     if not (np.isfinite(min_size) and min_size >= 0.0):
         raise ValueError(f"min_size must be finite and >= 0, got {min_size}")
-    nb = int(row_off[-1])
-    cls = np.ascontiguousarray(cls, dtype=np.int32)
-    width = np.ascontiguousarray(width, dtype=np.float64)
-    height = np.ascontiguousarray(height, dtype=np.float64)
-    size_status = np.ascontiguousarray(size_status, dtype=np.uint8)
-    if cls.size != nb or width.size != n or height.size != n or size_status.size != n:
-        raise ValueError("cls must hold one id per box; width, height and size_status one value per row")
     action = np.zeros(nb, np.uint8)
     out_box = np.zeros((nb, 4), np.float64)
     rows = np.zeros((n, REPAIR_ACTIONS), np.int32)

@@ -865,13 +865,36 @@ def iou_filter_frame(df: pd.DataFrame, min_boxes: int = 2, iou_threshold: float 
     return df[mask], df[~mask]
 
 
-def _iou_csv_fast(input_csv_path, high_iou_csv, other_csv, min_boxes, iou_threshold, backend):
-    """CSV -> two CSVs IoU step on flat buffers (see _replace_csv_fast)."""
+def _csv_read_split(input_csv_path, heavy: list, col: str):
+    """fastcsv.read_split with `heavy` as its heavy columns -> the table, or NotImplemented (the pandas route decides then) when
+    it cannot read the file or `col` is not among its heavy columns"""
     try:
-        table = _fc.read_split(str(input_csv_path), [ANNOTATION_COL, BBOX_COL])
+        table = _fc.read_split(str(input_csv_path), heavy)
     except (OSError, ValueError, pd.errors.ParserError, UnicodeDecodeError):
         return NotImplemented
-    if table is None or BBOX_COL not in table.heavy:
+    if table is None or col not in table.heavy:
+        return NotImplemented
+    return table
+
+
+def _csv_read_pandas(input_csv_path, col: str):
+    """the pandas route's read, in the IoU step's conventions: utf-8-sig -> DataFrame; a read failure prints 读取失败：... and a
+    missing column 错误：缺少必要列 ..., both returning None"""
+    try:
+        df = pd.read_csv(input_csv_path, encoding="utf-8-sig")
+    except Exception as e:
+        print(f"读取失败：{e}")
+        return None
+    if col not in df.columns:
+        print(f"错误：缺少必要列 {col}")
+        return None
+    return df
+
+
+def _iou_csv_fast(input_csv_path, high_iou_csv, other_csv, min_boxes, iou_threshold, backend):
+    """CSV -> two CSVs IoU step on flat buffers (see _replace_csv_fast)."""
+    table = _csv_read_split(input_csv_path, [ANNOTATION_COL, BBOX_COL], BBOX_COL)
+    if table is NotImplemented:
         return NotImplemented
     be = _backend(backend)
     col = table.heavy[BBOX_COL]
@@ -907,13 +930,8 @@ def filter_by_box_count_and_iou(
             LAST_IO_PATH["iou"] = "native"
             return
     LAST_IO_PATH["iou"] = "pandas"
-    try:
-        df = pd.read_csv(input_csv_path, encoding="utf-8-sig")
-    except Exception as e:
-        print(f"读取失败：{e}")
-        return
-    if BBOX_COL not in df.columns:
-        print(f"错误：缺少必要列 {BBOX_COL}")
+    df = _csv_read_pandas(input_csv_path, BBOX_COL)
+    if df is None:
         return
     high, other = iou_filter_frame(df, min_boxes, iou_threshold, backend)
     Path(high_iou_csv).parent.mkdir(parents=True, exist_ok=True)
@@ -1048,13 +1066,19 @@ def _splice_column(col, texts: dict):
     return _fc.Utf8Column(new_data, new_off, col.na, blob)
 
 
+def _csv_write_spliced(output_csv_path, table, col: str, texts: dict) -> bool:
+    """writes every column of a fastcsv table, the cells of `texts` replaced in its heavy column `col`; False when
+    fastcsv.write_table declines (nothing written then)"""
+    new_col = _splice_column(table.heavy[col], texts)
+    columns = [new_col if nm == col else (table.heavy[nm] if nm in table.heavy else table.light[nm]) for nm in table.names]
+    Path(output_csv_path).parent.mkdir(parents=True, exist_ok=True)
+    return bool(_fc.write_table(str(output_csv_path), table.names, columns, table.n_rows))
+
+
 def _suppress_csv_fast(input_csv_path, output_csv_path, iou_threshold, by_label, backend):
     """-> (n_rows, texts count, recs, sources) or NotImplemented (nothing written then)"""
-    try:
-        table = _fc.read_split(str(input_csv_path), [ANNOTATION_COL, BBOX_COL])
-    except (OSError, ValueError, pd.errors.ParserError, UnicodeDecodeError):
-        return NotImplemented
-    if table is None or BBOX_COL not in table.heavy:
+    table = _csv_read_split(input_csv_path, [ANNOTATION_COL, BBOX_COL], BBOX_COL)
+    if table is NotImplemented:
         return NotImplemented
     be = _suppress_backend(backend)
     col = table.heavy[BBOX_COL]
@@ -1064,10 +1088,7 @@ def _suppress_csv_fast(input_csv_path, output_csv_path, iou_threshold, by_label,
         texts, recs = _suppress_decide(scan, col.cell, float(iou_threshold), bool(by_label), be, totals)
     finally:
         scan.close()
-    new_col = _splice_column(col, texts)
-    columns = [new_col if nm == BBOX_COL else (table.heavy[nm] if nm in table.heavy else table.light[nm]) for nm in table.names]
-    Path(output_csv_path).parent.mkdir(parents=True, exist_ok=True)
-    if not _fc.write_table(str(output_csv_path), table.names, columns, table.n_rows):
+    if not _csv_write_spliced(output_csv_path, table, BBOX_COL, texts):
         return NotImplemented
     sources = table.light["source"].tolist() if "source" in table.light.columns else None
     return table.n_rows, len(texts), recs, sources
@@ -1084,13 +1105,8 @@ def suppress_duplicate_boxes_csv(input_csv_path, output_csv_path="deduped_boxes.
         res = _suppress_csv_fast(input_csv_path, output_csv_path, iou_threshold, by_label, backend)
     if res is NotImplemented:
         LAST_IO_PATH["suppress"] = "pandas"
-        try:
-            df = pd.read_csv(input_csv_path, encoding="utf-8-sig")
-        except Exception as e:
-            print(f"读取失败：{e}")
-            return None
-        if BBOX_COL not in df.columns:
-            print(f"错误：缺少必要列 {BBOX_COL}")
+        df = _csv_read_pandas(input_csv_path, BBOX_COL)
+        if df is None:
             return None
         be = _suppress_backend(backend)
         stats = {}
@@ -2114,8 +2130,10 @@ def _audit_size_py(w, h) -> tuple:
 
 
 def _audit_sizes(widths, heights, n: int) -> tuple:
-    """-> (status u8, W f64, H f64) per row; numpy when both columns are numeric, Python per row otherwise"""
-    if widths is None or heights is None:                # no size columns: row.get gives None
+    """-> (status u8, W f64, H f64) per row of n cells; numpy when both columns are numeric, Python per row otherwise"""
+    if (widths is None) != (heights is None) or (widths is not None and (len(widths) != n or len(heights) != n)):
+        raise ValueError("widths and heights must both be given with one value per cell, or both be None")
+    if widths is None:                                   # no size columns: row.get gives None
         return np.ones(n, np.uint8), np.zeros(n), np.zeros(n)
     kinds = ("integer", "floating", "mixed-integer-float")
     if n and pd.api.types.infer_dtype(widths, skipna=False) in kinds and pd.api.types.infer_dtype(heights, skipna=False) in kinds:
@@ -2133,6 +2151,14 @@ def _audit_sizes(widths, heights, n: int) -> tuple:
     return status, np.fromiter((r[1] for r in res), np.float64, count=n), np.fromiter((r[2] for r in res), np.float64, count=n)
 
 
+def _size_columns(frame, width_col: str = "width", height_col: str = "height") -> tuple:
+    """-> (widths, heights, sources) columns of a DataFrame or of fastcsv's light table; None for what it lacks (both sizes
+    unless it has both)"""
+    has_size = width_col in frame.columns and height_col in frame.columns
+    return (frame[width_col].to_numpy() if has_size else None, frame[height_col].to_numpy() if has_size else None,
+            frame["source"].to_numpy() if "source" in frame.columns else None)
+
+
 def _audit_backend(backend):
     be = _backend(backend)
     if not hasattr(be, "box_audit"):
@@ -2140,85 +2166,118 @@ def _audit_backend(backend):
     return be
 
 
-class _AuditTotals:
-    """class-keyed sums over the chunks, classes in first-seen order until the end"""
+class _ClassSums:
+    """class-keyed int64 sums over the chunks: one array per quantity, its first axis the classes in first-seen order"""
 
-    def __init__(self, nbins):
-        self.nbins = nbins
+    def __init__(self, *shapes):
         self.index = {}
-        self.cc = np.zeros((0, len(_AUDIT_CLASS_COLS)), np.int64)
-        self.wh = np.zeros((0, nbins, nbins), np.int64)
-        self.xy = np.zeros((0, nbins, nbins), np.int64)
-        self.bpi = np.zeros(257, np.int64)
-        self.rows, self.n_boxes, self.status, self.problems = [], [], [], []
-        self.python_cells = 0
+        self.sums = [np.zeros((0, *shape), np.int64) for shape in shapes]
 
-    def add_classes(self, names, cc, wh, xy):
+    def add(self, names, *parts):
+        """adds parts[k][j] to quantity k of class names[j]"""
         g = np.asarray([self.index.setdefault(nm, len(self.index)) for nm in names], np.int64)
-        grow = len(self.index) - len(self.cc)
+        grow = len(self.index) - len(self.sums[0])
         if grow:
-            nb = self.nbins
-            self.cc = np.concatenate([self.cc, np.zeros((grow, self.cc.shape[1]), np.int64)])
-            self.wh = np.concatenate([self.wh, np.zeros((grow, nb, nb), np.int64)])
-            self.xy = np.concatenate([self.xy, np.zeros((grow, nb, nb), np.int64)])
+            self.sums = [np.concatenate([a, np.zeros((grow, *a.shape[1:]), np.int64)]) for a in self.sums]
         if len(g):
-            self.cc[g] += cc
-            self.wh[g] += wh
-            self.xy[g] += xy
+            for a, part in zip(self.sums, parts):
+                a[g] += part
+
+    def sorted(self) -> tuple:
+        """-> (classes sorted as str, the sums in that order)"""
+        classes = sorted(self.index)
+        perm = np.asarray([self.index[c] for c in classes], np.int64)
+        return classes, [a[perm] for a in self.sums]
 
 
-def _audit_chunk(cells, status, W, H, be, acc: _AuditTotals, start: int):
-    """one chunk of rows: scan (native, CPython for irregular cells) -> K10 -> class-keyed sums, per-row counts, problems"""
+class _BoxChunk:
+    """the box table of one chunk of cells, see _box_chunk"""
+
+    def __init__(self, scan, row_off, box4, obj, cls, names, irregular, odd_names, dest):
+        self.scan, self.row_off, self.box4, self.obj, self.cls, self.names = scan, row_off, box4, obj, cls, names
+        self.irregular, self.odd_names, self.dest = irregular, odd_names, dest
+
+
+def _box_chunk(cells) -> _BoxChunk:
+    """one chunk of cells -> its box table: the native scan's boxes with the CPython boxes of the irregular cells
+    (flatten.audit_cell_boxes) spliced in at their rows.  row_off (int64 [n + 1]), box4, obj and cls per box (cls -1: the name
+    is no str; odd_names = {box: that name}), names (class id -> name), irregular (the cells scanned by CPython), dest (native
+    box -> box; None when nothing was spliced) and scan: the NamedBoxScan, still open (None without one): the caller closes it."""
     n = len(cells)
     try:
         scan = _nj.scan_named_boxes(cells) if _nj.enabled() else None
     except UnicodeEncodeError:                           # a lone surrogate: every cell of the chunk through CPython
         scan = None
-    if scan is not None:
-        try:
+    try:
+        if scan is not None:
             nat_off = scan.cell_box_off.astype(np.int64)
-            counts = np.diff(nat_off)
             irregular = np.flatnonzero(scan.status == _nj.IRREGULAR).tolist()
             names = list(scan.names)
             box4, obj, cls = scan.box4, scan.box_object, scan.box_class
-        finally:
-            scan.close()
-    else:
-        nat_off = np.zeros(n + 1, np.int64)
-        counts = np.zeros(n, np.int64)
-        irregular = list(range(n))
-        names, box4, obj, cls = [], np.zeros((0, 4)), np.zeros(0, np.int32), np.zeros(0, np.int32)
-    acc.python_cells += len(irregular)
-    py = {}
-    for i in irregular:
-        boxes = _fl.audit_cell_boxes(cells[i])
-        if boxes:
-            py[i] = boxes
-            counts[i] = len(boxes)
-    row_off = np.zeros(n + 1, np.int64)
-    np.cumsum(counts, out=row_off[1:])
-    if py:                                               # splice the CPython boxes in at their rows
-        nat_counts = np.diff(nat_off)
-        dest = np.repeat(row_off[:-1] - nat_off[:-1], nat_counts) + np.arange(len(obj), dtype=np.int64)
+        else:
+            nat_off = np.zeros(n + 1, np.int64)
+            irregular = list(range(n))
+            names, box4, obj, cls = [], np.zeros((0, 4)), np.zeros(0, np.int32), np.zeros(0, np.int32)
+        counts = np.diff(nat_off)
+        py = {}
+        for i in irregular:
+            boxes = _fl.audit_cell_boxes(cells[i])
+            if boxes:
+                py[i] = boxes
+                counts[i] = len(boxes)
+        row_off = np.zeros(n + 1, np.int64)
+        np.cumsum(counts, out=row_off[1:])
         nb = int(row_off[-1])
-        b4, ob, cl = np.empty((nb, 4)), np.empty(nb, np.int32), np.empty(nb, np.int32)
-        b4[dest], ob[dest], cl[dest] = box4, obj, cls
-        ids = {nm: k for k, nm in enumerate(names)}
-        for i, boxes in py.items():
-            p = int(row_off[i])
-            for k, (o, nm, *xy) in enumerate(boxes):
-                b4[p + k] = [_audit_number(v) for v in xy]
-                ob[p + k] = o
-                cl[p + k] = ids.setdefault(nm, len(ids)) if isinstance(nm, str) else -1
-        names = list(ids)
-        box4, obj, cls = b4, ob, cl
-    if row_off[-1] >= (1 << 31):
-        raise ValueError("a chunk holds 2^31 boxes or more")
+        if nb >= (1 << 31):
+            raise ValueError("a chunk holds 2^31 boxes or more")
+        odd_names, dest = {}, None
+        if py:                                           # splice the CPython boxes in at their rows
+            dest = np.repeat(row_off[:-1] - nat_off[:-1], np.diff(nat_off)) + np.arange(len(obj), dtype=np.int64)
+            b4, ob, cl = np.empty((nb, 4)), np.empty(nb, np.int32), np.empty(nb, np.int32)
+            b4[dest], ob[dest], cl[dest] = box4, obj, cls
+            ids = {nm: k for k, nm in enumerate(names)}
+            for i, boxes in py.items():
+                p = int(row_off[i])
+                for k, (o, nm, *xy) in enumerate(boxes):
+                    b4[p + k] = [_audit_number(v) for v in xy]
+                    ob[p + k] = o
+                    if isinstance(nm, str):
+                        cl[p + k] = ids.setdefault(nm, len(ids))
+                    else:
+                        cl[p + k] = -1
+                        odd_names[p + k] = nm
+            names = list(ids)
+            box4, obj, cls = b4, ob, cl
+    except BaseException:
+        if scan is not None:
+            scan.close()
+        raise
+    return _BoxChunk(scan, row_off, box4, obj, cls, names, irregular, odd_names, dest)
+
+
+class _AuditTotals:
+    """sums over the chunks, classes in first-seen order until the end"""
+
+    def __init__(self, nbins):
+        self.nbins = nbins
+        self.classes = _ClassSums((len(_AUDIT_CLASS_COLS),), (nbins, nbins), (nbins, nbins))
+        self.bpi = np.zeros(257, np.int64)
+        self.rows, self.n_boxes, self.status, self.problems = [], [], [], []
+        self.python_cells = 0
+
+
+def _audit_chunk(cells, status, W, H, be, acc: _AuditTotals, start: int):
+    """one chunk of rows: box table (_box_chunk) -> K10 -> class-keyed sums, per-row counts, problems"""
+    t = _box_chunk(cells)
+    if t.scan is not None:
+        t.scan.close()
+    n, row_off, box4, obj, cls, names = len(cells), t.row_off, t.box4, t.obj, t.cls, t.names
+    acc.python_cells += len(t.irregular)
     flag, rows, cc, wh, xy, bpi = be.box_audit(box4, row_off.astype(np.int32), cls, W, H, status, len(names), acc.nbins)
-    acc.add_classes(names, np.asarray(cc, np.int64), np.asarray(wh, np.int64), np.asarray(xy, np.int64))
+    acc.classes.add(names, np.asarray(cc, np.int64), np.asarray(wh, np.int64), np.asarray(xy, np.int64))
     acc.bpi += np.asarray(bpi, np.int64)
     acc.rows.append(np.asarray(rows, np.int64).reshape(n, len(_AUDIT_ROW_COLS)))
-    acc.n_boxes.append(counts)
+    acc.n_boxes.append(np.diff(row_off))
     acc.status.append(status)
     flag = np.asarray(flag, np.uint8)
     cat = flag & 3
@@ -2241,8 +2300,6 @@ def audit_boxes_cells(cells, widths, heights, nbins: int = 16, backend=None, sta
     be = _audit_backend(backend)
     cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
     n = len(cells)
-    if (widths is None) != (heights is None) or (widths is not None and (len(widths) != n or len(heights) != n)):
-        raise ValueError("widths and heights must both be given with one value per cell, or both be None")
     status, W, H = _audit_sizes(widths, heights, n)
     acc = _AuditTotals(nbins)
     for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
@@ -2252,9 +2309,7 @@ def audit_boxes_cells(cells, widths, heights, nbins: int = 16, backend=None, sta
 
 
 def _audit_result(acc: _AuditTotals, n: int, status, sources, stats) -> BoxAudit:
-    classes = sorted(acc.index)
-    perm = np.asarray([acc.index[c] for c in classes], np.int64)
-    cc, wh, xy = acc.cc[perm], acc.wh[perm], acc.xy[perm]
+    classes, (cc, wh, xy) = acc.classes.sorted()
     cols = dict(zip(_AUDIT_CLASS_COLS, cc.T)) if len(classes) else {k: np.zeros(0, np.int64) for k in _AUDIT_CLASS_COLS}
     per_class = pd.DataFrame({"class": pd.Series(classes, dtype=object),
                               "boxes": cols["no_size"] + cols["bad_coords"] + cols["degenerate"] + cols["writable"],
@@ -2292,32 +2347,26 @@ def audit_boxes_frame(df: pd.DataFrame, json_col: str = BBOX_COL, width_col: str
                       nbins: int = 16, backend=None, stats: Optional[dict] = None) -> BoxAudit:
     """Box audit of a processed table (after the IoU filter or the label replace, before the split).  A frame without the
     size columns has every row `missing`.  per_row["row"] / problems["row"] are positions in df."""
-    has_size = width_col in df.columns and height_col in df.columns
-    return audit_boxes_cells(df[json_col].to_numpy(), df[width_col].to_numpy() if has_size else None,
-                             df[height_col].to_numpy() if has_size else None, nbins, backend, stats,
-                             df["source"].to_numpy() if "source" in df.columns else None)
+    cells = df[json_col].to_numpy()
+    widths, heights, sources = _size_columns(df, width_col, height_col)
+    return audit_boxes_cells(cells, widths, heights, nbins, backend, stats, sources)
 
 
 def _audit_csv_fast(input_csv_path, json_col, nbins, backend):
     """-> BoxAudit, or NotImplemented (the pandas route decides then)"""
-    try:
-        table = _fc.read_split(str(input_csv_path), [json_col])
-    except (OSError, ValueError, pd.errors.ParserError, UnicodeDecodeError):
-        return NotImplemented
-    if table is None or json_col not in table.heavy:
+    table = _csv_read_split(input_csv_path, [json_col], json_col)
+    if table is NotImplemented:
         return NotImplemented
     be = _audit_backend(backend)
     col = table.heavy[json_col]
-    light = table.light
     n = table.n_rows
-    has_size = "width" in light.columns and "height" in light.columns
-    status, W, H = _audit_sizes(light["width"].to_numpy() if has_size else None,
-                                light["height"].to_numpy() if has_size else None, n)
+    widths, heights, sources = _size_columns(table.light)
+    status, W, H = _audit_sizes(widths, heights, n)
     acc = _AuditTotals(nbins)
     for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
         s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
         _audit_chunk(_fc_cells(col, s0, s1), status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0)
-    return _audit_result(acc, n, status, light["source"].to_numpy() if "source" in light.columns else None, None)
+    return _audit_result(acc, n, status, sources, None)
 
 
 def _fc_cells(col, s0, s1):
@@ -2350,13 +2399,8 @@ def audit_boxes_csv(input_csv_path, output_dir, json_col: str = BBOX_COL, nbins:
         audit = _audit_csv_fast(input_csv_path, json_col, int(nbins), backend)
     if audit is NotImplemented:
         LAST_IO_PATH["audit"] = "pandas"
-        try:
-            df = pd.read_csv(input_csv_path, encoding="utf-8-sig")
-        except Exception as e:
-            print(f"读取失败：{e}")
-            return None
-        if json_col not in df.columns:
-            print(f"错误：缺少必要列 {json_col}")
+        df = _csv_read_pandas(input_csv_path, json_col)
+        if df is None:
             return None
         audit = audit_boxes_frame(df, json_col, nbins=int(nbins), backend=backend)
     else:
@@ -2403,89 +2447,36 @@ class _RepairTotals:
     """class-keyed action counts over the chunks, changes per chunk, totals"""
 
     def __init__(self):
-        self.index = {}
-        self.cc = np.zeros((0, len(REPAIR_ACTIONS)), np.int64)
+        self.classes = _ClassSums((len(REPAIR_ACTIONS),))
         self.changes = []
         self.rows_changed = self.boxes = self.clipped = self.removed = self.python_cells = 0
 
-    def add_classes(self, names, cc):
-        g = np.asarray([self.index.setdefault(nm, len(self.index)) for nm in names], np.int64)
-        grow = len(self.index) - len(self.cc)
-        if grow:
-            self.cc = np.concatenate([self.cc, np.zeros((grow, self.cc.shape[1]), np.int64)])
-        if len(g):
-            self.cc[g] += cc
-
 
 def _repair_chunk(cells, status, W, H, be, acc: _RepairTotals, start: int, min_vis: float, min_size: float) -> tuple:
-    """one chunk of rows: scan (native, CPython for irregular cells) -> K11 -> emit -> (rows in the chunk, their new texts)
+    """one chunk of rows: box table (_box_chunk) -> K11 -> emit -> (rows in the chunk, their new texts)
     as int64 and object arrays; the class counts and the changed boxes go to acc"""
-    n = len(cells)
+    t = _box_chunk(cells)
+    row_off, box4, obj, cls, names, odd_names = t.row_off, t.box4, t.obj, t.cls, t.names, t.odd_names
+    nb = int(row_off[-1])
+    acc.python_cells += len(t.irregular)
     try:
-        scan = _nj.scan_named_boxes(cells) if _nj.enabled() else None
-    except UnicodeEncodeError:                           # a lone surrogate: every cell of the chunk through CPython
-        scan = None
-    try:
-        if scan is not None:
-            nat_off = scan.cell_box_off.astype(np.int64)
-            counts = np.diff(nat_off)
-            irregular = np.flatnonzero(scan.status == _nj.IRREGULAR).tolist()
-            names = list(scan.names)
-            box4, obj, cls = scan.box4, scan.box_object, scan.box_class
-        else:
-            nat_off = np.zeros(n + 1, np.int64)
-            counts = np.zeros(n, np.int64)
-            irregular = list(range(n))
-            names, box4, obj, cls = [], np.zeros((0, 4)), np.zeros(0, np.int32), np.zeros(0, np.int32)
-        acc.python_cells += len(irregular)
-        py = {}
-        for i in irregular:
-            boxes = _fl.audit_cell_boxes(cells[i])
-            if boxes:
-                py[i] = boxes
-                counts[i] = len(boxes)
-        row_off = np.zeros(n + 1, np.int64)
-        np.cumsum(counts, out=row_off[1:])
-        nb = int(row_off[-1])
-        if nb >= (1 << 31):
-            raise ValueError("a chunk holds 2^31 boxes or more")
-        odd_names = {}                                   # box -> its name when that is no str (class id -1)
-        dest = None
-        if py:                                           # splice the CPython boxes in at their rows
-            nat_counts = np.diff(nat_off)
-            dest = np.repeat(row_off[:-1] - nat_off[:-1], nat_counts) + np.arange(len(obj), dtype=np.int64)
-            b4, ob, cl = np.empty((nb, 4)), np.empty(nb, np.int32), np.empty(nb, np.int32)
-            b4[dest], ob[dest], cl[dest] = box4, obj, cls
-            ids = {nm: k for k, nm in enumerate(names)}
-            for i, boxes in py.items():
-                p = int(row_off[i])
-                for k, (o, nm, *xy) in enumerate(boxes):
-                    b4[p + k] = [_audit_number(v) for v in xy]
-                    ob[p + k] = o
-                    if isinstance(nm, str):
-                        cl[p + k] = ids.setdefault(nm, len(ids))
-                    else:
-                        cl[p + k] = -1
-                        odd_names[p + k] = nm
-            names = list(ids)
-            box4, obj, cls = b4, ob, cl
         action, obox, _rows, cc = be.repair_boxes(box4, row_off.astype(np.int32), cls, W, H, status, len(names), min_vis,
                                                   min_size)
-        acc.add_classes(names, np.asarray(cc, np.int64).reshape(len(names), len(REPAIR_ACTIONS)))
+        acc.classes.add(names, np.asarray(cc, np.int64).reshape(len(names), len(REPAIR_ACTIONS)))
         code = np.asarray(action, np.uint8) & 7
         obox = np.asarray(obox, np.float64).reshape(-1, 4)
         idx, strs, redo = np.zeros(0, np.int64), np.zeros(0, object), []
-        if scan is not None and scan.n_boxes and ((code == 1) | (code >= 3)).any():
-            nat = slice(None) if dest is None else dest
-            changed, strs = scan.emit_repaired(code[nat], obox[nat])
+        if t.scan is not None and t.scan.n_boxes and ((code == 1) | (code >= 3)).any():
+            nat = slice(None) if t.dest is None else t.dest
+            changed, strs = t.scan.emit_repaired(code[nat], obox[nat])
             idx = np.flatnonzero(changed == 1)
             redo = np.flatnonzero(changed == 2).tolist()
     finally:
-        if scan is not None:
-            scan.close()
+        if t.scan is not None:
+            t.scan.close()
     touched = (code == 1) | (code >= 3)
     py_idx, py_strs = [], []
-    for i in redo + sorted(py):                          # decided by K11 above, re-spelled by CPython
+    for i in redo + t.irregular:                         # decided by K11 above, re-spelled by CPython
         b0, b1 = int(row_off[i]), int(row_off[i + 1])
         if touched[b0:b1].any():
             py_idx.append(i)
@@ -2527,8 +2518,7 @@ def _repair_result(acc: _RepairTotals, n: int, status, sources) -> tuple:
     ch.update({"row": r, "object": o, "name": nm, "action": act, "x1": b[:, 0], "y1": b[:, 1], "x2": b[:, 2], "y2": b[:, 3],
                "nx1": nb4[:, 0], "ny1": nb4[:, 1], "nx2": nb4[:, 2], "ny2": nb4[:, 3]})
     changes = pd.DataFrame(ch)                           # rows ascend; within a row the boxes keep their object order
-    classes = sorted(acc.index)
-    cc = acc.cc[np.asarray([acc.index[c] for c in classes], np.int64)] if classes else np.zeros((0, len(REPAIR_ACTIONS)), np.int64)
+    classes, (cc,) = acc.classes.sorted()
     per_class = pd.DataFrame({"class": pd.Series(classes, dtype=object), "boxes": cc.sum(axis=1),
                               **{k: cc[:, j] for j, k in enumerate(REPAIR_ACTIONS)}})
     totals = {"rows": n, "rows_changed": acc.rows_changed, "boxes": acc.boxes, "boxes_clipped": acc.clipped,
@@ -2553,8 +2543,6 @@ def _repair_cells_array(cells, widths, heights, min_visibility, min_size, backen
     be = _repair_backend(backend)
     cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
     n = len(cells)
-    if (widths is None) != (heights is None) or (widths is not None and (len(widths) != n or len(heights) != n)):
-        raise ValueError("widths and heights must both be given with one value per cell, or both be None")
     status, W, H = _audit_sizes(widths, heights, n)
     out = np.fromiter(cells, object, n)                  # the same objects; only the changed rows are replaced
     acc = _RepairTotals()
@@ -2573,10 +2561,9 @@ def repair_boxes_frame(df: pd.DataFrame, json_col: str = BBOX_COL, width_col: st
     """Box repair of a processed table (after the IoU filter / suppression, before the label replace and the split) ->
     (copy of df in which only json_col differs, changes, per_class).  A frame without the size columns has every row
     `no_size`: nothing changes.  changes["row"] is the position in df."""
-    has_size = width_col in df.columns and height_col in df.columns
-    cells, changes, per_class = _repair_cells_array(df[json_col].to_numpy(), df[width_col].to_numpy() if has_size else None,
-                                                    df[height_col].to_numpy() if has_size else None, min_visibility, min_size,
-                                                    backend, stats, df["source"].to_numpy() if "source" in df.columns else None)
+    cells = df[json_col].to_numpy()
+    widths, heights, sources = _size_columns(df, width_col, height_col)
+    cells, changes, per_class = _repair_cells_array(cells, widths, heights, min_visibility, min_size, backend, stats, sources)
     out = df.copy()
     if len(changes):
         out[json_col] = pd.Series(cells, index=out.index, dtype=object)
@@ -2585,31 +2572,23 @@ def repair_boxes_frame(df: pd.DataFrame, json_col: str = BBOX_COL, width_col: st
 
 def _repair_csv_fast(input_csv_path, output_csv_path, json_col, min_vis, min_size, backend):
     """-> (changes, per_class, totals), or NotImplemented (nothing written then; the pandas route decides)"""
-    try:
-        table = _fc.read_split(str(input_csv_path), [json_col])
-    except (OSError, ValueError, pd.errors.ParserError, UnicodeDecodeError):
-        return NotImplemented
-    if table is None or json_col not in table.heavy:
+    table = _csv_read_split(input_csv_path, [json_col], json_col)
+    if table is NotImplemented:
         return NotImplemented
     be = _repair_backend(backend)
     col = table.heavy[json_col]
-    light = table.light
     n = table.n_rows
-    has_size = "width" in light.columns and "height" in light.columns
-    status, W, H = _audit_sizes(light["width"].to_numpy() if has_size else None,
-                                light["height"].to_numpy() if has_size else None, n)
+    widths, heights, sources = _size_columns(table.light)
+    status, W, H = _audit_sizes(widths, heights, n)
     acc = _RepairTotals()
     texts = {}
     for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
         s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
         idx, strs = _repair_chunk(_fc_cells(col, s0, s1), status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, min_vis, min_size)
         texts.update(zip((s0 + idx).tolist(), strs))
-    new_col = _splice_column(col, texts)
-    columns = [new_col if nm == json_col else (table.heavy[nm] if nm in table.heavy else light[nm]) for nm in table.names]
-    Path(output_csv_path).parent.mkdir(parents=True, exist_ok=True)
-    if not _fc.write_table(str(output_csv_path), table.names, columns, n):
+    if not _csv_write_spliced(output_csv_path, table, json_col, texts):
         return NotImplemented
-    return _repair_result(acc, n, status, light["source"].to_numpy() if "source" in light.columns else None)
+    return _repair_result(acc, n, status, sources)
 
 
 def repair_boxes_csv(input_csv_path, output_csv_path="repaired_boxes.csv", changes_csv=None, classes_csv=None,
@@ -2624,13 +2603,8 @@ def repair_boxes_csv(input_csv_path, output_csv_path="repaired_boxes.csv", chang
         res = _repair_csv_fast(input_csv_path, output_csv_path, json_col, min_vis, min_size, backend)
     if res is NotImplemented:
         LAST_IO_PATH["repair"] = "pandas"
-        try:
-            df = pd.read_csv(input_csv_path, encoding="utf-8-sig")
-        except Exception as e:
-            print(f"读取失败：{e}")
-            return None
-        if json_col not in df.columns:
-            print(f"错误：缺少必要列 {json_col}")
+        df = _csv_read_pandas(input_csv_path, json_col)
+        if df is None:
             return None
         totals = {}
         out, changes, per_class = repair_boxes_frame(df, json_col, min_visibility=min_vis, min_size=min_size,

@@ -1821,55 +1821,6 @@ int emit_changed_cells(dyd_scan *h, int n_threads, uint8_t *out_changed, const u
     return DYD_OK;
 }
 
-// the whole document of one cell with the objects whose drop_obj[k] is set left out ("objects" is a list: the cell had boxes)
-void emit_dropping_cell(Span cell, const std::vector<uint8_t> &drop_obj, std::string &out) {
-    Parser ps{cell.b, cell.e};
-    ps.ws();
-    if (ps.p >= ps.end || *ps.p != '{') ps.irregular();
-    ++ps.p;
-    out += '{';
-    bool first = true;
-    if (ps.peek() == '}') { ++ps.p; out += '}'; return; }
-    while (true) {
-        ps.ws();
-        const Span k = ps.string_token();
-        if (!first) out += ", ";
-        first = false;
-        ps.emit_string(out, k);
-        out += ": ";
-        ps.ws();
-        if (ps.p >= ps.end || *ps.p != ':') ps.bad();
-        ++ps.p;
-        if (Parser::span_is(k, "objects") && ps.peek() == '[') {
-            ++ps.p;
-            out += '[';
-            bool efirst = true;
-            if (ps.peek() == ']') {
-                ++ps.p;
-            } else {
-                for (size_t ko = 0;; ++ko) {
-                    const bool drop = ko < drop_obj.size() && drop_obj[ko];
-                    if (!drop && !efirst) out += ", ";
-                    if (!drop) efirst = false;
-                    ps.value(drop ? nullptr : &out);
-                    const char d = ps.peek();
-                    if (d == ',') { ++ps.p; continue; }
-                    if (d == ']') { ++ps.p; break; }
-                    ps.bad();
-                }
-            }
-            out += ']';
-        } else {
-            ps.value(&out);
-        }
-        const char d = ps.peek();
-        if (d == ',') { ++ps.p; continue; }
-        if (d == '}') { ++ps.p; break; }
-        ps.bad();
-    }
-    out += '}';
-}
-
 // box repair: K11's action code (bits 0-2) -> what happens to the box's object
 enum RepairMode : uint8_t { REPAIR_KEEP = 0, REPAIR_CLIP = 1, REPAIR_DROP = 2 };
 inline RepairMode repair_mode(uint8_t action) {
@@ -2035,15 +1986,15 @@ int dyd_json_emit_dropping(dyd_scan *h, const uint8_t *drop_per_box, int n_threa
     const int64_t nb = h->cell_box_off.empty() ? 0 : h->cell_box_off[(size_t)h->n_cells];
     if (nb > 0 && (!drop_per_box || (int64_t)h->box_obj.size() != nb)) return DYD_ERR_INVALID;
     return emit_changed_cells(h, n_threads, out_changed, out_text, out_off,
-                              [&](int64_t i, std::string &buf, std::vector<uint8_t> &drop_obj) {
+                              [&](int64_t i, std::string &buf, std::vector<uint8_t> &mode) {
         const int32_t b0 = h->cell_box_off[(size_t)i], b1 = h->cell_box_off[(size_t)i + 1];
         bool any = false;
         for (int32_t b = b0; b < b1; ++b) any |= drop_per_box[b] != 0;
         if (!any) return false;
-        drop_obj.assign((size_t)h->box_obj[(size_t)b1 - 1] + 1, 0);
+        mode.assign((size_t)h->box_obj[(size_t)b1 - 1] + 1, REPAIR_KEEP);
         for (int32_t b = b0; b < b1; ++b)
-            if (drop_per_box[b]) drop_obj[(size_t)h->box_obj[(size_t)b]] = 1;
-        emit_dropping_cell(h->src.get(i), drop_obj, buf);
+            if (drop_per_box[b]) mode[(size_t)h->box_obj[(size_t)b]] = REPAIR_DROP;
+        emit_repaired_cell(h->src.get(i), mode, {}, buf);
         return true;
     });
 }

@@ -26,7 +26,7 @@
 //   - "images" (rows with a box of the class): a box counts when no earlier box of its row has its class — the earlier lanes of
 //     its row in the wave's LDS copy of the class ids, and for a row that started in an earlier 64-box chunk its earlier ids in
 //     HBM (L2).
-#include "dyd_common.h"
+#include "box_table.h"
 
 namespace dyd {
 
@@ -49,11 +49,6 @@ struct K10Shared {
     uint32_t rowc[K10_WAVES][K10_WROWS * K10_ROWC];
     int32_t ids[K10_WAVES][kWave];
 };
-
-__device__ __forceinline__ void k10_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __device__ __forceinline__ int k10_bin(double v, int nb) {
     double f = floor(v * (double)nb);
@@ -104,7 +99,7 @@ __global__ __launch_bounds__(K10_BLOCK) void k10_audit_kernel(const double *__re
             atomicAdd(&S.bpi[n_row < K10_BPI - 1 ? n_row : K10_BPI - 1], 1u);
         }
         for (int k = lane; k < K10_WROWS * K10_ROWC; k += kWave) rowc[k] = 0u;
-        k10_wave_sync();
+        box_wave_sync();
         const int32_t base = __shfl(my_off, 0);
         const int32_t end = __shfl(my_off, nr);
         for (int32_t cb = base; cb < end; cb += kWave) {   // wave-uniform
@@ -174,7 +169,7 @@ __global__ __launch_bounds__(K10_BLOCK) void k10_audit_kernel(const double *__re
             }
             // images: first box of its class in its row
             ids[lane] = c;
-            k10_wave_sync();
+            box_wave_sync();
             if (c >= 0) {
                 const int j0 = rs - cb;   // the row's first lane in this chunk (negative: the row started earlier)
                 bool seen = false;
@@ -185,7 +180,7 @@ __global__ __launch_bounds__(K10_BLOCK) void k10_audit_kernel(const double *__re
                         if (cls[k] == c) { seen = true; break; }
                 if (!seen) bits |= 1u << 8;
             }
-            k10_wave_sync();   // the next chunk overwrites ids
+            box_wave_sync();   // the next chunk overwrites ids
             // per-class counters: one group of equal class ids at a time
             unsigned long long pending = __ballot(bits != 0u);
             while (pending) {
@@ -217,9 +212,9 @@ __global__ __launch_bounds__(K10_BLOCK) void k10_audit_kernel(const double *__re
                 }
             }
         }
-        k10_wave_sync();
+        box_wave_sync();
         for (int k = lane; k < nr * K10_ROWC; k += kWave) out_rows[r0 * K10_ROWC + k] = (int32_t)rowc[k];
-        k10_wave_sync();   // the next tile clears rowc
+        box_wave_sync();   // the next tile clears rowc
     }
 
     __syncthreads();
@@ -292,40 +287,23 @@ int dyd_box_audit(const double *box4, const int32_t *row_off, int64_t n_rows, co
     DYD_REQUIRE(nbins >= 1 && nbins <= 64, "nbins must lie in 1..64");
     DYD_REQUIRE(out_boxes_per_image, "null pointer");
     DYD_REQUIRE(n_classes == 0 || (out_class_counts && out_hist_wh && out_hist_xy), "null pointer");
-    int64_t nb = 0;
-    if (n_rows > 0) {
-        DYD_REQUIRE(row_off && width && height && size_status && out_row_counts, "null pointer");
-        DYD_REQUIRE(row_off[0] == 0, "row_off[0] != 0");
-        for (int64_t i = 0; i < n_rows; ++i) DYD_REQUIRE(row_off[i + 1] >= row_off[i], "row_off not monotone");
-        nb = row_off[n_rows];
-    }
-    if (nb > 0) {
-        DYD_REQUIRE(box4 && cls && out_flag, "null pointer");
-        for (int64_t b = 0; b < nb; ++b) DYD_REQUIRE(cls[b] >= -1 && cls[b] < n_classes, "class id outside -1..n_classes-1");
-    }
-    const size_t hist_bytes = 8 * (size_t)n_classes * (size_t)nbins * (size_t)nbins;
-    DevBuf d_box, d_off, d_cls, d_w, d_h, d_st, d_flag, d_rows, d_cc, d_wh, d_xy, d_bpi;
+    int64_t nb;
     int rc;
-    if ((rc = d_box.alloc(32 * (size_t)nb)) || (rc = d_off.alloc(4 * (size_t)(n_rows + 1))) || (rc = d_cls.alloc(4 * (size_t)nb)) ||
-        (rc = d_w.alloc(8 * (size_t)n_rows)) || (rc = d_h.alloc(8 * (size_t)n_rows)) || (rc = d_st.alloc((size_t)n_rows)) ||
-        (rc = d_flag.alloc((size_t)nb)) || (rc = d_rows.alloc(4 * K10_ROWC * (size_t)n_rows)) ||
+    if ((rc = box_table_check(box4, row_off, n_rows, cls, width, height, size_status, n_classes, out_row_counts != nullptr,
+                              out_flag != nullptr, &nb)))
+        return rc;
+    BoxTableDev d;
+    if ((rc = d.upload(box4, row_off, n_rows, cls, width, height, size_status, nb))) return rc;
+    const size_t hist_bytes = 8 * (size_t)n_classes * (size_t)nbins * (size_t)nbins;
+    DevBuf d_flag, d_rows, d_cc, d_wh, d_xy, d_bpi;
+    if ((rc = d_flag.alloc((size_t)nb)) || (rc = d_rows.alloc(4 * K10_ROWC * (size_t)n_rows)) ||
         (rc = d_cc.alloc(8 * K10_CLSC * (size_t)n_classes)) || (rc = d_wh.alloc(hist_bytes)) || (rc = d_xy.alloc(hist_bytes)) ||
         (rc = d_bpi.alloc(8 * K10_BPI)))
         return rc;
     hipStream_t st = ctx().stream;
-    if (nb) {
-        DYD_HIP(hipMemcpyAsync(d_box.p, box4, 32 * (size_t)nb, hipMemcpyHostToDevice, st));
-        DYD_HIP(hipMemcpyAsync(d_cls.p, cls, 4 * (size_t)nb, hipMemcpyHostToDevice, st));
-    }
-    if (n_rows) {
-        DYD_HIP(hipMemcpyAsync(d_off.p, row_off, 4 * (size_t)(n_rows + 1), hipMemcpyHostToDevice, st));
-        DYD_HIP(hipMemcpyAsync(d_w.p, width, 8 * (size_t)n_rows, hipMemcpyHostToDevice, st));
-        DYD_HIP(hipMemcpyAsync(d_h.p, height, 8 * (size_t)n_rows, hipMemcpyHostToDevice, st));
-        DYD_HIP(hipMemcpyAsync(d_st.p, size_status, (size_t)n_rows, hipMemcpyHostToDevice, st));
-    }
     KernelTimer t(st);
-    rc = launch_k10(d_box.as<double>(), d_off.as<int32_t>(), n_rows, d_cls.as<int32_t>(), d_w.as<double>(), d_h.as<double>(),
-                    d_st.as<uint8_t>(), n_classes, nbins, d_flag.as<uint8_t>(), d_rows.as<int32_t>(), d_cc.as<int64_t>(),
+    rc = launch_k10(d.box.as<double>(), d.off.as<int32_t>(), n_rows, d.cls.as<int32_t>(), d.w.as<double>(), d.h.as<double>(),
+                    d.st.as<uint8_t>(), n_classes, nbins, d_flag.as<uint8_t>(), d_rows.as<int32_t>(), d_cc.as<int64_t>(),
                     d_wh.as<int64_t>(), d_xy.as<int64_t>(), d_bpi.as<int64_t>(), st);
     if (rc) return rc;
     t.finish();

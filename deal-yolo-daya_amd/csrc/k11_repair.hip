@@ -25,7 +25,7 @@
 //   - per-class counts: eight wave-wide ballots (one per action) per 64 boxes, then a match-any walk over the class ids
 //     (leader's class -> ballot of equal lanes -> popcount of its AND with each action ballot, all on the scalar unit) and one add
 //     per (class, action) into the block's LDS copy when C <= K11_LDS_CLASSES, else one u64 global atomic.
-#include "dyd_common.h"
+#include "box_table.h"
 
 namespace dyd {
 
@@ -40,11 +40,6 @@ struct K11Shared {
     uint32_t cls_cnt[K11_LDS_CLASSES * K11_ACT];
     uint32_t rowc[K11_WAVES][K11_WROWS * K11_ACT];
 };
-
-__device__ __forceinline__ void k11_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __global__ __launch_bounds__(K11_BLOCK) void k11_repair_kernel(const double *__restrict__ box4, const int32_t *__restrict__ row_off,
                                                                int64_t n_rows, const int32_t *__restrict__ cls,
@@ -75,7 +70,7 @@ __global__ __launch_bounds__(K11_BLOCK) void k11_repair_kernel(const double *__r
             my_h = height[r0 + lane];
         }
         for (int k = lane; k < K11_WROWS * K11_ACT; k += kWave) rowc[k] = 0u;
-        k11_wave_sync();
+        box_wave_sync();
         const int32_t base = __shfl(my_off, 0);
         const int32_t end = __shfl(my_off, nr);
         for (int32_t cb = base; cb < end; cb += kWave) {   // wave-uniform
@@ -156,9 +151,9 @@ __global__ __launch_bounds__(K11_BLOCK) void k11_repair_kernel(const double *__r
                 }
             }
         }
-        k11_wave_sync();
+        box_wave_sync();
         for (int k = lane; k < nr * K11_ACT; k += kWave) out_rows[r0 * K11_ACT + k] = (int32_t)rowc[k];
-        k11_wave_sync();   // the next tile clears rowc
+        box_wave_sync();   // the next tile clears rowc
     }
 
     if (lds_cls) {
@@ -215,38 +210,21 @@ int dyd_repair_boxes(const double *box4, const int32_t *row_off, int64_t n_rows,
     DYD_REQUIRE(min_visibility >= 0.0 && min_visibility <= 1.0, "min_visibility must lie in [0, 1]");
     DYD_REQUIRE(std::isfinite(min_size) && min_size >= 0.0, "min_size must be finite and >= 0");
     DYD_REQUIRE(n_classes == 0 || out_class_counts, "null pointer");
-    int64_t nb = 0;
-    if (n_rows > 0) {
-        DYD_REQUIRE(row_off && width && height && size_status && out_row_counts, "null pointer");
-        DYD_REQUIRE(row_off[0] == 0, "row_off[0] != 0");
-        for (int64_t i = 0; i < n_rows; ++i) DYD_REQUIRE(row_off[i + 1] >= row_off[i], "row_off not monotone");
-        nb = row_off[n_rows];
-    }
-    if (nb > 0) {
-        DYD_REQUIRE(box4 && cls && out_action && out_box4, "null pointer");
-        for (int64_t b = 0; b < nb; ++b) DYD_REQUIRE(cls[b] >= -1 && cls[b] < n_classes, "class id outside -1..n_classes-1");
-    }
-    DevBuf d_box, d_off, d_cls, d_w, d_h, d_st, d_act, d_obox, d_rows, d_cc;
+    int64_t nb;
     int rc;
-    if ((rc = d_box.alloc(32 * (size_t)nb)) || (rc = d_off.alloc(4 * (size_t)(n_rows + 1))) || (rc = d_cls.alloc(4 * (size_t)nb)) ||
-        (rc = d_w.alloc(8 * (size_t)n_rows)) || (rc = d_h.alloc(8 * (size_t)n_rows)) || (rc = d_st.alloc((size_t)n_rows)) ||
-        (rc = d_act.alloc((size_t)nb)) || (rc = d_obox.alloc(32 * (size_t)nb)) || (rc = d_rows.alloc(4 * K11_ACT * (size_t)n_rows)) ||
+    if ((rc = box_table_check(box4, row_off, n_rows, cls, width, height, size_status, n_classes, out_row_counts != nullptr,
+                              out_action && out_box4, &nb)))
+        return rc;
+    BoxTableDev d;
+    if ((rc = d.upload(box4, row_off, n_rows, cls, width, height, size_status, nb))) return rc;
+    DevBuf d_act, d_obox, d_rows, d_cc;
+    if ((rc = d_act.alloc((size_t)nb)) || (rc = d_obox.alloc(32 * (size_t)nb)) || (rc = d_rows.alloc(4 * K11_ACT * (size_t)n_rows)) ||
         (rc = d_cc.alloc(8 * K11_ACT * (size_t)n_classes)))
         return rc;
     hipStream_t st = ctx().stream;
-    if (nb) {
-        DYD_HIP(hipMemcpyAsync(d_box.p, box4, 32 * (size_t)nb, hipMemcpyHostToDevice, st));
-        DYD_HIP(hipMemcpyAsync(d_cls.p, cls, 4 * (size_t)nb, hipMemcpyHostToDevice, st));
-    }
-    if (n_rows) {
-        DYD_HIP(hipMemcpyAsync(d_off.p, row_off, 4 * (size_t)(n_rows + 1), hipMemcpyHostToDevice, st));
-        DYD_HIP(hipMemcpyAsync(d_w.p, width, 8 * (size_t)n_rows, hipMemcpyHostToDevice, st));
-        DYD_HIP(hipMemcpyAsync(d_h.p, height, 8 * (size_t)n_rows, hipMemcpyHostToDevice, st));
-        DYD_HIP(hipMemcpyAsync(d_st.p, size_status, (size_t)n_rows, hipMemcpyHostToDevice, st));
-    }
     KernelTimer t(st);
-    rc = launch_k11(d_box.as<double>(), d_off.as<int32_t>(), n_rows, d_cls.as<int32_t>(), d_w.as<double>(), d_h.as<double>(),
-                    d_st.as<uint8_t>(), n_classes, min_visibility, min_size, d_act.as<uint8_t>(), d_obox.as<double>(),
+    rc = launch_k11(d.box.as<double>(), d.off.as<int32_t>(), n_rows, d.cls.as<int32_t>(), d.w.as<double>(), d.h.as<double>(),
+                    d.st.as<uint8_t>(), n_classes, min_visibility, min_size, d_act.as<uint8_t>(), d_obox.as<double>(),
                     d_rows.as<int32_t>(), d_cc.as<int64_t>(), st);
     if (rc) return rc;
     t.finish();
