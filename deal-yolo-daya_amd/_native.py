@@ -119,6 +119,15 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "dyd_yolo_lines_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+    "dyd_yolo_seg_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "dyd_yolo_seg_lines_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.POINTER(C.c_int64), C.c_void_p]),
+    "dyd_json_scan_labelled_polygons": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+                                                  C.POINTER(C.c_void_p)]),
+    "dyd_json_scan_labelled_polygons_v": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+                                                    C.POINTER(C.c_void_p)]),
     "dyd_json_scan_polygons": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "dyd_json_emit_polygons": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
@@ -576,3 +585,39 @@ def yolo_lines(box4, row_off, sel, width, height, class_id):
     finally:
         L.dyd_host_free(text)
     return off, flag, data
+
+
+def yolo_seg_lines(xy, pt_off, row_off, sel, width, height, class_id):
+    """K13 over host arrays -> (text_off int64 [n+1], flag u8 [n], action u8 [n_polys], text bytes).  flag 2 rows carry no
+    text: the caller decides them (zero image size, negative class id).  Action codes: include/dyd.h."""
+    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1)
+    pt_off = np.ascontiguousarray(pt_off, dtype=np.int32)
+    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
+    n = len(row_off) - 1
+    width = np.ascontiguousarray(width, dtype=np.float64)
+    height = np.ascontiguousarray(height, dtype=np.float64)
+    class_id = np.ascontiguousarray(class_id, dtype=np.int32)
+    if n < 0 or len(width) != n or len(height) != n or len(class_id) != n:
+        raise ValueError("row_off / width / height / class_id sizes disagree")
+    nb = int(row_off[-1]) if n else 0
+    if len(pt_off) != nb + 1 or (nb and 2 * int(pt_off[-1]) != len(xy)):
+        raise ValueError("pt_off must hold one entry per polygon plus one and end at the number of points")
+    sel_p = None
+    if sel is not None:
+        sel = np.ascontiguousarray(sel, dtype=np.uint8)
+        if len(sel) != nb:
+            raise ValueError("sel size != number of polygons")
+        sel_p = _ptr(sel) if nb else None
+    off = np.zeros(n + 1, np.int64)
+    flag = np.zeros(n, np.uint8)
+    action = np.zeros(nb, np.uint8)
+    text, total = C.c_void_p(), C.c_int64()
+    L = lib()
+    check(L.dyd_yolo_seg_lines(_ptr(xy) if xy.size else None, _ptr(pt_off), _ptr(row_off), sel_p, _ptr(width), _ptr(height),
+                               _ptr(class_id), n, _ptr(off), _ptr(flag), _ptr(action) if nb else None, C.byref(text),
+                               C.byref(total)), "dyd_yolo_seg_lines")
+    try:
+        data = C.string_at(text.value, total.value) if total.value else b""
+    finally:
+        L.dyd_host_free(text)
+    return off, flag, action, data

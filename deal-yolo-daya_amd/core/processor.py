@@ -2621,6 +2621,181 @@ def repair_boxes_csv(input_csv_path, output_csv_path="repaired_boxes.csv", chang
     return {**totals, "output": output_csv_path, "changes_output": changes_csv, "classes_output": classes_csv}
 
 
+# =============================================================================== f7  YOLO segmentation label lines
+# One line per matched polygon, "cls x1 y1 ... xn yn" normalised to [0, 1] (YOLO segment models), each polygon clipped to the image
+# (include/dyd.h, K13, has the definition).  Native labelled-polygon scan (csrc/host_json.cpp; flatten.seg_cell_polygons for
+# irregular cells) -> K13 (csrc/k13_seg.hip) -> strings.
+SEG_ACTIONS = ("written", "clipped", "bad_coords", "too_few_points", "empty", "no_size")   # K13 codes 0..5
+_SEG_LIMIT = float(1 << 43)
+
+
+def _seg_backend(backend):
+    be = _backend(backend)
+    if not hasattr(be, "yolo_seg_lines"):
+        raise TypeError("backend lacks ['yolo_seg_lines']")
+    return be
+
+
+def _seg_size(v):
+    """float(v) of a usable image size, else None"""
+    if not isinstance(v, _NUMBER_TYPES):
+        return None
+    try:
+        f = float(v)
+    except OverflowError:
+        return None
+    return f if 0.0 < f < _SEG_LIMIT else None
+
+
+def _seg_clip(pts, W, H) -> list:
+    """Sutherland-Hodgman: x >= 0, x <= W, y >= 0, y <= H, intersections from p towards q"""
+    for axis, c, keep_ge in ((0, 0.0, True), (0, W, False), (1, 0.0, True), (1, H, False)):
+        out, n = [], len(pts)
+        for k in range(n):
+            p, q = pts[k], pts[(k + 1) % n]
+            pin = p[axis] >= c if keep_ge else p[axis] <= c
+            qin = q[axis] >= c if keep_ge else q[axis] <= c
+            if pin:
+                out.append(p)
+            if pin != qin:
+                if axis == 0:
+                    t = (c - p[0]) / (q[0] - p[0])
+                    out.append((c, p[1] + t * (q[1] - p[1])))
+                else:
+                    t = (c - p[1]) / (q[1] - p[1])
+                    out.append((p[0] + t * (q[0] - p[0]), c))
+        pts = out
+    return pts
+
+
+def _seg_lines_python(polygons, class_id, width, height) -> tuple:
+    """K13's definition on Python values, for the rows the device leaves to the host (class ids it does not print) and for
+    image sizes read from the image file: polygons = [[(x, y) as read]] -> (lines, action codes)"""
+    W, H = _seg_size(width), _seg_size(height)
+    if W is None or H is None:
+        return [], [5] * len(polygons)
+    lines, actions = [], []
+    for raw in polygons:
+        V = [(_audit_number(x), _audit_number(y)) for x, y in raw]
+        if not all(abs(v) < _SEG_LIMIT for pt in V for v in pt):        # NaN and inf fail too
+            actions.append(2)
+            continue
+        if len(V) < 2:
+            actions.append(3)
+            continue
+        if len(V) == 2:
+            (xa, ya), (xb, yb) = V
+            x1, x2, y1, y2 = min(xa, xb), max(xa, xb), min(ya, yb), max(ya, yb)
+            V = [(x1, y1), (x2, y1), (x2, y2), (x1, y2)]
+        out = _seg_clip(V, W, H)
+        xs, ys = [p[0] for p in out], [p[1] for p in out]
+        if len(out) < 3 or max(xs) - min(xs) <= 0 or max(ys) - min(ys) <= 0:
+            actions.append(4)
+            continue
+        actions.append(1 if any(not (0.0 <= x <= W and 0.0 <= y <= H) for x, y in V) else 0)
+        n = lambda v: 0.0 if v <= 0.0 else (1.0 if v >= 1.0 else v)   # noqa: E731
+        lines.append(f"{class_id}" + "".join(f" {n(x / W):.6f} {n(y / H):.6f}" for x, y in out))
+    return lines, actions
+
+
+def yolo_seg_label_texts(cells, label_values, class_ids, widths, heights, backend=None, stats: Optional[dict] = None):
+    """Segmentation label-file text per row of a split sheet, with the conventions of ``yolo_label_texts``: -> (texts, reasons),
+    texts[i] = the row's lines joined with "\n" or None, reasons[i] = 无匹配标签框 (no polygon carries the row's label), 缺少图像尺寸
+    (`not w or not h`) or 标注框无效 (no line) for a None.  cells[i] is the polygon column's JSON, the other arguments as in
+    yolo_label_texts.  ``stats`` gets rows, polygons (matched polygons given an action), one count per SEG_ACTIONS entry and
+    two_point (matched polygons of exactly two points).
+    Host: native labelled-polygon scan (csrc/host_json.cpp; CPython json for irregular cells) + label match; device: K13
+    (clipping, exact "%.6f", joining)."""
+    be = _seg_backend(backend)
+    n = len(cells)
+    texts, reasons = [None] * n, [None] * n
+    acts = np.zeros(256, np.int64)
+    st = {"rows": n, "device_rows": 0, "python_rows": 0, "python_cells": 0, "two_point": 0}
+    status, W, H = _audit_sizes(widths, heights, n) if n else (np.zeros(0, np.uint8), np.zeros(0), np.zeros(0))
+    W, H = np.where(status == 2, np.nan, W), np.where(status == 2, np.nan, H)     # unusable sizes: every polygon no_size
+    cid_dev = np.zeros(n, np.int32)
+    cid_ok = np.zeros(n, bool)
+    for i, c in enumerate(class_ids):
+        if isinstance(c, (int, np.integer)) and not isinstance(c, (bool, np.bool_)) and 0 <= c < (1 << 31):
+            cid_dev[i], cid_ok[i] = c, True
+    rest = list(range(n))
+    host_rows = {}                                       # row -> matched polygons, printed by _seg_lines_python
+
+    def run(rows, xy, pt_off, row_off, sel):
+        """K13 over the batch whose k-th row is rows[k]; rows the host decides (missing size, no match) get zero sizes"""
+        live = np.zeros(len(rows), bool)
+        for k, i in enumerate(rows):
+            b0, b1 = row_off[k], row_off[k + 1]
+            n_sel = int(sel[b0:b1].sum()) if sel is not None else b1 - b0
+            if n_sel == 0:
+                reasons[i] = REASON_NO_MATCHING_BOX
+            elif status[i] == 1:
+                reasons[i] = REASON_NO_IMAGE_SIZE
+            else:
+                live[k] = True
+        if not live.any():
+            return
+        ridx = np.asarray(rows, np.int64)
+        w_dev, h_dev = np.where(live, W[ridx], 0.0), np.where(live, H[ridx], 0.0)
+        off, flag, action, data = be.yolo_seg_lines(xy, pt_off, row_off, sel, w_dev, h_dev, cid_dev[ridx])
+        row_off = np.asarray(row_off, np.int64)
+        npts = np.diff(np.asarray(pt_off, np.int64))
+        for k in np.flatnonzero(live).tolist():
+            i, b0, b1 = rows[k], int(row_off[k]), int(row_off[k + 1])
+            m = slice(b0, b1)
+            chosen = action[m] != 255
+            st["two_point"] += int((npts[m][chosen] == 2).sum())
+            if not cid_ok[i]:                            # the device printed nothing for this class id
+                host_rows[i] = [xy[2 * pt_off[b]:2 * pt_off[b + 1]].reshape(-1, 2).tolist()
+                                for b in range(b0, b1) if sel is None or sel[b]]
+                continue
+            np.add.at(acts, action[m][chosen], 1)
+            if flag[k] == 0:
+                texts[i] = data[off[k]:off[k + 1]].decode("ascii")
+            else:
+                reasons[i] = REASON_NO_VALID_BOX
+            st["device_rows"] += 1
+
+    if n and _nj.enabled() and all(type(v) is str for v in label_values):
+        try:
+            scan = _nj.scan_labelled_polygons(cells, label_values)
+        except UnicodeEncodeError:
+            scan = None
+        if scan is not None:
+            regular = scan.status != _nj.IRREGULAR
+            rows = list(range(n))
+            off = scan.cell_box_off.astype(np.int64)
+            run(rows, scan.xy, scan.pt_off, off, scan.sel)
+            for i in np.flatnonzero(~regular).tolist():   # irregular cells hold no polygons here: the Python path decides them
+                reasons[i] = None
+            rest = np.flatnonzero(~regular).tolist()
+            scan.close()
+    st["python_cells"] = len(rest)
+    if rest:
+        xy, pt_off, row_off = [], [0], [0]
+        for i in rest:
+            for _, name, pts in _fl.seg_cell_polygons(cells[i]):
+                if name == label_values[i]:
+                    for x, y in pts:
+                        xy.extend((_audit_number(x), _audit_number(y)))
+                    pt_off.append(len(xy) // 2)
+            row_off.append(len(pt_off) - 1)
+        run(rest, np.asarray(xy, np.float64), np.asarray(pt_off, np.int32), np.asarray(row_off, np.int32), None)
+        for i in rest:                                   # the host prints from the values as read, not their float()
+            if i in host_rows:
+                host_rows[i] = [pts for _, name, pts in _fl.seg_cell_polygons(cells[i]) if name == label_values[i]]
+    for i, polys in host_rows.items():
+        lines, actions = _seg_lines_python(polys, class_ids[i], widths[i], heights[i])
+        np.add.at(acts, np.asarray(actions, np.int64), 1)
+        texts[i], reasons[i] = ("\n".join(lines), None) if lines else (None, REASON_NO_VALID_BOX)
+        st["python_rows"] += 1
+    st["polygons"] = int(acts[:len(SEG_ACTIONS)].sum())
+    st.update({a: int(acts[k]) for k, a in enumerate(SEG_ACTIONS)})
+    if stats is not None:
+        stats.update(st)
+    return texts, reasons
+
+
 def generate_yolo_datasets_from_excels(
         category_excels: list,
         output_dir: str,
@@ -2637,9 +2812,14 @@ def generate_yolo_datasets_from_excels(
         resume: bool = True,
         progress_callback=None,
         backend=None,
+        task: str = "detect",
 ):
     """Drop-in for reference processor.py:893-1093: one YOLO dataset directory per category workbook
     (images/<split>, labels/<split>, data.yaml) plus yolo_skipped.xlsx.
+
+    task="detect" writes box lines (the reference's); task="segment" writes one polygon line per matched object for YOLO
+    segment models (``yolo_seg_label_texts`` -> K13), reading ``row.get(json_col_fallback) or row.get(json_col_primary)``: the
+    annotation polygons first, which a split with json_columns=[ANNOTATION_COL, BBOX_COL] carries.
 
     Per split sheet the rows are shuffled like ``sample(frac=1, random_state=seed)`` (host MT19937), the label
     texts of all rows are produced in one batch (``yolo_label_texts`` -> K7) and the per-row side effects (resume
@@ -2647,7 +2827,11 @@ def generate_yolo_datasets_from_excels(
     size comes from the image file rather than from the sheet (:1015-1020) are printed on the host."""
     import yaml
 
-    be = _backend(backend)
+    if task not in ("detect", "segment"):
+        raise ValueError(f"task must be 'detect' or 'segment', not {task!r}")
+    segment = task == "segment"
+    be = _seg_backend(backend) if segment else _backend(backend)
+    seg_stats = {"polygons": 0, "two_point": 0}
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     cache_dir = Path(image_cache_dir) if image_cache_dir else (output_dir / "image_cache")
@@ -2708,12 +2892,21 @@ def generate_yolo_datasets_from_excels(
             sources, widths, heights = get(source_col), get(width_col), get(height_col)
             labels = [str(v) for v in get(label_col, "")]
             primary, fallback = get(json_col_primary), get(json_col_fallback)
-            cells = [a or b for a, b in zip(primary, fallback)]          # row.get(primary) or row.get(fallback) (:1004)
+            if segment:                                                  # the polygons first
+                cells = [b or a for a, b in zip(primary, fallback)]
+            else:
+                cells = [a or b for a, b in zip(primary, fallback)]      # row.get(primary) or row.get(fallback) (:1004)
             usable = [bool(src) and bool(lab) and lab in class_to_id for src, lab in zip(sources, labels)]
             batch = [i for i, ok in enumerate(usable) if ok]
-            texts, reasons = yolo_label_texts([cells[i] for i in batch], [labels[i] for i in batch],
-                                              [class_to_id[labels[i]] for i in batch], [widths[i] for i in batch],
-                                              [heights[i] for i in batch], be)
+            args = ([cells[i] for i in batch], [labels[i] for i in batch], [class_to_id[labels[i]] for i in batch],
+                    [widths[i] for i in batch], [heights[i] for i in batch], be)
+            if segment:
+                sst = {}
+                texts, reasons = yolo_seg_label_texts(*args, stats=sst)
+                for key in seg_stats:
+                    seg_stats[key] += sst[key]
+            else:
+                texts, reasons = yolo_label_texts(*args)
             text_of = dict(zip(batch, zip(texts, reasons)))
 
             for idx in range(len(frame)):
@@ -2747,8 +2940,12 @@ def generate_yolo_datasets_from_excels(
                         from PIL import Image
                         with Image.open(image_path) as img:
                             width, height = img.size
-                        boxes = [b for b in _extract_boxes_with_labels(cells[idx]) if b[0] == label_value]
-                        lines = _label_lines_python(boxes, class_to_id[label_value], width, height)
+                        if segment:
+                            polys = [pts for _, name, pts in _fl.seg_cell_polygons(cells[idx]) if name == label_value]
+                            lines = _seg_lines_python(polys, class_to_id[label_value], width, height)[0]
+                        else:
+                            boxes = [b for b in _extract_boxes_with_labels(cells[idx]) if b[0] == label_value]
+                            lines = _label_lines_python(boxes, class_to_id[label_value], width, height)
                         text, reason = ("\n".join(lines), None) if lines else (None, REASON_NO_VALID_BOX)
                     except Exception:  # noqa: BLE001
                         pass
@@ -2777,6 +2974,10 @@ def generate_yolo_datasets_from_excels(
             "nc": len(classes), "names": classes}, sort_keys=False, allow_unicode=True), encoding="utf-8")
         datasets.append(dataset_dir)
 
+    if segment and seg_stats["polygons"] and seg_stats["two_point"] == seg_stats["polygons"]:
+        print(f"task='segment': every one of the {seg_stats['polygons']} matched polygons has 2 points, so every label is a "
+              f"rectangle: the workbooks hold boxes only.  Split with json_columns=[ANNOTATION_COL, BBOX_COL] to carry the "
+              f"annotation polygons.")
     skipped_path = output_dir / "yolo_skipped.xlsx"
     pd.DataFrame(skipped if skipped else [{"category": "无", "reason": "无", "split": "无"}]).to_excel(skipped_path, index=False)
     if progress_callback and last is not None:

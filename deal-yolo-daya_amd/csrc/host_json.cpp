@@ -2958,7 +2958,9 @@ double coord_value(Parser &ps, Span tok) {
 
 // regular cells only; anything the reference treats through an exception or a non-list container throws Fail{2}.
 // Every box goes to sk.box(object index, decoded name, {min x, min y, max x, max y}): the YOLO step compares the name with the
-// row's label (LabelSink), the box audit numbers the names (NameSink).
+// row's label (LabelSink), the box audit numbers the names (NameSink).  A sink with kPoints also gets the object's polygon:
+// sk.begin_object() before each dict object, sk.point(x, y) for every ptList dict holding both "x" and "y", and
+// sk.drop_object() after an object that gives no box (SegSink).
 template <class Sink>
 void named_boxes_cell(Span cell, Sink &sk, int32_t &count) {
     count = 0;
@@ -2990,6 +2992,7 @@ void named_boxes_cell(Span cell, Sink &sk, int32_t &count) {
                         ps.value(nullptr);                      // non-dict objects are skipped (:689)
                     } else {
                         ++ps.p;
+                        if constexpr (Sink::kPoints) sk.begin_object();
                         KeySet oks;
                         bool has_name = false, truthy = false, has_box = false;
                         MinMax xs, ys;
@@ -3037,6 +3040,8 @@ void named_boxes_cell(Span cell, Sink &sk, int32_t &count) {
                                                         } else {
                                                             ++ps.p;
                                                             KeySet qks;
+                                                            bool has_x = false, has_y = false;
+                                                            double vx = 0, vy = 0;
                                                             if (ps.peek() == '}') {
                                                                 ++ps.p;
                                                             } else {
@@ -3050,13 +3055,16 @@ void named_boxes_cell(Span cell, Sink &sk, int32_t &count) {
                                                                     ps.ws();
                                                                     const char *b = ps.p;
                                                                     ps.value(nullptr);
-                                                                    if (Parser::span_is(qk, "x")) xs.add(coord_value(ps, Span{b, ps.p}));
-                                                                    else if (Parser::span_is(qk, "y")) ys.add(coord_value(ps, Span{b, ps.p}));
+                                                                    if (Parser::span_is(qk, "x")) { vx = coord_value(ps, Span{b, ps.p}); xs.add(vx); has_x = true; }
+                                                                    else if (Parser::span_is(qk, "y")) { vy = coord_value(ps, Span{b, ps.p}); ys.add(vy); has_y = true; }
                                                                     const char d = ps.peek();
                                                                     if (d == ',') { ++ps.p; continue; }
                                                                     if (d == '}') { ++ps.p; break; }
                                                                     ps.bad();
                                                                 }
+                                                            }
+                                                            if constexpr (Sink::kPoints) {
+                                                                if (has_x && has_y) sk.point(vx, vy);
                                                             }
                                                         }
                                                         const char d = ps.peek();
@@ -3086,6 +3094,8 @@ void named_boxes_cell(Span cell, Sink &sk, int32_t &count) {
                             const double v[4] = {xs.lo, ys.lo, xs.hi, ys.hi};
                             sk.box(k_obj, name, v);
                             ++count;
+                        } else {
+                            if constexpr (Sink::kPoints) sk.drop_object();
                         }
                     }
                     const char d = ps.peek();
@@ -3105,6 +3115,7 @@ void named_boxes_cell(Span cell, Sink &sk, int32_t &count) {
 }
 
 struct LabelSink {
+    static constexpr bool kPoints = false;
     std::string_view label;
     std::vector<double> &box4;
     std::vector<uint8_t> &sel;
@@ -3119,8 +3130,85 @@ void labelled_cell(Span cell, std::string_view label, std::vector<double> &box4,
     named_boxes_cell(cell, sk, count);
 }
 
+// segmentation labels: LabelSink's boxes with each object's points
+struct SegSink {
+    static constexpr bool kPoints = true;
+    std::string_view label;
+    std::vector<double> xy;       // points of the kept objects, (x, y)
+    std::vector<int32_t> npts;    // points per kept object
+    std::vector<uint8_t> sel;
+    size_t mark = 0;              // xy.size() when the current object began
+    void begin_object() { mark = xy.size(); }
+    void point(double x, double y) {
+        xy.push_back(x);
+        xy.push_back(y);
+    }
+    void drop_object() { xy.resize(mark); }
+    void box(int32_t, const std::string &name, const double *) {
+        npts.push_back((int32_t)((xy.size() - mark) / 2));
+        sel.push_back(std::string_view(name) == label ? 1 : 0);
+    }
+};
+
+int scan_labelled_polygons_src(const CellSrc &src, const uint8_t *missing, int64_t n_cells, const uint8_t *label_text,
+                               const int64_t *label_off, int n_threads, dyd_scan **out) {
+    dyd_scan *h = new (std::nothrow) dyd_scan();
+    if (!h) return DYD_ERR_OOM;
+    h->n_cells = n_cells;
+    h->src = src;
+    try {
+        h->status.assign((size_t)n_cells, CELL_OK);
+        std::vector<int32_t> counts((size_t)n_cells, 0);
+        struct Part { SegSink sk; int64_t lo = 0, hi = 0; };
+        std::vector<Part> parts(64);
+        if (n_threads <= 0 || n_threads > 64) n_threads = default_threads();
+        const bool ok = parallel_cells_safe(n_cells, n_threads, [&](int t, int64_t lo, int64_t hi) {
+            Part &pt = parts[(size_t)t];
+            pt.lo = lo; pt.hi = hi;
+            for (int64_t i = lo; i < hi; ++i) {
+                if (missing && missing[i]) { h->status[(size_t)i] = CELL_MISSING; continue; }
+                const size_t mxy = pt.sk.xy.size(), mb = pt.sk.sel.size();
+                pt.sk.label = std::string_view((const char *)label_text + label_off[i], (size_t)(label_off[i + 1] - label_off[i]));
+                int32_t c = 0;
+                try {
+                    named_boxes_cell(src.get(i), pt.sk, c);
+                } catch (Fail f) {
+                    pt.sk.xy.resize(mxy); pt.sk.npts.resize(mb); pt.sk.sel.resize(mb);
+                    c = 0;
+                    h->status[(size_t)i] = (f.code == 1) ? CELL_UNDECODABLE : CELL_IRREGULAR;
+                }
+                counts[(size_t)i] = c;
+            }
+        });
+        if (!ok) { delete h; return DYD_ERR_OOM; }
+        std::sort(parts.begin(), parts.end(), [](const Part &a, const Part &b) { return a.lo < b.lo; });
+        size_t nb = 0, np = 0;
+        for (auto &pt : parts) { nb += pt.sk.sel.size(); np += pt.sk.xy.size() / 2; }
+        if (nb >= (size_t)1 << 31 || np >= (size_t)1 << 31) { delete h; return DYD_ERR_RANGE; }
+        h->xy.reserve(2 * np);
+        h->sel.reserve(nb);
+        h->pt_off.reserve(nb + 1);
+        h->pt_off.assign(1, 0);
+        for (auto &pt : parts) {
+            h->xy.insert(h->xy.end(), pt.sk.xy.begin(), pt.sk.xy.end());
+            h->sel.insert(h->sel.end(), pt.sk.sel.begin(), pt.sk.sel.end());
+            for (int32_t k : pt.sk.npts) h->pt_off.push_back(h->pt_off.back() + k);
+            pt.sk = SegSink();
+        }
+        h->cell_box_off.resize((size_t)n_cells + 1);
+        h->cell_box_off[0] = 0;
+        for (int64_t i = 0; i < n_cells; ++i) h->cell_box_off[(size_t)i + 1] = h->cell_box_off[(size_t)i] + counts[(size_t)i];
+    } catch (const std::bad_alloc &) {
+        delete h;
+        return DYD_ERR_OOM;
+    }
+    *out = h;
+    return DYD_OK;
+}
+
 // box audit: per box its object index and a class id local to the thread's part (first occurrence in the part's cell order)
 struct NameSink {
+    static constexpr bool kPoints = false;
     std::vector<double> box4;
     std::vector<int32_t> obj, name;
     std::vector<std::string> names;
@@ -3301,6 +3389,24 @@ int dyd_json_scan_labelled(const uint8_t *text, const int64_t *cell_off, const u
 }
 
 const uint8_t *dyd_scan_sel(const dyd_scan *h) { return h->sel.data(); }
+
+// Segmentation labels: the labelled scan's objects with their points (dyd_scan_xy, dyd_scan_pt_off), see include/dyd.h.
+int dyd_json_scan_labelled_polygons(const uint8_t *text, const int64_t *cell_off, const uint8_t *missing, int64_t n_cells,
+                                    const uint8_t *label_text, const int64_t *label_off, int n_threads, dyd_scan **out) {
+    if (!out || n_cells < 0 || (n_cells > 0 && (!cell_off || !text || !label_off))) return DYD_ERR_INVALID;
+    CellSrc src;
+    src.text = text; src.off = cell_off;
+    return scan_labelled_polygons_src(src, missing, n_cells, label_text, label_off, n_threads, out);
+}
+
+int dyd_json_scan_labelled_polygons_v(const uint8_t *const *cell_ptr, const int64_t *cell_len, const uint8_t *missing,
+                                      int64_t n_cells, const uint8_t *label_text, const int64_t *label_off, int n_threads,
+                                      dyd_scan **out) {
+    if (!out || n_cells < 0 || (n_cells > 0 && (!cell_ptr || !cell_len || !label_off))) return DYD_ERR_INVALID;
+    CellSrc src;
+    src.ptr = cell_ptr; src.len = cell_len;
+    return scan_labelled_polygons_src(src, missing, n_cells, label_text, label_off, n_threads, out);
+}
 
 }  // extern "C"
 

@@ -25,6 +25,7 @@
 // for more than the measuring of its predecessors), prints the rows into LDS at the same 16-byte phase as
 // their place in the output, and streams the LDS image out with 16-byte stores.
 #include "dyd_common.h"
+#include "round6.h"
 
 namespace dyd {
 
@@ -45,18 +46,6 @@ struct Num6 {
     __device__ __forceinline__ uint32_t kind() const { return meta & 3u; }
     __device__ __forceinline__ uint32_t neg() const { return meta >> 2; }
 };
-
-// round-half-even(a * 10^6) for 0 <= a < 4294, exactly: a * 10^6 = t + e with t the rounded product and e the
-// error term an FMA returns exactly; t = n + f (n integer, f exact).  f != 1/2 is at least ulp(t) >= 2|e| away
-// from one half, so it decides alone; at f == 1/2 the sign of e decides and e == 0 is a true tie.
-__device__ __forceinline__ uint32_t round6(double a) {
-    const double t = a * 1.0e6;
-    const double e = fma(a, 1.0e6, -t);
-    const uint32_t n = (uint32_t)t;
-    const double f = t - (double)n;
-    const bool up = (f > 0.5) || (f == 0.5 && (e > 0.0 || (e == 0.0 && (n & 1u))));
-    return n + (up ? 1u : 0u);
-}
 
 // exact |v| * 10^6 rounded half-to-even, split into integer part and six decimals
 __device__ __forceinline__ Num6 classify(double v) {

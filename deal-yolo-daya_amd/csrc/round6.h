@@ -1,0 +1,22 @@
+// round6.h — exact "%.6f" rounding shared by the label-line kernels (K7 boxes, K13 polygons).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace dyd {
+
+// round-half-even(a * 10^6) for 0 <= a < 4294, exactly: a * 10^6 = t + e with t the rounded product and e the
+// error term an FMA returns exactly; t = n + f (n integer, f exact).  f != 1/2 is at least ulp(t) >= 2|e| away
+// from one half, so it decides alone; at f == 1/2 the sign of e decides and e == 0 is a true tie.
+__device__ __forceinline__ uint32_t round6(double a) {
+    const double t = a * 1.0e6;
+    const double e = fma(a, 1.0e6, -t);
+    const uint32_t n = (uint32_t)t;
+    const double f = t - (double)n;
+    const bool up = (f > 0.5) || (f == 0.5 && (e > 0.0 || (e == 0.0 && (n & 1u))));
+    return n + (up ? 1u : 0u);
+}
+
+}  // namespace dyd

@@ -303,6 +303,21 @@ def audit_cell_boxes(cell) -> list:
     return collected
 
 
+def seg_cell_polygons(cell) -> list:
+    """The segmentation step's polygons of one cell on the host, for the cells the native scanner leaves to Python: the
+    objects of audit_cell_boxes (the YOLO step's objects, the prefix kept on any exception) with their points ->
+    [(index of the object in "objects", name, [(x, y) of every ptList dict holding both "x" and "y", as read])]."""
+    boxes = audit_cell_boxes(cell)
+    if not boxes:
+        return []
+    objs = json.loads(cell)["objects"]                  # the walk above got this far without an exception
+    out = []
+    for k, name, *_ in boxes:
+        pts = objs[k]["polygon"]["ptList"]
+        out.append((k, name, [(pt["x"], pt["y"]) for pt in pts if isinstance(pt, dict) and "x" in pt and "y" in pt]))
+    return out
+
+
 def repair_cell(cell, decisions) -> str:
     """One cell re-spelled by the box repair step from decisions already made (K11): ``decisions`` maps the index of an object
     in "objects" to None (the object is left out) or to the clipped corners (x1', y1', x2', y2'), which replace its

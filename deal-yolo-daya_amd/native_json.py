@@ -958,3 +958,41 @@ def scan_labelled(cells, labels, n_threads: int = 0) -> LabelledScan:
     _native.check(L.dyd_json_scan_labelled(buf.ctypes.data, off.ctypes.data, missing.ctypes.data, len(cells), lab_buf.ctypes.data,
                                            lab_off.ctypes.data, n_threads, C.byref(h)), "dyd_json_scan_labelled")
     return LabelledScan(h, len(cells), (keep, lab_buf, lab_off))
+
+
+class LabelledPolygonScan(_Scan):
+    """scan_labelled's objects with their polygons: xy (x, y) f64 [2*P] (ptList dicts holding both "x" and "y", in order),
+    pt_off [n_boxes+1], cell_box_off, sel (name == the row's label).  Arrays are copies: they outlive the handle."""
+
+    def __init__(self, handle, n_cells, keep):
+        super().__init__(handle, n_cells, keep)
+        L = _native.load_library()
+        nb = int(self.cell_box_off[-1]) if n_cells else 0
+        self.n_boxes = nb
+        self.pt_off = _view(L.dyd_scan_pt_off(handle), np.int32, nb + 1).copy()
+        self.xy = _view(L.dyd_scan_xy(handle), np.float64, 2 * int(self.pt_off[-1])).copy()
+        self.sel = _view(L.dyd_scan_sel(handle), np.uint8, nb).copy()
+
+
+def scan_labelled_polygons(cells, labels, n_threads: int = 0) -> LabelledPolygonScan:
+    """cells: annotation JSON per row; labels: the row's label value (str) per row.  Raises UnicodeEncodeError for a label or,
+    when the cells have to be encoded, a cell holding a lone surrogate."""
+    from . import pycells
+
+    L = _native.load_library()
+    lab = [s.encode("utf-8") for s in labels]
+    lab_off = np.zeros(len(lab) + 1, np.int64)
+    np.cumsum(np.fromiter(map(len, lab), dtype=np.int64, count=len(lab)), out=lab_off[1:])
+    lab_buf = np.frombuffer(b"".join(lab) or b"\0", dtype=np.uint8)
+    h = C.c_void_p()
+    if pycells.available():
+        v = pycells.CellViews(cells.to_numpy() if hasattr(cells, "to_numpy") else cells)
+        _native.check(L.dyd_json_scan_labelled_polygons_v(v.ptr.ctypes.data, v.len.ctypes.data, v.missing.ctypes.data, len(v),
+                                                          lab_buf.ctypes.data, lab_off.ctypes.data, n_threads, C.byref(h)),
+                      "dyd_json_scan_labelled_polygons_v")
+        return LabelledPolygonScan(h, len(v), (v, lab_buf, lab_off))
+    buf, off, missing, keep = cells_to_buffers(cells)
+    _native.check(L.dyd_json_scan_labelled_polygons(buf.ctypes.data, off.ctypes.data, missing.ctypes.data, len(off) - 1,
+                                                    lab_buf.ctypes.data, lab_off.ctypes.data, n_threads, C.byref(h)),
+                  "dyd_json_scan_labelled_polygons")
+    return LabelledPolygonScan(h, len(off) - 1, (keep, buf, off, missing, lab_buf, lab_off))

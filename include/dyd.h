@@ -349,6 +349,41 @@ int dyd_yolo_lines_dev(const double *box4, const int32_t *row_off, const uint8_t
                        int64_t n_boxes, int64_t *out_text_off, uint8_t *out_flag, uint8_t *out_text_or_null, int64_t text_cap,
                        int64_t *out_total, void *stream);
 
+/* ---- K13: YOLO segmentation label lines --------------------------------------------------
+ * One line per polygon that carries the row's label, "cls x1 y1 ... xn yn" (YOLO segment models), for
+ * generate_yolo_datasets_from_excels(task="segment").  Per polygon, the first rule that applies gives its action:
+ *   5 no_size        the row's width or height is not finite or not in (0, 2^43);
+ *   2 bad_coords     a coordinate is not finite or |v| >= 2^43;
+ *   3 too_few_points fewer than 2 points (two points become the four corners of their box);
+ *   then Sutherland-Hodgman clips the points to [0, W] x [0, H] (passes x >= 0, x <= W, y >= 0, y <= H, each
+ *   intersection from the edge's first point towards its second, IEEE f64 without contraction);
+ *   4 empty          fewer than 3 clipped vertices, or a clipped width or height <= 0;
+ *   1 clipped        some point lies outside the image;  0 written  otherwise;  255 the polygon is not selected.
+ * A line is "{cls}" then " {n(x/W):.6f} {n(y/H):.6f}" per clipped vertex, n clamping to [0, 1] (8 bytes per value,
+ * "%.6f" exact, ties to even), so digits(cls) + 18 * m bytes; a row's lines are joined with "\n".
+ * xy           : points as given, (x, y) f64                                   [2*n_points]
+ * pt_off       : points of polygon p are [pt_off[p], pt_off[p+1])             [n_polys+1]
+ * row_off      : polygons of row i are [row_off[i], row_off[i+1])             [n_rows+1]
+ * sel_or_null  : 1 = the polygon carries the row's label, NULL = all          [n_polys]
+ * width/height : the row's image size                                         [n_rows]
+ * class_id     : the row's class id                                           [n_rows]
+ * out_text_off : byte range of row i in the text = [off[i], off[i+1])         [n_rows+1]
+ * out_flag     : 0 text written, 1 no line, 2 left to the host (zero width / height, negative class id)  [n_rows]
+ * out_action   : the codes above                                              [n_polys]
+ * dyd_yolo_seg_lines     : host pointers; *out_text is allocated by the library (release with dyd_host_free).
+ * dyd_yolo_seg_lines_dev : device pointers; out_text_or_null == NULL only measures (offsets, flags, actions, total);
+ *                          otherwise text_cap bytes are available and DYD_ERR_RANGE is returned, with the needed size
+ *                          in *out_total, when that is too little.  *out_total is a HOST int64.
+ *                          n_polys = row_off[n_rows], n_points = pt_off[n_polys]. */
+int dyd_yolo_seg_lines(const double *xy, const int32_t *pt_off, const int32_t *row_off, const uint8_t *sel_or_null,
+                       const double *width, const double *height, const int32_t *class_id, int64_t n_rows,
+                       int64_t *out_text_off, uint8_t *out_flag, uint8_t *out_action, uint8_t **out_text,
+                       int64_t *out_text_len);
+int dyd_yolo_seg_lines_dev(const double *xy, const int32_t *pt_off, const int32_t *row_off, const uint8_t *sel_or_null,
+                           const double *width, const double *height, const int32_t *class_id, int64_t n_rows,
+                           int64_t n_polys, int64_t n_points, int64_t *out_text_off, uint8_t *out_flag, uint8_t *out_action,
+                           uint8_t *out_text_or_null, int64_t text_cap, int64_t *out_total, void *stream);
+
 /* ---- native flatten / emit (HOST code, multithreaded) ------------------------------
  * Schema-specialised JSON scanner + canonical re-emitter that replaces json.loads / json.dumps inside
  * parse_and_replace_ptlist (processor.py:262-281), extract_width_height (:285-292) and extract_boxes
@@ -406,6 +441,15 @@ int dyd_json_scan_polygons_v(const uint8_t *const *cell_ptr, const int64_t *cell
 int dyd_json_scan_labelled(const uint8_t *text, const int64_t *cell_off, const uint8_t *missing, int64_t n_cells,
                            const uint8_t *label_text, const int64_t *label_off, int n_threads, dyd_scan **out);
 const uint8_t *dyd_scan_sel(const dyd_scan *scan);             /* [n_boxes] (labelled scan only) */
+/* Segmentation labels: the labelled scan's walk (same objects, irregular cells and statuses) that also keeps each
+ * object's polygon: dyd_scan_xy = its points (x, y) as f64 [2*n_points], every ptList entry that is a dict holding both
+ * "x" and "y", in order; dyd_scan_pt_off [n_boxes+1]; dyd_scan_sel and dyd_scan_cell_box_off as dyd_json_scan_labelled.
+ * The _v form takes one (pointer, length) per cell. */
+int dyd_json_scan_labelled_polygons(const uint8_t *text, const int64_t *cell_off, const uint8_t *missing, int64_t n_cells,
+                                    const uint8_t *label_text, const int64_t *label_off, int n_threads, dyd_scan **out);
+int dyd_json_scan_labelled_polygons_v(const uint8_t *const *cell_ptr, const int64_t *cell_len, const uint8_t *missing,
+                                      int64_t n_cells, const uint8_t *label_text, const int64_t *label_off, int n_threads,
+                                      dyd_scan **out);
 /* Box audit: the labelled scan's walk (same boxes, same irregular cells) without a row label; per box
  * dyd_scan_box_object = index of its object in "objects" and dyd_scan_box_name = a table-wide class id, numbered
  * by first occurrence in cell order whatever the thread count.  The decoded names (UTF-8) of the ids are

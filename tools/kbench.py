@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmarks on one MI355X (device-resident inputs, HIP-event timing,
 interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant.
 
-    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone)
+    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k13: segmentation lines beside K7)
 """
 import argparse
 import json
@@ -429,6 +429,69 @@ def main():
             report(f"k7_yolo_lines_multi_box_rows_v{variant}", 32 * B + 4 * (N + 1) + 20 * N + 8 * (N + 1) + N + Tr, med, mn, rows=N, lines=B,
                    text_bytes=Tr, lines_per_s=round(B / med * 1e3))
         ck(L.dyd_set_option(b"k7_variant", -1), "opt")
+    if "k13" in only:
+        import ctypes as C
+        # K13 beside K7 on the same polygons.  Shapes: the split's record shape (one polygon per row: the 10 M-row table's 165 M
+        # polygons as 165 M rows, K7's "165 M records") and the synthetic rows as they are (U{1..32} polygons per row).
+        # Bytes: in 16*P + 4*(B+1) + B + 4*(N+1) + 20*N, out 8*(N+1) + N + B + T.
+        ck(L.dyd_bbox_minmax_dev(xy.data_ptr(), pt_off.data_ptr(), B, P, out_box.data_ptr(), out_arg.data_ptr(), sp), "k1")
+        total = C.c_int64()
+        act = torch.empty(B, dtype=torch.uint8, device=dev)
+
+        def shapes():
+            one = torch.arange(B + 1, dtype=torch.int32, device=dev)
+            yield "records", one, B
+            yield "rows", box_off, N
+
+        for shape, roff, nr in shapes():
+            w = torch.full((nr,), 1920.0, dtype=torch.float64, device=dev); h = torch.full((nr,), 1080.0, dtype=torch.float64, device=dev)
+            cid = (torch.arange(nr, device=dev, dtype=torch.int32) % 20).contiguous()
+            toff = torch.empty(nr + 1, dtype=torch.int64, device=dev); flag = torch.empty(nr, dtype=torch.uint8, device=dev)
+            seg_args = (xy.data_ptr(), pt_off.data_ptr(), roff.data_ptr(), None, w.data_ptr(), h.data_ptr(), cid.data_ptr(), nr, B, P,
+                        toff.data_ptr(), flag.data_ptr(), act.data_ptr())
+            ck(L.dyd_yolo_seg_lines_dev(*seg_args, None, 0, C.byref(total), sp), "k13 measure")
+            T13 = total.value
+            text = torch.empty(T13, dtype=torch.uint8, device=dev)
+            counts = torch.bincount(act.to(torch.int64), minlength=256)[:6].tolist()
+            ck(L.dyd_yolo_lines_dev(out_box.data_ptr(), roff.data_ptr(), None, w.data_ptr(), h.data_ptr(), cid.data_ptr(), nr, B,
+                                    toff.data_ptr(), flag.data_ptr(), None, 0, C.byref(total), sp), "k7 measure")
+            T7 = total.value
+            text7 = torch.empty(T7, dtype=torch.uint8, device=dev)
+            res = {}
+            for rnd in range(2):                      # interleaved rounds
+                res.setdefault("k7", []).append(timeit(lambda: ck(L.dyd_yolo_lines_dev(
+                    out_box.data_ptr(), roff.data_ptr(), None, w.data_ptr(), h.data_ptr(), cid.data_ptr(), nr, B, toff.data_ptr(),
+                    flag.data_ptr(), text7.data_ptr(), T7, C.byref(total), sp), "k7")))
+                res.setdefault("k13", []).append(timeit(lambda: ck(L.dyd_yolo_seg_lines_dev(*seg_args, text.data_ptr(), T13,
+                                                                                            C.byref(total), sp), "k13")))
+            k7_bytes = 32 * B + 4 * (nr + 1) + 20 * nr + 8 * (nr + 1) + nr + T7
+            k13_bytes = 16 * P + 4 * (B + 1) + B + 4 * (nr + 1) + 20 * nr + 8 * (nr + 1) + nr + B + T13
+            med7, mn7 = min(res["k7"])
+            med13, mn13 = min(res["k13"])
+            report(f"k7_yolo_lines_{shape}", k7_bytes, med7, mn7, rows=nr, lines=B, text_bytes=T7)
+            report(f"k13_yolo_seg_lines_{shape}", k13_bytes, med13, mn13, rows=nr, polygons=B, points=P, text_bytes=T13,
+                   actions=dict(zip(("written", "clipped", "bad_coords", "too_few_points", "empty", "no_size"), counts)),
+                   bytes_per_s_vs_k7=round((k13_bytes / med13) / (k7_bytes / med7), 3))
+            del text, text7
+        # every polygon clipped: the same polygons moved 60 px left, record shape
+        xs = xy.clone(); xs[:, 0] -= 60.0
+        first = pt_off[:-1].to(torch.int64)
+        xs[first, 0] = torch.clamp(xs[first, 0], max=-1.0)          # each polygon's first vertex outside
+        one = torch.arange(B + 1, dtype=torch.int32, device=dev)
+        w = torch.full((B,), 1920.0, dtype=torch.float64, device=dev); h = torch.full((B,), 1080.0, dtype=torch.float64, device=dev)
+        cid = (torch.arange(B, device=dev, dtype=torch.int32) % 20).contiguous()
+        toff = torch.empty(B + 1, dtype=torch.int64, device=dev); flag = torch.empty(B, dtype=torch.uint8, device=dev)
+        seg_args = (xs.data_ptr(), pt_off.data_ptr(), one.data_ptr(), None, w.data_ptr(), h.data_ptr(), cid.data_ptr(), B, B, P,
+                    toff.data_ptr(), flag.data_ptr(), act.data_ptr())
+        ck(L.dyd_yolo_seg_lines_dev(*seg_args, None, 0, C.byref(total), sp), "k13 measure")
+        T13 = total.value
+        text = torch.empty(T13, dtype=torch.uint8, device=dev)
+        med, mn = timeit(lambda: ck(L.dyd_yolo_seg_lines_dev(*seg_args, text.data_ptr(), T13, C.byref(total), sp), "k13"))
+        counts = torch.bincount(act.to(torch.int64), minlength=256)[:6].tolist()
+        report("k13_yolo_seg_lines_records_all_clipped", 16 * P + 4 * (B + 1) + B + 4 * (B + 1) + 20 * B + 8 * (B + 1) + B + B + T13,
+               med, mn, rows=B, text_bytes=T13,
+               actions=dict(zip(("written", "clipped", "bad_coords", "too_few_points", "empty", "no_size"), counts)))
+        del xs, text
     if "k7mix" in only:
         # where the box-tiled kernel overtakes the row kernels: rows of one box with a share of two-box rows mixed in
         import ctypes as C
