@@ -124,6 +124,13 @@ SIGNATURES = {
     "dyd_yolo_seg_lines_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.POINTER(C.c_int64), C.c_void_p]),
+    "dyd_audit_polygons": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dyd_audit_polygons_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dyd_json_scan_named_polygons": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    "dyd_json_scan_named_polygons_v": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "dyd_json_scan_labelled_polygons": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
                                                   C.POINTER(C.c_void_p)]),
     "dyd_json_scan_labelled_polygons_v": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
@@ -384,6 +391,34 @@ def box_audit(box4: np.ndarray, row_off: np.ndarray, cls: np.ndarray, width: np.
     check(lib().dyd_box_audit(_ptr(box4), _ptr(row_off), n, _ptr(cls), _ptr(width), _ptr(height), _ptr(size_status), n_classes,
                               nbins, _ptr(flag), _ptr(rows), _ptr(cc), _ptr(wh), _ptr(xy), _ptr(bpi)), "dyd_box_audit")
     return flag, rows, cc, wh, xy, bpi
+
+
+POLY_CLASS_COLS = 14   # K14 per-class counters: polygons, images, 6 categories, 3 defects, 3 area buckets
+POLY_HIST_BINS = 11    # K14 vertex-count bins: <= 2, 3, 4, 8, 16, 32, 64, 128, 256, 1024, the rest
+
+
+def audit_polygons(xy, pt_off, row_off, cls, width, height, size_status, n_classes: int, min_area: float = 1.0):
+    """K14 over host arrays -> (category u8 [B], defects u8 [B], area f64 [B], class_counts i64 [C, 14], hist_vertices
+    i64 [C, 11]).  Codes, bits and columns: include/dyd.h."""
+    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1)
+    pt_off = np.ascontiguousarray(pt_off, dtype=np.int32)
+    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
+    cls = np.ascontiguousarray(cls, dtype=np.int32)
+    width = np.ascontiguousarray(width, dtype=np.float64)
+    height = np.ascontiguousarray(height, dtype=np.float64)
+    size_status = np.ascontiguousarray(size_status, dtype=np.uint8)
+    n, n_classes, min_area = len(row_off) - 1, int(n_classes), float(min_area)
+    if n < 0 or len(width) != n or len(height) != n or len(size_status) != n:
+        raise ValueError("row_off / width / height / size_status sizes disagree")
+    nb = int(row_off[-1]) if n else 0
+    if len(cls) != nb or len(pt_off) != nb + 1 or (nb and 2 * int(pt_off[-1]) != len(xy)):
+        raise ValueError("cls and pt_off must hold one entry per polygon (pt_off one more), ending at the number of points")
+    cat, dfc, area = np.zeros(nb, np.uint8), np.zeros(nb, np.uint8), np.zeros(nb, np.float64)
+    cc, hist = np.zeros((n_classes, POLY_CLASS_COLS), np.int64), np.zeros((n_classes, POLY_HIST_BINS), np.int64)
+    check(lib().dyd_audit_polygons(_ptr(xy) if xy.size else None, _ptr(pt_off), _ptr(row_off), _ptr(cls), _ptr(width),
+                                   _ptr(height), _ptr(size_status), n, n_classes, min_area, _ptr(cat), _ptr(dfc), _ptr(area),
+                                   _ptr(cc), _ptr(hist)), "dyd_audit_polygons")
+    return cat, dfc, area, cc, hist
 
 
 REPAIR_ACTIONS = 8   # action codes of K11: keep, clip, no_size, bad_coords, degenerate, outside, low_visibility, small

@@ -2796,6 +2796,227 @@ def yolo_seg_label_texts(cells, label_values, class_ids, widths, heights, backen
     return texts, reasons
 
 
+# =============================================================================== f7b  polygon audit
+# What the segment step (K13) will make of a table's polygons, per class, before any label file exists: every object the YOLO
+# step keeps (utils._extract_boxes_with_labels' walk, whatever the row's label) with its points as K13 reads them and the row's
+# size as _audit_sizes reads it.  K14 (csrc/k14_poly_audit.hip, rules in include/dyd.h and DESIGN §5m) gives each polygon K13's
+# action as its category, and for the written and clipped ones the defects duplicate_vertices, self_intersecting and tiny_area
+# and the clipped area, in IEEE f64.  Native named-polygon scan; the cells it leaves to CPython through flatten.seg_cell_polygons.
+POLY_DEFECTS = ("duplicate_vertices", "self_intersecting", "tiny_area")             # K14 defect bits 1, 2, 4
+POLY_HIST_EDGES = (2, 3, 4, 8, 16, 32, 64, 128, 256, 1024)                         # upper edges of hist_vertices' bins, then inf
+_POLY_CLASS_COLS = ("polygons", "images", *SEG_ACTIONS, *POLY_DEFECTS, "small", "medium", "large")
+_POLY_UNMATCHABLE = 255
+
+
+class PolygonAudit:
+    """Result of audit_polygons_*: classes (sorted as str), per_class (one column per _POLY_CLASS_COLS entry), hist_vertices
+    (int64 [C, 11], bins over the point count with upper edges POLY_HIST_EDGES and inf), problems (one row per polygon that is
+    not written or has a defect) and totals."""
+
+    def __init__(self, classes, per_class, hist_vertices, problems, totals):
+        self.classes = classes
+        self.per_class = per_class
+        self.hist_vertices = hist_vertices
+        self.problems = problems
+        self.totals = totals
+
+    def __repr__(self):
+        return f"PolygonAudit({len(self.classes)} classes, {self.totals})"
+
+
+def _poly_backend(backend):
+    be = _backend(backend)
+    if not hasattr(be, "audit_polygons"):
+        raise TypeError("backend lacks ['audit_polygons']")
+    return be
+
+
+def _poly_min_area(min_area) -> float:
+    if isinstance(min_area, bool) or not isinstance(min_area, _NUMBER_TYPES):
+        raise ValueError(f"min_area must be a finite number >= 0, got {min_area!r}")
+    v = float(min_area)
+    if not (np.isfinite(v) and v >= 0.0):
+        raise ValueError(f"min_area must be a finite number >= 0, got {min_area!r}")
+    return v
+
+
+def _poly_chunk(cells) -> tuple:
+    """one chunk of cells -> (row_off int64 [n+1], xy f64 [2P], pt_off int32 [B+1], obj int32 [B], cls int32 [B] (-1: the name
+    is no str), names, number of cells scanned by CPython): the native scan's polygons with the CPython ones of the irregular
+    cells (flatten.seg_cell_polygons) spliced in at their rows"""
+    n = len(cells)
+    try:
+        scan = _nj.scan_named_polygons(cells) if _nj.enabled() else None
+    except UnicodeEncodeError:                           # a lone surrogate: every cell of the chunk through CPython
+        scan = None
+    if scan is not None:
+        nat_off = scan.cell_box_off.astype(np.int64)
+        irregular = np.flatnonzero(scan.status == _nj.IRREGULAR).tolist()
+        names, xy, pt_off, obj, cls = list(scan.names), scan.xy, scan.pt_off, scan.box_object, scan.box_class
+        scan.close()
+    else:
+        nat_off = np.zeros(n + 1, np.int64)
+        irregular = list(range(n))
+        names, xy, pt_off = [], np.zeros(0), np.zeros(1, np.int32)
+        obj, cls = np.zeros(0, np.int32), np.zeros(0, np.int32)
+    counts = np.diff(nat_off)
+    py = {}
+    for i in irregular:
+        polys = _fl.seg_cell_polygons(cells[i])
+        if polys:
+            py[i] = polys
+            counts[i] = len(polys)
+    row_off = np.zeros(n + 1, np.int64)
+    np.cumsum(counts, out=row_off[1:])
+    nb = int(row_off[-1])
+    if py:                                               # splice the CPython polygons in at their rows
+        dest = np.repeat(row_off[:-1] - nat_off[:-1], np.diff(nat_off)) + np.arange(len(obj), dtype=np.int64)
+        npts = np.zeros(nb, np.int64)
+        nat_npts = np.diff(pt_off.astype(np.int64))
+        npts[dest] = nat_npts
+        ob, cl = np.empty(nb, np.int32), np.empty(nb, np.int32)
+        ob[dest], cl[dest] = obj, cls
+        ids = {nm: k for k, nm in enumerate(names)}
+        for i, polys in py.items():
+            p = int(row_off[i])
+            for k, (o, nm, pts) in enumerate(polys):
+                npts[p + k] = len(pts)
+                ob[p + k] = o
+                cl[p + k] = ids.setdefault(nm, len(ids)) if isinstance(nm, str) else -1
+        off = np.zeros(nb + 1, np.int64)
+        np.cumsum(npts, out=off[1:])
+        if off[-1] >= (1 << 31):
+            raise ValueError("a chunk holds 2^31 points or more")
+        xy2 = np.empty((int(off[-1]), 2))
+        pdest = np.repeat(off[dest] - pt_off[:-1].astype(np.int64), nat_npts) + np.arange(len(xy) // 2, dtype=np.int64)
+        xy2[pdest] = np.asarray(xy, np.float64).reshape(-1, 2)
+        for i, polys in py.items():
+            p = int(row_off[i])
+            for k, (_, _, pts) in enumerate(polys):
+                if pts:
+                    xy2[off[p + k]:off[p + k + 1]] = [(_audit_number(x), _audit_number(y)) for x, y in pts]
+        xy, pt_off, obj, cls, names = xy2.reshape(-1), off.astype(np.int32), ob, cl, list(ids)
+    if nb >= (1 << 31):
+        raise ValueError("a chunk holds 2^31 polygons or more")
+    return row_off, xy, pt_off, obj, cls, names, len(irregular)
+
+
+class _PolyTotals:
+    def __init__(self):
+        self.classes = _ClassSums((len(_POLY_CLASS_COLS),), (len(POLY_HIST_EDGES) + 1,))
+        self.problems = []
+        self.polygons = self.unmatchable = self.python_cells = 0
+
+
+def _poly_audit_chunk(cells, status, W, H, be, acc: _PolyTotals, start: int, min_area: float):
+    """one chunk of rows: polygon table (_poly_chunk) -> K14 -> class-keyed sums and problems"""
+    row_off, xy, pt_off, obj, cls, names, n_py = _poly_chunk(cells)
+    acc.python_cells += n_py
+    cat, dfc, area, cc, hist = be.audit_polygons(xy, pt_off, row_off.astype(np.int32), cls, W, H, status, len(names), min_area)
+    acc.classes.add(names, np.asarray(cc, np.int64), np.asarray(hist, np.int64))
+    cat, dfc, area = np.asarray(cat, np.uint8), np.asarray(dfc, np.uint8), np.asarray(area, np.float64)
+    acc.polygons += len(cat)
+    acc.unmatchable += int((cat == _POLY_UNMATCHABLE).sum())
+    bad = np.flatnonzero((cat != _POLY_UNMATCHABLE) & ((cat > 1) | (dfc != 0)))
+    if len(bad):
+        name_arr = np.asarray(names, object)
+        cats = np.asarray(SEG_ACTIONS, object)[cat[bad]]
+        dtext = np.asarray(["|".join(d for k, d in enumerate(POLY_DEFECTS) if m >> k & 1) for m in range(8)], object)[dfc[bad]]
+        acc.problems.append((start + np.searchsorted(row_off, bad, side="right") - 1, obj[bad].astype(np.int64),
+                             name_arr[cls[bad]], cats, dtext, np.diff(pt_off.astype(np.int64))[bad], area[bad]))
+
+
+def _poly_result(acc: _PolyTotals, n: int, status, sources, min_area, stats) -> PolygonAudit:
+    classes, (cc, hist) = acc.classes.sorted()
+    cols = dict(zip(_POLY_CLASS_COLS, cc.T)) if len(classes) else {k: np.zeros(0, np.int64) for k in _POLY_CLASS_COLS}
+    per_class = pd.DataFrame({"class": pd.Series(classes, dtype=object), **cols})
+    if acc.problems:
+        parts = [np.concatenate([p[k] for p in acc.problems]) for k in range(7)]
+    else:
+        parts = [np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, object), np.zeros(0, object), np.zeros(0, object),
+                 np.zeros(0, np.int64), np.zeros(0)]
+    pc = {}
+    if sources is not None:
+        pc["source"] = np.asarray(sources, object)[parts[0]] if len(parts[0]) else np.zeros(0, object)
+    pc.update(dict(zip(("row", "object", "name", "category", "defects", "points", "area"), parts)))
+    problems = pd.DataFrame(pc)                          # rows ascend; within a row the polygons keep their object order
+    status = np.asarray(status)
+    totals = {"rows": n, "rows_ok": int((status == 0).sum()), "rows_missing": int((status == 1).sum()),
+              "rows_invalid": int((status == 2).sum()), "polygons": acc.polygons, "unmatchable_name_polygons": acc.unmatchable,
+              **{k: int(cols[k].sum()) for k in (*SEG_ACTIONS, *POLY_DEFECTS)}, "python_cells": acc.python_cells,
+              "min_area": min_area}
+    if stats is not None:
+        stats.update(totals)
+    return PolygonAudit(classes, per_class, hist, problems, totals)
+
+
+def _poly_audit_rows(cells, n, widths, heights, be, min_area, sources, stats, cells_of=None) -> PolygonAudit:
+    status, W, H = _audit_sizes(widths, heights, n)
+    acc = _PolyTotals()
+    for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
+        s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
+        chunk = cells_of(s0, s1) if cells_of is not None else cells[s0:s1]
+        _poly_audit_chunk(chunk, status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, min_area)
+    return _poly_result(acc, n, status, sources, min_area, stats)
+
+
+def audit_polygons_cells(cells, widths, heights, min_area: float = 1.0, backend=None, stats: Optional[dict] = None,
+                         sources=None) -> PolygonAudit:
+    """Polygon audit of the annotation cells of a table (see the section comment; widths / heights as in audit_boxes_cells).
+    -> PolygonAudit.  ``sources`` (optional) adds a source column to problems."""
+    min_area = _poly_min_area(min_area)
+    be = _poly_backend(backend)
+    cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
+    return _poly_audit_rows(cells, len(cells), widths, heights, be, min_area, sources, stats)
+
+
+def audit_polygons_frame(df: pd.DataFrame, json_col: str = ANNOTATION_COL, width_col: str = "width",
+                         height_col: str = "height", min_area: float = 1.0, backend=None,
+                         stats: Optional[dict] = None) -> PolygonAudit:
+    """Polygon audit of a table's polygon column (the segment step's input).  A frame without the size columns has every row
+    `missing`, so every polygon no_size.  problems["row"] are positions in df."""
+    cells = df[json_col].to_numpy()
+    widths, heights, sources = _size_columns(df, width_col, height_col)
+    return audit_polygons_cells(cells, widths, heights, min_area, backend, stats, sources)
+
+
+def _write_poly_audit(audit: PolygonAudit, output_dir) -> dict:
+    out = Path(output_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    paths = {"classes": str(out / "polygon_audit_classes.csv"), "problems": str(out / "polygon_audit_problems.csv"),
+             "hist": str(out / "polygon_audit_hist.npz")}
+    audit.per_class.to_csv(paths["classes"], index=False, encoding="utf-8-sig")
+    audit.problems.to_csv(paths["problems"], index=False, encoding="utf-8-sig")
+    np.savez(paths["hist"], classes=np.asarray(audit.classes, dtype=str), hist_vertices=audit.hist_vertices,
+             edges=np.asarray(POLY_HIST_EDGES, np.int64))
+    return paths
+
+
+def audit_polygons_csv(input_csv_path, output_dir, json_col: str = ANNOTATION_COL, min_area: float = 1.0, backend=None):
+    """CSV -> polygon_audit_classes.csv, polygon_audit_problems.csv and polygon_audit_hist.npz (classes, hist_vertices, edges)
+    under output_dir, in the box audit's conventions (audit_boxes_csv).  -> dict(totals, paths=...), or None when the file
+    cannot be read or lacks the column."""
+    min_area = _poly_min_area(min_area)
+    audit = NotImplemented
+    if _fc.enabled() and os.path.isfile(str(input_csv_path)):
+        table = _csv_read_split(input_csv_path, [json_col], json_col)
+        if table is not NotImplemented:
+            be = _poly_backend(backend)
+            col = table.heavy[json_col]
+            widths, heights, sources = _size_columns(table.light)
+            audit = _poly_audit_rows(None, table.n_rows, widths, heights, be, min_area, sources, None,
+                                     cells_of=lambda s0, s1: _fc_cells(col, s0, s1))
+    if audit is NotImplemented:
+        LAST_IO_PATH["polygon_audit"] = "pandas"
+        df = _csv_read_pandas(input_csv_path, json_col)
+        if df is None:
+            return None
+        audit = audit_polygons_frame(df, json_col, min_area=min_area, backend=backend)
+    else:
+        LAST_IO_PATH["polygon_audit"] = "native"
+    return {**audit.totals, "paths": _write_poly_audit(audit, output_dir)}
+
+
 def generate_yolo_datasets_from_excels(
         category_excels: list,
         output_dir: str,

@@ -3215,6 +3215,9 @@ struct NameSink {
     std::unordered_map<std::string, int32_t> ids;
     void box(int32_t k_obj, const std::string &nm, const double v[4]) {
         box4.insert(box4.end(), v, v + 4);
+        object(k_obj, nm);
+    }
+    void object(int32_t k_obj, const std::string &nm) {   // the object index and the name's id
         obj.push_back(k_obj);
         auto it = ids.find(nm);
         if (it == ids.end()) {
@@ -3230,6 +3233,32 @@ struct NameSink {
     }
 };
 
+// polygon audit: NameSink's objects and class ids with each object's points (SegSink's rule)
+struct NamedSegSink : NameSink {
+    static constexpr bool kPoints = true;
+    std::vector<double> xy;       // points of the kept objects, (x, y)
+    std::vector<int32_t> npts;    // points per kept object
+    size_t mark = 0;              // xy.size() when the current object began
+    void begin_object() { mark = xy.size(); }
+    void point(double x, double y) {
+        xy.push_back(x);
+        xy.push_back(y);
+    }
+    void drop_object() { xy.resize(mark); }
+    void box(int32_t k_obj, const std::string &nm, const double *) {   // the points replace the box
+        object(k_obj, nm);
+        npts.push_back((int32_t)((xy.size() - mark) / 2));
+    }
+    size_t point_mark() const { return xy.size(); }
+    void truncate(size_t nbox, size_t npt) {
+        NameSink::truncate(nbox);
+        npts.resize(nbox);
+        xy.resize(npt);
+    }
+};
+
+// the named-box walk with NameSink (boxes in dyd_scan_xy) or NamedSegSink (points in dyd_scan_xy, dyd_scan_pt_off)
+template <class Sink>
 int scan_named_boxes_src(const CellSrc &src, const uint8_t *missing, int64_t n_cells, int n_threads, dyd_scan **out) {
     dyd_scan *h = new (std::nothrow) dyd_scan();
     if (!h) return DYD_ERR_OOM;
@@ -3238,7 +3267,7 @@ int scan_named_boxes_src(const CellSrc &src, const uint8_t *missing, int64_t n_c
     try {
         h->status.assign((size_t)n_cells, CELL_OK);
         std::vector<int32_t> counts((size_t)n_cells, 0);
-        struct Part { NameSink sk; int64_t lo = 0, hi = 0; };
+        struct Part { Sink sk; int64_t lo = 0, hi = 0; };
         std::vector<Part> parts(64);
         if (n_threads <= 0 || n_threads > 64) n_threads = default_threads();
         const bool ok = parallel_cells_safe(n_cells, n_threads, [&](int t, int64_t lo, int64_t hi) {
@@ -3247,11 +3276,14 @@ int scan_named_boxes_src(const CellSrc &src, const uint8_t *missing, int64_t n_c
             for (int64_t i = lo; i < hi; ++i) {
                 if (missing && missing[i]) { h->status[(size_t)i] = CELL_MISSING; continue; }
                 const size_t mark = pt.sk.obj.size();
+                size_t pmark = 0;
+                if constexpr (Sink::kPoints) pmark = pt.sk.point_mark();
                 int32_t c = 0;
                 try {
                     named_boxes_cell(src.get(i), pt.sk, c);
                 } catch (Fail f) {
-                    pt.sk.truncate(mark);
+                    if constexpr (Sink::kPoints) pt.sk.truncate(mark, pmark);
+                    else pt.sk.truncate(mark);
                     c = 0;
                     h->status[(size_t)i] = (f.code == 1) ? CELL_UNDECODABLE : CELL_IRREGULAR;
                 }
@@ -3260,17 +3292,26 @@ int scan_named_boxes_src(const CellSrc &src, const uint8_t *missing, int64_t n_c
         });
         if (!ok) { delete h; return DYD_ERR_OOM; }
         std::sort(parts.begin(), parts.end(), [](const Part &a, const Part &b) { return a.lo < b.lo; });
-        size_t tot = 0;
+        size_t tot = 0, np = 0;
         for (auto &pt : parts) tot += pt.sk.obj.size();
-        if (tot >= (size_t)1 << 31) { delete h; return DYD_ERR_RANGE; }
-        h->xy.reserve(4 * tot);
+        if constexpr (Sink::kPoints)
+            for (auto &pt : parts) np += pt.sk.xy.size() / 2;
+        if (tot >= (size_t)1 << 31 || np >= (size_t)1 << 31) { delete h; return DYD_ERR_RANGE; }
+        h->xy.reserve(Sink::kPoints ? 2 * np : 4 * tot);
+        h->pt_off.assign(1, 0);
+        if constexpr (Sink::kPoints) h->pt_off.reserve(tot + 1);
         h->box_obj.reserve(tot);
         h->box_name.reserve(tot);
         // table-wide ids: the parts in cell order, each part's boxes in order -> numbered by first occurrence in the table
         std::unordered_map<std::string, int32_t> global;
         std::vector<int32_t> remap;
         for (auto &pt : parts) {
-            h->xy.insert(h->xy.end(), pt.sk.box4.begin(), pt.sk.box4.end());
+            if constexpr (Sink::kPoints) {
+                h->xy.insert(h->xy.end(), pt.sk.xy.begin(), pt.sk.xy.end());
+                for (int32_t k : pt.sk.npts) h->pt_off.push_back(h->pt_off.back() + k);
+            } else {
+                h->xy.insert(h->xy.end(), pt.sk.box4.begin(), pt.sk.box4.end());
+            }
             h->box_obj.insert(h->box_obj.end(), pt.sk.obj.begin(), pt.sk.obj.end());
             remap.assign(pt.sk.names.size(), -1);
             for (int32_t id : pt.sk.name) {
@@ -3285,7 +3326,7 @@ int scan_named_boxes_src(const CellSrc &src, const uint8_t *missing, int64_t n_c
                 }
                 h->box_name.push_back(g);
             }
-            pt.sk = NameSink();
+            pt.sk = Sink();
         }
         h->name_off.assign(1, 0);
         h->name_text.clear();
@@ -3296,7 +3337,6 @@ int scan_named_boxes_src(const CellSrc &src, const uint8_t *missing, int64_t n_c
         h->cell_box_off.resize((size_t)n_cells + 1);
         h->cell_box_off[0] = 0;
         for (int64_t i = 0; i < n_cells; ++i) h->cell_box_off[(size_t)i + 1] = h->cell_box_off[(size_t)i] + counts[(size_t)i];
-        h->pt_off.assign(1, 0);
     } catch (const std::bad_alloc &) {
         delete h;
         return DYD_ERR_OOM;
@@ -3314,7 +3354,7 @@ int dyd_json_scan_named_boxes(const uint8_t *text, const int64_t *cell_off, cons
     if (!out || n_cells < 0 || (n_cells > 0 && (!cell_off || !text))) return DYD_ERR_INVALID;
     CellSrc src;
     src.text = text; src.off = cell_off;
-    return scan_named_boxes_src(src, missing, n_cells, n_threads, out);
+    return scan_named_boxes_src<NameSink>(src, missing, n_cells, n_threads, out);
 }
 
 int dyd_json_scan_named_boxes_v(const uint8_t *const *cell_ptr, const int64_t *cell_len, const uint8_t *missing, int64_t n_cells,
@@ -3322,7 +3362,23 @@ int dyd_json_scan_named_boxes_v(const uint8_t *const *cell_ptr, const int64_t *c
     if (!out || n_cells < 0 || (n_cells > 0 && (!cell_ptr || !cell_len))) return DYD_ERR_INVALID;
     CellSrc src;
     src.ptr = cell_ptr; src.len = cell_len;
-    return scan_named_boxes_src(src, missing, n_cells, n_threads, out);
+    return scan_named_boxes_src<NameSink>(src, missing, n_cells, n_threads, out);
+}
+
+int dyd_json_scan_named_polygons(const uint8_t *text, const int64_t *cell_off, const uint8_t *missing, int64_t n_cells,
+                                 int n_threads, dyd_scan **out) {
+    if (!out || n_cells < 0 || (n_cells > 0 && (!cell_off || !text))) return DYD_ERR_INVALID;
+    CellSrc src;
+    src.text = text; src.off = cell_off;
+    return scan_named_boxes_src<NamedSegSink>(src, missing, n_cells, n_threads, out);
+}
+
+int dyd_json_scan_named_polygons_v(const uint8_t *const *cell_ptr, const int64_t *cell_len, const uint8_t *missing,
+                                   int64_t n_cells, int n_threads, dyd_scan **out) {
+    if (!out || n_cells < 0 || (n_cells > 0 && (!cell_ptr || !cell_len))) return DYD_ERR_INVALID;
+    CellSrc src;
+    src.ptr = cell_ptr; src.len = cell_len;
+    return scan_named_boxes_src<NamedSegSink>(src, missing, n_cells, n_threads, out);
 }
 
 int64_t dyd_scan_names(const dyd_scan *h, const uint8_t **text, const int64_t **off) {

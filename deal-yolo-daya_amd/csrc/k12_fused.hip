@@ -226,6 +226,7 @@ int launch_k2_big_rows(const double *box4, const int32_t *row_off, unsigned long
 void set_k1_variant(int v);
 void set_k2_variant(int v);
 void set_k7_variant(int v);
+void set_k14_lane_edges(int v);
 void set_k6_variant(int v);
 void set_k4_capacity_shift(int v);
 void set_k8_band(int v);
@@ -441,6 +442,10 @@ int dyd_set_option(const char *key, int64_t value) {
     }
     if (!strcmp(key, "k7_variant")) {
         set_k7_variant((int)value);
+        return DYD_OK;
+    }
+    if (!strcmp(key, "k14_lane_edges")) {   // K14's in-lane / wave tier threshold (A/B)
+        set_k14_lane_edges((int)value);
         return DYD_OK;
     }
     if (!strcmp(key, "k7_trace_ptr")) {   // device buffer of 8 x n_tiles u64 (0 = off)

@@ -495,6 +495,50 @@ def scan_named_boxes(cells, n_threads: int = 0) -> NamedBoxScan:
     return scan_named_boxes_buffers(data, off, missing, n_threads, keep)
 
 
+class NamedPolygonScan(NamedBoxScan):
+    """Result of scan_named_polygons: NamedBoxScan's objects, class ids and names with each object's points instead of its box:
+    xy (x, y) f64 [2*P] (ptList dicts holding both "x" and "y", in order) and pt_off [n_boxes+1].  Arrays are copies."""
+
+    def __init__(self, handle, n_cells, keep):
+        _Scan.__init__(self, handle, n_cells, keep)
+        L = _native.load_library()
+        nb = int(self.cell_box_off[-1]) if n_cells else 0
+        self.n_boxes = nb
+        self.pt_off = _view(L.dyd_scan_pt_off(handle), np.int32, nb + 1).copy()
+        self.xy = _view(L.dyd_scan_xy(handle), np.float64, 2 * int(self.pt_off[-1])).copy()
+        self.box_object = _view(L.dyd_scan_box_object(handle), np.int32, nb).copy()
+        self.box_class = _view(L.dyd_scan_box_name(handle), np.int32, nb).copy()
+        tp, op = C.c_void_p(), C.c_void_p()
+        k = int(L.dyd_scan_names(handle, C.byref(tp), C.byref(op)))
+        if k:
+            off = _view(op.value, np.int64, k + 1)
+            text = bytes(_view(tp.value, np.uint8, int(off[-1])) if off[-1] else b"")
+            self.names = [text[off[i]:off[i + 1]].decode("utf-8") for i in range(k)]
+        else:
+            self.names = []
+
+    def emit_repaired(self, *args, **kwargs):
+        raise TypeError("a polygon scan holds no boxes to repair")
+
+
+def scan_named_polygons(cells, n_threads: int = 0) -> NamedPolygonScan:
+    """cells -> NamedPolygonScan (the polygon audit's objects).  Raises UnicodeEncodeError for a cell holding a lone surrogate
+    when the cells have to be encoded."""
+    from . import pycells
+
+    L = _native.load_library()
+    h = C.c_void_p()
+    if pycells.available():
+        v = pycells.CellViews(cells.to_numpy() if hasattr(cells, "to_numpy") else cells)
+        _native.check(L.dyd_json_scan_named_polygons_v(v.ptr.ctypes.data, v.len.ctypes.data, v.missing.ctypes.data, len(v),
+                                                       n_threads, C.byref(h)), "dyd_json_scan_named_polygons_v")
+        return NamedPolygonScan(h, len(v), v)
+    data, off, missing, keep = cells_to_buffers(cells)
+    _native.check(L.dyd_json_scan_named_polygons(data.ctypes.data, off.ctypes.data, missing.ctypes.data, len(off) - 1, n_threads,
+                                                 C.byref(h)), "dyd_json_scan_named_polygons")
+    return NamedPolygonScan(h, len(off) - 1, (keep, data, off, missing))
+
+
 # ------------------------------------------------------------------------------------------ split step
 SP_OK, SP_EMPTY, SP_UNDECODABLE, SP_NOT_A_LIST, SP_NO_OBJECTS, SP_IRREGULAR = 0, 1, 2, 3, 4, 5
 EV_NO_NAME, EV_UNDEFINED, EV_NOTHING_CLASSIFIED = 1, 2, 3

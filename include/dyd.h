@@ -384,6 +384,40 @@ int dyd_yolo_seg_lines_dev(const double *xy, const int32_t *pt_off, const int32_
                            int64_t n_polys, int64_t n_points, int64_t *out_text_off, uint8_t *out_flag, uint8_t *out_action,
                            uint8_t *out_text_or_null, int64_t text_cap, int64_t *out_total, void *stream);
 
+/* ---- K14: polygon audit — per-class polygon statistics and defects ---------------------------
+ * Polygons: every object the YOLO step keeps (utils._extract_boxes_with_labels: named, non-empty ptList, the prefix kept on any
+ * exception), whatever the row's label, with its points V = (float(x), float(y)) of every ptList dict holding both keys
+ * (K13's rule; a value that is no number is NaN).  cls -1: the name is no str; the polygon is only counted as unmatchable
+ * (category 255, defects 0, area NaN).  Per polygon:
+ *   category     exactly K13's action (codes 0..5 of the K13 block, the same device code), with no_size for a row whose
+ *                size_status is not 0 (missing or invalid, as _audit_sizes reads the size columns) or outside (0, 2^43);
+ *   defects      written and clipped polygons only, bits:
+ *                1 duplicate_vertices  len(V) >= 3 and some V[k] == V[k-1], cyclically, exact == (a closing point counts);
+ *                2 self_intersecting   len(V) >= 3; U = V without cyclically consecutive duplicates, m = len(U) >= 3, and
+ *                                      an adjacent edge pair doubles back (o(a,b,c) == 0 and (b-a).(c-b) < 0) or two
+ *                                      non-adjacent edges share a point (a proper crossing by strict signs, or o == 0 with
+ *                                      the point in the other segment's closed bounding box);
+ *                                      o(p,q,r) = (q.x-p.x)*(r.y-p.y) - (q.y-p.y)*(r.x-p.x), on V as drawn;
+ *                4 tiny_area           area < min_area;
+ *   area         written and clipped: |s| * 0.5, s = sum_k (x_k*y_{k+1} - x_{k+1}*y_k) over K13's clipped vertices in their
+ *                order (signed: the two loops of a bow-tie cancel); NaN otherwise.
+ * All of it IEEE f64 without contraction.  The self-intersection test costs O(m^2) edge pairs per polygon (no sweep).
+ * Per class c (u64): class_counts[c * 14 + j], j = 0 polygons, 1 images (rows holding a polygon of c), 2..7 one per
+ * category code 0..5, 8..10 one per defect bit, 11..13 area small (< 32^2), medium (< 96^2), large over written and clipped;
+ * hist_vertices[c * 11 + b] over len(V), upper bin edges 2, 3, 4, 8, 16, 32, 64, 128, 256, 1024, inf.
+ * Inputs follow K13: xy [2*n_points] (16-B aligned), pt_off [n_polys+1], row_off [n_rows+1], cls [n_polys], width / height /
+ * size_status [n_rows].  min_area finite and >= 0.
+ * dyd_audit_polygons     : host pointers (n_polys = row_off[n_rows], n_points = pt_off[n_polys]);
+ * dyd_audit_polygons_dev : device pointers, enqueued on stream (NULL: the library's stream). */
+int dyd_audit_polygons(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *cls, const double *width,
+                       const double *height, const uint8_t *size_status, int64_t n_rows, int32_t n_classes, double min_area,
+                       uint8_t *out_category, uint8_t *out_defects, double *out_area, int64_t *out_class_counts,
+                       int64_t *out_hist_vertices);
+int dyd_audit_polygons_dev(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *cls, const double *width,
+                           const double *height, const uint8_t *size_status, int64_t n_rows, int64_t n_polys, int64_t n_points,
+                           int32_t n_classes, double min_area, uint8_t *out_category, uint8_t *out_defects, double *out_area,
+                           int64_t *out_class_counts, int64_t *out_hist_vertices, void *stream);
+
 /* ---- native flatten / emit (HOST code, multithreaded) ------------------------------
  * Schema-specialised JSON scanner + canonical re-emitter that replaces json.loads / json.dumps inside
  * parse_and_replace_ptlist (processor.py:262-281), extract_width_height (:285-292) and extract_boxes
@@ -460,6 +494,12 @@ int dyd_json_scan_named_boxes(const uint8_t *text, const int64_t *cell_off, cons
 int dyd_json_scan_named_boxes_v(const uint8_t *const *cell_ptr, const int64_t *cell_len, const uint8_t *missing,
                                 int64_t n_cells, int n_threads, dyd_scan **out);
 int64_t dyd_scan_names(const dyd_scan *scan, const uint8_t **text, const int64_t **off);
+/* Polygon audit (K14): the named-box scan's objects, names and class ids with the points of each (the labelled-polygon
+ * scan's dyd_scan_xy = (x, y) per point and dyd_scan_pt_off), see K14 above; same irregular cells. */
+int dyd_json_scan_named_polygons(const uint8_t *text, const int64_t *cell_off, const uint8_t *missing,
+                                 int64_t n_cells, int n_threads, dyd_scan **out);
+int dyd_json_scan_named_polygons_v(const uint8_t *const *cell_ptr, const int64_t *cell_len, const uint8_t *missing,
+                                   int64_t n_cells, int n_threads, dyd_scan **out);
 /* Box repair, after dyd_json_scan_named_boxes(_v): for every cell with a box whose action (bits 0-2 of
  * action_per_box, K11's codes) is 1 or 3..7, the whole document as json.dumps(..., ensure_ascii=False) writes it
  * with the objects of codes 3..7 left out and, for code 1, the object's polygon.ptList replaced by
@@ -600,7 +640,8 @@ void dyd_host_free(void *p);
  * 2 / 22 row tiles (one / two per ticket), 30 box tiles (rows of many boxes); "fused_variant": -1 by the table's shape (default:
  * 4 up to 32 boxes per image on average, 10 beyond, 6 / 9 for polygons of 20..48 points), 4 = wave kernel, 10 = its dense
  * instantiation (rows of 40..256 boxes sorted and swept), 6 / 9 = workgroup tilings, 1 = two launches;
- * "k2_variant": -1 by shape, 4 = the wave kernel's pair stage, 0..3 / 5 = tile kernels (2 / 3 / 5 with the f32 filter and the sweep). */
+ * "k2_variant": -1 by shape, 4 = the wave kernel's pair stage, 0..3 / 5 = tile kernels (2 / 3 / 5 with the f32 filter and the sweep);
+ * "k14_lane_edges": the largest number of edges of U whose self-intersection test K14 runs in one lane (<= 0: the default). */
 int dyd_set_option(const char *key, int64_t value);
 /* measurement aid: plain streaming kernel (mode 0 copy, 1 read-only, 2 write-only, 3-5 the same non-temporal, 16 B per
  * lane) used to record the box's HBM ceiling next to the kernels' achieved GB/s; modes 6 / 7 / 8: one 8-byte word per lane

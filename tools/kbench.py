@@ -2,7 +2,8 @@
 """Per-kernel micro-benchmarks on one MI355X (device-resident inputs, HIP-event timing,
 interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant.
 
-    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k13: segmentation lines beside K7)
+    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k13: segmentation lines beside K7;
+     k14: polygon audit; k14tier: its in-lane / wave threshold)
 """
 import argparse
 import json
@@ -492,6 +493,62 @@ def main():
                med, mn, rows=B, text_bytes=T13,
                actions=dict(zip(("written", "clipped", "bad_coords", "too_few_points", "empty", "no_size"), counts)))
         del xs, text
+    if "k14" in only:
+        import ctypes as C
+        # K14 (polygon audit) on K13's two shapes, and long polygons (convex rings of 256 vertices: no crossing, so the wave
+        # tier tests every edge pair).  Bytes: in 16*P + 4*(B+1) + 4*B + 4*(N+1) + 17*N, out 10*B + the class counters.
+        nc = 20
+        cat = torch.empty(B, dtype=torch.uint8, device=dev); dfc = torch.empty(B, dtype=torch.uint8, device=dev)
+        area = torch.empty(B, dtype=torch.float64, device=dev)
+        cc = torch.empty((nc, 14), dtype=torch.int64, device=dev); hist = torch.empty((nc, 11), dtype=torch.int64, device=dev)
+
+        def k14_leg(name, xy_, pt_, roff, nr, nb, npts):
+            w = torch.full((nr,), 1920.0, dtype=torch.float64, device=dev); h = torch.full((nr,), 1080.0, dtype=torch.float64, device=dev)
+            st = torch.zeros(nr, dtype=torch.uint8, device=dev)
+            cls = (torch.arange(nb, device=dev, dtype=torch.int32) % nc).contiguous()
+            a14 = (xy_.data_ptr(), pt_.data_ptr(), roff.data_ptr(), cls.data_ptr(), w.data_ptr(), h.data_ptr(), st.data_ptr(), nr, nb,
+                   npts, nc, 1.0, cat.data_ptr(), dfc.data_ptr(), area.data_ptr(), cc.data_ptr(), hist.data_ptr(), sp)
+            med, mn = timeit(lambda: ck(L.dyd_audit_polygons_dev(*a14), "k14"))
+            c = cc.sum(0).tolist()
+            report(f"k14_audit_polygons_{name}", 16 * npts + 4 * (nb + 1) + 4 * nb + 4 * (nr + 1) + 17 * nr + 10 * nb, med, mn,
+                   rows=nr, polygons=nb, points=npts, polygons_per_s=round(nb / med * 1e3),
+                   categories=dict(zip(("written", "clipped", "bad_coords", "too_few_points", "empty", "no_size"), c[2:8])),
+                   defects=dict(zip(("duplicate_vertices", "self_intersecting", "tiny_area"), c[8:11])))
+
+        k14_leg("records", xy, pt_off, torch.arange(B + 1, dtype=torch.int32, device=dev), B, B, P)
+        k14_leg("rows", xy, pt_off, box_off, N, B, P)
+        nl, m = 1_000_000, 256
+        th = torch.arange(m, dtype=torch.float64, device=dev) * (2 * np.pi / m)
+        ring = torch.stack([500.0 + 400.0 * torch.cos(th), 500.0 + 400.0 * torch.sin(th)], 1)
+        xl = ring.repeat(nl, 1).contiguous()
+        ptl = torch.arange(nl + 1, dtype=torch.int32, device=dev) * m
+        k14_leg("long_256", xl, ptl, torch.arange(nl + 1, dtype=torch.int32, device=dev), nl, nl, nl * m)
+        del xl, cat, dfc, area
+    if "k14tier" in only:
+        import ctypes as C
+        # K14's tier threshold: 1 M convex rings of m vertices (no crossing: every edge pair tested) with the in-lane limit
+        # ("k14_lane_edges") below and above m, so each m runs once in its lane and once on the wave tier
+        nl, nc = 1_000_000, 20
+        cat = torch.empty(nl, dtype=torch.uint8, device=dev); dfc = torch.empty(nl, dtype=torch.uint8, device=dev)
+        area = torch.empty(nl, dtype=torch.float64, device=dev)
+        cc = torch.empty((nc, 14), dtype=torch.int64, device=dev); hist = torch.empty((nc, 11), dtype=torch.int64, device=dev)
+        one = torch.arange(nl + 1, dtype=torch.int32, device=dev)
+        w = torch.full((nl,), 1920.0, dtype=torch.float64, device=dev); h = torch.full((nl,), 1080.0, dtype=torch.float64, device=dev)
+        st = torch.zeros(nl, dtype=torch.uint8, device=dev)
+        cls = (torch.arange(nl, device=dev, dtype=torch.int32) % nc).contiguous()
+        for m in (8, 16, 24, 32, 48, 64, 96):
+            th = torch.arange(m, dtype=torch.float64, device=dev) * (2 * np.pi / m)
+            xl = torch.stack([500.0 + 400.0 * torch.cos(th), 500.0 + 400.0 * torch.sin(th)], 1).repeat(nl, 1).contiguous()
+            ptl = one * m
+            a14 = (xl.data_ptr(), ptl.data_ptr(), one.data_ptr(), cls.data_ptr(), w.data_ptr(), h.data_ptr(), st.data_ptr(), nl, nl,
+                   nl * m, nc, 1.0, cat.data_ptr(), dfc.data_ptr(), area.data_ptr(), cc.data_ptr(), hist.data_ptr(), sp)
+            for lim in (m - 1, m):
+                ck(L.dyd_set_option(b"k14_lane_edges", lim), "opt")
+                med, mn = timeit(lambda: ck(L.dyd_audit_polygons_dev(*a14), "k14"), iters=5)
+                report(f"k14_tier_ring{m}_{'wave' if lim < m else 'lane'}", 16 * nl * m, med, mn, polygons=nl, vertices=m,
+                       selfx=int(cc[:, 9].sum()))
+            del xl
+        ck(L.dyd_set_option(b"k14_lane_edges", 0), "opt")
     if "k7mix" in only:
         # where the box-tiled kernel overtakes the row kernels: rows of one box with a share of two-box rows mixed in
         import ctypes as C
