@@ -129,6 +129,12 @@ SIGNATURES = {
     "dyd_audit_polygons_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dyd_coco_annotations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_int64)]),
+    "dyd_coco_annotations_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
     "dyd_json_scan_named_polygons": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "dyd_json_scan_named_polygons_v": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "dyd_json_scan_labelled_polygons": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
@@ -419,6 +425,40 @@ def audit_polygons(xy, pt_off, row_off, cls, width, height, size_status, n_class
                                    _ptr(height), _ptr(size_status), n, n_classes, min_area, _ptr(cat), _ptr(dfc), _ptr(area),
                                    _ptr(cc), _ptr(hist)), "dyd_audit_polygons")
     return cat, dfc, area, cc, hist
+
+
+COCO_SEGMENTATION = 1   # K16 flags bit 0: print the polygon into "segmentation" (clear: the detect flavour, an empty list)
+
+
+def coco_annotations(xy, pt_off, row_off, cat_id, width, height, size_status, image_id_base: int = 1, ann_id_base: int = 1,
+                     flags: int = COCO_SEGMENTATION):
+    """K16 over host arrays -> (action u8 [B], area f64 [B] (NaN unless printed), row_kept i32 [n], text bytes): one COCO
+    annotation object per polygon with cat_id >= 1 that K13 would write, joined with ",".  Definition: include/dyd.h."""
+    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1)
+    pt_off = np.ascontiguousarray(pt_off, dtype=np.int32)
+    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
+    cat_id = np.ascontiguousarray(cat_id, dtype=np.int32)
+    width = np.ascontiguousarray(width, dtype=np.float64)
+    height = np.ascontiguousarray(height, dtype=np.float64)
+    size_status = np.ascontiguousarray(size_status, dtype=np.uint8)
+    n = len(row_off) - 1
+    if n < 0 or len(width) != n or len(height) != n or len(size_status) != n:
+        raise ValueError("row_off / width / height / size_status sizes disagree")
+    nb = int(row_off[-1]) if n else 0
+    if len(cat_id) != nb or len(pt_off) != nb + 1 or (nb and 2 * int(pt_off[-1]) != len(xy)):
+        raise ValueError("cat_id and pt_off must hold one entry per polygon (pt_off one more), ending at the number of points")
+    action, area, kept = np.zeros(nb, np.uint8), np.zeros(nb, np.float64), np.zeros(n, np.int32)
+    text, total = C.c_void_p(), C.c_int64()
+    L = lib()
+    check(L.dyd_coco_annotations(_ptr(xy) if xy.size else None, _ptr(pt_off), _ptr(row_off), _ptr(cat_id) if nb else None,
+                                 _ptr(width), _ptr(height), _ptr(size_status), n, int(image_id_base), int(ann_id_base), int(flags),
+                                 _ptr(action) if nb else None, _ptr(area) if nb else None, _ptr(kept), C.byref(text),
+                                 C.byref(total)), "dyd_coco_annotations")
+    try:
+        data = C.string_at(text.value, total.value) if total.value else b""
+    finally:
+        L.dyd_host_free(text)
+    return action, area, kept, data
 
 
 REPAIR_ACTIONS = 8   # action codes of K11: keep, clip, no_size, bad_coords, degenerate, outside, low_visibility, small

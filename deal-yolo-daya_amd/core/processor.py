@@ -3017,6 +3017,290 @@ def audit_polygons_csv(input_csv_path, output_dir, json_col: str = ANNOTATION_CO
     return {**audit.totals, "paths": _write_poly_audit(audit, output_dir)}
 
 
+# =============================================================================== f7c  COCO export
+# One COCO instances_*.json from a table's annotation polygons, for the trainers and tools that do not read YOLO folders.  The
+# polygons, sizes and chunks are the polygon audit's (_poly_chunk, _audit_sizes); the host chooses each polygon's category id
+# and K16 (csrc/k16_coco.hip, rules in include/dyd.h and DESIGN §5n) prints the annotation objects: K13's clip, K14's area,
+# exact "%.2f".  Annotation ids are 1 + the polygon's position in the table (unique and ascending, not dense), image ids
+# 1 + the row's position.  Without `classes` the categories are numbered in order of first appearance among the selected
+# polygons (row order, then object order), so the file is written in one pass over the chunks.
+COCO_ACTIONS = (*SEG_ACTIONS, "too_large")                 # K16 codes 0..6
+_COCO_INFO = {"description": "COCO export of deal-yolo-daya_amd", "version": "1.0"}
+
+
+def _coco_backend(backend):
+    be = _backend(backend)
+    if not hasattr(be, "coco_annotations"):
+        raise TypeError("backend lacks ['coco_annotations']")
+    return be
+
+
+def _coco_json(value) -> bytes:
+    """compact JSON as UTF-8; a string holding a lone surrogate, which UTF-8 cannot carry, is escaped instead"""
+    try:
+        return json.dumps(value, ensure_ascii=False, separators=(",", ":")).encode("utf-8")
+    except UnicodeEncodeError:
+        return json.dumps(value, ensure_ascii=True, separators=(",", ":")).encode("ascii")
+
+
+def _coco_size(v: float):
+    return int(v) if v == int(v) else v
+
+
+class _CocoTotals:
+    def __init__(self, classes):
+        self.given = classes is not None
+        self.cat_of = {name: k + 1 for k, name in enumerate(classes)} if self.given else {}
+        self.actions = np.zeros(len(COCO_ACTIONS), np.int64)
+        self.polygons = self.unmatchable = self.unknown = self.python_cells = self.images = 0
+        self.image_parts, self.skipped = [], []
+        self.wrote_text = False
+
+
+def _coco_chunk(cells, labels, status, W, H, names_of_rows, be, acc: _CocoTotals, start: int, flags: int, keep_empty: bool, out):
+    """one chunk of rows: polygon table (_poly_chunk) -> category ids -> K16 -> the annotation text to `out`, image entries"""
+    row_off, xy, pt_off, obj, cls, names, n_py = _poly_chunk(cells)
+    acc.python_cells += n_py
+    n, nb = len(cells), len(cls)
+    sel = cls >= 0
+    acc.unmatchable += int(nb - sel.sum())
+    if labels is not None and nb:                        # the dataset step's rule: the polygon's name is the row's label
+        ids = {nm: k for k, nm in enumerate(names)}
+        want = np.fromiter((ids.get(str(v), -2) for v in labels), np.int64, count=n)
+        sel &= cls == np.repeat(want, np.diff(row_off))
+    lut = np.zeros(len(names) + 1, np.int32)             # local name id -> category id (0: none); the last entry serves cls -1
+    if acc.given:
+        for k, nm in enumerate(names):
+            lut[k] = acc.cat_of.get(nm, 0)
+    elif nb:
+        used, first = np.unique(cls[sel], return_index=True)
+        for k in used[np.argsort(first, kind="stable")].tolist():
+            lut[k] = acc.cat_of.setdefault(names[k], len(acc.cat_of) + 1)
+    cat = np.where(sel, lut[cls], 0).astype(np.int32) if nb else np.zeros(0, np.int32)
+    acc.unknown += int((sel & (cat == 0)).sum()) if nb else 0
+    action, _, kept, text = be.coco_annotations(xy, pt_off, row_off.astype(np.int32), cat, W, H, status, start + 1,
+                                                1 + acc.polygons, flags)
+    acc.polygons += nb
+    action, kept = np.asarray(action, np.uint8), np.asarray(kept)
+    chosen = cat > 0
+    acc.actions += np.bincount(action[chosen], minlength=len(COCO_ACTIONS))[:len(COCO_ACTIONS)]
+    if text:
+        out.write(b"," + text if acc.wrote_text else text)
+        acc.wrote_text = True
+    usable = (status == 0) & (W < _SEG_LIMIT) & (H < _SEG_LIMIT)
+    for k in np.flatnonzero(usable & ((kept > 0) | keep_empty)).tolist():
+        acc.image_parts.append(_coco_json({"id": start + k + 1, "width": _coco_size(float(W[k])), "height": _coco_size(float(H[k])),
+                                           "file_name": names_of_rows(start + k)}))
+    bad = np.flatnonzero(chosen & (action >= 2))
+    if len(bad):
+        acc.skipped.append((start + np.searchsorted(row_off, bad, side="right") - 1, obj[bad].astype(np.int64),
+                            np.asarray(names, object)[cls[bad]], np.asarray(COCO_ACTIONS, object)[action[bad]]))
+    return int(n - usable.sum())
+
+
+def _coco_export_rows(cells, n, widths, heights, sources, labels, classes, segmentation, keep_empty_images, file_names,
+                      output_json, skipped_csv, be, stats, cells_of=None) -> dict:
+    if classes is not None:
+        classes = list(classes)
+        if len(set(classes)) != len(classes) or not all(isinstance(c, str) for c in classes):
+            raise ValueError("classes must be distinct strings")
+    if file_names is not None and len(file_names) != n:
+        raise ValueError("file_names must hold one name per row")
+    if labels is not None and len(labels) != n:
+        raise ValueError("one label per row")
+    status, W, H = _audit_sizes(widths, heights, n)
+    if file_names is not None:
+        name_of = lambda i: str(file_names[i])                            # noqa: E731
+    elif sources is not None:
+        name_of = lambda i: str(sources[i])                               # noqa: E731
+    else:
+        name_of = str
+    acc = _CocoTotals(classes)
+    flags = 1 if segmentation else 0
+    output_json = str(output_json)
+    if os.path.dirname(output_json):
+        os.makedirs(os.path.dirname(output_json), exist_ok=True)
+    tmp = output_json + ".tmp"
+    no_size = 0
+    with open(tmp, "wb") as out:
+        out.write(b'{"info":' + _coco_json(_COCO_INFO) + b',"licenses":[],"annotations":[')
+        for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
+            s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
+            chunk = cells_of(s0, s1) if cells_of is not None else cells[s0:s1]
+            no_size += _coco_chunk(chunk, None if labels is None else labels[s0:s1], status[s0:s1], W[s0:s1], H[s0:s1], name_of, be,
+                                   acc, s0, flags, bool(keep_empty_images), out)
+        categories = [{"id": k, "name": nm, "supercategory": ""} for nm, k in acc.cat_of.items()]
+        out.write(b'],"images":[' + b",".join(acc.image_parts) + b'],"categories":[' +
+                  b",".join(_coco_json(c) for c in categories) + b"]}")
+    os.replace(tmp, output_json)
+    if skipped_csv:
+        parts = [np.concatenate([p[k] for p in acc.skipped]) if acc.skipped else np.zeros(0, np.int64 if k < 2 else object)
+                 for k in range(4)]
+        cols = {}
+        if sources is not None:
+            cols["source"] = np.asarray(sources, object)[parts[0]] if len(parts[0]) else np.zeros(0, object)
+        cols.update(dict(zip(("row", "object", "name", "action"), parts)))
+        pd.DataFrame(cols).to_csv(skipped_csv, index=False, encoding="utf-8-sig")
+    result = {"rows": n, "rows_no_size": no_size, "images": len(acc.image_parts), "polygons": acc.polygons,
+              **{a: int(acc.actions[k]) for k, a in enumerate(COCO_ACTIONS)}, "unmatchable_name_polygons": acc.unmatchable,
+              "unknown_class": acc.unknown, "annotations": int(acc.actions[0] + acc.actions[1]), "categories": categories,
+              "python_cells": acc.python_cells, "output": output_json, "skipped_output": skipped_csv}
+    if stats is not None:
+        stats.update(result)
+    return result
+
+
+def export_coco_frame(df: pd.DataFrame, output_json, json_col: str = ANNOTATION_COL, width_col: str = "width",
+                      height_col: str = "height", source_col: str = "source", label_col: Optional[str] = None, classes=None,
+                      segmentation: bool = True, keep_empty_images: bool = True, file_names=None, skipped_csv=None, backend=None,
+                      stats: Optional[dict] = None) -> dict:
+    """A table's annotation polygons as one COCO instances file (see the section comment).  Every polygon with a str name is
+    selected; with ``label_col`` only those whose name is str(row[label_col]) (the dataset step's rule).  ``classes`` fixes the
+    categories (id = index + 1; a selected polygon with another name is deselected and counted as unknown_class); without it
+    they are numbered by first appearance.  A row with a usable size gets an image entry (id = position + 1; file_name =
+    file_names[i], else str(source), else the position) unless it has no annotation and keep_empty_images is False; a row
+    without one gets none and its polygons are no_size.  segmentation=False leaves every "segmentation" empty (the detect
+    flavour).  ``skipped_csv``: [source,] row, object, name, action of every selected polygon that is not printed.  The file is
+    written to output_json + ".tmp" and moved into place.  -> dict(rows, rows_no_size, images, polygons, one count per
+    COCO_ACTIONS entry over the selected polygons, unmatchable_name_polygons, unknown_class, annotations, categories,
+    python_cells, output, skipped_output)."""
+    be = _coco_backend(backend)
+    if label_col is not None and label_col not in df.columns:
+        raise ValueError(f"no column {label_col!r}")
+    cells = df[json_col].to_numpy()
+    widths, heights, _ = _size_columns(df, width_col, height_col)
+    sources = df[source_col].to_numpy() if source_col in df.columns else None
+    labels = df[label_col].to_numpy() if label_col is not None else None
+    return _coco_export_rows(cells, len(cells), widths, heights, sources, labels, classes, segmentation, keep_empty_images,
+                             file_names, output_json, skipped_csv, be, stats)
+
+
+def export_coco_csv(input_csv_path, output_json, json_col: str = ANNOTATION_COL, width_col: str = "width",
+                    height_col: str = "height", source_col: str = "source", label_col: Optional[str] = None, classes=None,
+                    segmentation: bool = True, keep_empty_images: bool = True, file_names=None, skipped_csv=None, backend=None,
+                    stats: Optional[dict] = None):
+    """CSV -> COCO instances file, export_coco_frame on the native CSV hand-off (the polygon column is never parsed by pandas).
+    -> export_coco_frame's dict, or None when the file cannot be read or lacks the column."""
+    result = NotImplemented
+    if _fc.enabled() and os.path.isfile(str(input_csv_path)):
+        table = _csv_read_split(input_csv_path, [json_col], json_col)
+        if table is not NotImplemented and (label_col is None or label_col in table.light.columns):
+            be = _coco_backend(backend)
+            col, light = table.heavy[json_col], table.light
+            widths, heights, _ = _size_columns(light, width_col, height_col)
+            sources = light[source_col].to_numpy() if source_col in light.columns else None
+            labels = light[label_col].to_numpy() if label_col is not None else None
+            result = _coco_export_rows(None, table.n_rows, widths, heights, sources, labels, classes, segmentation,
+                                       keep_empty_images, file_names, output_json, skipped_csv, be, stats,
+                                       cells_of=lambda s0, s1: _fc_cells(col, s0, s1))
+    if result is NotImplemented:
+        LAST_IO_PATH["coco_export"] = "pandas"
+        df = _csv_read_pandas(input_csv_path, json_col)
+        if df is None:
+            return None
+        return export_coco_frame(df, output_json, json_col, width_col, height_col, source_col, label_col, classes, segmentation,
+                                 keep_empty_images, file_names, skipped_csv, backend, stats)
+    LAST_IO_PATH["coco_export"] = "native"
+    return result
+
+
+def _coco_image_suffix(images_dir: Path, stem: str, source) -> str:
+    """the extension of the image the YOLO step wrote for the row, else that of the source's last path component without its
+    query string, else .jpg"""
+    if images_dir.is_dir():
+        for found in sorted(images_dir.glob(f"{stem}.*")):
+            return found.suffix
+    return Path(Path(str(source)).name.split("?")[0]).suffix or ".jpg"
+
+
+def export_coco_from_excels(category_excels: list, output_dir: str, source_col: str = "source", label_col: str = "分类标签",
+                            json_col_primary: str = BBOX_COL, json_col_fallback: str = ANNOTATION_COL, width_col: str = "width",
+                            height_col: str = "height", random_seed: int = 42, class_order: Optional[list] = None,
+                            segmentation: bool = True, backend=None) -> dict:
+    """<output_dir>/<dataset dir>/annotations/instances_<split>.json per category workbook and split sheet, next to the folders
+    ``generate_yolo_datasets_from_excels`` writes: the same dataset directory names and classes (category id = YOLO class id
+    + 1), the rows in the same shuffled order, each row's polygons that carry its label (the cell is `fallback or primary`
+    with segmentation, `primary or fallback` without, as in the two tasks), file_name = the name of the image the YOLO step
+    writes for the row (`_safe_image_stem(source, idx)` + the extension of an existing images/<split>/<stem>.*, else the
+    source's own, else .jpg).  Rows without a source or with a label outside the classes are left out and counted.  It
+    downloads nothing and writes no image.  -> dict(outputs=[paths], stats={category: {split: export_coco_frame's dict plus
+    rows_without_source and rows_invalid_label}}, dataset_name_map)."""
+    be = _coco_backend(backend)
+    output_dir = Path(output_dir)
+    splits = ["train", "val", "test"]
+    outputs, all_stats, dataset_name_map, used_dir_names = [], {}, {}, set()
+    for idx_excel, excel_path in enumerate(category_excels):
+        if not excel_path or not Path(excel_path).exists():
+            continue
+        excel_path = Path(excel_path)
+        category_name, dir_name = _dataset_dir_name(excel_path, idx_excel, used_dir_names)
+        dataset_dir = output_dir / dir_name
+        dataset_name_map[dataset_dir.name] = category_name
+        split_sheets, frames, classes = _dataset_sheets(excel_path, splits, label_col, class_order)
+        class_to_id = {name: i for i, name in enumerate(classes)}
+        all_stats[category_name] = {}
+        for split in split_sheets:
+            frame = frames[split]
+            order = be.mt19937_permutation(random_seed, len(frame))
+            frame = frame.iloc[order].reset_index(drop=True)
+            columns = set(frame.columns)
+            get = lambda name, default=None: (frame[name].tolist() if name in columns else [default] * len(frame))  # noqa: E731
+            sources, widths, heights = get(source_col), get(width_col), get(height_col)
+            labels = [str(v) for v in get(label_col, "")]
+            primary, fallback = get(json_col_primary), get(json_col_fallback)
+            cells = [b or a for a, b in zip(primary, fallback)] if segmentation else [a or b for a, b in zip(primary, fallback)]
+            no_source = [i for i, src in enumerate(sources) if not src]
+            keep = [i for i, (src, lab) in enumerate(zip(sources, labels)) if src and lab and lab in class_to_id]
+            images_dir = dataset_dir / "images" / split
+            names = []
+            for i in keep:
+                stem = _safe_image_stem(str(sources[i]), i)
+                names.append(stem + _coco_image_suffix(images_dir, stem, sources[i]))
+            cells_kept = np.empty(len(keep), object)
+            cells_kept[:] = [cells[i] for i in keep]
+            has_size = width_col in columns and height_col in columns
+            out_path = dataset_dir / "annotations" / f"instances_{split}.json"
+            res = _coco_export_rows(cells_kept, len(keep), [widths[i] for i in keep] if has_size else None,
+                                    [heights[i] for i in keep] if has_size else None,
+                                    np.asarray([sources[i] for i in keep], object), np.asarray([labels[i] for i in keep], object),
+                                    classes, segmentation, True, names, out_path, None, be, None)
+            res["rows_without_source"] = len(no_source)
+            res["rows_invalid_label"] = len(frame) - len(keep) - len(no_source)
+            all_stats[category_name][split] = res
+            outputs.append(out_path)
+    return {"outputs": outputs, "stats": all_stats, "dataset_name_map": dataset_name_map}
+
+
+def _dataset_dir_name(excel_path: Path, idx_excel: int, used_dir_names: set) -> tuple:
+    """-> (category name, directory name) of one category workbook: safe_filename of the stem, with _1, _2, ... when an earlier
+    workbook took the name (reference processor.py:931-936); the name is added to used_dir_names"""
+    category_name = excel_path.stem
+    base_dir_name = safe_filename(str(category_name)) if category_name else f"category_{idx_excel:03d}"
+    dir_name, suffix = base_dir_name, 1
+    while dir_name in used_dir_names:                                # :931-936
+        dir_name = f"{base_dir_name}_{suffix}"
+        suffix += 1
+    used_dir_names.add(dir_name)
+    return category_name, dir_name
+
+
+def _dataset_sheets(excel_path, splits, label_col: str, class_order) -> tuple:
+    """-> (the split sheets present, their frames, the classes) of one category workbook: the sorted labels of all its split
+    sheets, class_order's members first (:958-963)"""
+    book = pd.ExcelFile(excel_path)
+    split_sheets = [sp for sp in splits if sp in book.sheet_names]
+    all_labels, frames = [], {}
+    for split in split_sheets:
+        frames[split] = pd.read_excel(excel_path, sheet_name=split)
+        if label_col in frames[split].columns:
+            all_labels.extend(str(v) for v in frames[split][label_col].dropna())
+    classes = sorted(dict.fromkeys(all_labels))                      # :958-963
+    if class_order:
+        head = [c for c in class_order if c in classes]
+        classes = head + [c for c in classes if c not in head]
+    return split_sheets, frames, classes
+
+
 def generate_yolo_datasets_from_excels(
         category_excels: list,
         output_dir: str,
@@ -3076,13 +3360,7 @@ def generate_yolo_datasets_from_excels(
         if not excel_path or not Path(excel_path).exists():
             continue
         excel_path = Path(excel_path)
-        category_name = excel_path.stem
-        base_dir_name = safe_filename(str(category_name)) if category_name else f"category_{idx_excel:03d}"
-        dir_name, suffix = base_dir_name, 1
-        while dir_name in used_dir_names:                                # :931-936
-            dir_name = f"{base_dir_name}_{suffix}"
-            suffix += 1
-        used_dir_names.add(dir_name)
+        category_name, dir_name = _dataset_dir_name(excel_path, idx_excel, used_dir_names)
         dataset_dir = output_dir / dir_name
         dataset_name_map[dataset_dir.name] = category_name
         images_root, labels_root = dataset_dir / "images", dataset_dir / "labels"
@@ -3090,17 +3368,7 @@ def generate_yolo_datasets_from_excels(
             (images_root / split).mkdir(parents=True, exist_ok=True)
             (labels_root / split).mkdir(parents=True, exist_ok=True)
 
-        book = pd.ExcelFile(excel_path)
-        split_sheets = [sp for sp in splits if sp in book.sheet_names]
-        all_labels, frames = [], {}
-        for split in split_sheets:
-            frames[split] = pd.read_excel(excel_path, sheet_name=split)
-            if label_col in frames[split].columns:
-                all_labels.extend(str(v) for v in frames[split][label_col].dropna())
-        classes = sorted(dict.fromkeys(all_labels))                      # :958-963
-        if class_order:
-            head = [c for c in class_order if c in classes]
-            classes = head + [c for c in classes if c not in head]
+        split_sheets, frames, classes = _dataset_sheets(excel_path, splits, label_col, class_order)
         class_to_id = {name: i for i, name in enumerate(classes)}
         dataset_stats[category_name] = {sp: 0 for sp in splits}
 

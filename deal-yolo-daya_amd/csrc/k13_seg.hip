@@ -23,6 +23,7 @@
 //      it into LDS (a lane per polygon, clipping again where needed), and the window streams out with 16-byte stores.
 //      The window is aligned to 16 bytes of the text's address, so neighbouring workgroups share no 16-byte chunk.
 #include "k13_poly.h"
+#include "k13_scan.h"
 #include "round6.h"
 
 namespace dyd {
@@ -177,6 +178,16 @@ __global__ __launch_bounds__(K13_BLOCK) void k13_scan_apply_kernel(int64_t *__re
     }
 }
 
+// the three launches on v[0..n), part = ceil(n / K13_SCAN_TILE) int64 of scratch (K16 scans its polygons' byte counts with them)
+int64_t k13_scan_parts(int64_t n) { return ceil_div(n, (int64_t)K13_SCAN_TILE); }
+
+void k13_scan_inclusive(int64_t *v, int64_t n, int64_t *part, hipStream_t st) {
+    const int64_t n_parts = k13_scan_parts(n);
+    hipLaunchKernelGGL(k13_scan_reduce_kernel, dim3((unsigned)n_parts), dim3(K13_BLOCK), 0, st, v, n, part);
+    hipLaunchKernelGGL(k13_scan_parts_kernel, dim3(1), dim3(K13_BLOCK), 0, st, part, n_parts);
+    hipLaunchKernelGGL(k13_scan_apply_kernel, dim3((unsigned)n_parts), dim3(K13_BLOCK), 0, st, v, n, part);
+}
+
 // ---- 3. print ------------------------------------------------------------------------------------------------
 // last i in [0, n] with off[i] <= x (off non-decreasing, off[0] <= x)
 template <class T>
@@ -282,7 +293,7 @@ static int seg_launch(const double *xy, const int32_t *pt_off, const int32_t *ro
                       const double *height, const int32_t *class_id, int64_t n_rows, int64_t n_polys, int64_t n_points,
                       int64_t *text_off, uint8_t *flag, uint8_t *action, uint8_t *text, int64_t text_cap, int64_t *total_out,
                       hipStream_t st) {
-    const int64_t n_parts = ceil_div(n_rows, (int64_t)K13_SCAN_TILE);
+    const int64_t n_parts = k13_scan_parts(n_rows);
     const size_t rel_bytes = 8 * (size_t)max(n_polys, (int64_t)1), m_bytes = 4 * (size_t)max(n_polys, (int64_t)1);
     const size_t part_bytes = 8 * (size_t)n_parts;
     void *scr = nullptr;
@@ -292,9 +303,7 @@ static int seg_launch(const double *xy, const int32_t *pt_off, const int32_t *ro
     int32_t *mcount = reinterpret_cast<int32_t *>(part + n_parts);
     hipLaunchKernelGGL(k13_measure_kernel, dim3((unsigned)ceil_div(n_rows, (int64_t)K13_BLOCK)), dim3(K13_BLOCK), 0, st, xy, pt_off,
                        row_off, sel, width, height, class_id, n_rows, n_polys, n_points, text_off, flag, action, rel, mcount);
-    hipLaunchKernelGGL(k13_scan_reduce_kernel, dim3((unsigned)n_parts), dim3(K13_BLOCK), 0, st, text_off + 1, n_rows, part);
-    hipLaunchKernelGGL(k13_scan_parts_kernel, dim3(1), dim3(K13_BLOCK), 0, st, part, n_parts);
-    hipLaunchKernelGGL(k13_scan_apply_kernel, dim3((unsigned)n_parts), dim3(K13_BLOCK), 0, st, text_off + 1, n_rows, part);
+    k13_scan_inclusive(text_off + 1, n_rows, part, st);
     DYD_HIP(hipGetLastError());
     int64_t total = 0;
     DYD_HIP(hipMemcpyAsync(&total, text_off + n_rows, 8, hipMemcpyDeviceToHost, st));

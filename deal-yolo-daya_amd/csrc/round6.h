@@ -1,4 +1,5 @@
-// round6.h — exact "%.6f" rounding shared by the label-line kernels (K7 boxes, K13 polygons).
+// round6.h — exact "%.6f" rounding shared by the label-line kernels (K7 boxes, K13 polygons), and its
+// two-decimal sibling for the COCO text (K16).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,6 +18,17 @@ __device__ __forceinline__ uint32_t round6(double a) {
     const double f = t - (double)n;
     const bool up = (f > 0.5) || (f == 0.5 && (e > 0.0 || (e == 0.0 && (n & 1u))));
     return n + (up ? 1u : 0u);
+}
+
+// round-half-even(v * 100) for 0 <= v < 2^43, exactly, so "%.2f" of v is this integer with a dot before its last two digits
+// (K16).  The same argument: t < 2^50 has ulp(t) <= 2^-3, so f is exact, and f != 1/2 is at least ulp(t) >= 2|e| away from it.
+__device__ __forceinline__ uint64_t fix2(double v) {
+    const double t = v * 100.0;
+    const double e = fma(v, 100.0, -t);
+    const uint64_t n = (uint64_t)t;
+    const double f = t - (double)n;
+    const bool up = (f > 0.5) || (f == 0.5 && (e > 0.0 || (e == 0.0 && (n & 1ull))));
+    return n + (up ? 1ull : 0ull);
 }
 
 }  // namespace dyd

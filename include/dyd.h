@@ -418,6 +418,48 @@ int dyd_audit_polygons_dev(const double *xy, const int32_t *pt_off, const int32_
                            int32_t n_classes, double min_area, uint8_t *out_category, uint8_t *out_defects, double *out_area,
                            int64_t *out_class_counts, int64_t *out_hist_vertices, void *stream);
 
+/* ---- K16: COCO annotation objects from the annotation polygons (the COCO export step) --------
+ * (K15 is not in use.)  Polygons are K14's, unchanged: every object the YOLO step keeps, V = (float(x), float(y)) of every
+ * ptList dict holding both keys, a value that is no number NaN.  cat_id[p] >= 1 is the polygon's COCO category id;
+ * cat_id[p] <= 0: the polygon is not selected (action 255).  width / height / size_status per row as K14 takes them.
+ * Action, the first rule that applies:
+ *   0..5  exactly K13's and K14's written, clipped, bad_coords, too_few_points, empty, no_size (no_size also for a row whose
+ *         size_status is not 0): the same device code, two points become the four corners of their box, Sutherland-Hodgman
+ *         clip to [0, W] x [0, H];
+ *   6     too_large: a written or clipped polygon whose area is not < 2^43 (a polygon that winds round the image several
+ *         times can exceed W * H; fix2 below is exact only below 2^43).
+ * Only written and clipped polygons are printed.  area = K14's, |s| * 0.5 with the shoelace sum s over the clipped vertices C
+ * in their order (bit for bit K14's area); out_area is NaN for a polygon that is not printed.
+ * fix2(v), 0 <= v < 2^43, is the text of Python's "%.2f" % v: in IEEE f64 without contraction t = v * 100.0,
+ * e = fma(v, 100.0, -t), n = (uint64)t, f = t - (double)n; n is rounded up when f > 0.5 or when f == 0.5 and (e > 0 or
+ * (e == 0 and n is odd)); the text is n / 100, a dot and two digits of n % 100: max(digits(n), 3) + 1 bytes.
+ * P = C with each coordinate clamped, px = 0.0 if not x > 0.0 else (W if x > W else x), py likewise with H (no -0.0, no
+ * rounding overshoot of an intersection).  bx = min px, by = min py, bw = max px - bx, bh = max py - by.
+ * Text of one polygon, no spaces:
+ *   {"id":A,"image_id":I,"category_id":K,"bbox":[fix2(bx),fix2(by),fix2(bw),fix2(bh)],"area":fix2(area),"iscrowd":0,
+ *    "segmentation":[[fix2(px0),fix2(py0),fix2(px1),...]]}
+ * A = ann_id_base + the polygon's index in the call (over all polygons, selected or not: ids are unique and ascending, not
+ * dense), I = image_id_base + the row's index, K = cat_id.  flags bit 0 clear: "segmentation":[] (the detect flavour; the box
+ * is still the clipped polygon's).  The text of a call is the printed polygons in polygon order joined with "," (nothing
+ * before the first or after the last; empty when none is printed).
+ * Invalid arguments: a negative id base, image_id_base + n_rows >= 2^53, ann_id_base + n_polys >= 2^53.
+ * xy [2*n_points] (16-B aligned), pt_off [n_polys+1], row_off [n_rows+1], cat_id [n_polys], width / height / size_status [n_rows].
+ * out_action u8 [n_polys], out_area f64 [n_polys], out_row_kept i32 [n_rows] = the row's printed polygons.
+ * dyd_coco_annotations     : host pointers; *out_text is allocated by the library (release with dyd_host_free).
+ * dyd_coco_annotations_dev : device pointers; out_text_or_null == NULL only measures (actions, areas, row counts, total);
+ *                            otherwise text_cap bytes are available and DYD_ERR_RANGE is returned, with the needed size in
+ *                            *out_total, when that is too little.  *out_total is a HOST int64. */
+#define DYD_COCO_SEGMENTATION 1u
+int dyd_coco_annotations(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *cat_id, const double *width,
+                         const double *height, const uint8_t *size_status, int64_t n_rows, int64_t image_id_base, int64_t ann_id_base,
+                         uint32_t flags, uint8_t *out_action, double *out_area, int32_t *out_row_kept, uint8_t **out_text,
+                         int64_t *out_text_len);
+int dyd_coco_annotations_dev(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *cat_id,
+                             const double *width, const double *height, const uint8_t *size_status, int64_t n_rows, int64_t n_polys,
+                             int64_t n_points, int64_t image_id_base, int64_t ann_id_base, uint32_t flags, uint8_t *out_action,
+                             double *out_area, int32_t *out_row_kept, uint8_t *out_text_or_null, int64_t text_cap, int64_t *out_total,
+                             void *stream);
+
 /* ---- native flatten / emit (HOST code, multithreaded) ------------------------------
  * Schema-specialised JSON scanner + canonical re-emitter that replaces json.loads / json.dumps inside
  * parse_and_replace_ptlist (processor.py:262-281), extract_width_height (:285-292) and extract_boxes

@@ -3,7 +3,7 @@
 interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant.
 
     python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k13: segmentation lines beside K7;
-     k14: polygon audit; k14tier: its in-lane / wave threshold)
+     k14: polygon audit; k14tier: its in-lane / wave threshold; k16: COCO annotation objects beside K13)
 """
 import argparse
 import json
@@ -524,6 +524,49 @@ def main():
         ptl = torch.arange(nl + 1, dtype=torch.int32, device=dev) * m
         k14_leg("long_256", xl, ptl, torch.arange(nl + 1, dtype=torch.int32, device=dev), nl, nl, nl * m)
         del xl, cat, dfc, area
+    if "k16" in only:
+        import ctypes as C
+        # K16 (COCO annotation objects) beside K13 on K13's two shapes, rounds interleaved.  K16 bytes: in 16*P + 4*(B+1) + 4*B +
+        # 4*(N+1) + 17*N, out 9*B + 4*N + T; K13 bytes as in its leg.
+        total = C.c_int64()
+        act = torch.empty(B, dtype=torch.uint8, device=dev)
+        area = torch.empty(B, dtype=torch.float64, device=dev)
+        cat = (torch.arange(B, device=dev, dtype=torch.int32) % 20 + 1).contiguous()
+        for shape, roff, nr in (("records", torch.arange(B + 1, dtype=torch.int32, device=dev), B), ("rows", box_off, N)):
+            w = torch.full((nr,), 1920.0, dtype=torch.float64, device=dev); h = torch.full((nr,), 1080.0, dtype=torch.float64, device=dev)
+            st = torch.zeros(nr, dtype=torch.uint8, device=dev)
+            cid = (torch.arange(nr, device=dev, dtype=torch.int32) % 20).contiguous()
+            toff = torch.empty(nr + 1, dtype=torch.int64, device=dev); flag = torch.empty(nr, dtype=torch.uint8, device=dev)
+            kept = torch.empty(nr, dtype=torch.int32, device=dev)
+            seg_args = (xy.data_ptr(), pt_off.data_ptr(), roff.data_ptr(), None, w.data_ptr(), h.data_ptr(), cid.data_ptr(), nr, B, P,
+                        toff.data_ptr(), flag.data_ptr(), act.data_ptr())
+            ck(L.dyd_yolo_seg_lines_dev(*seg_args, None, 0, C.byref(total), sp), "k13 measure")
+            T13 = total.value
+            text13 = torch.empty(T13, dtype=torch.uint8, device=dev)
+            for flags, name in ((1, "segment"), (0, "detect")):
+                coco_args = (xy.data_ptr(), pt_off.data_ptr(), roff.data_ptr(), cat.data_ptr(), w.data_ptr(), h.data_ptr(), st.data_ptr(),
+                             nr, B, P, 1, 1, flags, act.data_ptr(), area.data_ptr(), kept.data_ptr())
+                ck(L.dyd_coco_annotations_dev(*coco_args, None, 0, C.byref(total), sp), "k16 measure")
+                T16 = total.value
+                counts = torch.bincount(act.to(torch.int64), minlength=256)[:7].tolist()
+                text16 = torch.empty(T16, dtype=torch.uint8, device=dev)
+                res = {}
+                for rnd in range(2):                  # interleaved rounds
+                    res.setdefault("k13", []).append(timeit(lambda: ck(L.dyd_yolo_seg_lines_dev(*seg_args, text13.data_ptr(), T13,
+                                                                                                C.byref(total), sp), "k13")))
+                    res.setdefault("k16", []).append(timeit(lambda: ck(L.dyd_coco_annotations_dev(*coco_args, text16.data_ptr(), T16,
+                                                                                                  C.byref(total), sp), "k16")))
+                k13_bytes = 16 * P + 4 * (B + 1) + B + 4 * (nr + 1) + 20 * nr + 8 * (nr + 1) + nr + B + T13
+                k16_bytes = 16 * P + 4 * (B + 1) + 4 * B + 4 * (nr + 1) + 17 * nr + 9 * B + 4 * nr + T16
+                med13, mn13 = min(res["k13"])
+                med16, mn16 = min(res["k16"])
+                report(f"k13_yolo_seg_lines_{shape}", k13_bytes, med13, mn13, rows=nr, polygons=B, points=P, text_bytes=T13)
+                report(f"k16_coco_{name}_{shape}", k16_bytes, med16, mn16, rows=nr, polygons=B, points=P, text_bytes=T16,
+                       actions=dict(zip(("written", "clipped", "bad_coords", "too_few_points", "empty", "no_size", "too_large"), counts)),
+                       bytes_per_s_vs_k13=round((k16_bytes / med16) / (k13_bytes / med13), 3))
+                del text16
+            del text13
+        del act, area, cat
     if "k14tier" in only:
         import ctypes as C
         # K14's tier threshold: 1 M convex rings of m vertices (no crossing: every edge pair tested) with the in-lane limit
