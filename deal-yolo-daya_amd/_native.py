@@ -380,6 +380,35 @@ def _box_table(box4, row_off, cls, width, height, size_status) -> tuple:
     return box4, row_off, cls, width, height, size_status, n, nb
 
 
+def _poly_table(xy, pt_off, row_off, width, height, row_col: tuple, poly_col: tuple = None) -> tuple:
+    """the polygon table of K13 / K14 / K16 as contiguous arrays of the kernels' dtypes, its sizes checked -> (xy, pt_off, row_off,
+    width, height, the step's per-row column, its per-polygon column or None, n_rows, n_polys).  row_col / poly_col = (name, values,
+    dtype) of the step's own columns."""
+    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1)
+    pt_off = np.ascontiguousarray(pt_off, dtype=np.int32)
+    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
+    width = np.ascontiguousarray(width, dtype=np.float64)
+    height = np.ascontiguousarray(height, dtype=np.float64)
+    per_row = np.ascontiguousarray(row_col[1], dtype=row_col[2])
+    per_poly = np.ascontiguousarray(poly_col[1], dtype=poly_col[2]) if poly_col else None
+    n = len(row_off) - 1
+    if n < 0 or len(width) != n or len(height) != n or len(per_row) != n:
+        raise ValueError(f"row_off / width / height / {row_col[0]} sizes disagree")
+    nb = int(row_off[-1]) if n else 0
+    if (poly_col and len(per_poly) != nb) or len(pt_off) != nb + 1 or (nb and 2 * int(pt_off[-1]) != len(xy)):
+        raise ValueError(f"{poly_col[0]} and pt_off must hold one entry per polygon (pt_off one more), ending at the number of points"
+                         if poly_col else "pt_off must hold one entry per polygon plus one and end at the number of points")
+    return xy, pt_off, row_off, width, height, per_row, per_poly, n, nb
+
+
+def _take_text(text, total) -> bytes:
+    """the malloc'ed text an entry handed back, as bytes; the buffer is released"""
+    try:
+        return C.string_at(text.value, total.value) if total.value else b""
+    finally:
+        load_library().dyd_host_free(text)
+
+
 def box_audit(box4: np.ndarray, row_off: np.ndarray, cls: np.ndarray, width: np.ndarray, height: np.ndarray,
               size_status: np.ndarray, n_classes: int, nbins: int):
     """K10 over host arrays -> (flag [B] u8, row_counts [N,6] i32, class_counts [C,9] i64, hist_wh [C,nb,nb] i64,
@@ -406,19 +435,9 @@ POLY_HIST_BINS = 11    # K14 vertex-count bins: <= 2, 3, 4, 8, 16, 32, 64, 128, 
 def audit_polygons(xy, pt_off, row_off, cls, width, height, size_status, n_classes: int, min_area: float = 1.0):
     """K14 over host arrays -> (category u8 [B], defects u8 [B], area f64 [B], class_counts i64 [C, 14], hist_vertices
     i64 [C, 11]).  Codes, bits and columns: include/dyd.h."""
-    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1)
-    pt_off = np.ascontiguousarray(pt_off, dtype=np.int32)
-    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
-    cls = np.ascontiguousarray(cls, dtype=np.int32)
-    width = np.ascontiguousarray(width, dtype=np.float64)
-    height = np.ascontiguousarray(height, dtype=np.float64)
-    size_status = np.ascontiguousarray(size_status, dtype=np.uint8)
-    n, n_classes, min_area = len(row_off) - 1, int(n_classes), float(min_area)
-    if n < 0 or len(width) != n or len(height) != n or len(size_status) != n:
-        raise ValueError("row_off / width / height / size_status sizes disagree")
-    nb = int(row_off[-1]) if n else 0
-    if len(cls) != nb or len(pt_off) != nb + 1 or (nb and 2 * int(pt_off[-1]) != len(xy)):
-        raise ValueError("cls and pt_off must hold one entry per polygon (pt_off one more), ending at the number of points")
+    xy, pt_off, row_off, width, height, size_status, cls, n, nb = _poly_table(
+        xy, pt_off, row_off, width, height, ("size_status", size_status, np.uint8), ("cls", cls, np.int32))
+    n_classes, min_area = int(n_classes), float(min_area)
     cat, dfc, area = np.zeros(nb, np.uint8), np.zeros(nb, np.uint8), np.zeros(nb, np.float64)
     cc, hist = np.zeros((n_classes, POLY_CLASS_COLS), np.int64), np.zeros((n_classes, POLY_HIST_BINS), np.int64)
     check(lib().dyd_audit_polygons(_ptr(xy) if xy.size else None, _ptr(pt_off), _ptr(row_off), _ptr(cls), _ptr(width),
@@ -434,31 +453,15 @@ def coco_annotations(xy, pt_off, row_off, cat_id, width, height, size_status, im
                      flags: int = COCO_SEGMENTATION):
     """K16 over host arrays -> (action u8 [B], area f64 [B] (NaN unless printed), row_kept i32 [n], text bytes): one COCO
     annotation object per polygon with cat_id >= 1 that K13 would write, joined with ",".  Definition: include/dyd.h."""
-    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1)
-    pt_off = np.ascontiguousarray(pt_off, dtype=np.int32)
-    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
-    cat_id = np.ascontiguousarray(cat_id, dtype=np.int32)
-    width = np.ascontiguousarray(width, dtype=np.float64)
-    height = np.ascontiguousarray(height, dtype=np.float64)
-    size_status = np.ascontiguousarray(size_status, dtype=np.uint8)
-    n = len(row_off) - 1
-    if n < 0 or len(width) != n or len(height) != n or len(size_status) != n:
-        raise ValueError("row_off / width / height / size_status sizes disagree")
-    nb = int(row_off[-1]) if n else 0
-    if len(cat_id) != nb or len(pt_off) != nb + 1 or (nb and 2 * int(pt_off[-1]) != len(xy)):
-        raise ValueError("cat_id and pt_off must hold one entry per polygon (pt_off one more), ending at the number of points")
+    xy, pt_off, row_off, width, height, size_status, cat_id, n, nb = _poly_table(
+        xy, pt_off, row_off, width, height, ("size_status", size_status, np.uint8), ("cat_id", cat_id, np.int32))
     action, area, kept = np.zeros(nb, np.uint8), np.zeros(nb, np.float64), np.zeros(n, np.int32)
     text, total = C.c_void_p(), C.c_int64()
-    L = lib()
-    check(L.dyd_coco_annotations(_ptr(xy) if xy.size else None, _ptr(pt_off), _ptr(row_off), _ptr(cat_id) if nb else None,
-                                 _ptr(width), _ptr(height), _ptr(size_status), n, int(image_id_base), int(ann_id_base), int(flags),
-                                 _ptr(action) if nb else None, _ptr(area) if nb else None, _ptr(kept), C.byref(text),
-                                 C.byref(total)), "dyd_coco_annotations")
-    try:
-        data = C.string_at(text.value, total.value) if total.value else b""
-    finally:
-        L.dyd_host_free(text)
-    return action, area, kept, data
+    check(lib().dyd_coco_annotations(_ptr(xy) if xy.size else None, _ptr(pt_off), _ptr(row_off), _ptr(cat_id) if nb else None,
+                                     _ptr(width), _ptr(height), _ptr(size_status), n, int(image_id_base), int(ann_id_base),
+                                     int(flags), _ptr(action) if nb else None, _ptr(area) if nb else None, _ptr(kept), C.byref(text),
+                                     C.byref(total)), "dyd_coco_annotations")
+    return action, area, kept, _take_text(text, total)
 
 
 REPAIR_ACTIONS = 8   # action codes of K11: keep, clip, no_size, bad_coords, degenerate, outside, low_visibility, small
@@ -652,31 +655,16 @@ def yolo_lines(box4, row_off, sel, width, height, class_id):
     off = np.zeros(n + 1, np.int64)
     flag = np.zeros(n, np.uint8)
     text, total = C.c_void_p(), C.c_int64()
-    L = lib()
-    check(L.dyd_yolo_lines(_ptr(box4), _ptr(row_off), sel_p, _ptr(width), _ptr(height), _ptr(class_id), n, _ptr(off),
-                           _ptr(flag), C.byref(text), C.byref(total)), "dyd_yolo_lines")
-    try:
-        data = C.string_at(text.value, total.value) if total.value else b""
-    finally:
-        L.dyd_host_free(text)
-    return off, flag, data
+    check(lib().dyd_yolo_lines(_ptr(box4), _ptr(row_off), sel_p, _ptr(width), _ptr(height), _ptr(class_id), n, _ptr(off),
+                               _ptr(flag), C.byref(text), C.byref(total)), "dyd_yolo_lines")
+    return off, flag, _take_text(text, total)
 
 
 def yolo_seg_lines(xy, pt_off, row_off, sel, width, height, class_id):
     """K13 over host arrays -> (text_off int64 [n+1], flag u8 [n], action u8 [n_polys], text bytes).  flag 2 rows carry no
     text: the caller decides them (zero image size, negative class id).  Action codes: include/dyd.h."""
-    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1)
-    pt_off = np.ascontiguousarray(pt_off, dtype=np.int32)
-    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
-    n = len(row_off) - 1
-    width = np.ascontiguousarray(width, dtype=np.float64)
-    height = np.ascontiguousarray(height, dtype=np.float64)
-    class_id = np.ascontiguousarray(class_id, dtype=np.int32)
-    if n < 0 or len(width) != n or len(height) != n or len(class_id) != n:
-        raise ValueError("row_off / width / height / class_id sizes disagree")
-    nb = int(row_off[-1]) if n else 0
-    if len(pt_off) != nb + 1 or (nb and 2 * int(pt_off[-1]) != len(xy)):
-        raise ValueError("pt_off must hold one entry per polygon plus one and end at the number of points")
+    xy, pt_off, row_off, width, height, class_id, _, n, nb = _poly_table(xy, pt_off, row_off, width, height,
+                                                                         ("class_id", class_id, np.int32))
     sel_p = None
     if sel is not None:
         sel = np.ascontiguousarray(sel, dtype=np.uint8)
@@ -687,12 +675,7 @@ def yolo_seg_lines(xy, pt_off, row_off, sel, width, height, class_id):
     flag = np.zeros(n, np.uint8)
     action = np.zeros(nb, np.uint8)
     text, total = C.c_void_p(), C.c_int64()
-    L = lib()
-    check(L.dyd_yolo_seg_lines(_ptr(xy) if xy.size else None, _ptr(pt_off), _ptr(row_off), sel_p, _ptr(width), _ptr(height),
-                               _ptr(class_id), n, _ptr(off), _ptr(flag), _ptr(action) if nb else None, C.byref(text),
-                               C.byref(total)), "dyd_yolo_seg_lines")
-    try:
-        data = C.string_at(text.value, total.value) if total.value else b""
-    finally:
-        L.dyd_host_free(text)
-    return off, flag, action, data
+    check(lib().dyd_yolo_seg_lines(_ptr(xy) if xy.size else None, _ptr(pt_off), _ptr(row_off), sel_p, _ptr(width), _ptr(height),
+                                   _ptr(class_id), n, _ptr(off), _ptr(flag), _ptr(action) if nb else None, C.byref(text),
+                                   C.byref(total)), "dyd_yolo_seg_lines")
+    return off, flag, action, _take_text(text, total)

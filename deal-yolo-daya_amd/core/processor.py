@@ -891,6 +891,63 @@ def _csv_read_pandas(input_csv_path, col: str):
     return df
 
 
+def _step_backend(backend, attr: str):
+    """the resolved backend, which must also have the step's own entry `attr` (backend.REQUIRED lists the core entries only)"""
+    be = _backend(backend)
+    if not hasattr(be, attr):
+        raise TypeError(f"backend lacks [{attr!r}]")
+    return be
+
+
+def _chunks(n: int, cells=None, cells_of=None):
+    """(s0, s1, the cells of rows [s0, s1)) over n rows in chunks of _NATIVE_CHUNK_CELLS; the cells are sliced from `cells` or
+    made by cells_of(s0, s1)"""
+    for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
+        s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
+        yield s0, s1, cells_of(s0, s1) if cells_of is not None else cells[s0:s1]
+
+
+def _table_rows(table, json_col: str, width_col: str = "width", height_col: str = "height") -> tuple:
+    """a fastcsv table as the chunked steps read it -> (n_rows, widths, heights, sources, cells_of), cells_of(s0, s1) = the
+    cells of its heavy column json_col as str objects"""
+    col = table.heavy[json_col]
+    return (table.n_rows, *_size_columns(table.light, width_col, height_col), lambda s0, s1: _fc_cells(col, s0, s1))
+
+
+def _csv_route(key: str, input_csv_path, json_col: str, native, pandas):
+    """The route of a CSV step: native(table) on the native CSV hand-off (fastcsv's split read with json_col as the heavy
+    column) when it can read the file; when it cannot, or native returns NotImplemented, pandas(df) on pandas' read.
+    LAST_IO_PATH[key] says which.  -> what the chosen one returns; None when pandas cannot read the file or it lacks json_col."""
+    res = NotImplemented
+    if _fc.enabled() and os.path.isfile(str(input_csv_path)):
+        table = _csv_read_split(input_csv_path, [json_col], json_col)
+        if table is not NotImplemented:
+            res = native(table)
+    if res is NotImplemented:
+        LAST_IO_PATH[key] = "pandas"
+        df = _csv_read_pandas(input_csv_path, json_col)
+        return None if df is None else pandas(df)
+    LAST_IO_PATH[key] = "native"
+    return res
+
+
+def _parts_frame(parts: list, spec: tuple, sources=None) -> pd.DataFrame:
+    """per-chunk tuples of arrays -> one frame.  spec = ((column name, dtype), ...), one entry per position of the tuples, the
+    first being the row; a tuple of names stands for the columns of a 2-D array.  Without parts the columns are empty arrays of
+    those dtypes.  `sources` (optional) puts source = sources[row] in front."""
+    arrays = [np.concatenate([p[k] for p in parts]) if parts else np.zeros((0, len(names)) if isinstance(names, tuple) else 0, dtype)
+              for k, (names, dtype) in enumerate(spec)]
+    cols = {}
+    if sources is not None:
+        cols["source"] = np.asarray(sources, object)[arrays[0]] if len(arrays[0]) else np.zeros(0, object)
+    for (names, _), a in zip(spec, arrays):
+        if isinstance(names, tuple):
+            cols.update({nm: a[:, j] for j, nm in enumerate(names)})
+        else:
+            cols[names] = a
+    return pd.DataFrame(cols)                            # rows ascend; within a row the items keep their object order
+
+
 def _iou_csv_fast(input_csv_path, high_iou_csv, other_csv, min_boxes, iou_threshold, backend):
     """CSV -> two CSVs IoU step on flat buffers (see _replace_csv_fast)."""
     table = _csv_read_split(input_csv_path, [ANNOTATION_COL, BBOX_COL], BBOX_COL)
@@ -985,13 +1042,6 @@ def _corners(b):
     return min(b[0], b[2]), min(b[1], b[3]), max(b[0], b[2]), max(b[1], b[3])
 
 
-def _suppress_backend(backend):
-    be = _backend(backend)
-    if not hasattr(be, "suppress_boxes"):
-        raise TypeError("backend lacks ['suppress_boxes']")
-    return be
-
-
 def _suppress_stats(stats, totals, n_rows, texts_count, recs_count):
     if stats is not None:
         stats.update({"rows": n_rows, "boxes": totals["boxes"], "python_cells": totals["python_cells"],
@@ -1002,7 +1052,7 @@ def suppress_duplicate_boxes_cells(cells, iou_threshold: float = 0.98, by_label:
                                    stats: Optional[dict] = None) -> tuple:
     """Per bbox-JSON cell: drop every box that an earlier kept box of the same cell overlaps with IoU >= iou_threshold (of
     the same name when by_label) -> (cells with only the changed ones replaced, [(cell, object, kept_object, iou)])."""
-    be = _suppress_backend(backend)
+    be = _step_backend(backend, "suppress_boxes")
     out = list(cells)
     totals = {"boxes": 0, "python_cells": 0}
     removed, changed = [], 0
@@ -1080,7 +1130,7 @@ def _suppress_csv_fast(input_csv_path, output_csv_path, iou_threshold, by_label,
     table = _csv_read_split(input_csv_path, [ANNOTATION_COL, BBOX_COL], BBOX_COL)
     if table is NotImplemented:
         return NotImplemented
-    be = _suppress_backend(backend)
+    be = _step_backend(backend, "suppress_boxes")
     col = table.heavy[BBOX_COL]
     totals = {"boxes": 0, "python_cells": 0}
     scan = _nj.scan_box_objects_buffers(col.data, col.off, col.na)
@@ -1108,7 +1158,7 @@ def suppress_duplicate_boxes_csv(input_csv_path, output_csv_path="deduped_boxes.
         df = _csv_read_pandas(input_csv_path, BBOX_COL)
         if df is None:
             return None
-        be = _suppress_backend(backend)
+        be = _step_backend(backend, "suppress_boxes")
         stats = {}
         out, removed = suppress_duplicate_boxes_frame(df, iou_threshold, by_label, be, stats)
         Path(output_csv_path).parent.mkdir(parents=True, exist_ok=True)
@@ -2159,13 +2209,6 @@ def _size_columns(frame, width_col: str = "width", height_col: str = "height") -
             frame["source"].to_numpy() if "source" in frame.columns else None)
 
 
-def _audit_backend(backend):
-    be = _backend(backend)
-    if not hasattr(be, "box_audit"):
-        raise TypeError("backend lacks ['box_audit']")
-    return be
-
-
 class _ClassSums:
     """class-keyed int64 sums over the chunks: one array per quantity, its first axis the classes in first-seen order"""
 
@@ -2198,56 +2241,77 @@ class _BoxChunk:
         self.irregular, self.odd_names, self.dest = irregular, odd_names, dest
 
 
+def _native_scan(scanner, cells):
+    """scanner(cells), or None when the native JSON path is off or a cell holds a lone surrogate: every cell of the chunk goes
+    through CPython then"""
+    try:
+        return scanner(cells) if _nj.enabled() else None
+    except UnicodeEncodeError:
+        return None
+
+
+def _splice_items(cells, scan, cell_items, what: str) -> tuple:
+    """The items (boxes, polygons) of one chunk of cells: the native scan's with the CPython items of the irregular cells
+    (cell_items(cell) -> [(object, name, ...)]) spliced in at their rows.  `scan` is None when every cell goes through CPython.
+    -> (row_off int64 [n + 1], dest (native item -> item; None when nothing was spliced), obj and cls per item (cls -1: the name
+    is no str), names (class id -> name), odd_names {item: that name}, irregular (the cells scanned by CPython), py {cell: its
+    CPython items})"""
+    n = len(cells)
+    if scan is not None:
+        nat_off = scan.cell_box_off.astype(np.int64)
+        irregular = np.flatnonzero(scan.status == _nj.IRREGULAR).tolist()
+        names, obj, cls = list(scan.names), scan.box_object, scan.box_class
+    else:
+        nat_off = np.zeros(n + 1, np.int64)
+        irregular = list(range(n))
+        names, obj, cls = [], np.zeros(0, np.int32), np.zeros(0, np.int32)
+    counts = np.diff(nat_off)
+    py = {}
+    for i in irregular:
+        items = cell_items(cells[i])
+        if items:
+            py[i] = items
+            counts[i] = len(items)
+    row_off = np.zeros(n + 1, np.int64)
+    np.cumsum(counts, out=row_off[1:])
+    nb = int(row_off[-1])
+    if nb >= (1 << 31):
+        raise ValueError(f"a chunk holds 2^31 {what} or more")
+    odd_names, dest = {}, None
+    if py:
+        dest = np.repeat(row_off[:-1] - nat_off[:-1], np.diff(nat_off)) + np.arange(len(obj), dtype=np.int64)
+        ob, cl = np.empty(nb, np.int32), np.empty(nb, np.int32)
+        ob[dest], cl[dest] = obj, cls
+        ids = {nm: k for k, nm in enumerate(names)}
+        for i, items in py.items():
+            p = int(row_off[i])
+            for k, (o, nm, *_) in enumerate(items):
+                ob[p + k] = o
+                if isinstance(nm, str):
+                    cl[p + k] = ids.setdefault(nm, len(ids))
+                else:
+                    cl[p + k] = -1
+                    odd_names[p + k] = nm
+        obj, cls, names = ob, cl, list(ids)
+    return row_off, dest, obj, cls, names, odd_names, irregular, py
+
+
 def _box_chunk(cells) -> _BoxChunk:
     """one chunk of cells -> its box table: the native scan's boxes with the CPython boxes of the irregular cells
-    (flatten.audit_cell_boxes) spliced in at their rows.  row_off (int64 [n + 1]), box4, obj and cls per box (cls -1: the name
-    is no str; odd_names = {box: that name}), names (class id -> name), irregular (the cells scanned by CPython), dest (native
-    box -> box; None when nothing was spliced) and scan: the NamedBoxScan, still open (None without one): the caller closes it."""
-    n = len(cells)
+    (flatten.audit_cell_boxes) spliced in at their rows (_splice_items' columns and box4 per box) and scan: the NamedBoxScan,
+    still open (None without one): the caller closes it."""
+    scan = _native_scan(_nj.scan_named_boxes, cells)
     try:
-        scan = _nj.scan_named_boxes(cells) if _nj.enabled() else None
-    except UnicodeEncodeError:                           # a lone surrogate: every cell of the chunk through CPython
-        scan = None
-    try:
-        if scan is not None:
-            nat_off = scan.cell_box_off.astype(np.int64)
-            irregular = np.flatnonzero(scan.status == _nj.IRREGULAR).tolist()
-            names = list(scan.names)
-            box4, obj, cls = scan.box4, scan.box_object, scan.box_class
-        else:
-            nat_off = np.zeros(n + 1, np.int64)
-            irregular = list(range(n))
-            names, box4, obj, cls = [], np.zeros((0, 4)), np.zeros(0, np.int32), np.zeros(0, np.int32)
-        counts = np.diff(nat_off)
-        py = {}
-        for i in irregular:
-            boxes = _fl.audit_cell_boxes(cells[i])
-            if boxes:
-                py[i] = boxes
-                counts[i] = len(boxes)
-        row_off = np.zeros(n + 1, np.int64)
-        np.cumsum(counts, out=row_off[1:])
-        nb = int(row_off[-1])
-        if nb >= (1 << 31):
-            raise ValueError("a chunk holds 2^31 boxes or more")
-        odd_names, dest = {}, None
-        if py:                                           # splice the CPython boxes in at their rows
-            dest = np.repeat(row_off[:-1] - nat_off[:-1], np.diff(nat_off)) + np.arange(len(obj), dtype=np.int64)
-            b4, ob, cl = np.empty((nb, 4)), np.empty(nb, np.int32), np.empty(nb, np.int32)
-            b4[dest], ob[dest], cl[dest] = box4, obj, cls
-            ids = {nm: k for k, nm in enumerate(names)}
+        row_off, dest, obj, cls, names, odd_names, irregular, py = _splice_items(cells, scan, _fl.audit_cell_boxes, "boxes")
+        box4 = scan.box4 if scan is not None else np.zeros((0, 4))
+        if py:
+            b4 = np.empty((int(row_off[-1]), 4))
+            b4[dest] = box4
             for i, boxes in py.items():
                 p = int(row_off[i])
-                for k, (o, nm, *xy) in enumerate(boxes):
+                for k, (_, _, *xy) in enumerate(boxes):
                     b4[p + k] = [_audit_number(v) for v in xy]
-                    ob[p + k] = o
-                    if isinstance(nm, str):
-                        cl[p + k] = ids.setdefault(nm, len(ids))
-                    else:
-                        cl[p + k] = -1
-                        odd_names[p + k] = nm
-            names = list(ids)
-            box4, obj, cls = b4, ob, cl
+            box4 = b4
     except BaseException:
         if scan is not None:
             scan.close()
@@ -2289,23 +2353,29 @@ def _audit_chunk(cells, status, W, H, be, acc: _AuditTotals, start: int):
                              name_arr[cls[bad]], issue, np.asarray(box4, np.float64).reshape(-1, 4)[bad]))
 
 
+def _audit_nbins(nbins) -> int:
+    if isinstance(nbins, bool) or not isinstance(nbins, (int, np.integer)) or not 1 <= int(nbins) <= 64:
+        raise ValueError(f"nbins must be an int in 1..64, got {nbins!r}")
+    return int(nbins)
+
+
+def _audit_rows(cells, n, widths, heights, be, nbins, sources, stats, cells_of=None) -> BoxAudit:
+    status, W, H = _audit_sizes(widths, heights, n)
+    acc = _AuditTotals(nbins)
+    for s0, s1, chunk in _chunks(n, cells, cells_of):
+        _audit_chunk(chunk, status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0)
+    return _audit_result(acc, n, status, sources, stats)
+
+
 def audit_boxes_cells(cells, widths, heights, nbins: int = 16, backend=None, stats: Optional[dict] = None,
                       sources=None) -> BoxAudit:
     """Box audit of the annotation cells of a table (see the section comment; widths / heights are the row's image size as the
     YOLO step reads it, None for a table without the columns).  -> BoxAudit.  ``sources`` (optional) adds a source column to
     per_row and problems."""
-    if isinstance(nbins, bool) or not isinstance(nbins, (int, np.integer)) or not 1 <= int(nbins) <= 64:
-        raise ValueError(f"nbins must be an int in 1..64, got {nbins!r}")
-    nbins = int(nbins)
-    be = _audit_backend(backend)
+    nbins = _audit_nbins(nbins)
+    be = _step_backend(backend, "box_audit")
     cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
-    n = len(cells)
-    status, W, H = _audit_sizes(widths, heights, n)
-    acc = _AuditTotals(nbins)
-    for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
-        s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
-        _audit_chunk(cells[s0:s1], status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0)
-    return _audit_result(acc, n, status, sources, stats)
+    return _audit_rows(cells, len(cells), widths, heights, be, nbins, sources, stats)
 
 
 def _audit_result(acc: _AuditTotals, n: int, status, sources, stats) -> BoxAudit:
@@ -2324,16 +2394,8 @@ def _audit_result(acc: _AuditTotals, n: int, status, sources, stats) -> BoxAudit
     pr["n_boxes"] = n_boxes
     pr.update({k: rows[:, j] for j, k in enumerate(_AUDIT_ROW_COLS)})
     per_row = pd.DataFrame(pr)
-    pc = {}
-    if acc.problems:
-        r, o, nm, issue, b = (np.concatenate([p[k] for p in acc.problems]) for k in range(5))
-    else:
-        r, o, nm, issue, b = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, object), np.zeros(0, object),
-                              np.zeros((0, 4)))
-    if sources is not None:
-        pc["source"] = np.asarray(sources, object)[r] if len(r) else np.zeros(0, object)
-    pc.update({"row": r, "object": o, "name": nm, "issue": issue, "x1": b[:, 0], "y1": b[:, 1], "x2": b[:, 2], "y2": b[:, 3]})
-    problems = pd.DataFrame(pc)                          # rows ascend; within a row the boxes keep their object order
+    problems = _parts_frame(acc.problems, (("row", np.int64), ("object", np.int64), ("name", object), ("issue", object),
+                                           (("x1", "y1", "x2", "y2"), np.float64)), sources)
     status = np.asarray(status)
     totals = {"rows": n, "rows_ok": int((status == 0).sum()), "rows_missing": int((status == 1).sum()),
               "rows_invalid": int((status == 2).sum()), "boxes": int(n_boxes.sum()),
@@ -2350,23 +2412,6 @@ def audit_boxes_frame(df: pd.DataFrame, json_col: str = BBOX_COL, width_col: str
     cells = df[json_col].to_numpy()
     widths, heights, sources = _size_columns(df, width_col, height_col)
     return audit_boxes_cells(cells, widths, heights, nbins, backend, stats, sources)
-
-
-def _audit_csv_fast(input_csv_path, json_col, nbins, backend):
-    """-> BoxAudit, or NotImplemented (the pandas route decides then)"""
-    table = _csv_read_split(input_csv_path, [json_col], json_col)
-    if table is NotImplemented:
-        return NotImplemented
-    be = _audit_backend(backend)
-    col = table.heavy[json_col]
-    n = table.n_rows
-    widths, heights, sources = _size_columns(table.light)
-    status, W, H = _audit_sizes(widths, heights, n)
-    acc = _AuditTotals(nbins)
-    for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
-        s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
-        _audit_chunk(_fc_cells(col, s0, s1), status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0)
-    return _audit_result(acc, n, status, sources, None)
 
 
 def _fc_cells(col, s0, s1):
@@ -2392,20 +2437,15 @@ def audit_boxes_csv(input_csv_path, output_dir, json_col: str = BBOX_COL, nbins:
     """CSV -> box_audit_classes.csv, box_audit_problems.csv and box_audit_hist.npz (classes, hist_wh, hist_xy,
     boxes_per_image) under output_dir, in the IoU step's conventions: read as utf-8-sig; a read failure prints 读取失败：...
     and a missing column 错误：缺少必要列 ..., both returning None.  -> dict(totals, paths=...)"""
-    if isinstance(nbins, bool) or not isinstance(nbins, (int, np.integer)) or not 1 <= int(nbins) <= 64:
-        raise ValueError(f"nbins must be an int in 1..64, got {nbins!r}")
-    audit = NotImplemented
-    if _fc.enabled() and os.path.isfile(str(input_csv_path)):
-        audit = _audit_csv_fast(input_csv_path, json_col, int(nbins), backend)
-    if audit is NotImplemented:
-        LAST_IO_PATH["audit"] = "pandas"
-        df = _csv_read_pandas(input_csv_path, json_col)
-        if df is None:
-            return None
-        audit = audit_boxes_frame(df, json_col, nbins=int(nbins), backend=backend)
-    else:
-        LAST_IO_PATH["audit"] = "native"
-    return {**audit.totals, "paths": _write_audit(audit, output_dir)}
+    nbins = _audit_nbins(nbins)
+
+    def native(table):
+        n, widths, heights, sources, cells_of = _table_rows(table, json_col)
+        return _audit_rows(None, n, widths, heights, _step_backend(backend, "box_audit"), nbins, sources, None, cells_of)
+
+    audit = _csv_route("audit", input_csv_path, json_col, native,
+                       lambda df: audit_boxes_frame(df, json_col, nbins=nbins, backend=backend))
+    return None if audit is None else {**audit.totals, "paths": _write_audit(audit, output_dir)}
 
 
 # =============================================================================== f6  box repair
@@ -2420,13 +2460,6 @@ def audit_boxes_csv(input_csv_path, output_dir, json_col: str = BBOX_COL, nbins:
 # the same K11 launch and re-spelled by flatten.repair_cell.
 REPAIR_ACTIONS = ("keep", "clip", "no_size", "bad_coords", "degenerate", "outside", "low_visibility", "small")   # K11 codes 0..7
 _REPAIR_CHANGE_COLS = ("row", "object", "name", "action", "x1", "y1", "x2", "y2", "nx1", "ny1", "nx2", "ny2")
-
-
-def _repair_backend(backend):
-    be = _backend(backend)
-    if not hasattr(be, "repair_boxes"):
-        raise TypeError("backend lacks ['repair_boxes']")
-    return be
 
 
 def _repair_params(min_visibility, min_size) -> tuple:
@@ -2507,17 +2540,8 @@ def _repair_chunk(cells, status, W, H, be, acc: _RepairTotals, start: int, min_v
 
 def _repair_result(acc: _RepairTotals, n: int, status, sources) -> tuple:
     """-> (changes frame, per_class frame, totals)"""
-    if acc.changes:
-        r, o, nm, act, b, nb4 = (np.concatenate([c[k] for c in acc.changes]) for k in range(6))
-    else:
-        r, o, nm, act, b, nb4 = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, object), np.zeros(0, object),
-                                 np.zeros((0, 4)), np.zeros((0, 4)))
-    ch = {}
-    if sources is not None:
-        ch["source"] = np.asarray(sources, object)[r] if len(r) else np.zeros(0, object)
-    ch.update({"row": r, "object": o, "name": nm, "action": act, "x1": b[:, 0], "y1": b[:, 1], "x2": b[:, 2], "y2": b[:, 3],
-               "nx1": nb4[:, 0], "ny1": nb4[:, 1], "nx2": nb4[:, 2], "ny2": nb4[:, 3]})
-    changes = pd.DataFrame(ch)                           # rows ascend; within a row the boxes keep their object order
+    changes = _parts_frame(acc.changes, (("row", np.int64), ("object", np.int64), ("name", object), ("action", object),
+                                         (_REPAIR_CHANGE_COLS[4:8], np.float64), (_REPAIR_CHANGE_COLS[8:], np.float64)), sources)
     classes, (cc,) = acc.classes.sorted()
     per_class = pd.DataFrame({"class": pd.Series(classes, dtype=object), "boxes": cc.sum(axis=1),
                               **{k: cc[:, j] for j, k in enumerate(REPAIR_ACTIONS)}})
@@ -2537,20 +2561,26 @@ def repair_boxes_cells(cells, widths, heights, min_visibility: float = 0.0, min_
     return out.tolist(), changes, per_class
 
 
+def _repair_rows(cells, n, widths, heights, min_vis, min_size, be, sources, cells_of=None) -> tuple:
+    """-> ([(changed rows, their new texts) per chunk], changes frame, per_class frame, totals)"""
+    status, W, H = _audit_sizes(widths, heights, n)
+    acc = _RepairTotals()
+    texts = []
+    for s0, s1, chunk in _chunks(n, cells, cells_of):
+        idx, strs = _repair_chunk(chunk, status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, min_vis, min_size)
+        texts.append((s0 + idx, strs))
+    return (texts, *_repair_result(acc, n, status, sources))
+
+
 def _repair_cells_array(cells, widths, heights, min_visibility, min_size, backend, stats, sources) -> tuple:
     """repair_boxes_cells with the cells as an object array"""
     min_vis, min_size = _repair_params(min_visibility, min_size)
-    be = _repair_backend(backend)
+    be = _step_backend(backend, "repair_boxes")
     cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
-    n = len(cells)
-    status, W, H = _audit_sizes(widths, heights, n)
-    out = np.fromiter(cells, object, n)                  # the same objects; only the changed rows are replaced
-    acc = _RepairTotals()
-    for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
-        s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
-        idx, strs = _repair_chunk(cells[s0:s1], status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, min_vis, min_size)
-        out[s0 + idx] = strs
-    changes, per_class, totals = _repair_result(acc, n, status, sources)
+    texts, changes, per_class, totals = _repair_rows(cells, len(cells), widths, heights, min_vis, min_size, be, sources)
+    out = np.fromiter(cells, object, len(cells))         # the same objects; only the changed rows are replaced
+    for idx, strs in texts:
+        out[idx] = strs
     if stats is not None:
         stats.update(totals)
     return out, changes, per_class
@@ -2570,27 +2600,6 @@ def repair_boxes_frame(df: pd.DataFrame, json_col: str = BBOX_COL, width_col: st
     return out, changes, per_class
 
 
-def _repair_csv_fast(input_csv_path, output_csv_path, json_col, min_vis, min_size, backend):
-    """-> (changes, per_class, totals), or NotImplemented (nothing written then; the pandas route decides)"""
-    table = _csv_read_split(input_csv_path, [json_col], json_col)
-    if table is NotImplemented:
-        return NotImplemented
-    be = _repair_backend(backend)
-    col = table.heavy[json_col]
-    n = table.n_rows
-    widths, heights, sources = _size_columns(table.light)
-    status, W, H = _audit_sizes(widths, heights, n)
-    acc = _RepairTotals()
-    texts = {}
-    for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
-        s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
-        idx, strs = _repair_chunk(_fc_cells(col, s0, s1), status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, min_vis, min_size)
-        texts.update(zip((s0 + idx).tolist(), strs))
-    if not _csv_write_spliced(output_csv_path, table, json_col, texts):
-        return NotImplemented
-    return _repair_result(acc, n, status, sources)
-
-
 def repair_boxes_csv(input_csv_path, output_csv_path="repaired_boxes.csv", changes_csv=None, classes_csv=None,
                      json_col: str = BBOX_COL, min_visibility: float = 0.0, min_size: float = 0.0, backend=None):
     """CSV -> CSV twin of repair_boxes_frame, in the IoU step's conventions: read as utf-8-sig; a read failure prints
@@ -2598,22 +2607,26 @@ def repair_boxes_csv(input_csv_path, output_csv_path="repaired_boxes.csv", chang
     rewritten; `changes_csv` / `classes_csv` (optional) receive the two frames.  -> {"rows", "rows_changed", "boxes",
     "boxes_clipped", "boxes_removed", "rows_no_size", "python_cells", "output", "changes_output", "classes_output"}"""
     min_vis, min_size = _repair_params(min_visibility, min_size)
-    res = NotImplemented
-    if _fc.enabled() and os.path.isfile(str(input_csv_path)):
-        res = _repair_csv_fast(input_csv_path, output_csv_path, json_col, min_vis, min_size, backend)
-    if res is NotImplemented:
-        LAST_IO_PATH["repair"] = "pandas"
-        df = _csv_read_pandas(input_csv_path, json_col)
-        if df is None:
-            return None
+
+    def native(table):                                   # NotImplemented (nothing written) when the native writer declines
+        n, widths, heights, sources, cells_of = _table_rows(table, json_col)
+        texts, *res = _repair_rows(None, n, widths, heights, min_vis, min_size, _step_backend(backend, "repair_boxes"), sources,
+                                   cells_of)
+        texts = {i: t for idx, strs in texts for i, t in zip(idx.tolist(), strs)}
+        return res if _csv_write_spliced(output_csv_path, table, json_col, texts) else NotImplemented
+
+    def pandas(df):
         totals = {}
         out, changes, per_class = repair_boxes_frame(df, json_col, min_visibility=min_vis, min_size=min_size,
                                                      backend=backend, stats=totals)
         Path(output_csv_path).parent.mkdir(parents=True, exist_ok=True)
         out.to_csv(output_csv_path, index=False, encoding="utf-8-sig")
-    else:
-        LAST_IO_PATH["repair"] = "native"
-        changes, per_class, totals = res
+        return changes, per_class, totals
+
+    res = _csv_route("repair", input_csv_path, json_col, native, pandas)
+    if res is None:
+        return None
+    changes, per_class, totals = res
     for path, frame in ((changes_csv, changes), (classes_csv, per_class)):
         if path is not None:
             Path(path).parent.mkdir(parents=True, exist_ok=True)
@@ -2627,13 +2640,6 @@ def repair_boxes_csv(input_csv_path, output_csv_path="repaired_boxes.csv", chang
 # irregular cells) -> K13 (csrc/k13_seg.hip) -> strings.
 SEG_ACTIONS = ("written", "clipped", "bad_coords", "too_few_points", "empty", "no_size")   # K13 codes 0..5
 _SEG_LIMIT = float(1 << 43)
-
-
-def _seg_backend(backend):
-    be = _backend(backend)
-    if not hasattr(be, "yolo_seg_lines"):
-        raise TypeError("backend lacks ['yolo_seg_lines']")
-    return be
 
 
 def _seg_size(v):
@@ -2706,7 +2712,7 @@ def yolo_seg_label_texts(cells, label_values, class_ids, widths, heights, backen
     two_point (matched polygons of exactly two points).
     Host: native labelled-polygon scan (csrc/host_json.cpp; CPython json for irregular cells) + label match; device: K13
     (clipping, exact "%.6f", joining)."""
-    be = _seg_backend(backend)
+    be = _step_backend(backend, "yolo_seg_lines")
     n = len(cells)
     texts, reasons = [None] * n, [None] * n
     acts = np.zeros(256, np.int64)
@@ -2824,13 +2830,6 @@ class PolygonAudit:
         return f"PolygonAudit({len(self.classes)} classes, {self.totals})"
 
 
-def _poly_backend(backend):
-    be = _backend(backend)
-    if not hasattr(be, "audit_polygons"):
-        raise TypeError("backend lacks ['audit_polygons']")
-    return be
-
-
 def _poly_min_area(min_area) -> float:
     if isinstance(min_area, bool) or not isinstance(min_area, _NUMBER_TYPES):
         raise ValueError(f"min_area must be a finite number >= 0, got {min_area!r}")
@@ -2843,46 +2842,21 @@ def _poly_min_area(min_area) -> float:
 def _poly_chunk(cells) -> tuple:
     """one chunk of cells -> (row_off int64 [n+1], xy f64 [2P], pt_off int32 [B+1], obj int32 [B], cls int32 [B] (-1: the name
     is no str), names, number of cells scanned by CPython): the native scan's polygons with the CPython ones of the irregular
-    cells (flatten.seg_cell_polygons) spliced in at their rows"""
-    n = len(cells)
+    cells (flatten.seg_cell_polygons) spliced in at their rows (_splice_items), and their points"""
+    scan = _native_scan(_nj.scan_named_polygons, cells)
     try:
-        scan = _nj.scan_named_polygons(cells) if _nj.enabled() else None
-    except UnicodeEncodeError:                           # a lone surrogate: every cell of the chunk through CPython
-        scan = None
-    if scan is not None:
-        nat_off = scan.cell_box_off.astype(np.int64)
-        irregular = np.flatnonzero(scan.status == _nj.IRREGULAR).tolist()
-        names, xy, pt_off, obj, cls = list(scan.names), scan.xy, scan.pt_off, scan.box_object, scan.box_class
-        scan.close()
-    else:
-        nat_off = np.zeros(n + 1, np.int64)
-        irregular = list(range(n))
-        names, xy, pt_off = [], np.zeros(0), np.zeros(1, np.int32)
-        obj, cls = np.zeros(0, np.int32), np.zeros(0, np.int32)
-    counts = np.diff(nat_off)
-    py = {}
-    for i in irregular:
-        polys = _fl.seg_cell_polygons(cells[i])
-        if polys:
-            py[i] = polys
-            counts[i] = len(polys)
-    row_off = np.zeros(n + 1, np.int64)
-    np.cumsum(counts, out=row_off[1:])
-    nb = int(row_off[-1])
-    if py:                                               # splice the CPython polygons in at their rows
-        dest = np.repeat(row_off[:-1] - nat_off[:-1], np.diff(nat_off)) + np.arange(len(obj), dtype=np.int64)
-        npts = np.zeros(nb, np.int64)
+        row_off, dest, obj, cls, names, _, irregular, py = _splice_items(cells, scan, _fl.seg_cell_polygons, "polygons")
+        xy, pt_off = (scan.xy, scan.pt_off) if scan is not None else (np.zeros(0), np.zeros(1, np.int32))
+    finally:
+        if scan is not None:
+            scan.close()
+    if py:
+        nb = int(row_off[-1])
         nat_npts = np.diff(pt_off.astype(np.int64))
+        npts = np.zeros(nb, np.int64)
         npts[dest] = nat_npts
-        ob, cl = np.empty(nb, np.int32), np.empty(nb, np.int32)
-        ob[dest], cl[dest] = obj, cls
-        ids = {nm: k for k, nm in enumerate(names)}
         for i, polys in py.items():
-            p = int(row_off[i])
-            for k, (o, nm, pts) in enumerate(polys):
-                npts[p + k] = len(pts)
-                ob[p + k] = o
-                cl[p + k] = ids.setdefault(nm, len(ids)) if isinstance(nm, str) else -1
+            npts[row_off[i]:row_off[i] + len(polys)] = [len(pts) for _, _, pts in polys]
         off = np.zeros(nb + 1, np.int64)
         np.cumsum(npts, out=off[1:])
         if off[-1] >= (1 << 31):
@@ -2895,9 +2869,7 @@ def _poly_chunk(cells) -> tuple:
             for k, (_, _, pts) in enumerate(polys):
                 if pts:
                     xy2[off[p + k]:off[p + k + 1]] = [(_audit_number(x), _audit_number(y)) for x, y in pts]
-        xy, pt_off, obj, cls, names = xy2.reshape(-1), off.astype(np.int32), ob, cl, list(ids)
-    if nb >= (1 << 31):
-        raise ValueError("a chunk holds 2^31 polygons or more")
+        xy, pt_off = xy2.reshape(-1), off.astype(np.int32)
     return row_off, xy, pt_off, obj, cls, names, len(irregular)
 
 
@@ -2930,16 +2902,8 @@ def _poly_result(acc: _PolyTotals, n: int, status, sources, min_area, stats) -> 
     classes, (cc, hist) = acc.classes.sorted()
     cols = dict(zip(_POLY_CLASS_COLS, cc.T)) if len(classes) else {k: np.zeros(0, np.int64) for k in _POLY_CLASS_COLS}
     per_class = pd.DataFrame({"class": pd.Series(classes, dtype=object), **cols})
-    if acc.problems:
-        parts = [np.concatenate([p[k] for p in acc.problems]) for k in range(7)]
-    else:
-        parts = [np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, object), np.zeros(0, object), np.zeros(0, object),
-                 np.zeros(0, np.int64), np.zeros(0)]
-    pc = {}
-    if sources is not None:
-        pc["source"] = np.asarray(sources, object)[parts[0]] if len(parts[0]) else np.zeros(0, object)
-    pc.update(dict(zip(("row", "object", "name", "category", "defects", "points", "area"), parts)))
-    problems = pd.DataFrame(pc)                          # rows ascend; within a row the polygons keep their object order
+    problems = _parts_frame(acc.problems, (("row", np.int64), ("object", np.int64), ("name", object), ("category", object),
+                                           ("defects", object), ("points", np.int64), ("area", np.float64)), sources)
     status = np.asarray(status)
     totals = {"rows": n, "rows_ok": int((status == 0).sum()), "rows_missing": int((status == 1).sum()),
               "rows_invalid": int((status == 2).sum()), "polygons": acc.polygons, "unmatchable_name_polygons": acc.unmatchable,
@@ -2953,9 +2917,7 @@ def _poly_result(acc: _PolyTotals, n: int, status, sources, min_area, stats) -> 
 def _poly_audit_rows(cells, n, widths, heights, be, min_area, sources, stats, cells_of=None) -> PolygonAudit:
     status, W, H = _audit_sizes(widths, heights, n)
     acc = _PolyTotals()
-    for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
-        s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
-        chunk = cells_of(s0, s1) if cells_of is not None else cells[s0:s1]
+    for s0, s1, chunk in _chunks(n, cells, cells_of):
         _poly_audit_chunk(chunk, status[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, min_area)
     return _poly_result(acc, n, status, sources, min_area, stats)
 
@@ -2965,7 +2927,7 @@ def audit_polygons_cells(cells, widths, heights, min_area: float = 1.0, backend=
     """Polygon audit of the annotation cells of a table (see the section comment; widths / heights as in audit_boxes_cells).
     -> PolygonAudit.  ``sources`` (optional) adds a source column to problems."""
     min_area = _poly_min_area(min_area)
-    be = _poly_backend(backend)
+    be = _step_backend(backend, "audit_polygons")
     cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
     return _poly_audit_rows(cells, len(cells), widths, heights, be, min_area, sources, stats)
 
@@ -2997,24 +2959,14 @@ def audit_polygons_csv(input_csv_path, output_dir, json_col: str = ANNOTATION_CO
     under output_dir, in the box audit's conventions (audit_boxes_csv).  -> dict(totals, paths=...), or None when the file
     cannot be read or lacks the column."""
     min_area = _poly_min_area(min_area)
-    audit = NotImplemented
-    if _fc.enabled() and os.path.isfile(str(input_csv_path)):
-        table = _csv_read_split(input_csv_path, [json_col], json_col)
-        if table is not NotImplemented:
-            be = _poly_backend(backend)
-            col = table.heavy[json_col]
-            widths, heights, sources = _size_columns(table.light)
-            audit = _poly_audit_rows(None, table.n_rows, widths, heights, be, min_area, sources, None,
-                                     cells_of=lambda s0, s1: _fc_cells(col, s0, s1))
-    if audit is NotImplemented:
-        LAST_IO_PATH["polygon_audit"] = "pandas"
-        df = _csv_read_pandas(input_csv_path, json_col)
-        if df is None:
-            return None
-        audit = audit_polygons_frame(df, json_col, min_area=min_area, backend=backend)
-    else:
-        LAST_IO_PATH["polygon_audit"] = "native"
-    return {**audit.totals, "paths": _write_poly_audit(audit, output_dir)}
+
+    def native(table):
+        n, widths, heights, sources, cells_of = _table_rows(table, json_col)
+        return _poly_audit_rows(None, n, widths, heights, _step_backend(backend, "audit_polygons"), min_area, sources, None, cells_of)
+
+    audit = _csv_route("polygon_audit", input_csv_path, json_col, native,
+                       lambda df: audit_polygons_frame(df, json_col, min_area=min_area, backend=backend))
+    return None if audit is None else {**audit.totals, "paths": _write_poly_audit(audit, output_dir)}
 
 
 # =============================================================================== f7c  COCO export
@@ -3026,13 +2978,6 @@ def audit_polygons_csv(input_csv_path, output_dir, json_col: str = ANNOTATION_CO
 # polygons (row order, then object order), so the file is written in one pass over the chunks.
 COCO_ACTIONS = (*SEG_ACTIONS, "too_large")                 # K16 codes 0..6
 _COCO_INFO = {"description": "COCO export of deal-yolo-daya_amd", "version": "1.0"}
-
-
-def _coco_backend(backend):
-    be = _backend(backend)
-    if not hasattr(be, "coco_annotations"):
-        raise TypeError("backend lacks ['coco_annotations']")
-    return be
 
 
 def _coco_json(value) -> bytes:
@@ -3124,9 +3069,7 @@ def _coco_export_rows(cells, n, widths, heights, sources, labels, classes, segme
     no_size = 0
     with open(tmp, "wb") as out:
         out.write(b'{"info":' + _coco_json(_COCO_INFO) + b',"licenses":[],"annotations":[')
-        for s0 in range(0, n, _NATIVE_CHUNK_CELLS):
-            s1 = min(n, s0 + _NATIVE_CHUNK_CELLS)
-            chunk = cells_of(s0, s1) if cells_of is not None else cells[s0:s1]
+        for s0, s1, chunk in _chunks(n, cells, cells_of):
             no_size += _coco_chunk(chunk, None if labels is None else labels[s0:s1], status[s0:s1], W[s0:s1], H[s0:s1], name_of, be,
                                    acc, s0, flags, bool(keep_empty_images), out)
         categories = [{"id": k, "name": nm, "supercategory": ""} for nm, k in acc.cat_of.items()]
@@ -3134,13 +3077,8 @@ def _coco_export_rows(cells, n, widths, heights, sources, labels, classes, segme
                   b",".join(_coco_json(c) for c in categories) + b"]}")
     os.replace(tmp, output_json)
     if skipped_csv:
-        parts = [np.concatenate([p[k] for p in acc.skipped]) if acc.skipped else np.zeros(0, np.int64 if k < 2 else object)
-                 for k in range(4)]
-        cols = {}
-        if sources is not None:
-            cols["source"] = np.asarray(sources, object)[parts[0]] if len(parts[0]) else np.zeros(0, object)
-        cols.update(dict(zip(("row", "object", "name", "action"), parts)))
-        pd.DataFrame(cols).to_csv(skipped_csv, index=False, encoding="utf-8-sig")
+        skipped = _parts_frame(acc.skipped, (("row", np.int64), ("object", np.int64), ("name", object), ("action", object)), sources)
+        skipped.to_csv(skipped_csv, index=False, encoding="utf-8-sig")
     result = {"rows": n, "rows_no_size": no_size, "images": len(acc.image_parts), "polygons": acc.polygons,
               **{a: int(acc.actions[k]) for k, a in enumerate(COCO_ACTIONS)}, "unmatchable_name_polygons": acc.unmatchable,
               "unknown_class": acc.unknown, "annotations": int(acc.actions[0] + acc.actions[1]), "categories": categories,
@@ -3164,7 +3102,7 @@ def export_coco_frame(df: pd.DataFrame, output_json, json_col: str = ANNOTATION_
     written to output_json + ".tmp" and moved into place.  -> dict(rows, rows_no_size, images, polygons, one count per
     COCO_ACTIONS entry over the selected polygons, unmatchable_name_polygons, unknown_class, annotations, categories,
     python_cells, output, skipped_output)."""
-    be = _coco_backend(backend)
+    be = _step_backend(backend, "coco_annotations")
     if label_col is not None and label_col not in df.columns:
         raise ValueError(f"no column {label_col!r}")
     cells = df[json_col].to_numpy()
@@ -3181,27 +3119,19 @@ def export_coco_csv(input_csv_path, output_json, json_col: str = ANNOTATION_COL,
                     stats: Optional[dict] = None):
     """CSV -> COCO instances file, export_coco_frame on the native CSV hand-off (the polygon column is never parsed by pandas).
     -> export_coco_frame's dict, or None when the file cannot be read or lacks the column."""
-    result = NotImplemented
-    if _fc.enabled() and os.path.isfile(str(input_csv_path)):
-        table = _csv_read_split(input_csv_path, [json_col], json_col)
-        if table is not NotImplemented and (label_col is None or label_col in table.light.columns):
-            be = _coco_backend(backend)
-            col, light = table.heavy[json_col], table.light
-            widths, heights, _ = _size_columns(light, width_col, height_col)
-            sources = light[source_col].to_numpy() if source_col in light.columns else None
-            labels = light[label_col].to_numpy() if label_col is not None else None
-            result = _coco_export_rows(None, table.n_rows, widths, heights, sources, labels, classes, segmentation,
-                                       keep_empty_images, file_names, output_json, skipped_csv, be, stats,
-                                       cells_of=lambda s0, s1: _fc_cells(col, s0, s1))
-    if result is NotImplemented:
-        LAST_IO_PATH["coco_export"] = "pandas"
-        df = _csv_read_pandas(input_csv_path, json_col)
-        if df is None:
-            return None
-        return export_coco_frame(df, output_json, json_col, width_col, height_col, source_col, label_col, classes, segmentation,
-                                 keep_empty_images, file_names, skipped_csv, backend, stats)
-    LAST_IO_PATH["coco_export"] = "native"
-    return result
+    def native(table):
+        light = table.light
+        if label_col is not None and label_col not in light.columns:
+            return NotImplemented                        # the pandas route raises export_coco_frame's error
+        n, widths, heights, _, cells_of = _table_rows(table, json_col, width_col, height_col)
+        sources = light[source_col].to_numpy() if source_col in light.columns else None
+        labels = light[label_col].to_numpy() if label_col is not None else None
+        return _coco_export_rows(None, n, widths, heights, sources, labels, classes, segmentation, keep_empty_images, file_names,
+                                 output_json, skipped_csv, _step_backend(backend, "coco_annotations"), stats, cells_of)
+
+    return _csv_route("coco_export", input_csv_path, json_col, native,
+                      lambda df: export_coco_frame(df, output_json, json_col, width_col, height_col, source_col, label_col, classes,
+                                                   segmentation, keep_empty_images, file_names, skipped_csv, backend, stats))
 
 
 def _coco_image_suffix(images_dir: Path, stem: str, source) -> str:
@@ -3225,7 +3155,7 @@ def export_coco_from_excels(category_excels: list, output_dir: str, source_col: 
     source's own, else .jpg).  Rows without a source or with a label outside the classes are left out and counted.  It
     downloads nothing and writes no image.  -> dict(outputs=[paths], stats={category: {split: export_coco_frame's dict plus
     rows_without_source and rows_invalid_label}}, dataset_name_map)."""
-    be = _coco_backend(backend)
+    be = _step_backend(backend, "coco_annotations")
     output_dir = Path(output_dir)
     splits = ["train", "val", "test"]
     outputs, all_stats, dataset_name_map, used_dir_names = [], {}, {}, set()
@@ -3335,7 +3265,7 @@ def generate_yolo_datasets_from_excels(
     if task not in ("detect", "segment"):
         raise ValueError(f"task must be 'detect' or 'segment', not {task!r}")
     segment = task == "segment"
-    be = _seg_backend(backend) if segment else _backend(backend)
+    be = _step_backend(backend, "yolo_seg_lines") if segment else _backend(backend)
     seg_stats = {"polygons": 0, "two_point": 0}
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)

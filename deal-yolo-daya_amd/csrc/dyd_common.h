@@ -7,6 +7,8 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <initializer_list>
 #include <mutex>
 
 #include "../../include/dyd.h"
@@ -141,6 +143,37 @@ struct KernelTimer {
 };
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// one device -> host copy of an entry's results
+struct CopyBack {
+    void *dst;
+    const void *src;
+    size_t bytes;
+};
+
+// The end of a host-pointer entry that returns a text (K7, K13, K16): the `total` bytes at d_text go into a malloc'ed buffer
+// (one byte for an empty text), `others` are copied back, st is synchronised, and *out_text / *out_text_len receive the
+// buffer, which the caller releases with dyd_host_free.  On any failure the buffer is freed here and the outputs stay as they were.
+inline int hand_back_text(const void *d_text, int64_t total, std::initializer_list<CopyBack> others, hipStream_t st,
+                          uint8_t **out_text, int64_t *out_text_len) {
+    uint8_t *host_text = static_cast<uint8_t *>(malloc((size_t)(total > 0 ? total : 1)));
+    if (!host_text) {
+        set_error("malloc(%lld) failed", (long long)total);
+        return DYD_ERR_OOM;
+    }
+    hipError_t e = total > 0 ? hipMemcpyAsync(host_text, d_text, (size_t)total, hipMemcpyDeviceToHost, st) : hipSuccess;
+    for (const CopyBack &c : others)
+        if (e == hipSuccess && c.bytes) e = hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        free(host_text);
+        set_error("copy back failed: %s", hipGetErrorString(e));
+        return DYD_ERR_HIP;
+    }
+    *out_text = host_text;
+    *out_text_len = total;
+    return DYD_OK;
+}
 
 #if defined(__HIPCC__)
 // Streaming (read-once) 16-byte load: `global_load_dwordx4 ... nt`.  Measured on MI355X with

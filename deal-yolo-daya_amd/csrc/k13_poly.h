@@ -1,6 +1,13 @@
-// k13_poly.h — the polygon handling K13 (k13_seg.hip) and K14 (k14_poly_audit.hip) share: a polygon's checks before
-// clipping, its vertex list V and the Sutherland-Hodgman pipeline that clips it to the image (include/dyd.h).
-// K14 gives every polygon the action K13 would give it by calling this same code.
+// k13_poly.h — the polygon handling K13 (k13_seg.hip), K14 (k14_poly_audit.hip) and K16 (k16_coco.hip) share: a polygon's
+// checks before clipping, its vertex list V, the Sutherland-Hodgman pipeline that clips it to the image (include/dyd.h, DESIGN
+// §5l) and the walk over the clipped vertices that decides `empty` and gives the area; the search of an offsets array and a
+// polygon tile's row range.  K14 and K16 give every polygon the action K13 would give it by calling this same code.
+//
+// Two pieces stay written out in their kernels, because sharing them changed a kernel's registers (the rule of box_table.h:
+// a helper has to cost nothing).  K14 keeps its own copy of ClipWalk's walk: through the struct k14_poly_kernel takes 105 VGPRs
+// instead of 103.  K13 and K16 keep their print windows (LDS image, base / wlo / whi, put, the 16-byte stream-out): one struct
+// for both, with the image as a member, an argument or an array reference, took k13_print_kernel from 78 VGPRs and no scratch
+// to 106 VGPRs and 16 bytes of scratch per lane.
 #pragma once
 
 #include "dyd_common.h"
@@ -143,6 +150,42 @@ __device__ __forceinline__ uint8_t k13_prepare(const double *xy, int32_t a, int3
 
 __device__ __forceinline__ bool k13_outside(const Poly &pg, double W, double H) {
     return pg.x1 < 0.0 || pg.x2 > W || pg.y1 < 0.0 || pg.y2 > H;
+}
+
+// What the steps take from one pass over the clipped vertices C: their count, extent and shoelace sum.
+struct ClipWalk {
+    int m = 0;
+    double lx = 0.0, ly = 0.0, hx = 0.0, hy = 0.0, fx = 0.0, fy = 0.0, px = 0.0, py = 0.0, s = 0.0;
+
+    __device__ __forceinline__ void add(double x, double y) {
+        if (m == 0) { lx = hx = fx = x; ly = hy = fy = y; }
+        else s += px * y - x * py;
+        lx = fmin(lx, x); hx = fmax(hx, x);
+        ly = fmin(ly, y); hy = fmax(hy, y);
+        px = x; py = y;
+        ++m;
+    }
+    __device__ __forceinline__ bool empty() const { return m < 3 || !(hx - lx > 0.0) || !(hy - ly > 0.0); }
+    // |shoelace sum| * 0.5, the closing edge included
+    __device__ __forceinline__ double area() const { return fabs(s + (px * fy - fx * py)) * 0.5; }
+};
+
+// last i in [lo, hi] with off[i] <= x (off non-decreasing, off[lo] <= x)
+template <class T>
+__device__ __forceinline__ int64_t last_le(const T *off, int64_t lo, int64_t hi, int64_t x) {
+    while (lo < hi) {   // invariant: off[lo] <= x; answer in [lo, hi]
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if ((int64_t)off[mid] <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// A lane per polygon over the tile [p0, p1): two lanes find the rows of its first and last polygon (rows[0], rows[1], in LDS),
+// every lane then searches its own row only between them.  Ends with a barrier.
+__device__ __forceinline__ void poly_tile_rows(const int32_t *__restrict__ row_off, int64_t n_rows, int64_t p0, int64_t p1, int32_t *rows) {
+    if (threadIdx.x < 2) rows[threadIdx.x] = (int32_t)last_le(row_off, 0, n_rows - 1, threadIdx.x == 0 ? p0 : p1 - 1);
+    __syncthreads();
 }
 
 }  // namespace dyd

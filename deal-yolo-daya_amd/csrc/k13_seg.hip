@@ -24,6 +24,7 @@
 //      The window is aligned to 16 bytes of the text's address, so neighbouring workgroups share no 16-byte chunk.
 #include "k13_poly.h"
 #include "k13_scan.h"
+#include "poly_table.h"
 #include "round6.h"
 
 namespace dyd {
@@ -86,20 +87,17 @@ __global__ __launch_bounds__(K13_BLOCK) void k13_measure_kernel(const double *__
             act = k13_prepare(xy, a, b, pg);
             if (act == 0xff) {
                 const bool clip = k13_outside(pg, W, H);
-                double lx = 0.0, ly = 0.0, hx = 0.0, hy = 0.0;
+                ClipWalk w;
                 auto count = [&](double x, double y) {
-                    if (m == 0) { lx = hx = x; ly = hy = y; }
-                    lx = fmin(lx, x); hx = fmax(hx, x);
-                    ly = fmin(ly, y); hy = fmax(hy, y);
-                    ++m;
+                    w.add(x, y);
                     return true;
                 };
                 k13_vertices(pg, clip, W, H, count);
-                if (m < 3 || !(hx - lx > 0.0) || !(hy - ly > 0.0)) {
+                if (w.empty()) {
                     act = SEG_EMPTY;
-                    m = 0;
                 } else {
                     act = clip ? SEG_CLIPPED : SEG_WRITTEN;
+                    m = w.m;
                 }
             }
         }
@@ -189,17 +187,6 @@ void k13_scan_inclusive(int64_t *v, int64_t n, int64_t *part, hipStream_t st) {
 }
 
 // ---- 3. print ------------------------------------------------------------------------------------------------
-// last i in [0, n] with off[i] <= x (off non-decreasing, off[0] <= x)
-template <class T>
-__device__ __forceinline__ int64_t k13_last_le(const T *off, int64_t lo, int64_t hi, int64_t x) {
-    while (lo < hi) {   // invariant: off[lo] <= x; answer in [lo, hi]
-        const int64_t mid = lo + (hi - lo + 1) / 2;
-        if ((int64_t)off[mid] <= x) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // window t = text bytes [t * K13_WINDOW - phase, (t + 1) * K13_WINDOW - phase) within [0, T): rows[2t], rows[2t + 1] = the rows
 // holding its first and its last byte
 __global__ __launch_bounds__(K13_BLOCK) void k13_tile_rows_kernel(const int64_t *__restrict__ text_off, int64_t n_rows, int64_t total,
@@ -207,8 +194,8 @@ __global__ __launch_bounds__(K13_BLOCK) void k13_tile_rows_kernel(const int64_t 
     const int64_t t = (int64_t)blockIdx.x * K13_BLOCK + threadIdx.x;
     if (t >= n_tiles) return;
     const int64_t lo = max(t * K13_WINDOW - phase, (int64_t)0), hi = min((t + 1) * K13_WINDOW - phase, total);
-    rows[2 * t] = min(k13_last_le(text_off, 0, n_rows, lo), n_rows - 1);
-    rows[2 * t + 1] = min(k13_last_le(text_off, 0, n_rows, hi - 1), n_rows - 1);
+    rows[2 * t] = min(last_le(text_off, 0, n_rows, lo), n_rows - 1);
+    rows[2 * t + 1] = min(last_le(text_off, 0, n_rows, hi - 1), n_rows - 1);
 }
 
 __global__ __launch_bounds__(K13_BLOCK) void k13_print_kernel(const double *__restrict__ xy, const int32_t *__restrict__ pt_off,
@@ -237,7 +224,7 @@ __global__ __launch_bounds__(K13_BLOCK) void k13_print_kernel(const double *__re
     };
     for (int64_t p = q0 + threadIdx.x; p < q1; p += K13_BLOCK) {
         if (action[p] > SEG_CLIPPED) continue;
-        const int64_t r = staged ? ra + k13_last_le(srow, 0, nr - 2, p) : k13_last_le(row_off, ra, rb, p);
+        const int64_t r = staged ? ra + last_le(srow, 0, nr - 2, p) : last_le(row_off, ra, rb, p);
         if (flag[r] != 0) continue;
         const int32_t cid = class_id[r];
         const int cd = k13_digits(cid);
@@ -371,77 +358,36 @@ int dyd_yolo_seg_lines(const double *xy, const int32_t *pt_off, const int32_t *r
     *out_text_len = 0;
     out_text_off[0] = 0;
     if (n_rows == 0) return DYD_OK;
-    DYD_REQUIRE(row_off && width && height && class_id && out_flag, "null pointer");
-    DYD_REQUIRE(row_off[0] == 0, "row_off[0] != 0");
-    for (int64_t i = 0; i < n_rows; ++i) DYD_REQUIRE(row_off[i + 1] >= row_off[i], "row_off not monotone");
-    const int64_t n_polys = row_off[n_rows];
-    DYD_REQUIRE(n_polys == 0 || (pt_off && out_action), "null pointer");
-    if (n_polys) {
-        DYD_REQUIRE(pt_off[0] == 0, "pt_off[0] != 0");
-        for (int64_t p = 0; p < n_polys; ++p) DYD_REQUIRE(pt_off[p + 1] >= pt_off[p], "pt_off not monotone");
-    }
-    const int64_t n_points = n_polys ? pt_off[n_polys] : 0;
-    DYD_REQUIRE(n_points == 0 || xy, "null pointer");
+    int64_t n_polys = 0, n_points = 0;
+    int rc = poly_table_check(xy, pt_off, row_off, n_rows, width, height, class_id && out_flag, out_action, nullptr, 0, &n_polys,
+                              &n_points);
+    if (rc) return rc;
     hipStream_t st = ctx().stream;
-    DevBuf d_xy, d_pt, d_off, d_sel, d_w, d_h, d_cid, d_toff, d_flag, d_act, d_text;
-    int rc;
-    if ((rc = d_xy.alloc(16 * (size_t)n_points)) || (rc = d_pt.alloc(4 * (size_t)(n_polys + 1))) ||
-        (rc = d_off.alloc(4 * (size_t)(n_rows + 1))) || (rc = d_sel.alloc((size_t)n_polys)) || (rc = d_w.alloc(8 * (size_t)n_rows)) ||
-        (rc = d_h.alloc(8 * (size_t)n_rows)) || (rc = d_cid.alloc(4 * (size_t)n_rows)) ||
+    PolyTableDev t;
+    DevBuf d_sel, d_cid, d_toff, d_flag, d_act, d_text;
+    if ((rc = t.upload(xy, pt_off, row_off, width, height, n_rows, n_polys, n_points)) ||
+        (rc = poly_column(d_sel, sel_or_null, (size_t)n_polys)) || (rc = poly_column(d_cid, class_id, 4 * (size_t)n_rows)) ||
         (rc = d_toff.alloc(8 * (size_t)(n_rows + 1))) || (rc = d_flag.alloc((size_t)n_rows)) || (rc = d_act.alloc((size_t)n_polys)))
         return rc;
-    if (n_points) DYD_HIP(hipMemcpyAsync(d_xy.p, xy, 16 * (size_t)n_points, hipMemcpyHostToDevice, st));
-    if (n_polys) DYD_HIP(hipMemcpyAsync(d_pt.p, pt_off, 4 * (size_t)(n_polys + 1), hipMemcpyHostToDevice, st));
-    if (n_polys && sel_or_null) DYD_HIP(hipMemcpyAsync(d_sel.p, sel_or_null, (size_t)n_polys, hipMemcpyHostToDevice, st));
-    DYD_HIP(hipMemcpyAsync(d_off.p, row_off, 4 * (size_t)(n_rows + 1), hipMemcpyHostToDevice, st));
-    DYD_HIP(hipMemcpyAsync(d_w.p, width, 8 * (size_t)n_rows, hipMemcpyHostToDevice, st));
-    DYD_HIP(hipMemcpyAsync(d_h.p, height, 8 * (size_t)n_rows, hipMemcpyHostToDevice, st));
-    DYD_HIP(hipMemcpyAsync(d_cid.p, class_id, 4 * (size_t)n_rows, hipMemcpyHostToDevice, st));
     const uint8_t *sel = sel_or_null ? d_sel.as<uint8_t>() : nullptr;
     // first launch measures (no text buffer), second prints into a buffer of exactly that size
     int64_t total = 0;
-    rc = seg_launch(d_xy.as<double>(), d_pt.as<int32_t>(), d_off.as<int32_t>(), sel, d_w.as<double>(), d_h.as<double>(),
-                    d_cid.as<int32_t>(), n_rows, n_polys, n_points, d_toff.as<int64_t>(), d_flag.as<uint8_t>(), d_act.as<uint8_t>(),
-                    nullptr, 0, &total, st);
-    if (rc) return rc;
-    uint8_t *host_text = static_cast<uint8_t *>(malloc((size_t)(total > 0 ? total : 1)));
-    if (!host_text) {
-        set_error("malloc(%lld) failed", (long long)total);
-        return DYD_ERR_OOM;
-    }
+    auto launch = [&](uint8_t *text, int64_t cap) {
+        return seg_launch(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), sel, t.w.as<double>(), t.h.as<double>(),
+                          d_cid.as<int32_t>(), n_rows, n_polys, n_points, d_toff.as<int64_t>(), d_flag.as<uint8_t>(),
+                          d_act.as<uint8_t>(), text, cap, &total, st);
+    };
+    if ((rc = launch(nullptr, 0))) return rc;
     if (total > 0) {
-        if ((rc = d_text.alloc((size_t)total))) {
-            free(host_text);
-            return rc;
-        }
-        KernelTimer t(st);
-        rc = seg_launch(d_xy.as<double>(), d_pt.as<int32_t>(), d_off.as<int32_t>(), sel, d_w.as<double>(), d_h.as<double>(),
-                        d_cid.as<int32_t>(), n_rows, n_polys, n_points, d_toff.as<int64_t>(), d_flag.as<uint8_t>(),
-                        d_act.as<uint8_t>(), d_text.as<uint8_t>(), total, &total, st);
-        if (rc) {
-            free(host_text);
-            return rc;
-        }
-        t.finish();
-        hipError_t e = hipMemcpyAsync(host_text, d_text.p, (size_t)total, hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) {
-            free(host_text);
-            set_error("hipMemcpyAsync failed: %s", hipGetErrorString(e));
-            return DYD_ERR_HIP;
-        }
+        if ((rc = d_text.alloc((size_t)total))) return rc;
+        KernelTimer timer(st);
+        if ((rc = launch(d_text.as<uint8_t>(), total))) return rc;
+        timer.finish();
     }
-    hipError_t e = hipMemcpyAsync(out_text_off, d_toff.p, 8 * (size_t)(n_rows + 1), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_flag, d_flag.p, (size_t)n_rows, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && n_polys) e = hipMemcpyAsync(out_action, d_act.p, (size_t)n_polys, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        free(host_text);
-        set_error("copy back failed: %s", hipGetErrorString(e));
-        return DYD_ERR_HIP;
-    }
-    *out_text = host_text;
-    *out_text_len = total;
-    return DYD_OK;
+    return hand_back_text(d_text.p, total,
+                          {{out_text_off, d_toff.p, 8 * (size_t)(n_rows + 1)}, {out_flag, d_flag.p, (size_t)n_rows},
+                           {out_action, d_act.p, (size_t)n_polys}},
+                          st, out_text, out_text_len);
 }
 
 }  // extern "C"

@@ -29,6 +29,7 @@
 //      sweep (O(m log m)) here, see DESIGN §5m.
 // No kernel indexes a per-lane array at run time: no scratch.
 #include "k13_poly.h"
+#include "poly_table.h"
 
 namespace dyd {
 
@@ -119,17 +120,7 @@ __global__ __launch_bounds__(K14_BLOCK) void k14_poly_kernel(const double *__res
     for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
         const int64_t p0 = t * K14_BLOCK;
         __syncthreads();                       // the previous tile's lanes are done with S.rows (and the zeroing is visible)
-        if (threadIdx.x < 2) {
-            const int64_t q = threadIdx.x == 0 ? p0 : min(p0 + K14_BLOCK, n_polys) - 1;
-            int64_t lo = 0, hi = n_rows - 1;   // the last row whose first polygon is <= q
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if (row_off[mid] <= q) lo = mid;
-                else hi = mid - 1;
-            }
-            S.rows[threadIdx.x] = (int32_t)lo;
-        }
-        __syncthreads();
+        poly_tile_rows(row_off, n_rows, p0, min(p0 + K14_BLOCK, n_polys), S.rows);
         const int64_t p = p0 + threadIdx.x;
         if (p >= n_polys) continue;
         const int32_t c = cls[p];
@@ -139,13 +130,7 @@ __global__ __launch_bounds__(K14_BLOCK) void k14_poly_kernel(const double *__res
             out_area[p] = __builtin_nan("");
             continue;
         }
-        int64_t lo = S.rows[0], hi = S.rows[1];
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) >> 1;
-            if (row_off[mid] <= p) lo = mid;
-            else hi = mid - 1;
-        }
-        const int64_t r = lo;
+        const int64_t r = last_le(row_off, S.rows[0], S.rows[1], p);
         const double W = width[r], H = height[r];
         const int32_t a = max(pt_off[p], 0), b = (int32_t)min((int64_t)max(pt_off[p + 1], a), n_points);   // as K13
         uint8_t cat, def = 0;
@@ -159,6 +144,7 @@ __global__ __launch_bounds__(K14_BLOCK) void k14_poly_kernel(const double *__res
             cat = k13_prepare(xy, a, b, pg);
             if (cat == 0xff) {
                 const bool clip = k13_outside(pg, W, H);
+                // k13_poly.h's ClipWalk, written out: through the struct this kernel takes 105 VGPRs, not 103
                 int m = 0;
                 double lx = 0.0, ly = 0.0, hx = 0.0, hy = 0.0, fx = 0.0, fy = 0.0, px = 0.0, py = 0.0, s = 0.0;
                 auto walk = [&](double x, double y) {
@@ -363,48 +349,23 @@ int dyd_audit_polygons(const double *xy, const int32_t *pt_off, const int32_t *r
     DYD_REQUIRE(std::isfinite(min_area) && min_area >= 0.0, "min_area must be finite and >= 0");
     DYD_REQUIRE(n_classes == 0 || (out_class_counts && out_hist_vertices), "null pointer");
     int64_t nb = 0, np = 0;
-    if (n_rows > 0) {
-        DYD_REQUIRE(row_off && width && height && size_status, "null pointer");
-        DYD_REQUIRE(row_off[0] == 0, "row_off[0] != 0");
-        for (int64_t i = 0; i < n_rows; ++i) DYD_REQUIRE(row_off[i + 1] >= row_off[i], "row_off not monotone");
-        nb = row_off[n_rows];
-    }
-    if (nb > 0) {
-        DYD_REQUIRE(pt_off && cls && out_category && out_defects && out_area, "null pointer");
-        DYD_REQUIRE(pt_off[0] == 0, "pt_off[0] != 0");
-        for (int64_t p = 0; p < nb; ++p) {
-            DYD_REQUIRE(pt_off[p + 1] >= pt_off[p], "pt_off not monotone");
-            DYD_REQUIRE(cls[p] >= -1 && cls[p] < n_classes, "class id outside -1..n_classes-1");
-        }
-        np = pt_off[nb];
-        DYD_REQUIRE(np == 0 || xy, "null pointer");
-    }
+    int rc = poly_table_check(xy, pt_off, row_off, n_rows, width, height, size_status,
+                              cls && out_category && out_defects && out_area, cls, n_classes, &nb, &np);
+    if (rc) return rc;
     hipStream_t st = ctx().stream;
-    DevBuf d_xy, d_pt, d_row, d_cls, d_w, d_h, d_st, d_cat, d_def, d_area, d_cc, d_hist;
-    int rc;
-    if ((rc = d_xy.alloc(16 * (size_t)np)) || (rc = d_pt.alloc(4 * (size_t)(nb + 1))) || (rc = d_row.alloc(4 * (size_t)(n_rows + 1))) ||
-        (rc = d_cls.alloc(4 * (size_t)nb)) || (rc = d_w.alloc(8 * (size_t)n_rows)) || (rc = d_h.alloc(8 * (size_t)n_rows)) ||
-        (rc = d_st.alloc((size_t)n_rows)) || (rc = d_cat.alloc((size_t)nb)) || (rc = d_def.alloc((size_t)nb)) ||
+    PolyTableDev t;
+    DevBuf d_cls, d_st, d_cat, d_def, d_area, d_cc, d_hist;
+    if ((rc = t.upload(xy, pt_off, row_off, width, height, n_rows, nb, np)) || (rc = poly_column(d_cls, cls, 4 * (size_t)nb)) ||
+        (rc = poly_column(d_st, size_status, (size_t)n_rows)) || (rc = d_cat.alloc((size_t)nb)) || (rc = d_def.alloc((size_t)nb)) ||
         (rc = d_area.alloc(8 * (size_t)nb)) || (rc = d_cc.alloc(8 * K14_CLSC * (size_t)n_classes)) ||
         (rc = d_hist.alloc(8 * K14_HIST * (size_t)n_classes)))
         return rc;
-    if (np) DYD_HIP(hipMemcpyAsync(d_xy.p, xy, 16 * (size_t)np, hipMemcpyHostToDevice, st));
-    if (nb) {
-        DYD_HIP(hipMemcpyAsync(d_pt.p, pt_off, 4 * (size_t)(nb + 1), hipMemcpyHostToDevice, st));
-        DYD_HIP(hipMemcpyAsync(d_cls.p, cls, 4 * (size_t)nb, hipMemcpyHostToDevice, st));
-    }
-    if (n_rows) {
-        DYD_HIP(hipMemcpyAsync(d_row.p, row_off, 4 * (size_t)(n_rows + 1), hipMemcpyHostToDevice, st));
-        DYD_HIP(hipMemcpyAsync(d_w.p, width, 8 * (size_t)n_rows, hipMemcpyHostToDevice, st));
-        DYD_HIP(hipMemcpyAsync(d_h.p, height, 8 * (size_t)n_rows, hipMemcpyHostToDevice, st));
-        DYD_HIP(hipMemcpyAsync(d_st.p, size_status, (size_t)n_rows, hipMemcpyHostToDevice, st));
-    }
-    KernelTimer t(st);
-    rc = k14_launch(d_xy.as<double>(), d_pt.as<int32_t>(), d_row.as<int32_t>(), d_cls.as<int32_t>(), d_w.as<double>(), d_h.as<double>(),
+    KernelTimer timer(st);
+    rc = k14_launch(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), d_cls.as<int32_t>(), t.w.as<double>(), t.h.as<double>(),
                     d_st.as<uint8_t>(), n_rows, nb, n_classes, np, min_area, d_cat.as<uint8_t>(), d_def.as<uint8_t>(),
                     d_area.as<double>(), d_cc.as<int64_t>(), d_hist.as<int64_t>(), st);
     if (rc) return rc;
-    t.finish();
+    timer.finish();
     if (nb) {
         DYD_HIP(hipMemcpyAsync(out_category, d_cat.p, (size_t)nb, hipMemcpyDeviceToHost, st));
         DYD_HIP(hipMemcpyAsync(out_defects, d_def.p, (size_t)nb, hipMemcpyDeviceToHost, st));

@@ -31,6 +31,7 @@
 // No kernel indexes a per-lane array at run time: no scratch.
 #include "k13_poly.h"
 #include "k13_scan.h"
+#include "poly_table.h"
 #include "round6.h"
 
 namespace dyd {
@@ -60,16 +61,6 @@ __device__ __forceinline__ int k16_fix2_len(uint64_t n) { return max(k16_digits(
 
 __device__ __forceinline__ double k16_clamp(double v, double hi) { return !(v > 0.0) ? 0.0 : (v > hi ? hi : v); }
 
-// row of polygon p: the last row in [lo, hi] whose first polygon is <= p
-__device__ __forceinline__ int64_t k16_row_of(const int32_t *__restrict__ row_off, int64_t lo, int64_t hi, int64_t p) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (row_off[mid] <= p) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // ---- 1. measure: a lane per polygon --------------------------------------------------------------------------
 // poff[p + 1] = the object's bytes with its comma (0: not printed), box[4p..] = bx, by, bw, bh
 __global__ __launch_bounds__(K16_BLOCK) void k16_measure_kernel(const double *__restrict__ xy, const int32_t *__restrict__ pt_off,
@@ -83,11 +74,7 @@ __global__ __launch_bounds__(K16_BLOCK) void k16_measure_kernel(const double *__
                                                                 double *__restrict__ box) {
     __shared__ int32_t rows[2];
     const int64_t p0 = (int64_t)blockIdx.x * K16_BLOCK;
-    if (threadIdx.x < 2) {
-        const int64_t q = threadIdx.x == 0 ? p0 : min(p0 + K16_BLOCK, n_polys) - 1;
-        rows[threadIdx.x] = (int32_t)k16_row_of(row_off, 0, n_rows - 1, q);
-    }
-    __syncthreads();
+    poly_tile_rows(row_off, n_rows, p0, min(p0 + K16_BLOCK, n_polys), rows);
     const int64_t p = p0 + threadIdx.x;
     if (p >= n_polys) return;
     if (p == 0) poff[0] = 0;
@@ -96,7 +83,7 @@ __global__ __launch_bounds__(K16_BLOCK) void k16_measure_kernel(const double *__
     double area = __builtin_nan("");
     int64_t bytes = 0;
     if (cat > 0) {
-        const int64_t r = k16_row_of(row_off, rows[0], rows[1], p);
+        const int64_t r = last_le(row_off, rows[0], rows[1], p);
         const double W = width[r], H = height[r];
         if (size_status[r] != 0 || !k13_size_ok(W) || !k13_size_ok(H)) {
             act = SEG_NO_SIZE;
@@ -107,33 +94,23 @@ __global__ __launch_bounds__(K16_BLOCK) void k16_measure_kernel(const double *__
             if (act == 0xff) {
                 const bool clip = k13_outside(pg, W, H);
                 const bool seg = flags & COCO_SEGMENTATION;
-                int m = 0;
                 int64_t nlen = 0;              // bytes of the segmentation's numbers
-                double lx = 0.0, ly = 0.0, hx = 0.0, hy = 0.0, fx = 0.0, fy = 0.0, px = 0.0, py = 0.0, s = 0.0;
-                double plx = 0.0, ply = 0.0, phx = 0.0, phy = 0.0;
+                ClipWalk w;
+                double plx = 0.0, ply = 0.0, phx = 0.0, phy = 0.0;   // the extent of P
                 auto walk = [&](double x, double y) {
                     const double cx = k16_clamp(x, W), cy = k16_clamp(y, H);
-                    if (m == 0) {
-                        lx = hx = fx = x; ly = hy = fy = y;
-                        plx = phx = cx; ply = phy = cy;
-                    } else {
-                        s += px * y - x * py;
-                    }
-                    lx = fmin(lx, x); hx = fmax(hx, x);
-                    ly = fmin(ly, y); hy = fmax(hy, y);
+                    if (w.m == 0) { plx = phx = cx; ply = phy = cy; }
                     plx = fmin(plx, cx); phx = fmax(phx, cx);
                     ply = fmin(ply, cy); phy = fmax(phy, cy);
                     if (seg) nlen += k16_fix2_len(fix2(cx)) + k16_fix2_len(fix2(cy));
-                    px = x; py = y;
-                    ++m;
+                    w.add(x, y);
                     return true;
                 };
                 k13_vertices(pg, clip, W, H, walk);
-                if (m < 3 || !(hx - lx > 0.0) || !(hy - ly > 0.0)) {
+                if (w.empty()) {
                     act = SEG_EMPTY;
                 } else {
-                    s += px * fy - fx * py;
-                    const double ar = fabs(s) * 0.5;
+                    const double ar = w.area();
                     if (!(ar < K13_LIMIT)) {
                         act = COCO_TOO_LARGE;
                     } else {
@@ -144,7 +121,7 @@ __global__ __launch_bounds__(K16_BLOCK) void k16_measure_kernel(const double *__
                         bytes = K16_FIXED + k16_digits((uint64_t)(ann_id_base + p)) + k16_digits((uint64_t)(image_id_base + r)) +
                                 k16_digits((uint64_t)cat) + k16_fix2_len(fix2(plx)) + k16_fix2_len(fix2(ply)) +
                                 k16_fix2_len(fix2(bw)) + k16_fix2_len(fix2(bh)) + k16_fix2_len(fix2(ar));
-                        if (seg) bytes += 2 + nlen + (2 * (int64_t)m - 1);
+                        if (seg) bytes += 2 + nlen + (2 * (int64_t)w.m - 1);
                     }
                 }
             }
@@ -167,16 +144,6 @@ __global__ __launch_bounds__(K16_BLOCK) void k16_row_kept_kernel(const int32_t *
 }
 
 // ---- 3. print ------------------------------------------------------------------------------------------------
-// last i in [lo, hi] with off[i] <= x (off non-decreasing, off[lo] <= x)
-__device__ __forceinline__ int64_t k16_last_le(const int64_t *__restrict__ off, int64_t lo, int64_t hi, int64_t x) {
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo + 1) / 2;
-        if (off[mid] <= x) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // what a print lane writes through: text position `at`, bytes outside the window [wlo, whi) dropped
 struct K16Out {
     uint8_t *img;
@@ -248,16 +215,16 @@ __global__ __launch_bounds__(K16_BLOCK) void k16_print_kernel(const double *__re
     const int64_t wlo = max(base, (int64_t)0), whi = min(base + K16_WINDOW, total);
     if (threadIdx.x < 2) {
         // poff[n_polys] = total + 1 > whi - 1, so both answers are polygons
-        const int64_t q = k16_last_le(poff, 0, n_polys, threadIdx.x == 0 ? wlo : whi - 1);
+        const int64_t q = last_le(poff, 0, n_polys, threadIdx.x == 0 ? wlo : whi - 1);
         ends[threadIdx.x] = q;
-        ends[2 + threadIdx.x] = k16_row_of(row_off, 0, n_rows - 1, q);
+        ends[2 + threadIdx.x] = last_le(row_off, 0, n_rows - 1, q);
     }
     __syncthreads();
     const int64_t q0 = ends[0], q1 = ends[1], ra = ends[2], rb = ends[3];
     for (int64_t p = q0 + threadIdx.x; p <= q1; p += K16_BLOCK) {
         const int64_t start = poff[p], end = poff[p + 1];
         if (end == start || end <= wlo || start >= whi) continue;
-        const int64_t r = k16_row_of(row_off, ra, rb, p);
+        const int64_t r = last_le(row_off, ra, rb, p);
         K16Out o{img, base, wlo, whi, start};
         o.lit("{\"id\":");
         o.integer((uint64_t)(ann_id_base + p));
@@ -411,77 +378,37 @@ int dyd_coco_annotations(const double *xy, const int32_t *pt_off, const int32_t 
     *out_text_len = 0;
     DYD_REQUIRE(image_id_base >= 0 && ann_id_base >= 0, "negative id base");
     int64_t nb = 0, np = 0;
-    if (n_rows > 0) {
-        DYD_REQUIRE(row_off && width && height && size_status && out_row_kept, "null pointer");
-        DYD_REQUIRE(row_off[0] == 0, "row_off[0] != 0");
-        for (int64_t i = 0; i < n_rows; ++i) DYD_REQUIRE(row_off[i + 1] >= row_off[i], "row_off not monotone");
-        nb = row_off[n_rows];
-    }
+    int rc = poly_table_check(xy, pt_off, row_off, n_rows, width, height, size_status && out_row_kept,
+                              cat_id && out_action && out_area, nullptr, 0, &nb, &np);
+    if (rc) return rc;
     DYD_REQUIRE(image_id_base < K16_ID_LIMIT - n_rows && ann_id_base < K16_ID_LIMIT - nb, "ids reach 2^53");
-    if (nb > 0) {
-        DYD_REQUIRE(pt_off && cat_id && out_action && out_area, "null pointer");
-        DYD_REQUIRE(pt_off[0] == 0, "pt_off[0] != 0");
-        for (int64_t p = 0; p < nb; ++p) DYD_REQUIRE(pt_off[p + 1] >= pt_off[p], "pt_off not monotone");
-        np = pt_off[nb];
-        DYD_REQUIRE(np == 0 || xy, "null pointer");
-    }
     if (n_rows == 0) return DYD_OK;
     hipStream_t st = ctx().stream;
-    DevBuf d_xy, d_pt, d_row, d_cat, d_w, d_h, d_st, d_act, d_area, d_kept, d_text;
-    int rc;
-    if ((rc = d_xy.alloc(16 * (size_t)np)) || (rc = d_pt.alloc(4 * (size_t)(nb + 1))) || (rc = d_row.alloc(4 * (size_t)(n_rows + 1))) ||
-        (rc = d_cat.alloc(4 * (size_t)nb)) || (rc = d_w.alloc(8 * (size_t)n_rows)) || (rc = d_h.alloc(8 * (size_t)n_rows)) ||
-        (rc = d_st.alloc((size_t)n_rows)) || (rc = d_act.alloc((size_t)nb)) || (rc = d_area.alloc(8 * (size_t)nb)) ||
-        (rc = d_kept.alloc(4 * (size_t)n_rows)))
+    PolyTableDev t;
+    DevBuf d_cat, d_st, d_act, d_area, d_kept, d_text;
+    if ((rc = t.upload(xy, pt_off, row_off, width, height, n_rows, nb, np)) || (rc = poly_column(d_cat, cat_id, 4 * (size_t)nb)) ||
+        (rc = poly_column(d_st, size_status, (size_t)n_rows)) || (rc = d_act.alloc((size_t)nb)) ||
+        (rc = d_area.alloc(8 * (size_t)nb)) || (rc = d_kept.alloc(4 * (size_t)n_rows)))
         return rc;
-    if (np) DYD_HIP(hipMemcpyAsync(d_xy.p, xy, 16 * (size_t)np, hipMemcpyHostToDevice, st));
-    if (nb) {
-        DYD_HIP(hipMemcpyAsync(d_pt.p, pt_off, 4 * (size_t)(nb + 1), hipMemcpyHostToDevice, st));
-        DYD_HIP(hipMemcpyAsync(d_cat.p, cat_id, 4 * (size_t)nb, hipMemcpyHostToDevice, st));
-    }
-    DYD_HIP(hipMemcpyAsync(d_row.p, row_off, 4 * (size_t)(n_rows + 1), hipMemcpyHostToDevice, st));
-    DYD_HIP(hipMemcpyAsync(d_w.p, width, 8 * (size_t)n_rows, hipMemcpyHostToDevice, st));
-    DYD_HIP(hipMemcpyAsync(d_h.p, height, 8 * (size_t)n_rows, hipMemcpyHostToDevice, st));
-    DYD_HIP(hipMemcpyAsync(d_st.p, size_status, (size_t)n_rows, hipMemcpyHostToDevice, st));
     CocoWork w;
     int64_t total = 0;
-    KernelTimer t(st);
-    rc = coco_measure(d_xy.as<double>(), d_pt.as<int32_t>(), d_row.as<int32_t>(), d_cat.as<int32_t>(), d_w.as<double>(),
-                      d_h.as<double>(), d_st.as<uint8_t>(), n_rows, nb, np, image_id_base, ann_id_base, flags, d_act.as<uint8_t>(),
+    KernelTimer timer(st);
+    rc = coco_measure(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), d_cat.as<int32_t>(), t.w.as<double>(),
+                      t.h.as<double>(), d_st.as<uint8_t>(), n_rows, nb, np, image_id_base, ann_id_base, flags, d_act.as<uint8_t>(),
                       d_area.as<double>(), d_kept.as<int32_t>(), w, &total, st);
     if (rc) return rc;
-    uint8_t *host_text = static_cast<uint8_t *>(malloc((size_t)(total > 0 ? total : 1)));
-    if (!host_text) {
-        set_error("malloc(%lld) failed", (long long)total);
-        return DYD_ERR_OOM;
-    }
-    hipError_t e = hipSuccess;
     if (total > 0) {
-        if (!(rc = d_text.alloc((size_t)total)))
-            rc = coco_print(d_xy.as<double>(), d_pt.as<int32_t>(), d_row.as<int32_t>(), d_cat.as<int32_t>(), d_w.as<double>(),
-                            d_h.as<double>(), n_rows, nb, np, image_id_base, ann_id_base, flags, d_area.as<double>(), w, total,
-                            d_text.as<uint8_t>(), st);
-        if (rc) {
-            free(host_text);
-            return rc;
-        }
-        t.finish();
-        e = hipMemcpyAsync(host_text, d_text.p, (size_t)total, hipMemcpyDeviceToHost, st);
-    } else {
-        t.finish();
+        if ((rc = d_text.alloc((size_t)total))) return rc;
+        rc = coco_print(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), d_cat.as<int32_t>(), t.w.as<double>(),
+                        t.h.as<double>(), n_rows, nb, np, image_id_base, ann_id_base, flags, d_area.as<double>(), w, total,
+                        d_text.as<uint8_t>(), st);
+        if (rc) return rc;
     }
-    if (e == hipSuccess && nb) e = hipMemcpyAsync(out_action, d_act.p, (size_t)nb, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && nb) e = hipMemcpyAsync(out_area, d_area.p, 8 * (size_t)nb, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_row_kept, d_kept.p, 4 * (size_t)n_rows, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        free(host_text);
-        set_error("copy back failed: %s", hipGetErrorString(e));
-        return DYD_ERR_HIP;
-    }
-    *out_text = host_text;
-    *out_text_len = total;
-    return DYD_OK;
+    timer.finish();
+    return hand_back_text(d_text.p, total,
+                          {{out_action, d_act.p, (size_t)nb}, {out_area, d_area.p, 8 * (size_t)nb},
+                           {out_row_kept, d_kept.p, 4 * (size_t)n_rows}},
+                          st, out_text, out_text_len);
 }
 
 }  // extern "C"

@@ -1398,43 +1398,17 @@ int dyd_yolo_lines(const double *box4, const int32_t *row_off, const uint8_t *se
     rc = yolo_launch(d_box.as<double>(), d_off.as<int32_t>(), sel, d_w.as<double>(), d_h.as<double>(),
                      d_cid.as<int32_t>(), n_rows, n_boxes, d_toff.as<int64_t>(), d_flag.as<uint8_t>(), nullptr, 0, &total, st);
     if (rc) return rc;
-    uint8_t *host_text = static_cast<uint8_t *>(malloc((size_t)(total > 0 ? total : 1)));
-    if (!host_text) {
-        set_error("malloc(%lld) failed", (long long)total);
-        return DYD_ERR_OOM;
-    }
     if (total > 0) {
-        if ((rc = d_text.alloc((size_t)total))) {
-            free(host_text);
-            return rc;
-        }
+        if ((rc = d_text.alloc((size_t)total))) return rc;
         KernelTimer t(st);
         rc = yolo_launch(d_box.as<double>(), d_off.as<int32_t>(), sel, d_w.as<double>(), d_h.as<double>(),
                          d_cid.as<int32_t>(), n_rows, n_boxes, d_toff.as<int64_t>(), d_flag.as<uint8_t>(),
                          d_text.as<uint8_t>(), total, &total, st);
-        if (rc) {
-            free(host_text);
-            return rc;
-        }
+        if (rc) return rc;
         t.finish();
-        hipError_t e = hipMemcpyAsync(host_text, d_text.p, (size_t)total, hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) {
-            free(host_text);
-            set_error("hipMemcpyAsync failed: %s", hipGetErrorString(e));
-            return DYD_ERR_HIP;
-        }
     }
-    hipError_t e = hipMemcpyAsync(out_text_off, d_toff.p, 8 * (size_t)(n_rows + 1), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_flag, d_flag.p, (size_t)n_rows, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        free(host_text);
-        set_error("copy back failed: %s", hipGetErrorString(e));
-        return DYD_ERR_HIP;
-    }
-    *out_text = host_text;
-    *out_text_len = total;
-    return DYD_OK;
+    return hand_back_text(d_text.p, total, {{out_text_off, d_toff.p, 8 * (size_t)(n_rows + 1)}, {out_flag, d_flag.p, (size_t)n_rows}},
+                          st, out_text, out_text_len);
 }
 
 }  // extern "C"
