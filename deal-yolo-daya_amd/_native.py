@@ -124,6 +124,12 @@ SIGNATURES = {
     "dyd_yolo_seg_lines_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.POINTER(C.c_int64), C.c_void_p]),
+    "dyd_yolo_obb_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_int64)]),
+    "dyd_yolo_obb_lines_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
     "dyd_audit_polygons": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dyd_audit_polygons_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -679,3 +685,29 @@ def yolo_seg_lines(xy, pt_off, row_off, sel, width, height, class_id):
                                    _ptr(class_id), n, _ptr(off), _ptr(flag), _ptr(action) if nb else None, C.byref(text),
                                    C.byref(total)), "dyd_yolo_seg_lines")
     return off, flag, action, _take_text(text, total)
+
+
+def yolo_obb_lines(xy, pt_off, row_off, sel, width, height, class_id, corners=False):
+    """K17 over host arrays -> (text_off int64 [n+1], flag u8 [n], action u8 [n_polys], text bytes, clamped u8 [n_polys]), and
+    with corners=True the pixel corners f64 [n_polys, 8] (x1 y1 .. x4 y4 before clamping, NaN for a polygon without a line) as a
+    sixth item.  Flags as yolo_seg_lines.  Action codes: include/dyd.h (K13's and 6 flat)."""
+    xy, pt_off, row_off, width, height, class_id, _, n, nb = _poly_table(xy, pt_off, row_off, width, height,
+                                                                         ("class_id", class_id, np.int32))
+    sel_p = None
+    if sel is not None:
+        sel = np.ascontiguousarray(sel, dtype=np.uint8)
+        if len(sel) != nb:
+            raise ValueError("sel size != number of polygons")
+        sel_p = _ptr(sel) if nb else None
+    off = np.zeros(n + 1, np.int64)
+    flag = np.zeros(n, np.uint8)
+    action = np.zeros(nb, np.uint8)
+    clamped = np.zeros(nb, np.uint8)
+    cor = np.full((nb, 8), np.nan) if corners else None
+    text, total = C.c_void_p(), C.c_int64()
+    check(lib().dyd_yolo_obb_lines(_ptr(xy) if xy.size else None, _ptr(pt_off), _ptr(row_off), sel_p, _ptr(width), _ptr(height),
+                                   _ptr(class_id), n, _ptr(off), _ptr(flag), _ptr(action) if nb else None,
+                                   _ptr(clamped) if nb else None, _ptr(cor) if corners and nb else None, C.byref(text),
+                                   C.byref(total)), "dyd_yolo_obb_lines")
+    res = (off, flag, action, _take_text(text, total), clamped)
+    return res + (cor,) if corners else res

@@ -2674,20 +2674,20 @@ def _seg_clip(pts, W, H) -> list:
     return pts
 
 
-def _seg_lines_python(polygons, class_id, width, height) -> tuple:
-    """K13's definition on Python values, for the rows the device leaves to the host (class ids it does not print) and for
-    image sizes read from the image file: polygons = [[(x, y) as read]] -> (lines, action codes)"""
+def _seg_clipped_python(polygons, width, height) -> list:
+    """K13's checks and clip on Python values: polygons = [[(x, y) as read]] -> [(action code, clipped vertices or None)], the
+    vertices for the written and clipped polygons only"""
     W, H = _seg_size(width), _seg_size(height)
     if W is None or H is None:
-        return [], [5] * len(polygons)
-    lines, actions = [], []
+        return [(5, None)] * len(polygons)
+    res = []
     for raw in polygons:
         V = [(_audit_number(x), _audit_number(y)) for x, y in raw]
         if not all(abs(v) < _SEG_LIMIT for pt in V for v in pt):        # NaN and inf fail too
-            actions.append(2)
+            res.append((2, None))
             continue
         if len(V) < 2:
-            actions.append(3)
+            res.append((3, None))
             continue
         if len(V) == 2:
             (xa, ya), (xb, yb) = V
@@ -2696,27 +2696,34 @@ def _seg_lines_python(polygons, class_id, width, height) -> tuple:
         out = _seg_clip(V, W, H)
         xs, ys = [p[0] for p in out], [p[1] for p in out]
         if len(out) < 3 or max(xs) - min(xs) <= 0 or max(ys) - min(ys) <= 0:
-            actions.append(4)
+            res.append((4, None))
             continue
-        actions.append(1 if any(not (0.0 <= x <= W and 0.0 <= y <= H) for x, y in V) else 0)
-        n = lambda v: 0.0 if v <= 0.0 else (1.0 if v >= 1.0 else v)   # noqa: E731
-        lines.append(f"{class_id}" + "".join(f" {n(x / W):.6f} {n(y / H):.6f}" for x, y in out))
-    return lines, actions
+        res.append((1 if any(not (0.0 <= x <= W and 0.0 <= y <= H) for x, y in V) else 0, out))
+    return res
 
 
-def yolo_seg_label_texts(cells, label_values, class_ids, widths, heights, backend=None, stats: Optional[dict] = None):
-    """Segmentation label-file text per row of a split sheet, with the conventions of ``yolo_label_texts``: -> (texts, reasons),
-    texts[i] = the row's lines joined with "\n" or None, reasons[i] = 无匹配标签框 (no polygon carries the row's label), 缺少图像尺寸
-    (`not w or not h`) or 标注框无效 (no line) for a None.  cells[i] is the polygon column's JSON, the other arguments as in
-    yolo_label_texts.  ``stats`` gets rows, polygons (matched polygons given an action), one count per SEG_ACTIONS entry and
-    two_point (matched polygons of exactly two points).
-    Host: native labelled-polygon scan (csrc/host_json.cpp; CPython json for irregular cells) + label match; device: K13
-    (clipping, exact "%.6f", joining)."""
-    be = _step_backend(backend, "yolo_seg_lines")
+def _seg_line(class_id, pts, W, H) -> str:
+    n = lambda v: 0.0 if v <= 0.0 else (1.0 if v >= 1.0 else v)   # noqa: E731
+    return f"{class_id}" + "".join(f" {n(x / W):.6f} {n(y / H):.6f}" for x, y in pts)
+
+
+def _seg_lines_python(polygons, class_id, width, height) -> tuple:
+    """K13's definition on Python values, for the rows the device leaves to the host (class ids it does not print) and for
+    image sizes read from the image file: polygons = [[(x, y) as read]] -> (lines, action codes)"""
+    res = _seg_clipped_python(polygons, width, height)
+    W, H = _seg_size(width), _seg_size(height)
+    return [_seg_line(class_id, out, W, H) for _, out in res if out is not None], [act for act, _ in res]
+
+
+def _poly_label_texts(cells, label_values, class_ids, widths, heights, device, lines_python, action_names) -> tuple:
+    """The driver yolo_seg_label_texts and yolo_obb_label_texts share (their docstrings have the contract) -> (texts, reasons,
+    stats).  device(xy, pt_off, row_off, sel, widths, heights, class ids) -> (text_off, flag, action, text, clamped per polygon
+    or None) is the kernel; lines_python(polygons, class id, width, height) -> (lines, action codes, clamped polygons) prints
+    the rows the device leaves to the host; action_names name the kernel's action codes."""
     n = len(cells)
     texts, reasons = [None] * n, [None] * n
     acts = np.zeros(256, np.int64)
-    st = {"rows": n, "device_rows": 0, "python_rows": 0, "python_cells": 0, "two_point": 0}
+    st = {"rows": n, "device_rows": 0, "python_rows": 0, "python_cells": 0, "two_point": 0, "clamped": 0}
     status, W, H = _audit_sizes(widths, heights, n) if n else (np.zeros(0, np.uint8), np.zeros(0), np.zeros(0))
     W, H = np.where(status == 2, np.nan, W), np.where(status == 2, np.nan, H)     # unusable sizes: every polygon no_size
     cid_dev = np.zeros(n, np.int32)
@@ -2725,10 +2732,10 @@ def yolo_seg_label_texts(cells, label_values, class_ids, widths, heights, backen
         if isinstance(c, (int, np.integer)) and not isinstance(c, (bool, np.bool_)) and 0 <= c < (1 << 31):
             cid_dev[i], cid_ok[i] = c, True
     rest = list(range(n))
-    host_rows = {}                                       # row -> matched polygons, printed by _seg_lines_python
+    host_rows = {}                                       # row -> matched polygons, printed by lines_python
 
     def run(rows, xy, pt_off, row_off, sel):
-        """K13 over the batch whose k-th row is rows[k]; rows the host decides (missing size, no match) get zero sizes"""
+        """the kernel over the batch whose k-th row is rows[k]; rows the host decides (missing size, no match) get zero sizes"""
         live = np.zeros(len(rows), bool)
         for k, i in enumerate(rows):
             b0, b1 = row_off[k], row_off[k + 1]
@@ -2743,7 +2750,7 @@ def yolo_seg_label_texts(cells, label_values, class_ids, widths, heights, backen
             return
         ridx = np.asarray(rows, np.int64)
         w_dev, h_dev = np.where(live, W[ridx], 0.0), np.where(live, H[ridx], 0.0)
-        off, flag, action, data = be.yolo_seg_lines(xy, pt_off, row_off, sel, w_dev, h_dev, cid_dev[ridx])
+        off, flag, action, data, clamped = device(xy, pt_off, row_off, sel, w_dev, h_dev, cid_dev[ridx])
         row_off = np.asarray(row_off, np.int64)
         npts = np.diff(np.asarray(pt_off, np.int64))
         for k in np.flatnonzero(live).tolist():
@@ -2756,6 +2763,7 @@ def yolo_seg_label_texts(cells, label_values, class_ids, widths, heights, backen
                                 for b in range(b0, b1) if sel is None or sel[b]]
                 continue
             np.add.at(acts, action[m][chosen], 1)
+            st["clamped"] += int(clamped[m].sum()) if clamped is not None else 0
             if flag[k] == 0:
                 texts[i] = data[off[k]:off[k + 1]].decode("ascii")
             else:
@@ -2791,12 +2799,112 @@ def yolo_seg_label_texts(cells, label_values, class_ids, widths, heights, backen
             if i in host_rows:
                 host_rows[i] = [pts for _, name, pts in _fl.seg_cell_polygons(cells[i]) if name == label_values[i]]
     for i, polys in host_rows.items():
-        lines, actions = _seg_lines_python(polys, class_ids[i], widths[i], heights[i])
+        lines, actions, n_clamped = lines_python(polys, class_ids[i], widths[i], heights[i])
+        st["clamped"] += n_clamped
         np.add.at(acts, np.asarray(actions, np.int64), 1)
         texts[i], reasons[i] = ("\n".join(lines), None) if lines else (None, REASON_NO_VALID_BOX)
         st["python_rows"] += 1
-    st["polygons"] = int(acts[:len(SEG_ACTIONS)].sum())
-    st.update({a: int(acts[k]) for k, a in enumerate(SEG_ACTIONS)})
+    st["polygons"] = int(acts[:len(action_names)].sum())
+    st.update({a: int(acts[k]) for k, a in enumerate(action_names)})
+    return texts, reasons, st
+
+
+def yolo_seg_label_texts(cells, label_values, class_ids, widths, heights, backend=None, stats: Optional[dict] = None):
+    """Segmentation label-file text per row of a split sheet, with the conventions of ``yolo_label_texts``: -> (texts, reasons),
+    texts[i] = the row's lines joined with "\n" or None, reasons[i] = 无匹配标签框 (no polygon carries the row's label), 缺少图像尺寸
+    (`not w or not h`) or 标注框无效 (no line) for a None.  cells[i] is the polygon column's JSON, the other arguments as in
+    yolo_label_texts.  ``stats`` gets rows, polygons (matched polygons given an action), one count per SEG_ACTIONS entry and
+    two_point (matched polygons of exactly two points).
+    Host: native labelled-polygon scan (csrc/host_json.cpp; CPython json for irregular cells) + label match; device: K13
+    (clipping, exact "%.6f", joining)."""
+    be = _step_backend(backend, "yolo_seg_lines")
+    texts, reasons, st = _poly_label_texts(cells, label_values, class_ids, widths, heights,
+                                           lambda *table: (*be.yolo_seg_lines(*table), None),
+                                           lambda *row: (*_seg_lines_python(*row), 0), SEG_ACTIONS)
+    del st["clamped"]                                    # K13 clamps no corner
+    if stats is not None:
+        stats.update(st)
+    return texts, reasons
+
+
+# =============================================================================== f7a  YOLO oriented-box label lines
+# One line per matched polygon, "cls x1 y1 x2 y2 x3 y3 x4 y4" normalised to [0, 1] (YOLO OBB models): the corners of a
+# minimum-area rectangle that encloses the polygon's clipped vertices (include/dyd.h, K17, and DESIGN §5o have the definition).
+# The segment step's scan and driver -> K17 (csrc/k17_obb.hip) -> strings.
+OBB_ACTIONS = SEG_ACTIONS + ("flat",)                      # K17 codes 0..6
+
+
+def _obb_rectangle(C) -> tuple:
+    """K17's walk on Python floats: the clipped vertices C -> (kept area or None, its four corners)"""
+    s = C[0]
+    lx = hx = s[0]
+    ly = hy = s[1]
+    for x, y in C[1:]:
+        if y < s[1] or (y == s[1] and x < s[0]):
+            s = (x, y)
+        lx, hx = (x if x < lx else lx), (x if x > hx else hx)
+        ly, hy = (y if y < ly else ly), (y if y > hy else hy)
+    (cx, cy), kept_area, kept = s, None, None
+    for _ in range(len(C)):
+        best, bd = None, 0.0
+        for kx, ky in C:
+            if kx == cx and ky == cy:
+                continue
+            d = (kx - cx) * (kx - cx) + (ky - cy) * (ky - cy)
+            if best is not None:
+                cr = (best[0] - cx) * (ky - cy) - (best[1] - cy) * (kx - cx)
+                if not (cr < 0 or (cr == 0 and d > bd)):
+                    continue
+            best, bd = (kx, ky), d
+        if best is None:
+            break
+        dx, dy = best[0] - cx, best[1] - cy
+        if dx == 0 or dy == 0:
+            area, corners = (hx - lx) * (hy - ly), [(lx, ly), (hx, ly), (hx, hy), (lx, hy)]
+        else:
+            a = b = (C[0][0] - cx) * dx + (C[0][1] - cy) * dy
+            e = f = (C[0][1] - cy) * dx - (C[0][0] - cx) * dy
+            for x, y in C[1:]:
+                u, v = (x - cx) * dx + (y - cy) * dy, (y - cy) * dx - (x - cx) * dy
+                a, b = (u if u < a else a), (u if u > b else b)
+                e, f = (v if v < e else e), (v if v > f else f)
+            L = dx * dx + dy * dy
+            area = ((b - a) * (f - e)) / L
+            corners = [(cx + (u * dx - v * dy) / L, cy + (u * dy + v * dx) / L) for u, v in ((a, e), (b, e), (b, f), (a, f))]
+        if kept_area is None or area < kept_area:
+            kept_area, kept = area, corners
+        cx, cy = best
+        if cx == s[0] and cy == s[1]:
+            break
+    return kept_area, kept
+
+
+def _obb_lines_python(polygons, class_id, width, height) -> tuple:
+    """K17's definition on Python values, for the rows the device leaves to the host and for image sizes read from the image
+    file, as _seg_lines_python: polygons = [[(x, y) as read]] -> (lines, action codes, polygons with a clamped corner)"""
+    W, H = _seg_size(width), _seg_size(height)
+    lines, actions, clamped = [], [], 0
+    for act, out in _seg_clipped_python(polygons, width, height):
+        if out is not None:
+            area, corners = _obb_rectangle(out)
+            if area is None or not area > 0:
+                act = 6
+            else:
+                clamped += any(x < 0 or x > W or y < 0 or y > H for x, y in corners)
+                lines.append(_seg_line(class_id, corners, W, H))
+        actions.append(act)
+    return lines, actions, clamped
+
+
+def yolo_obb_label_texts(cells, label_values, class_ids, widths, heights, backend=None, stats: Optional[dict] = None):
+    """Oriented-box label-file text per row of a split sheet: ``yolo_seg_label_texts``' contract, arguments and reasons, with
+    one "cls x1 y1 x2 y2 x3 y3 x4 y4" line per matched polygon instead of its outline.  A polygon whose points are collinear
+    is `flat` and has no line.  ``stats`` is as there with one count per OBB_ACTIONS entry, plus clamped (lines with a corner
+    outside the image, which prints clamped to [0, 1]).
+    Host: the segment step's scan and label match; device: K17 (clipping, the rectangle, exact "%.6f", joining)."""
+    be = _step_backend(backend, "yolo_obb_lines")
+    texts, reasons, st = _poly_label_texts(cells, label_values, class_ids, widths, heights,
+                                           lambda *table: be.yolo_obb_lines(*table)[:5], _obb_lines_python, OBB_ACTIONS)
     if stats is not None:
         stats.update(st)
     return texts, reasons
@@ -3231,41 +3339,17 @@ def _dataset_sheets(excel_path, splits, label_col: str, class_order) -> tuple:
     return split_sheets, frames, classes
 
 
-def generate_yolo_datasets_from_excels(
-        category_excels: list,
-        output_dir: str,
-        image_cache_dir: Optional[str] = None,
-        source_col: str = "source",
-        label_col: str = "分类标签",
-        json_col_primary: str = BBOX_COL,
-        json_col_fallback: str = ANNOTATION_COL,
-        width_col: str = "width",
-        height_col: str = "height",
-        download_images: bool = True,
-        random_seed: int = 42,
-        class_order: Optional[list] = None,
-        resume: bool = True,
-        progress_callback=None,
-        backend=None,
-        task: str = "detect",
-):
-    """Drop-in for reference processor.py:893-1093: one YOLO dataset directory per category workbook
-    (images/<split>, labels/<split>, data.yaml) plus yolo_skipped.xlsx.
-
-    task="detect" writes box lines (the reference's); task="segment" writes one polygon line per matched object for YOLO
-    segment models (``yolo_seg_label_texts`` -> K13), reading ``row.get(json_col_fallback) or row.get(json_col_primary)``: the
-    annotation polygons first, which a split with json_columns=[ANNOTATION_COL, BBOX_COL] carries.
-
-    Per split sheet the rows are shuffled like ``sample(frac=1, random_state=seed)`` (host MT19937), the label
-    texts of all rows are produced in one batch (``yolo_label_texts`` -> K7) and the per-row side effects (resume
-    check, image copy, label file, skip records) are then replayed in the reference's order.  Rows whose image
-    size comes from the image file rather than from the sheet (:1015-1020) are printed on the host."""
+def _generate_yolo_datasets(category_excels, output_dir, image_cache_dir, source_col, label_col, json_col_primary,
+                            json_col_fallback, width_col, height_col, download_images, random_seed, class_order, resume,
+                            progress_callback, backend, task):
+    """The body of generate_yolo_datasets_from_excels (task "detect" or "segment") and of
+    generate_yolo_obb_datasets_from_excels (task "obb"); their docstrings have the contract."""
     import yaml
 
-    if task not in ("detect", "segment"):
-        raise ValueError(f"task must be 'detect' or 'segment', not {task!r}")
-    segment = task == "segment"
-    be = _step_backend(backend, "yolo_seg_lines") if segment else _backend(backend)
+    polygons = task != "detect"                                          # "segment" or "obb": lines from the polygons
+    label_texts, lines_python = ((yolo_obb_label_texts, _obb_lines_python) if task == "obb" else
+                                 (yolo_seg_label_texts, _seg_lines_python))
+    be = _step_backend(backend, "yolo_obb_lines" if task == "obb" else "yolo_seg_lines") if polygons else _backend(backend)
     seg_stats = {"polygons": 0, "two_point": 0}
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
@@ -3311,7 +3395,7 @@ def generate_yolo_datasets_from_excels(
             sources, widths, heights = get(source_col), get(width_col), get(height_col)
             labels = [str(v) for v in get(label_col, "")]
             primary, fallback = get(json_col_primary), get(json_col_fallback)
-            if segment:                                                  # the polygons first
+            if polygons:                                                 # the polygons first
                 cells = [b or a for a, b in zip(primary, fallback)]
             else:
                 cells = [a or b for a, b in zip(primary, fallback)]      # row.get(primary) or row.get(fallback) (:1004)
@@ -3319,9 +3403,9 @@ def generate_yolo_datasets_from_excels(
             batch = [i for i, ok in enumerate(usable) if ok]
             args = ([cells[i] for i in batch], [labels[i] for i in batch], [class_to_id[labels[i]] for i in batch],
                     [widths[i] for i in batch], [heights[i] for i in batch], be)
-            if segment:
+            if polygons:
                 sst = {}
-                texts, reasons = yolo_seg_label_texts(*args, stats=sst)
+                texts, reasons = label_texts(*args, stats=sst)
                 for key in seg_stats:
                     seg_stats[key] += sst[key]
             else:
@@ -3359,9 +3443,9 @@ def generate_yolo_datasets_from_excels(
                         from PIL import Image
                         with Image.open(image_path) as img:
                             width, height = img.size
-                        if segment:
+                        if polygons:
                             polys = [pts for _, name, pts in _fl.seg_cell_polygons(cells[idx]) if name == label_value]
-                            lines = _seg_lines_python(polys, class_to_id[label_value], width, height)[0]
+                            lines = lines_python(polys, class_to_id[label_value], width, height)[0]
                         else:
                             boxes = [b for b in _extract_boxes_with_labels(cells[idx]) if b[0] == label_value]
                             lines = _label_lines_python(boxes, class_to_id[label_value], width, height)
@@ -3393,9 +3477,9 @@ def generate_yolo_datasets_from_excels(
             "nc": len(classes), "names": classes}, sort_keys=False, allow_unicode=True), encoding="utf-8")
         datasets.append(dataset_dir)
 
-    if segment and seg_stats["polygons"] and seg_stats["two_point"] == seg_stats["polygons"]:
-        print(f"task='segment': every one of the {seg_stats['polygons']} matched polygons has 2 points, so every label is a "
-              f"rectangle: the workbooks hold boxes only.  Split with json_columns=[ANNOTATION_COL, BBOX_COL] to carry the "
+    if polygons and seg_stats["polygons"] and seg_stats["two_point"] == seg_stats["polygons"]:
+        print(f"task='{task}': every one of the {seg_stats['polygons']} matched polygons has 2 points, so every label is "
+              f"{'an axis-aligned' if task == 'obb' else 'a'} rectangle: the workbooks hold boxes only.  Split with json_columns=[ANNOTATION_COL, BBOX_COL] to carry the "
               f"annotation polygons.")
     skipped_path = output_dir / "yolo_skipped.xlsx"
     pd.DataFrame(skipped if skipped else [{"category": "无", "reason": "无", "split": "无"}]).to_excel(skipped_path, index=False)
@@ -3404,6 +3488,69 @@ def generate_yolo_datasets_from_excels(
         progress_callback(processed_rows, *last[1:])
     return {"datasets": datasets, "skipped": skipped_path, "stats": dataset_stats, "total": total_rows,
             "processed": processed_rows, "downloaded": downloaded_images, "dataset_name_map": dataset_name_map}
+
+
+def generate_yolo_datasets_from_excels(
+        category_excels: list,
+        output_dir: str,
+        image_cache_dir: Optional[str] = None,
+        source_col: str = "source",
+        label_col: str = "分类标签",
+        json_col_primary: str = BBOX_COL,
+        json_col_fallback: str = ANNOTATION_COL,
+        width_col: str = "width",
+        height_col: str = "height",
+        download_images: bool = True,
+        random_seed: int = 42,
+        class_order: Optional[list] = None,
+        resume: bool = True,
+        progress_callback=None,
+        backend=None,
+        task: str = "detect",
+):
+    """Drop-in for reference processor.py:893-1093: one YOLO dataset directory per category workbook
+    (images/<split>, labels/<split>, data.yaml) plus yolo_skipped.xlsx.
+
+    task="detect" writes box lines (the reference's); task="segment" writes one polygon line per matched object for YOLO
+    segment models (``yolo_seg_label_texts`` -> K13), reading ``row.get(json_col_fallback) or row.get(json_col_primary)``: the
+    annotation polygons first, which a split with json_columns=[ANNOTATION_COL, BBOX_COL] carries.  Oriented boxes for YOLO OBB
+    models come from ``generate_yolo_obb_datasets_from_excels``; any other task raises ValueError.
+
+    Per split sheet the rows are shuffled like ``sample(frac=1, random_state=seed)`` (host MT19937), the label
+    texts of all rows are produced in one batch (``yolo_label_texts`` -> K7) and the per-row side effects (resume
+    check, image copy, label file, skip records) are then replayed in the reference's order.  Rows whose image
+    size comes from the image file rather than from the sheet (:1015-1020) are printed on the host."""
+    if task not in ("detect", "segment"):
+        raise ValueError(f"task must be 'detect' or 'segment', not {task!r}")
+    return _generate_yolo_datasets(category_excels, output_dir, image_cache_dir, source_col, label_col, json_col_primary,
+                                   json_col_fallback, width_col, height_col, download_images, random_seed, class_order, resume,
+                                   progress_callback, backend, task)
+
+
+def generate_yolo_obb_datasets_from_excels(
+        category_excels: list,
+        output_dir: str,
+        image_cache_dir: Optional[str] = None,
+        source_col: str = "source",
+        label_col: str = "分类标签",
+        json_col_primary: str = BBOX_COL,
+        json_col_fallback: str = ANNOTATION_COL,
+        width_col: str = "width",
+        height_col: str = "height",
+        download_images: bool = True,
+        random_seed: int = 42,
+        class_order: Optional[list] = None,
+        resume: bool = True,
+        progress_callback=None,
+        backend=None,
+):
+    """``generate_yolo_datasets_from_excels`` for YOLO OBB models: the same arguments (there is no task), folders, data.yaml,
+    shuffle, resume and skip records, and the cells of task="segment" (``row.get(json_col_fallback) or
+    row.get(json_col_primary)``, the annotation polygons first), with one "cls x1 y1 x2 y2 x3 y3 x4 y4" line per matched object:
+    the corners of a minimum-area rectangle round its polygon (``yolo_obb_label_texts`` -> K17)."""
+    return _generate_yolo_datasets(category_excels, output_dir, image_cache_dir, source_col, label_col, json_col_primary,
+                                   json_col_fallback, width_col, height_col, download_images, random_seed, class_order, resume,
+                                   progress_callback, backend, "obb")
 
 
 # =============================================================================== label_replace (pipeline step between a4 and a5)

@@ -1,5 +1,5 @@
 // k13_scan.h — the int64 inclusive scan of k13_seg.hip (reduce, scan of the block sums, apply), for the kernels that turn
-// byte counts into text offsets: K13 over rows, K16 over polygons.  The kernels live in k13_seg.hip.
+// byte counts into text offsets: K13 and K17 over rows, K16 over polygons.  The kernels live in k13_seg.hip.
 #pragma once
 
 #include "dyd_common.h"

@@ -35,27 +35,6 @@ constexpr int K13_SCAN_TILE = K13_BLOCK * K13_SCAN_PER_LANE;
 constexpr int K13_WINDOW = 32 * 1024;       // bytes of text per print workgroup (multiple of 16)
 constexpr int K13_ROWS_LDS = 1024;          // row_off entries a print workgroup stages in LDS for its row lookups
 
-__device__ __forceinline__ int k13_digits(int32_t cid) {   // cid >= 0
-    int n = 1;
-    for (uint32_t v = (uint32_t)cid; v >= 10u; v /= 10u) ++n;
-    return n;
-}
-
-// "%.6f" of n(v) as 8 ASCII bytes, the first in the low byte
-__device__ __forceinline__ uint64_t k13_num8(double v) {
-    v = (v <= 0.0) ? 0.0 : ((v >= 1.0) ? 1.0 : v);
-    uint32_t q = round6(v);
-    if (q >= 1000000u) return 0x3030303030302e31ull;   // "1.000000"
-    uint64_t r = 0x2e30ull;                             // "0."
-#pragma unroll
-    for (int k = 7; k >= 2; --k) {
-        const uint32_t t = q / 10u;
-        r |= (uint64_t)('0' + (q - t * 10u)) << (8 * k);
-        q = t;
-    }
-    return r;
-}
-
 // ---- 1. measure: a lane per row ------------------------------------------------------------------------------
 // rel[p] = the line's first byte within the row, m[p] = its clipped vertex count; text_off[i + 1] = the row's byte count
 __global__ __launch_bounds__(K13_BLOCK) void k13_measure_kernel(const double *__restrict__ xy, const int32_t *__restrict__ pt_off,

@@ -460,6 +460,47 @@ int dyd_coco_annotations_dev(const double *xy, const int32_t *pt_off, const int3
                              double *out_area, int32_t *out_row_kept, uint8_t *out_text_or_null, int64_t text_cap, int64_t *out_total,
                              void *stream);
 
+/* ---- K17: YOLO oriented-box label lines ---------------------------------------------------
+ * One line per polygon that carries the row's label, "cls x1 y1 x2 y2 x3 y3 x4 y4" (YOLO OBB models), for
+ * generate_yolo_obb_datasets_from_excels: the corners of a minimum-area rectangle that encloses the polygon.  Polygons,
+ * points, sizes, sel and the class id are K13's, unchanged; actions 0..5 are exactly K13's (the same device code), 255 the
+ * polygon is not selected; a two-point polygon is its box's four corners.  For a polygon K13 would write or clip, let
+ * C = c_0..c_{m-1} be K13's clipped vertices in order.  All arithmetic is IEEE f64 without contraction in the order written;
+ * every min or max replaces only on a strict comparison (the first value wins ties).
+ *   1. start   s = the first vertex with the smallest y, among those the smallest x; cur = s.
+ *   2. step    (gift wrapping, one pass over C) best = none; for each c_k in order whose coordinates differ from cur's:
+ *              take it if best is none; else cr = (bx-cx)*(ky-cy) - (by-cy)*(kx-cx); take it when cr < 0, or when cr == 0 and
+ *              (kx-cx)*(kx-cx) + (ky-cy)*(ky-cy) is strictly larger than best's.  No candidate: the walk ends.
+ *   3. rectangle of the edge cur -> best, dx = bx-cx, dy = by-cy.  dx == 0 or dy == 0: the extent of C, corners
+ *              (lx,ly),(hx,ly),(hx,hy),(lx,hy), area = (hx-lx)*(hy-ly).  Otherwise over all of C u = (x-cx)*dx + (y-cy)*dy,
+ *              v = (y-cy)*dx - (x-cx)*dy, a = min u, b = max u, e = min v, f = max v, L = dx*dx + dy*dy,
+ *              area = ((b-a)*(f-e))/L, and the corners for (u,v) in (a,e),(b,e),(b,f),(a,f) are
+ *              (cx + (u*dx - v*dy)/L, cy + (u*dy + v*dx)/L).  The first rectangle is kept; a strictly smaller area replaces it.
+ *   4. advance cur = best; the walk ends when cur has s's coordinates, or after m steps.
+ *   6 flat     the kept area is not > 0 (collinear points): no line.  (K17's own code 6; K16's too_large is unrelated.)
+ * clamped[p] = 1 when a kept corner has x < 0, x > W, y < 0 or y > H (the printer clamps it; Ultralytics rejects values
+ * outside [0, 1]).  A line is "{cls}" then " {n(x/W):.6f} {n(y/H):.6f}" per corner, n and the printer K13's, so
+ * digits(cls) + 72 bytes; a row's lines are joined with "\n".
+ * xy (16-B aligned), pt_off, row_off, sel_or_null, width / height, class_id, out_text_off, out_flag: as K13.
+ * out_action          : the codes above                                                  [n_polys]
+ * out_clamped         : 1 = a corner of the polygon's line was clamped, else 0           [n_polys]
+ * out_corners_or_null : x1 y1 .. x4 y4 in pixels, before clamping; untouched for a polygon without a line (16-B aligned
+ *                       for the _dev entry)                                              [8*n_polys]
+ * dyd_yolo_obb_lines     : host pointers; *out_text is allocated by the library (release with dyd_host_free).
+ * dyd_yolo_obb_lines_dev : device pointers; out_text_or_null == NULL only measures (offsets, flags, actions, clamped,
+ *                          corners, total); otherwise text_cap bytes are available and DYD_ERR_RANGE is returned, with the
+ *                          needed size in *out_total, when that is too little.  *out_total is a HOST int64.
+ *                          n_polys = row_off[n_rows], n_points = pt_off[n_polys]. */
+int dyd_yolo_obb_lines(const double *xy, const int32_t *pt_off, const int32_t *row_off, const uint8_t *sel_or_null,
+                       const double *width, const double *height, const int32_t *class_id, int64_t n_rows,
+                       int64_t *out_text_off, uint8_t *out_flag, uint8_t *out_action, uint8_t *out_clamped,
+                       double *out_corners_or_null, uint8_t **out_text, int64_t *out_text_len);
+int dyd_yolo_obb_lines_dev(const double *xy, const int32_t *pt_off, const int32_t *row_off, const uint8_t *sel_or_null,
+                           const double *width, const double *height, const int32_t *class_id, int64_t n_rows,
+                           int64_t n_polys, int64_t n_points, int64_t *out_text_off, uint8_t *out_flag, uint8_t *out_action,
+                           uint8_t *out_clamped, double *out_corners_or_null, uint8_t *out_text_or_null, int64_t text_cap,
+                           int64_t *out_total, void *stream);
+
 /* ---- native flatten / emit (HOST code, multithreaded) ------------------------------
  * Schema-specialised JSON scanner + canonical re-emitter that replaces json.loads / json.dumps inside
  * parse_and_replace_ptlist (processor.py:262-281), extract_width_height (:285-292) and extract_boxes

@@ -3,7 +3,7 @@
 interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant.
 
     python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k13: segmentation lines beside K7;
-     k14: polygon audit; k14tier: its in-lane / wave threshold; k16: COCO annotation objects beside K13)
+     k14: polygon audit; k14tier: its in-lane / wave threshold; k16: COCO annotation objects beside K13; k17: oriented-box lines beside K13)
 """
 import argparse
 import json
@@ -567,6 +567,57 @@ def main():
                 del text16
             del text13
         del act, area, cat
+    if "k17" in only:
+        import ctypes as C
+        # K17 (oriented-box lines) beside K13 on K13's two shapes, rounds interleaved, then long polygons (K14's long_256 rings,
+        # a tenth as many: every vertex is a hull vertex, so a lane makes 258 passes over its 256 points).  K17 bytes: in as K13,
+        # out 8*(N+1) + N + 2*B + T (the 64*B of corners stay inside the library when the caller asks for none).
+        total = C.c_int64()
+        names17 = ("written", "clipped", "bad_coords", "too_few_points", "empty", "no_size", "flat")
+
+        def k17_leg(shape, xy_, pt_, roff, nr, nb, npts, with_k13=True, iters=args.iters):
+            w = torch.full((nr,), 1920.0, dtype=torch.float64, device=dev); h = torch.full((nr,), 1080.0, dtype=torch.float64, device=dev)
+            cid = (torch.arange(nr, device=dev, dtype=torch.int32) % 20).contiguous()
+            toff = torch.empty(nr + 1, dtype=torch.int64, device=dev); flag = torch.empty(nr, dtype=torch.uint8, device=dev)
+            act = torch.empty(nb, dtype=torch.uint8, device=dev); cl = torch.empty(nb, dtype=torch.uint8, device=dev)
+            seg_args = (xy_.data_ptr(), pt_.data_ptr(), roff.data_ptr(), None, w.data_ptr(), h.data_ptr(), cid.data_ptr(), nr, nb, npts,
+                        toff.data_ptr(), flag.data_ptr(), act.data_ptr())
+            obb_args = seg_args + (cl.data_ptr(), None)
+            ck(L.dyd_yolo_obb_lines_dev(*obb_args, None, 0, C.byref(total), sp), "k17 measure")
+            T17 = total.value
+            counts = torch.bincount(act.to(torch.int64), minlength=256)[:7].tolist()
+            text17 = torch.empty(T17, dtype=torch.uint8, device=dev)
+            ck(L.dyd_yolo_seg_lines_dev(*seg_args, None, 0, C.byref(total), sp), "k13 measure")
+            T13 = total.value
+            text13 = torch.empty(T13, dtype=torch.uint8, device=dev)
+            res = {}
+            for rnd in range(2):                      # interleaved rounds
+                if with_k13:
+                    res.setdefault("k13", []).append(timeit(lambda: ck(L.dyd_yolo_seg_lines_dev(*seg_args, text13.data_ptr(), T13,
+                                                                                                C.byref(total), sp), "k13"), iters=iters))
+                res.setdefault("k17", []).append(timeit(lambda: ck(L.dyd_yolo_obb_lines_dev(*obb_args, text17.data_ptr(), T17,
+                                                                                            C.byref(total), sp), "k17"), iters=iters))
+            base = 16 * npts + 4 * (nb + 1) + nb + 4 * (nr + 1) + 20 * nr + 8 * (nr + 1) + nr
+            k17_bytes = base + 2 * nb + T17
+            med17, mn17 = min(res["k17"])
+            extra = {}
+            if with_k13:
+                k13_bytes = base + nb + T13
+                med13, mn13 = min(res["k13"])
+                report(f"k13_yolo_seg_lines_{shape}", k13_bytes, med13, mn13, rows=nr, polygons=nb, points=npts, text_bytes=T13)
+                extra = {"bytes_per_s_vs_k13": round((k17_bytes / med17) / (k13_bytes / med13), 3), "ms_vs_k13": round(med17 / med13, 3)}
+            report(f"k17_yolo_obb_lines_{shape}", k17_bytes, med17, mn17, rows=nr, polygons=nb, points=npts, text_bytes=T17,
+                   polygons_per_s=round(nb / med17 * 1e3), clamped=int(cl.sum().item()), actions=dict(zip(names17, counts)), **extra)
+
+        k17_leg("records", xy, pt_off, torch.arange(B + 1, dtype=torch.int32, device=dev), B, B, P)
+        k17_leg("rows", xy, pt_off, box_off, N, B, P)
+        nl, m = 100_000, 256
+        th = torch.arange(m, dtype=torch.float64, device=dev) * (2 * np.pi / m)
+        ring = torch.stack([500.0 + 400.0 * torch.cos(th), 500.0 + 400.0 * torch.sin(th)], 1)
+        xl = ring.repeat(nl, 1).contiguous()
+        k17_leg("long_256", xl, torch.arange(nl + 1, dtype=torch.int32, device=dev) * m, torch.arange(nl + 1, dtype=torch.int32, device=dev),
+                nl, nl, nl * m, iters=3)
+        del xl
     if "k14tier" in only:
         import ctypes as C
         # K14's tier threshold: 1 M convex rings of m vertices (no crossing: every edge pair tested) with the in-lane limit
