@@ -20,11 +20,13 @@
 //
 // One pass: a workgroup takes the next tile of 256 x RPT rows from a ticket counter, measures its rows (RPT rows
 // per lane, the converted numbers of each row's first line stay in registers), scans the lengths in the workgroup, obtains the byte offset of the tile with a decoupled
-// look-back over the tiles before it (one 8-byte {flag, bytes} word per tile, written and polled with
-// agent-scope relaxed atomics; a tile publishes its own byte count before it looks back, so no tile waits
-// for more than the measuring of its predecessors), prints the rows into LDS at the same 16-byte phase as
-// their place in the output, and streams the LDS image out with 16-byte stores.
+// look-back over the tiles before it (lookback.h, shared with K8: one 8-byte {flag, bytes} word per tile; a tile
+// publishes its own byte count before it looks back, so no tile waits for more than the measuring of its
+// predecessors), prints the rows into LDS at tile-relative offsets, and streams the LDS image out with 16-byte
+// stores realigned to the destination's phase (k7_flush).  The three tile kernels below (one row tile per ticket, two
+// pipelined, tiles cut by boxes) share the look-back, the flush, the workgroup scan and the row helpers.
 #include "dyd_common.h"
+#include "lookback.h"
 #include "round6.h"
 
 namespace dyd {
@@ -32,10 +34,7 @@ namespace dyd {
 constexpr int K7_BLOCK = 256;
 constexpr int K7_WAVES = K7_BLOCK / kWave;
 constexpr int K7_LDS_TEXT = 24 * 1024;          // bytes of text staged per tile (typical tile: 256 x 38 B)
-constexpr uint64_t K7_FLAG_AGG = 1ull << 62;    // the word holds the tile's own byte count
-constexpr uint64_t K7_FLAG_PFX = 2ull << 62;    // the word holds the inclusive prefix up to this tile
-constexpr uint64_t K7_VALUE = (1ull << 62) - 1;
-constexpr int K7_SPIN_LIMIT = 1 << 22;          // polls before a tile gives up (sets the error word)
+
 
 enum : uint32_t { K7_FINITE = 0, K7_NAN = 1, K7_INF = 2, K7_EXOTIC = 3 };
 
@@ -347,6 +346,120 @@ __device__ __forceinline__ void row_print(const RowIn &r, const double *__restri
     }
 }
 
+// ---- what the tile kernels share ------------------------------------------------------------------------------
+// the rows row0 + k * K7_BLOCK of a tile; rows past the end read as empty
+template <int RPT>
+__device__ __forceinline__ void k7_load_rows(int64_t row0, int64_t n_rows, const int32_t *__restrict__ row_off,
+                                             const double *__restrict__ width, const double *__restrict__ height,
+                                             const int32_t *__restrict__ class_id, RowIn (&r)[RPT]) {
+#pragma unroll
+    for (int k = 0; k < RPT; ++k) {
+        const int64_t row = row0 + (int64_t)k * K7_BLOCK;
+        r[k].b0 = r[k].b1 = 0;
+        r[k].w = r[k].h = 1.0;
+        r[k].cid = 0;
+        if (row < n_rows) {
+            r[k].b0 = row_off[row];
+            r[k].b1 = row_off[row + 1];
+            r[k].w = width[row];
+            r[k].h = height[row];
+            r[k].cid = class_id[row];
+        }
+        r[k].host = (r[k].w == 0.0) || (r[k].h == 0.0) || (r[k].cid < 0);
+    }
+}
+
+template <int RPT>
+__device__ __forceinline__ void k7_measure_rows(int64_t row0, int64_t n_rows, const RowIn (&r)[RPT], const double *__restrict__ box4,
+                                                const uint8_t *__restrict__ sel, RowState (&st)[RPT], bool (&plain)[RPT]) {
+#pragma unroll
+    for (int k = 0; k < RPT; ++k) {
+        const bool live = row0 + (int64_t)k * K7_BLOCK < n_rows;
+        plain[k] = live && plain_row(r[k], box4, sel, st[k].q);
+        if (plain[k]) {
+            st[k].len = plain_len(r[k], st[k].q);
+            st[k].flag = 0;
+        } else {
+            row_measure(r[k], box4, sel, st[k]);
+            if (!live) st[k].len = 0;
+        }
+    }
+}
+
+// exclusive workgroup scan of the rows' lengths in row order (k major): toff = a row's text offset inside the tile; returns the
+// tile's bytes.  One barrier; s_wave must be free on entry.
+template <int RPT>
+__device__ __forceinline__ uint32_t k7_scan_rows(const RowState (&st)[RPT], uint32_t (&s_wave)[RPT][K7_WAVES], int lane, int wave,
+                                                 uint32_t (&toff)[RPT]) {
+    uint32_t incl[RPT];
+#pragma unroll
+    for (int k = 0; k < RPT; ++k) {
+        incl[k] = st[k].len;
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const uint32_t up = __shfl_up(incl[k], d);
+            if (lane >= d) incl[k] += up;
+        }
+        if (lane == kWave - 1) s_wave[k][wave] = incl[k];
+    }
+    __syncthreads();
+    uint32_t bytes = 0;
+#pragma unroll
+    for (int k = 0; k < RPT; ++k) {
+        uint32_t before = bytes;
+#pragma unroll
+        for (int w = 0; w < K7_WAVES; ++w) {
+            if (w < wave) before += s_wave[k][w];
+            bytes += s_wave[k][w];
+        }
+        toff[k] = before + incl[k] - st[k].len;
+    }
+    return bytes;
+}
+
+// the tile's rows at where + toff (LDS or memory)
+template <int RPT>
+__device__ __forceinline__ void k7_print_rows(const RowIn (&r)[RPT], const RowState (&st)[RPT], const bool (&plain)[RPT],
+                                              const uint32_t (&toff)[RPT], const double *__restrict__ box4,
+                                              const uint8_t *__restrict__ sel, unsigned char *where) {
+#pragma unroll
+    for (int k = 0; k < RPT; ++k) {
+        unsigned char *mine = where + toff[k];
+        if (plain[k])
+            plain_print(r[k], st[k], [&](int p, char c) { mine[p] = (unsigned char)c; });
+        else if (st[k].len)
+            row_print(r[k], box4, sel, [&](int p, char c) { mine[p] = (unsigned char)c; });
+    }
+}
+
+// LDS -> memory: dst[i] = s_text[i] for i < bytes.  The 16-byte store k goes to the aligned address dst - phase + 16k and
+// takes the LDS bytes from 16k - phase on: five aligned dwords funnel-shifted by (-phase) & 3 bytes (s_text is 16-byte
+// aligned and has 32 spare bytes behind the text).  The partial chunks at either end go byte by byte.
+__device__ __forceinline__ void k7_flush(const unsigned char *s_text, unsigned char *dst, uint32_t bytes, int tid) {
+    const uint32_t phase = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
+    const uint32_t end = phase + bytes;
+    const uint32_t n_chunks = (end + 15u) >> 4;
+    unsigned char *aligned = dst - phase;
+    const uint32_t *s32 = reinterpret_cast<const uint32_t *>(s_text);
+    const uint32_t sh = (0u - phase) & 3u;
+    for (uint32_t c = tid; c < n_chunks; c += K7_BLOCK) {
+        const uint32_t lo = c << 4, hi = lo + 16u;
+        if (lo >= phase && hi <= end) {
+            const uint32_t m = (lo - phase) >> 2;
+            const uint32_t d0 = s32[m], d1 = s32[m + 1], d2 = s32[m + 2], d3 = s32[m + 3], d4 = s32[m + 4];
+            uint4 v;
+            v.x = __builtin_amdgcn_alignbyte(d1, d0, sh);
+            v.y = __builtin_amdgcn_alignbyte(d2, d1, sh);
+            v.z = __builtin_amdgcn_alignbyte(d3, d2, sh);
+            v.w = __builtin_amdgcn_alignbyte(d4, d3, sh);
+            *reinterpret_cast<uint4 *>(aligned + lo) = v;
+        } else {
+            const uint32_t a = lo < phase ? phase : lo, b = hi > end ? end : hi;
+            for (uint32_t i = a; i < b; ++i) aligned[i] = s_text[i - phase];
+        }
+    }
+}
+
 // state[0] = ticket counter, state[1] = error word, state[2 + t] = look-back word of tile t
 template <int RPT>
 __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_kernel(const double *__restrict__ box4,
@@ -370,7 +483,6 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_kernel(const double *__restr
     if (tid == 0) s_bcast[0] = atomicAdd(&state[0], 1ull);
     __syncthreads();
     const int64_t tile = (int64_t)s_bcast[0];
-    unsigned long long *words = state + 2;
     const int64_t n_tiles = (n_rows + TILE - 1) / TILE;
     if (tile >= n_tiles) return;
     const int64_t row0 = tile * TILE + tid;   // the thread's rows are row0 + k * K7_BLOCK
@@ -380,123 +492,30 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_kernel(const double *__restr
     // ---- measure --------------------------------------------------------------------------------
     RowIn r[RPT];
     RowState st[RPT];
-#pragma unroll
-    for (int k = 0; k < RPT; ++k) {
-        const int64_t row = row0 + (int64_t)k * K7_BLOCK;
-        r[k].b0 = r[k].b1 = 0;
-        r[k].w = r[k].h = 1.0;
-        r[k].cid = 0;
-        if (row < n_rows) {
-            r[k].b0 = row_off[row];
-            r[k].b1 = row_off[row + 1];
-            r[k].w = width[row];
-            r[k].h = height[row];
-            r[k].cid = class_id[row];
-        }
-        r[k].host = (r[k].w == 0.0) || (r[k].h == 0.0) || (r[k].cid < 0);
-    }
-    K7_STAMP(1);
     bool plain[RPT];
-#pragma unroll
-    for (int k = 0; k < RPT; ++k) {
-        const bool live = row0 + (int64_t)k * K7_BLOCK < n_rows;
-        plain[k] = live && plain_row(r[k], box4, sel, st[k].q);
-        if (plain[k]) {
-            st[k].len = plain_len(r[k], st[k].q);
-            st[k].flag = 0;
-        } else {
-            row_measure(r[k], box4, sel, st[k]);
-            if (!live) st[k].len = 0;
-        }
-    }
+    k7_load_rows(row0, n_rows, row_off, width, height, class_id, r);
+    K7_STAMP(1);
+    k7_measure_rows(row0, n_rows, r, box4, sel, st, plain);
     if (trace && tid == 0) trace[tile * 8 + 7] = (unsigned long long)plain[0] | ((unsigned long long)plain[RPT - 1] << 1);
     K7_STAMP(2);
 
     // ---- exclusive scan of the lengths in row order (k major) ------------------------------------------
-    uint32_t incl[RPT];
-#pragma unroll
-    for (int k = 0; k < RPT; ++k) {
-        incl[k] = st[k].len;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const uint32_t up = __shfl_up(incl[k], d);
-            if (lane >= d) incl[k] += up;
-        }
-        if (lane == kWave - 1) s_wave[k][wave] = incl[k];
-    }
-    __syncthreads();
-    uint32_t toff[RPT], tile_bytes = 0;
-#pragma unroll
-    for (int k = 0; k < RPT; ++k) {
-        uint32_t before = tile_bytes;
-#pragma unroll
-        for (int w = 0; w < K7_WAVES; ++w) {
-            if (w < wave) before += s_wave[k][w];
-            tile_bytes += s_wave[k][w];
-        }
-        toff[k] = before + incl[k] - st[k].len;
-    }
+    uint32_t toff[RPT];
+    const uint32_t tile_bytes = k7_scan_rows(st, s_wave, lane, wave, toff);
 
     K7_STAMP(3);
     // the tile's own byte count goes out first: the tiles after this one need only that to move on
-    if (tid == 0) {
-        const unsigned long long mine = (tile == 0 ? K7_FLAG_PFX : K7_FLAG_AGG) | (unsigned long long)tile_bytes;
-        __hip_atomic_store(&words[tile], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (tid == 0) lookback_publish(state, tile, tile == 0 ? LB_PFX : LB_AGG, tile_bytes);
     // ---- print into LDS at tile-relative offsets while the words of the earlier tiles arrive ----------
     const bool staged = text && tile_bytes && tile_bytes <= (uint32_t)K7_LDS_TEXT;
-    if (staged) {
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-            unsigned char *mine = s_text + toff[k];
-            if (plain[k])
-                plain_print(r[k], st[k], [&](int p, char c) { mine[p] = (unsigned char)c; });
-            else if (st[k].len)
-                row_print(r[k], box4, sel, [&](int p, char c) { mine[p] = (unsigned char)c; });
-        }
-    }
+    if (staged) k7_print_rows(r, st, plain, toff, box4, sel, s_text);
     K7_STAMP(4);
     // ---- decoupled look-back (wave 0) -------------------------------------------------------------
     if (wave == 0) {
-        unsigned long long base = 0;
-        int64_t look = tile - 1;      // nearest tile not yet accounted for
-        bool failed = false;
-        while (look >= 0) {
-            const int64_t t = look - lane;
-            unsigned long long wv = K7_FLAG_PFX;   // lanes before tile 0 read as an empty prefix
-            if (t >= 0) {
-                int spins = 0;
-                do {
-                    wv = __hip_atomic_load(&words[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((wv >> 62) == 0 && ++spins > K7_SPIN_LIMIT) {
-                        failed = true;
-                        break;
-                    }
-                    if ((wv >> 62) == 0) __builtin_amdgcn_s_sleep(1);
-                } while ((wv >> 62) == 0);
-            }
-            if (__any(failed)) {
-                failed = true;
-                break;
-            }
-            const unsigned long long has_pfx = __ballot((wv >> 62) == 2);
-            const int first = has_pfx ? __ffsll((long long)has_pfx) - 1 : kWave;   // nearest lane holding a prefix
-            unsigned long long part = (lane <= first) ? (wv & K7_VALUE) : 0ull;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-            base += part;
-            if (has_pfx) break;
-            look -= kWave;
-        }
+        const unsigned long long before = lookback_sum(state, tile, lane);
         if (lane == 0) {
-            if (failed) {
-                atomicExch(&state[1], 1ull);
-                base = 0;
-            }
-            if (tile != 0)
-                __hip_atomic_store(&words[tile], K7_FLAG_PFX | ((base + tile_bytes) & K7_VALUE), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            s_bcast[1] = base;
+            if (tile != 0) lookback_publish(state, tile, LB_PFX, (before + tile_bytes) & LB_VALUE);
+            s_bcast[1] = before;
         }
     }
     __syncthreads();
@@ -517,42 +536,11 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_kernel(const double *__restr
         if (tid == 0) atomicExch(&state[1], 2ull);
         return;
     }
-    unsigned char *dst = text + base;
     if (staged) {
-        // dst[i] = s_text[i].  The 16-byte store k goes to the aligned address dst - phase + 16k and takes the LDS
-        // bytes from 16k - phase on: five aligned dwords funnel-shifted by (-phase) & 3 bytes.
-        const uint32_t phase = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
-        const uint32_t end = phase + tile_bytes;
-        const uint32_t n_chunks = (end + 15u) >> 4;
-        unsigned char *aligned = dst - phase;
-        const uint32_t *s32 = reinterpret_cast<const uint32_t *>(s_text);
-        const uint32_t sh = (0u - phase) & 3u;
-        for (uint32_t k = tid; k < n_chunks; k += K7_BLOCK) {
-            const uint32_t lo = k << 4, hi = lo + 16u;
-            if (lo >= phase && hi <= end) {
-                const uint32_t m = (lo - phase) >> 2;
-                const uint32_t d0 = s32[m], d1 = s32[m + 1], d2 = s32[m + 2], d3 = s32[m + 3], d4 = s32[m + 4];
-                uint4 v;
-                v.x = __builtin_amdgcn_alignbyte(d1, d0, sh);
-                v.y = __builtin_amdgcn_alignbyte(d2, d1, sh);
-                v.z = __builtin_amdgcn_alignbyte(d3, d2, sh);
-                v.w = __builtin_amdgcn_alignbyte(d4, d3, sh);
-                *reinterpret_cast<uint4 *>(aligned + lo) = v;
-            } else {
-                const uint32_t a = lo < phase ? phase : lo, b = hi > end ? end : hi;
-                for (uint32_t i = a; i < b; ++i) aligned[i] = s_text[i - phase];
-            }
-        }
+        k7_flush(s_text, text + base, tile_bytes, tid);
         K7_STAMP(6);
     } else {   // a tile of very long rows: print straight to memory
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-            unsigned char *mine = dst + toff[k];
-            if (plain[k])
-                plain_print(r[k], st[k], [&](int p, char c) { mine[p] = (unsigned char)c; });
-            else if (st[k].len)
-                row_print(r[k], box4, sel, [&](int p, char c) { mine[p] = (unsigned char)c; });
-        }
+        k7_print_rows(r, st, plain, toff, box4, sel, text + base);
     }
 }
 
@@ -584,7 +572,6 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_pair_kernel(const double *__
     if (tid == 0) s_bcast[0] = atomicAdd(&state[0], 1ull);
     __syncthreads();
     const int64_t ticket = (int64_t)s_bcast[0];
-    unsigned long long *words = state + 2;
     const int64_t n_tiles = (n_rows + TILE - 1) / TILE;
     const int64_t tile_a = 2 * ticket, tile_b = tile_a + 1;
     if (tile_a >= n_tiles) return;
@@ -598,93 +585,12 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_pair_kernel(const double *__
     // loads + lengths + workgroup scan of one tile; leaves the tile's state in r / st / plain / toff
     auto measure = [&](int64_t tile) -> uint32_t {
         const int64_t row0 = tile * TILE + tid;
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-            const int64_t row = row0 + (int64_t)k * K7_BLOCK;
-            r[k].b0 = r[k].b1 = 0;
-            r[k].w = r[k].h = 1.0;
-            r[k].cid = 0;
-            if (row < n_rows) {
-                r[k].b0 = row_off[row];
-                r[k].b1 = row_off[row + 1];
-                r[k].w = width[row];
-                r[k].h = height[row];
-                r[k].cid = class_id[row];
-            }
-            r[k].host = (r[k].w == 0.0) || (r[k].h == 0.0) || (r[k].cid < 0);
-        }
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-            const bool live = row0 + (int64_t)k * K7_BLOCK < n_rows;
-            plain[k] = live && plain_row(r[k], box4, sel, st[k].q);
-            if (plain[k]) {
-                st[k].len = plain_len(r[k], st[k].q);
-                st[k].flag = 0;
-            } else {
-                row_measure(r[k], box4, sel, st[k]);
-                if (!live) st[k].len = 0;
-            }
-        }
-        uint32_t incl[RPT];
+        k7_load_rows(row0, n_rows, row_off, width, height, class_id, r);
+        k7_measure_rows(row0, n_rows, r, box4, sel, st, plain);
         __syncthreads();   // s_wave of the previous tile has been read by everyone
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-            incl[k] = st[k].len;
-#pragma unroll
-            for (int d = 1; d < kWave; d <<= 1) {
-                const uint32_t up = __shfl_up(incl[k], d);
-                if (lane >= d) incl[k] += up;
-            }
-            if (lane == kWave - 1) s_wave[k][wave] = incl[k];
-        }
-        __syncthreads();
-        uint32_t bytes = 0;
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-            uint32_t before = bytes;
-#pragma unroll
-            for (int w = 0; w < K7_WAVES; ++w) {
-                if (w < wave) before += s_wave[k][w];
-                bytes += s_wave[k][w];
-            }
-            toff[k] = before + incl[k] - st[k].len;
-        }
-        return bytes;
+        return k7_scan_rows(st, s_wave, lane, wave, toff);
     };
-    auto print_rows = [&](unsigned char *where) {   // the current tile's rows at where + toff (LDS or memory)
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-            unsigned char *mine = where + toff[k];
-            if (plain[k])
-                plain_print(r[k], st[k], [&](int p, char c) { mine[p] = (unsigned char)c; });
-            else if (st[k].len)
-                row_print(r[k], box4, sel, [&](int p, char c) { mine[p] = (unsigned char)c; });
-        }
-    };
-    auto flush = [&](unsigned char *dst, uint32_t bytes) {   // dst[i] = s_text[i], 16-byte stores, see k7_yolo_kernel
-        const uint32_t phase = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
-        const uint32_t end = phase + bytes;
-        const uint32_t n_chunks = (end + 15u) >> 4;
-        unsigned char *aligned = dst - phase;
-        const uint32_t *s32 = reinterpret_cast<const uint32_t *>(s_text);
-        const uint32_t sh = (0u - phase) & 3u;
-        for (uint32_t c = tid; c < n_chunks; c += K7_BLOCK) {
-            const uint32_t lo = c << 4, hi = lo + 16u;
-            if (lo >= phase && hi <= end) {
-                const uint32_t m = (lo - phase) >> 2;
-                const uint32_t d0 = s32[m], d1 = s32[m + 1], d2 = s32[m + 2], d3 = s32[m + 3], d4 = s32[m + 4];
-                uint4 v;
-                v.x = __builtin_amdgcn_alignbyte(d1, d0, sh);
-                v.y = __builtin_amdgcn_alignbyte(d2, d1, sh);
-                v.z = __builtin_amdgcn_alignbyte(d3, d2, sh);
-                v.w = __builtin_amdgcn_alignbyte(d4, d3, sh);
-                *reinterpret_cast<uint4 *>(aligned + lo) = v;
-            } else {
-                const uint32_t a = lo < phase ? phase : lo, b = hi > end ? end : hi;
-                for (uint32_t i = a; i < b; ++i) aligned[i] = s_text[i - phase];
-            }
-        }
-    };
+    auto print_rows = [&](unsigned char *where) { k7_print_rows(r, st, plain, toff, box4, sel, where); };
     auto offsets_from_regs = [&](int64_t tile, int64_t base) {
         const int64_t row0 = tile * TILE + tid;
 #pragma unroll
@@ -700,9 +606,7 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_pair_kernel(const double *__
 
     // ---- tile A: measure, publish, print, park ---------------------------------------------------------------------
     const uint32_t bytes_a = measure(tile_a);
-    if (tid == 0)
-        __hip_atomic_store(&words[tile_a], (tile_a == 0 ? K7_FLAG_PFX : K7_FLAG_AGG) | (unsigned long long)bytes_a, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) lookback_publish(state, tile_a, tile_a == 0 ? LB_PFX : LB_AGG, bytes_a);
     const bool staged_a = text && bytes_a && bytes_a <= (uint32_t)LDS_TEXT;
     const bool pipelined = have_b && (staged_a || !text || bytes_a == 0);   // a tile too long for LDS is finished first
     if (staged_a) print_rows(s_text);
@@ -717,53 +621,16 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_pair_kernel(const double *__
     uint32_t bytes_b = 0;
     if (pipelined) {
         bytes_b = measure(tile_b);   // (its barriers also order A's printing before A's flush)
-        if (tid == 0)
-            __hip_atomic_store(&words[tile_b], K7_FLAG_AGG | (unsigned long long)bytes_b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) lookback_publish(state, tile_b, LB_AGG, bytes_b);
     }
     // ---- look-back for A (wave 0) -----------------------------------------------------------------------------------
     if (wave == 0) {
-        unsigned long long base = 0;
-        int64_t look = tile_a - 1;
-        bool failed = false;
-        while (look >= 0) {
-            const int64_t t = look - lane;
-            unsigned long long wv = K7_FLAG_PFX;
-            if (t >= 0) {
-                int spins = 0;
-                do {
-                    wv = __hip_atomic_load(&words[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((wv >> 62) == 0 && ++spins > K7_SPIN_LIMIT) {
-                        failed = true;
-                        break;
-                    }
-                    if ((wv >> 62) == 0) __builtin_amdgcn_s_sleep(1);
-                } while ((wv >> 62) == 0);
-            }
-            if (__any(failed)) {
-                failed = true;
-                break;
-            }
-            const unsigned long long has_pfx = __ballot((wv >> 62) == 2);
-            const int first = has_pfx ? __ffsll((long long)has_pfx) - 1 : kWave;
-            unsigned long long part = (lane <= first) ? (wv & K7_VALUE) : 0ull;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-            base += part;
-            if (has_pfx) break;
-            look -= kWave;
-        }
+        const unsigned long long before = lookback_sum(state, tile_a, lane);
         if (lane == 0) {
-            if (failed) {
-                atomicExch(&state[1], 1ull);
-                base = 0;
-            }
-            if (tile_a != 0)
-                __hip_atomic_store(&words[tile_a], K7_FLAG_PFX | ((base + bytes_a) & K7_VALUE), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
+            if (tile_a != 0) lookback_publish(state, tile_a, LB_PFX, (before + bytes_a) & LB_VALUE);
             if (pipelined)   // B's prefix is known without a look-back of its own
-                __hip_atomic_store(&words[tile_b], K7_FLAG_PFX | ((base + bytes_a + bytes_b) & K7_VALUE), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            s_bcast[1] = base;
+                lookback_publish(state, tile_b, LB_PFX, (before + bytes_a + bytes_b) & LB_VALUE);
+            s_bcast[1] = before;
         }
     }
     __syncthreads();
@@ -782,7 +649,7 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_pair_kernel(const double *__
                 flag_out[row] = (uint8_t)(s_park_meta[k][tid] & 3u);
             }
         }
-        if (staged_a && fits_a) flush(text + base_a, bytes_a);
+        if (staged_a && fits_a) k7_flush(s_text, text + base_a, bytes_a, tid);
         // ---- finish B: its state is still in registers --------------------------------------------------------------
         const int64_t base_b = base_a + (int64_t)bytes_a;
         offsets_from_regs(tile_b, base_b);
@@ -795,7 +662,7 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_pair_kernel(const double *__
             __syncthreads();                 // A has left LDS
             print_rows(s_text);
             __syncthreads();
-            flush(text + base_b, bytes_b);
+            k7_flush(s_text, text + base_b, bytes_b, tid);
         } else {
             print_rows(text + base_b);
         }
@@ -804,15 +671,13 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_pair_kernel(const double *__
     // ---- not pipelined: A alone (last tile of the grid, or a tile too long for LDS), then B the same way -----------
     offsets_from_regs(tile_a, base_a);
     if (text && bytes_a && fits_a) {
-        if (staged_a) flush(text + base_a, bytes_a);
+        if (staged_a) k7_flush(s_text, text + base_a, bytes_a, tid);
         else print_rows(text + base_a);
     }
     if (!have_b) return;
     const uint32_t bytes_b2 = measure(tile_b);
     const int64_t base_b = base_a + (int64_t)bytes_a;
-    if (tid == 0)
-        __hip_atomic_store(&words[tile_b], K7_FLAG_PFX | ((unsigned long long)(base_b + bytes_b2) & K7_VALUE), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) lookback_publish(state, tile_b, LB_PFX, (unsigned long long)(base_b + bytes_b2) & LB_VALUE);
     offsets_from_regs(tile_b, base_b);
     if (!text || bytes_b2 == 0) return;
     if (base_b + (int64_t)bytes_b2 > text_cap) {
@@ -822,7 +687,7 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_pair_kernel(const double *__
     if (bytes_b2 <= (uint32_t)LDS_TEXT) {
         print_rows(s_text);
         __syncthreads();
-        flush(text + base_b, bytes_b2);
+        k7_flush(s_text, text + base_b, bytes_b2, tid);
     } else {
         print_rows(text + base_b);
     }
@@ -960,7 +825,6 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_box_kernel(const double *__r
     if (tid == 0) s_bcast[0] = atomicAdd(&state[0], 1ull);   // ticket order, as in the row kernels
     __syncthreads();
     const int64_t tile = (int64_t)s_bcast[0];
-    unsigned long long *words = state + 2;
     if (tile >= n_tiles) return;
     if (tid == 0) s_bad = 0;
 #define K7B_STAMP(i) do { if (trace && tid == 0) trace[tile * 8 + (i)] = wall_clock64(); } while (0)
@@ -1138,9 +1002,7 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_box_kernel(const double *__r
 
     K7B_STAMP(3);
     // ---- publish; print into LDS while the tiles before publish theirs; look back (wave 0) ---------------------------------
-    if (tid == 0)
-        __hip_atomic_store(&words[tile], (tile == 0 ? K7_FLAG_PFX : K7_FLAG_AGG) | (unsigned long long)tile_bytes, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) lookback_publish(state, tile, tile == 0 ? LB_PFX : LB_AGG, tile_bytes);
     const bool staged = small && text && tile_bytes && tile_bytes <= (uint32_t)K7B_LDS_TEXT;
     auto print_box = [&](int k, int64_t j, unsigned char *where) {
         auto put = [&](int p, char c) { where[p] = (unsigned char)c; };
@@ -1164,47 +1026,10 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_box_kernel(const double *__r
     }
     K7B_STAMP(4);
     if (wave == 0) {
-        unsigned long long base = 0;
-        int64_t look = tile - 1;
-        bool failed = false;
-        while (look >= 0) {
-            const int64_t t = look - lane;
-            unsigned long long wv = K7_FLAG_PFX;
-            if (t >= 0) {
-                int spins = 0;
-                do {
-                    wv = __hip_atomic_load(&words[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((wv >> 62) == 0) {
-                        if (++spins > K7_SPIN_LIMIT) {
-                            failed = true;
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                } while ((wv >> 62) == 0);
-            }
-            if (__any(failed)) {
-                failed = true;
-                break;
-            }
-            const unsigned long long has_pfx = __ballot((wv >> 62) == 2);
-            const int first = has_pfx ? __ffsll((long long)has_pfx) - 1 : kWave;   // nearest lane holding a prefix
-            unsigned long long part = (lane <= first) ? (wv & K7_VALUE) : 0ull;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-            base += part;
-            if (has_pfx) break;
-            look -= kWave;
-        }
+        const unsigned long long before = lookback_sum(state, tile, lane);
         if (lane == 0) {
-            if (failed) {
-                atomicExch(&state[1], 1ull);
-                base = 0;
-            }
-            if (tile != 0)
-                __hip_atomic_store(&words[tile], K7_FLAG_PFX | ((base + tile_bytes) & K7_VALUE), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            s_bcast[1] = base;
+            if (tile != 0) lookback_publish(state, tile, LB_PFX, (before + tile_bytes) & LB_VALUE);
+            s_bcast[1] = before;
         }
     }
     __syncthreads();
@@ -1235,29 +1060,8 @@ __global__ __launch_bounds__(K7_BLOCK) void k7_yolo_box_kernel(const double *__r
         K7B_STAMP(6);
         if (!text || tile_bytes == 0 || !fits) return;
         unsigned char *dst = text + base;
-        if (staged) {   // LDS -> memory in 16-byte stores; the words are realigned to the destination's phase
-            const uint32_t phase = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
-            const uint32_t end = phase + tile_bytes;
-            const uint32_t n_chunks = (end + 15u) >> 4;
-            unsigned char *aligned = dst - phase;
-            const uint32_t *s32 = reinterpret_cast<const uint32_t *>(s_text);
-            const uint32_t sh = (0u - phase) & 3u;
-            for (uint32_t c = tid; c < n_chunks; c += K7_BLOCK) {
-                const uint32_t lo = c << 4, hi = lo + 16u;
-                if (lo >= phase && hi <= end) {
-                    const uint32_t m = (lo - phase) >> 2;
-                    const uint32_t d0 = s32[m], d1 = s32[m + 1], d2 = s32[m + 2], d3 = s32[m + 3], d4 = s32[m + 4];
-                    uint4 v;
-                    v.x = __builtin_amdgcn_alignbyte(d1, d0, sh);
-                    v.y = __builtin_amdgcn_alignbyte(d2, d1, sh);
-                    v.z = __builtin_amdgcn_alignbyte(d3, d2, sh);
-                    v.w = __builtin_amdgcn_alignbyte(d4, d3, sh);
-                    *reinterpret_cast<uint4 *>(aligned + lo) = v;
-                } else {
-                    const uint32_t a = lo < phase ? phase : lo, b = hi > end ? end : hi;
-                    for (uint32_t i = a; i < b; ++i) aligned[i] = s_text[i - phase];
-                }
-            }
+        if (staged) {
+            k7_flush(s_text, dst, tile_bytes, tid);
         } else {
 #pragma unroll
             for (int k = 0; k < K7B_PER; ++k) {
@@ -1287,18 +1091,22 @@ static unsigned long long *g_k7_trace = nullptr;   // tuning hook (single-tile k
 void set_k7_trace(void *p) { g_k7_trace = static_cast<unsigned long long *>(p); }
 void set_k7_variant(int v) { g_k7_variant = (v == 2 || v == 22 || v == 30) ? v : -1; }
 
+enum class K7Kernel { single, pair, box };
+
 static int yolo_launch(const double *box4, const int32_t *row_off, const uint8_t *sel, const double *width,
                        const double *height, const int32_t *class_id, int64_t n_rows, int64_t n_boxes,
                        int64_t *text_off, uint8_t *flag, uint8_t *text, int64_t text_cap, int64_t *total_out, hipStream_t st) {
-    // rows of several boxes go to the box-tiled kernel (a lane per box); it needs the box count, the last row offset
-    bool by_box = g_k7_variant == 30;
-    if (n_boxes < 0 && g_k7_variant != 2 && g_k7_variant != 22) {   // device-resident caller: fetch the last offset
+    // 2, 22 and 30 name the kernel; -1 chooses by the table's shape: rows of several boxes go to the box-tiled kernel (a lane per
+    // box), from 1.02 boxes per row on (measured: at 1.05 the row kernels already take 1.7x the box kernel's time, at 1.25 60x)
+    K7Kernel kernel = g_k7_variant == 2 ? K7Kernel::single : g_k7_variant == 22 ? K7Kernel::pair : K7Kernel::box;
+    if (kernel == K7Kernel::box && n_boxes < 0) {   // the box kernel and the choice need the box count; device-resident caller: fetch the last offset
         int32_t last = 0;
         DYD_HIP(hipMemcpyAsync(&last, row_off + n_rows, 4, hipMemcpyDeviceToHost, st));
         DYD_HIP(hipStreamSynchronize(st));
         n_boxes = last;
     }
-    if (g_k7_variant != 2 && g_k7_variant != 22 && !by_box) by_box = n_boxes > n_rows + n_rows / 50;   // -1: by the table's shape (measured: at 1.05 boxes per row the row kernels already take 1.7x the box kernel's time, at 1.25 60x)
+    if (g_k7_variant == -1 && n_boxes <= n_rows + n_rows / 50) kernel = K7Kernel::pair;
+    const bool by_box = kernel == K7Kernel::box;
     const int64_t n_tiles = by_box ? (n_boxes > 0 ? ceil_div(n_boxes, (int64_t)K7B_WINDOW) : 1) : ceil_div(n_rows, (int64_t)K7_BLOCK * 2);
     void *scr = nullptr;
     const size_t state_bytes = (size_t)(n_tiles + 2) * 8;
@@ -1306,19 +1114,24 @@ static int yolo_launch(const double *box4, const int32_t *row_off, const uint8_t
     if (rc) return rc;
     DYD_HIP(hipMemsetAsync(scr, 0, state_bytes, st));
     unsigned long long *state = static_cast<unsigned long long *>(scr);
-    if (by_box) {   // (the first tile's search for box 0 gives row 0: leading empty rows are its own)
+    switch (kernel) {
+    case K7Kernel::box: {   // (the first tile's search for box 0 gives row 0: leading empty rows are its own)
         int64_t *tile_row = reinterpret_cast<int64_t *>(state + n_tiles + 2), *tile_box = tile_row + n_tiles + 1;
         hipLaunchKernelGGL(k7_tile_rows_kernel, dim3((unsigned)ceil_div(n_tiles + 1, (int64_t)K7_BLOCK)), dim3(K7_BLOCK), 0, st, row_off,
                            n_rows, n_tiles, tile_row, tile_box);
         hipLaunchKernelGGL(k7_yolo_box_kernel, dim3((unsigned)n_tiles), dim3(K7_BLOCK), 0, st, box4, row_off, sel, width, height,
                            class_id, n_rows, n_tiles, tile_row, tile_box, text_off, flag, text, text_cap, state, g_k7_trace);
+        break;
     }
-    else if (g_k7_variant != 2)
+    case K7Kernel::pair:
         hipLaunchKernelGGL((k7_yolo_pair_kernel<2>), dim3((unsigned)ceil_div(n_tiles, 2)), dim3(K7_BLOCK), 0, st, box4, row_off, sel,
                            width, height, class_id, n_rows, text_off, flag, text, text_cap, state);
-    else
+        break;
+    case K7Kernel::single:
         hipLaunchKernelGGL((k7_yolo_kernel<2>), dim3((unsigned)n_tiles), dim3(K7_BLOCK), 0, st, box4, row_off, sel, width, height,
                            class_id, n_rows, text_off, flag, text, text_cap, state, g_k7_trace);
+        break;
+    }
     DYD_HIP(hipGetLastError());
     unsigned long long err = 0;
     int64_t total = 0;

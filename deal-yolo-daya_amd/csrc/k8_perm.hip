@@ -11,7 +11,7 @@
 //             F(k) = twist(s[k], s[k+1])), so one workgroup produces a whole block per barrier: k8_mt_stream;
 //   resolve   c(t) = number of accepted draws before draw t obeys c(t+1) = c(t) + [ (d[t] & mask(i)) <= i ], i = n-1-c(t).
 //             An analytic guess of c(t) is off by a few standard deviations of the rejection count at most, and for every count
-//             inside that band most draws are decided the same way: two hand-written single-pass scans (decoupled look-back)
+//             inside that band most draws are decided the same way: two hand-written single-pass scans (decoupled look-back, lookback.h)
 //             settle those, and the 1-3 % whose outcome depends on the exact count are listed and resolved by ONE workgroup
 //             that walks the list tile by tile (k8_scan_classify -> k8_list_resolve -> k8_scan_final; "the banded resolve").
 //             Short permutations, and a band that did not hold, take full-length rounds c <- scan(flags(c)) (rocPRIM);
@@ -40,6 +40,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "dyd_common.h"
+#include "lookback.h"
 
 #define K8_JUMP_QUALIFIER __device__ const
 #include "k8_jump_table.h"
@@ -389,49 +390,17 @@ __global__ __launch_bounds__(256) void k8_guess(K8Octaves oc, uint32_t n, int64_
 //   pass B  reads d, the byte (by now 0 / 1 everywhere) and the guess; scans the acceptances; the exclusive count says which step
 //           a draw belongs to, so the partner key[i] is written at once; no count is ever stored.
 constexpr int K8S_THREADS = 1024, K8S_EPT = 8, K8S_TILE = K8S_THREADS * K8S_EPT;
-constexpr unsigned long long K8S_AGG = 1ull << 62, K8S_PFX = 2ull << 62, K8S_VALUE = (1ull << 62) - 1;
-constexpr int K8S_SPIN_LIMIT = 1 << 22;
 
-// state[0] = ticket counter, state[1] = error word (a look-back gave up), state[2 + t] = look-back word of tile t.
-// Returns the sum of the aggregates of every tile before `tile` (all threads get it); publishes this tile's words.
+// Publishes this tile's aggregate, sums the aggregates of every tile before `tile` (lookback.h: the words' layout in `state`, the
+// loop, the error word), publishes the tile's prefix; all threads get the sum.
 __device__ __forceinline__ unsigned long long k8s_lookback(unsigned long long *state, int64_t tile, unsigned long long mine,
                                                            unsigned long long *s_bcast) {
-    unsigned long long *words = state + 2;
     const int tid = threadIdx.x, lane = tid & 63;
-    if (tid == 0)
-        __hip_atomic_store(&words[tile], (tile == 0 ? K8S_PFX : K8S_AGG) | mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) lookback_publish(state, tile, tile == 0 ? LB_PFX : LB_AGG, mine);
     if (tid < 64) {
-        unsigned long long base = 0;
-        int64_t look = tile - 1;
-        bool failed = false;
-        while (look >= 0) {
-            const int64_t t = look - lane;
-            unsigned long long wv = K8S_PFX;      // lanes before tile 0 read as an empty prefix
-            if (t >= 0) {
-                int spins = 0;
-                do {
-                    wv = __hip_atomic_load(&words[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((wv >> 62) == 0 && ++spins > K8S_SPIN_LIMIT) { failed = true; break; }
-                    if ((wv >> 62) == 0) __builtin_amdgcn_s_sleep(1);
-                } while ((wv >> 62) == 0);
-            }
-            if (__any(failed)) { failed = true; break; }
-            const unsigned long long has_pfx = __ballot((wv >> 62) == 2);
-            const int first = has_pfx ? __ffsll((long long)has_pfx) - 1 : kWave;
-            unsigned long long part = (lane <= first) ? (wv & K8S_VALUE) : 0ull;
-#pragma unroll
-            for (int dlt = 32; dlt >= 1; dlt >>= 1) {
-                const unsigned int lo = (unsigned int)__shfl_xor((int)(unsigned int)part, dlt), hi = (unsigned int)__shfl_xor((int)(unsigned int)(part >> 32), dlt);
-                part += ((unsigned long long)hi << 32) | lo;
-            }
-            base += part;
-            if (has_pfx) break;
-            look -= kWave;
-        }
+        const unsigned long long base = lookback_sum(state, tile, lane);
         if (lane == 0) {
-            if (failed) { atomicExch(&state[1], 1ull); base = 0; }
-            if (tile != 0)
-                __hip_atomic_store(&words[tile], K8S_PFX | ((base + mine) & K8S_VALUE), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tile != 0) lookback_publish(state, tile, LB_PFX, (base + mine) & LB_VALUE);
             *s_bcast = base;
         }
     }

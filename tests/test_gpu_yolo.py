@@ -262,6 +262,38 @@ def test_k7_dev_capacity_and_measure_mode(native, k7_variant):
     assert np.array_equal(d_flag.cpu().numpy(), want_flag)
 
 
+@pytest.mark.parametrize("n_rows", [1, 600, 1100])
+def test_k7_text_phase(native, k7_variant, n_rows):
+    """the LDS-to-memory flush at every 16-byte phase of the FIRST tile's destination (an allocation's start is always
+    aligned): one row is a tile of some 40 bytes (partial head, one or two whole chunks, partial tail), 600 rows are two row
+    tiles (one ticket of the pair kernel), 1100 rows three (a ticket with a lone tile A); the box variant cuts at 480 boxes"""
+    import torch
+    L = native.lib()
+    rng = np.random.default_rng(40 + n_rows)
+    box, row_off, _, w, h, cid = _random_case(rng, n_rows, 2, False, special=False)
+    want_off, want_flag, want_text = olib.yolo_lines(box, row_off, None, w, h, cid)
+    assert len(want_text) >= 36                                       # the single row has a box
+    dev = torch.device("cuda:0")
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    d_box, d_off, d_w, d_h, d_cid = t(box.reshape(-1)), t(row_off), t(w), t(h), t(cid)
+    total = C.c_int64()
+    st = torch.cuda.current_stream().cuda_stream
+    for p in range(16):
+        d_toff = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
+        d_flag = torch.full((n_rows,), 9, dtype=torch.uint8, device=dev)
+        buf = torch.full((64 + 16 + len(want_text) + 64,), 0x7e, dtype=torch.uint8, device=dev)
+        assert buf.data_ptr() % 16 == 0
+        at = 64 + p
+        rc = L.dyd_yolo_lines_dev(d_box.data_ptr(), d_off.data_ptr(), None, d_w.data_ptr(), d_h.data_ptr(), d_cid.data_ptr(), n_rows,
+                                  int(row_off[-1]), d_toff.data_ptr(), d_flag.data_ptr(), buf.data_ptr() + at, len(want_text),
+                                  C.byref(total), st)
+        assert rc == 0, (p, L.dyd_last_error())
+        out = buf.cpu().numpy()
+        assert out[at:at + len(want_text)].tobytes() == want_text, p
+        assert (out[:at] == 0x7e).all() and (out[at + len(want_text):] == 0x7e).all(), p
+        assert np.array_equal(d_toff.cpu().numpy(), want_off) and np.array_equal(d_flag.cpu().numpy(), want_flag), p
+
+
 def test_k7_full_size_properties(native, k7_variant):
     """20 M single-box rows (the shape of a split sheet): offsets are the running sum of the line lengths,
     the text is lines of five tokens, and sampled rows equal Python's own formatting."""
