@@ -77,6 +77,12 @@ SIGNATURES = {
     "dyd_repair_boxes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
+    "dyd_compare_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                    C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "dyd_compare_boxes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dyd_json_emit_repaired": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_void_p)]),
     "dyd_json_scan_named_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
@@ -491,6 +497,36 @@ def repair_boxes(box4: np.ndarray, row_off: np.ndarray, cls: np.ndarray, width: 
                                  n_classes, min_visibility, min_size, _ptr(action), _ptr(out_box), _ptr(rows), _ptr(cc)),
           "dyd_repair_boxes")
     return action, out_box, rows, cc
+
+
+def _compare_side(box4, row_off, cls, what: str) -> tuple:
+    """one table of K18 as contiguous arrays of the kernel's dtypes, its sizes checked -> (box4, row_off, cls, n_boxes)"""
+    box4 = np.ascontiguousarray(box4, dtype=np.float64).reshape(-1)
+    row_off = np.ascontiguousarray(row_off, dtype=np.int32)
+    if len(row_off) < 1 or row_off[0] != 0 or 4 * int(row_off[-1]) != box4.size:
+        raise ValueError(f"{what}: row_off must start at 0 and end at the number of boxes")
+    cls = np.ascontiguousarray(cls, dtype=np.int32)
+    if cls.size != int(row_off[-1]):
+        raise ValueError(f"{what}: cls must hold one id per box")
+    return box4, row_off, cls, int(row_off[-1])
+
+
+def compare_boxes(a_box4, a_row_off, a_cls, b_box4, b_row_off, b_cls, n_classes: int, thr: float, by_label: bool = False):
+    """K18 over host arrays: two box tables of the same rows -> (a_match [A] i32, b_match [B] i32, b_iou [B] f64, a_best [A] f64,
+    b_best [B] f64, row_counts [N,4] i32, confusion [C+1,C+1] u64).  See include/dyd.h for the matching rule."""
+    a_box4, a_row_off, a_cls, na = _compare_side(a_box4, a_row_off, a_cls, "A")
+    b_box4, b_row_off, b_cls, nb = _compare_side(b_box4, b_row_off, b_cls, "B")
+    n, n_classes = len(a_row_off) - 1, int(n_classes)
+    if len(b_row_off) - 1 != n:
+        raise ValueError("the two tables must cover the same rows")
+    a_match, a_best = np.full(na, -1, np.int32), np.zeros(na, np.float64)
+    b_match, b_iou, b_best = np.full(nb, -1, np.int32), np.zeros(nb, np.float64), np.zeros(nb, np.float64)
+    rows = np.zeros((n, 4), np.int32)
+    conf = np.zeros((n_classes + 1, n_classes + 1), np.uint64)
+    check(lib().dyd_compare_boxes(_ptr(a_box4), _ptr(a_row_off), _ptr(a_cls), _ptr(b_box4), _ptr(b_row_off), _ptr(b_cls), n,
+                                  n_classes, float(thr), int(bool(by_label)), _ptr(a_match), _ptr(b_match), _ptr(b_iou),
+                                  _ptr(a_best), _ptr(b_best), _ptr(rows), _ptr(conf)), "dyd_compare_boxes")
+    return a_match, b_match, b_iou, a_best, b_best, rows, conf
 
 
 def bbox_iou_fused(xy: np.ndarray, pt_off: np.ndarray, box_off: np.ndarray, min_boxes: int, thr: float,

@@ -2634,6 +2634,307 @@ def repair_boxes_csv(input_csv_path, output_csv_path="repaired_boxes.csv", chang
     return {**totals, "output": output_csv_path, "changes_output": changes_csv, "classes_output": classes_csv}
 
 
+# =============================================================================== f6a  box comparison
+# How two annotation sets of the same images differ: two annotators or rounds, pre-labels against their correction, an export
+# before and after a relabel or a repair.  Boxes are the audit's (the walk of utils._extract_boxes_with_labels, reference
+# utils.py:681-710, with the index of their object; a coordinate that is no number becomes NaN).  Per image row K18
+# (csrc/k18_compare.hip, rule in include/dyd.h and DESIGN §5p) matches the B boxes, in annotation order, greedily to the A boxes:
+# B box j takes the still free A box (of the same name when by_label) with the largest reference IoU >= iou_threshold, ties to
+# the lowest index.  A matched pair of equal names agrees, one of different names is `relabelled`, an unmatched A box is
+# `missing`, an unmatched B box `extra`.  Boxes whose name is no str share one class, reported as None and listed last.
+# Native scan of both sides -> one K18 launch per chunk -> frames.
+COMPARE_KINDS = ("missing", "extra", "relabelled")
+COMPARE_NONE = "(none)"                              # the confusion matrix's last row and column: no partner
+COMPARE_HIST_BINS = 20                               # hist_iou bins of width 0.05; the last takes IoU 1.0
+_COMPARE_ROW_COLS = ("agree", "relabelled", "missing", "extra")
+_COMPARE_DIFF_SPEC = (("row", np.int64), ("kind", object), ("a_object", np.int64), ("b_object", np.int64), ("a_name", object),
+                      ("b_name", object), ("iou", np.float64), ("best_iou", np.float64),
+                      (("ax1", "ay1", "ax2", "ay2"), np.float64), (("bx1", "by1", "bx2", "by2"), np.float64))
+
+
+class BoxComparison:
+    """Result of compare_boxes_*: classes (sorted as str, None last), confusion (frame, index = A class, columns = B class, plus
+    a last "(none)" row and column), per_class, hist_iou (int64 [C, 20], the IoU of the agreeing pairs), per_row, differences
+    (one line per missing / extra / relabelled box), unpaired (key, side: rows found in one frame only) and totals."""
+
+    def __init__(self, classes, confusion, per_class, hist_iou, per_row, differences, unpaired, totals):
+        self.classes = classes
+        self.confusion = confusion
+        self.per_class = per_class
+        self.hist_iou = hist_iou
+        self.per_row = per_row
+        self.differences = differences
+        self.unpaired = unpaired
+        self.totals = totals
+
+    def __repr__(self):
+        return f"BoxComparison({len(self.classes)} classes, {self.totals})"
+
+
+class _CompareTotals:
+    """class-keyed sums over the chunks (classes in first-seen order, None = the names that are no str), per-row counts and
+    differences per chunk"""
+
+    def __init__(self):
+        self.index = {}
+        self.pairs = np.zeros((0, 0), np.int64)          # [A class, B class] matched pairs
+        self.missing = np.zeros(0, np.int64)
+        self.extra = np.zeros(0, np.int64)
+        self.hist = np.zeros((0, COMPARE_HIST_BINS), np.int64)
+        self.rows, self.n_a, self.n_b, self.diffs = [], [], [], []
+        self.python_cells = 0
+
+    def add(self, names, conf, hist):
+        """adds a chunk's (C+1) x (C+1) confusion counts and [C, 20] histogram, C = len(names)"""
+        g = np.asarray([self.index.setdefault(nm, len(self.index)) for nm in names], np.int64)
+        grow = len(self.index) - len(self.missing)
+        if grow:
+            self.pairs = np.pad(self.pairs, ((0, grow), (0, grow)))
+            self.missing, self.extra = np.pad(self.missing, (0, grow)), np.pad(self.extra, (0, grow))
+            self.hist = np.pad(self.hist, ((0, grow), (0, 0)))
+        c = len(names)
+        if c:
+            self.pairs[np.ix_(g, g)] += conf[:c, :c]
+            self.missing[g] += conf[:c, c]
+            self.extra[g] += conf[c, :c]
+            self.hist[g] += hist
+
+
+def _compare_threshold(iou_threshold) -> float:
+    if isinstance(iou_threshold, bool) or not isinstance(iou_threshold, _NUMBER_TYPES):
+        raise ValueError(f"iou_threshold must be a number, got {iou_threshold!r}")
+    return float(iou_threshold)
+
+
+def _box_names(names: list, cls, odd_names: dict, sel) -> np.ndarray:
+    """the names of the boxes `sel` of one side: names[class id], None for class id -1, then the names that are no str"""
+    out = np.asarray(names + [None], object)[np.asarray(cls, np.int64)[sel]]
+    for b, nm in odd_names.items():
+        p = int(np.searchsorted(sel, b))
+        if p < len(sel) and sel[p] == b:
+            out[p] = nm
+    return out
+
+
+def _compare_chunk(cells_a, cells_b, thr: float, by_label: bool, be, acc: _CompareTotals, start: int):
+    """one chunk of rows: both box tables (_box_chunk) on one class list -> K18 -> class-keyed sums, per-row counts, differences"""
+    sides = []
+    for cells in (cells_a, cells_b):
+        t = _box_chunk(cells)
+        if t.scan is not None:
+            t.scan.close()
+        sides.append(t)
+    ta, tb = sides
+    n = len(cells_a)
+    acc.python_cells += len(ta.irregular) + len(tb.irregular)
+    ids, cls = {}, []
+    for t in sides:                                      # one class list for both sides, the names that are no str last
+        to = np.asarray([ids.setdefault(nm, len(ids)) for nm in t.names] + [-1], np.int32)
+        cls.append(to[np.asarray(t.cls, np.int64)])
+    names = list(ids)
+    if any((c < 0).any() for c in cls):
+        names.append(None)
+        cls = [np.where(c < 0, len(names) - 1, c).astype(np.int32) for c in cls]
+    C = len(names)
+    off_a, off_b = ta.row_off, tb.row_off
+    box_a, box_b = (np.asarray(t.box4, np.float64).reshape(-1, 4) for t in sides)
+    a_match, b_match, b_iou, a_best, b_best, rows, conf = be.compare_boxes(
+        box_a, off_a.astype(np.int32), cls[0], box_b, off_b.astype(np.int32), cls[1], C, thr, by_label)
+    a_match, b_match = np.asarray(a_match, np.int64), np.asarray(b_match, np.int64)
+    b_iou, a_best, b_best = (np.asarray(v, np.float64) for v in (b_iou, a_best, b_best))
+    row_a = np.repeat(np.arange(n, dtype=np.int64), np.diff(off_a))
+    row_b = np.repeat(np.arange(n, dtype=np.int64), np.diff(off_b))
+    hit = np.flatnonzero(b_match >= 0)                   # matched B boxes and their A boxes
+    hit_a = off_a[row_b[hit]] + b_match[hit]
+    same = cls[0][hit_a] == cls[1][hit]
+    hist = np.zeros((C, COMPARE_HIST_BINS), np.int64)
+    np.add.at(hist, (cls[1][hit[same]], np.minimum((b_iou[hit[same]] * COMPARE_HIST_BINS).astype(np.int64),
+                                                   COMPARE_HIST_BINS - 1)), 1)
+    acc.add(names, np.asarray(conf).astype(np.int64).reshape(C + 1, C + 1), hist)
+    acc.rows.append(np.asarray(rows, np.int64).reshape(n, 4))
+    acc.n_a.append(np.diff(off_a))
+    acc.n_b.append(np.diff(off_b))
+    miss, extra, rel_b = np.flatnonzero(a_match < 0), np.flatnonzero(b_match < 0), hit[~same]
+    rel_a = hit_a[~same]
+    k = (len(miss), len(extra), len(rel_b))
+    if sum(k):
+        nan4 = lambda m: np.full((m, 4), np.nan)         # noqa: E731
+        absent = lambda m: np.full(m, -1, np.int64)      # noqa: E731
+        none = lambda m: np.full(m, None, object)        # noqa: E731
+        row = np.concatenate([row_a[miss], row_b[extra], row_b[rel_b]])
+        kind = np.repeat(np.arange(3), k)
+        at = np.concatenate([miss - off_a[row_a[miss]], extra - off_b[row_b[extra]], rel_a - off_a[row_b[rel_b]]])
+        order = np.lexsort((at, kind, row))
+        obj_a, obj_b = np.asarray(ta.obj, np.int64), np.asarray(tb.obj, np.int64)
+        cols = (start + row, np.asarray(COMPARE_KINDS, object)[kind],
+                np.concatenate([obj_a[miss], absent(k[1]), obj_a[rel_a]]),
+                np.concatenate([absent(k[0]), obj_b[extra], obj_b[rel_b]]),
+                np.concatenate([_box_names(ta.names, ta.cls, ta.odd_names, miss), none(k[1]),
+                                _box_names(ta.names, ta.cls, ta.odd_names, rel_a)]),
+                np.concatenate([none(k[0]), _box_names(tb.names, tb.cls, tb.odd_names, extra),
+                                _box_names(tb.names, tb.cls, tb.odd_names, rel_b)]),
+                np.concatenate([np.zeros(k[0] + k[1]), b_iou[rel_b]]),
+                np.concatenate([a_best[miss], b_best[extra], b_iou[rel_b]]),
+                np.concatenate([box_a[miss], nan4(k[1]), box_a[rel_a]]),
+                np.concatenate([nan4(k[0]), box_b[extra], box_b[rel_b]]))
+        acc.diffs.append(tuple(c[order] for c in cols))
+
+
+def _compare_result(acc: _CompareTotals, n: int, sources, thr: float, by_label: bool, stats) -> BoxComparison:
+    classes = sorted(acc.index, key=lambda c: (c is None, str(c)))
+    perm = np.asarray([acc.index[c] for c in classes], np.int64)
+    pairs, missing, extra, hist = acc.pairs[np.ix_(perm, perm)], acc.missing[perm], acc.extra[perm], acc.hist[perm]
+    C = len(classes)
+    full = np.zeros((C + 1, C + 1), np.int64)
+    full[:C, :C], full[:C, C], full[C, :C] = pairs, missing, extra
+    labels = pd.Index(classes + [COMPARE_NONE], dtype=object)
+    confusion = pd.DataFrame(full, index=labels, columns=labels)
+    agree = np.diagonal(pairs).copy() if C else np.zeros(0, np.int64)
+    per_class = pd.DataFrame({"class": pd.Series(classes, dtype=object), "a_boxes": full[:C].sum(axis=1),
+                              "b_boxes": full[:, :C].sum(axis=0), "agree": agree,
+                              "relabelled_to_other": pairs.sum(axis=1) - agree, "relabelled_from_other": pairs.sum(axis=0) - agree,
+                              "missing": missing, "extra": extra})
+    rows = np.concatenate(acc.rows) if acc.rows else np.zeros((0, 4), np.int64)
+    pr = {"row": np.arange(n, dtype=np.int64)}
+    if sources is not None:
+        pr["source"] = np.asarray(sources, object)
+    pr["a_boxes"] = np.concatenate(acc.n_a) if acc.n_a else np.zeros(0, np.int64)
+    pr["b_boxes"] = np.concatenate(acc.n_b) if acc.n_b else np.zeros(0, np.int64)
+    pr.update({k: rows[:, j] for j, k in enumerate(_COMPARE_ROW_COLS)})
+    differences = _parts_frame(acc.diffs, _COMPARE_DIFF_SPEC, sources)
+    if sources is not None:                              # row first, as in per_row
+        differences = differences[["row", "source", *differences.columns[2:]]]
+    totals = {"rows": n, "a_boxes": int(pr["a_boxes"].sum()), "b_boxes": int(pr["b_boxes"].sum()),
+              "matched": int(rows[:, :2].sum()), "agree": int(rows[:, 0].sum()), "relabelled": int(rows[:, 1].sum()),
+              "missing": int(rows[:, 2].sum()), "extra": int(rows[:, 3].sum()), "python_cells": acc.python_cells,
+              "iou_threshold": thr, "by_label": by_label}
+    if stats is not None:
+        stats.update(totals)
+    unpaired = pd.DataFrame({"key": np.zeros(0, object), "side": np.zeros(0, object)})
+    return BoxComparison(classes, confusion, per_class, hist, pd.DataFrame(pr), differences, unpaired, totals)
+
+
+def compare_boxes_cells(cells_a, cells_b, iou_threshold: float = 0.5, by_label: bool = False, backend=None,
+                        stats: Optional[dict] = None, sources=None) -> BoxComparison:
+    """Box comparison of two lists of annotation cells of the same images, row by row (see the section comment): cells_a is the
+    base, cells_b the other set.  -> BoxComparison.  ``sources`` (optional) adds a source column to per_row and differences.
+    by_label=True matches boxes of equal names only, so it reports no `relabelled` line."""
+    thr, by_label = _compare_threshold(iou_threshold), bool(by_label)
+    be = _step_backend(backend, "compare_boxes")
+    cells_a = cells_a.to_numpy() if hasattr(cells_a, "to_numpy") else cells_a
+    cells_b = cells_b.to_numpy() if hasattr(cells_b, "to_numpy") else cells_b
+    n = len(cells_a)
+    if len(cells_b) != n:
+        raise ValueError(f"the two lists must hold one cell per image each: {n} against {len(cells_b)} cells")
+    acc = _CompareTotals()
+    for s0, s1, chunk in _chunks(n, cells_a):
+        _compare_chunk(chunk, cells_b[s0:s1], thr, by_label, be, acc, s0)
+    return _compare_result(acc, n, sources, thr, by_label, stats)
+
+
+def _compare_keyed(cells_a, keys_a, sources_a, cells_b, keys_b, key, thr, by_label, backend, stats) -> BoxComparison:
+    """the comparison of the rows of A whose key is also in B (each key at most once per side); rows are positions in A"""
+    ia, ib = pd.Index(keys_a), pd.Index(keys_b)
+    for side, idx in (("the base", ia), ("the other", ib)):
+        if idx.has_duplicates:
+            raise ValueError(f"{side} table holds the key {idx[idx.duplicated()][0]!r} of column {key!r} more than once: "
+                             "run the dedup step (dedup_frame / deduplicate_csv_by_source) on it first")
+    at = ib.get_indexer(ia)
+    rows_a = np.flatnonzero(at >= 0)
+    rows_b = at[rows_a]
+    only_a = np.flatnonzero(at < 0)
+    seen = np.zeros(len(ib), bool)
+    seen[rows_b] = True
+    only_b = np.flatnonzero(~seen)
+    cells_a, cells_b = np.asarray(cells_a, object), np.asarray(cells_b, object)
+    res = compare_boxes_cells(cells_a[rows_a], cells_b[rows_b], thr, by_label, backend, None,
+                              None if sources_a is None else np.asarray(sources_a, object)[rows_a])
+    res.per_row["row"] = rows_a[res.per_row["row"].to_numpy()]
+    res.differences["row"] = rows_a[res.differences["row"].to_numpy()]
+    res.unpaired = pd.DataFrame({"key": np.concatenate([np.asarray(keys_a, object)[only_a], np.asarray(keys_b, object)[only_b]]),
+                                 "side": np.asarray(["a"] * len(only_a) + ["b"] * len(only_b), object)})
+    res.totals.update(rows_only_a=len(only_a), rows_only_b=len(only_b))
+    if stats is not None:
+        stats.update(res.totals)
+    return res
+
+
+def compare_boxes_frame(df_a: pd.DataFrame, df_b: Optional[pd.DataFrame] = None, json_col: str = BBOX_COL, other_col=None,
+                        key="source", iou_threshold: float = 0.5, by_label: bool = False, backend=None,
+                        stats: Optional[dict] = None) -> BoxComparison:
+    """Box comparison of two annotation columns.  With df_b=None: json_col against other_col of df_a, row by row.  With two
+    frames and key=None: by position (equal lengths).  Otherwise the rows are aligned on the column `key`, which may hold each
+    value once per frame; rows found in one frame only are not compared: totals counts them (rows_only_a / rows_only_b) and
+    ``unpaired`` lists their keys.  per_row["row"] / differences["row"] are positions in df_a."""
+    thr = _compare_threshold(iou_threshold)
+    sources = df_a["source"].to_numpy() if "source" in df_a.columns else None
+    if df_b is None or key is None:
+        if df_b is None:
+            if other_col is None:
+                raise ValueError("with one frame, other_col names the column to compare json_col against")
+            cells_b = df_a[other_col].to_numpy()
+        else:
+            if len(df_b) != len(df_a):
+                raise ValueError(f"without a key the frames are compared by position: {len(df_a)} against {len(df_b)} rows")
+            cells_b = df_b[other_col if other_col is not None else json_col].to_numpy()
+        res = compare_boxes_cells(df_a[json_col].to_numpy(), cells_b, thr, by_label, backend, None, sources)
+        res.totals.update(rows_only_a=0, rows_only_b=0)
+        if stats is not None:
+            stats.update(res.totals)
+        return res
+    return _compare_keyed(df_a[json_col].to_numpy(), df_a[key].to_numpy(), sources,
+                          df_b[other_col if other_col is not None else json_col].to_numpy(), df_b[key].to_numpy(), key, thr,
+                          by_label, backend, stats)
+
+
+def _write_comparison(res: BoxComparison, output_dir) -> dict:
+    out = Path(output_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    paths = {k: str(out / f"box_compare_{k}.csv") for k in ("confusion", "classes", "differences", "rows")}
+    paths["hist"] = str(out / "box_compare_hist.npz")
+    res.confusion.to_csv(paths["confusion"], index_label="a_class", encoding="utf-8-sig")
+    res.per_class.to_csv(paths["classes"], index=False, encoding="utf-8-sig")
+    res.differences.to_csv(paths["differences"], index=False, encoding="utf-8-sig")
+    res.per_row.to_csv(paths["rows"], index=False, encoding="utf-8-sig")
+    np.savez(paths["hist"], classes=np.asarray([COMPARE_NONE if c is None else c for c in res.classes], dtype=str),
+             hist_iou=res.hist_iou)
+    return paths
+
+
+def compare_boxes_csv(a_csv, b_csv, output_dir, json_col: str = BBOX_COL, key="source", iou_threshold: float = 0.5,
+                      by_label: bool = False, backend=None):
+    """Two CSVs -> box_compare_confusion.csv, box_compare_classes.csv, box_compare_differences.csv, box_compare_rows.csv and
+    box_compare_hist.npz (classes, hist_iou) under output_dir, in the IoU step's conventions: read as utf-8-sig; a read failure
+    prints 读取失败：... and a missing column 错误：缺少必要列 ..., both returning None.  key=None compares by position.
+    -> dict(totals, paths=...)"""
+    thr = _compare_threshold(iou_threshold)
+    sides, routes = [], []
+    for path in (a_csv, b_csv):
+        side = _csv_route(
+            "compare", path, json_col,
+            lambda table: (table.light, _fc_cells(table.heavy[json_col], 0, table.n_rows)),
+            lambda df: (df, df[json_col].to_numpy()))
+        if side is None:
+            return None
+        routes.append(LAST_IO_PATH["compare"])
+        if key is not None and key not in side[0].columns:
+            print(f"错误：缺少必要列 {key}")
+            return None
+        sides.append(side)
+    LAST_IO_PATH["compare"] = "native" if routes == ["native", "native"] else "pandas"
+    (light_a, cells_a), (light_b, cells_b) = sides
+    sources = light_a["source"].to_numpy() if "source" in light_a.columns else None
+    if key is None:
+        if len(cells_a) != len(cells_b):
+            raise ValueError(f"without a key the files are compared by position: {len(cells_a)} against {len(cells_b)} rows")
+        res = compare_boxes_cells(cells_a, cells_b, thr, by_label, backend, None, sources)
+        res.totals.update(rows_only_a=0, rows_only_b=0)
+    else:
+        res = _compare_keyed(cells_a, light_a[key].to_numpy(), sources, cells_b, light_b[key].to_numpy(), key, thr, by_label,
+                             backend, None)
+    return {**res.totals, "paths": _write_comparison(res, output_dir)}
+
+
 # =============================================================================== f7  YOLO segmentation label lines
 # One line per matched polygon, "cls x1 y1 ... xn yn" normalised to [0, 1] (YOLO segment models), each polygon clipped to the image
 # (include/dyd.h, K13, has the definition).  Native labelled-polygon scan (csrc/host_json.cpp; flatten.seg_cell_polygons for

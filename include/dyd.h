@@ -197,6 +197,50 @@ int dyd_repair_boxes_dev(const double *box4, const int32_t *row_off, int64_t n_r
                          double min_size, uint8_t *out_action, double *out_box4,
                          int32_t *out_row_counts, int64_t *out_class_counts, void *stream);
 
+/* ---- K18: box comparison — match two box tables of the same image rows --------------
+ * Tables A ("base") and B ("other") cover the same n_rows rows and share one class list.
+ * iou(a, b) = calculate_iou(a, b) of processor.py:328-339 with the A box first (first-wins
+ * max / min, intersection == 0 -> 0.0, IEEE f64 rounded operation by operation), corners
+ * normalised as in extract_boxes :359-362.  Per row, independently, indices in-row:
+ *   for j in 0 .. nb-1 (B boxes in annotation order: no scores exist, order ranks, as in K9):
+ *     cand = { i : A box i not matched yet, (not by_label or a_cls[i] == b_cls[j]),
+ *              iou(a_i, b_j) >= thr }
+ *     cand not empty: i* = the i of cand with the largest iou, ties -> lowest i;
+ *                     b_match[j] = i*, a_match[i*] = j, b_iou[j] = iou(a_i*, b_j)
+ *     else:           b_match[j] = -1, b_iou[j] = 0.0
+ *   a_match[i] = -1 for every A box never taken
+ *   a_best[i] = max over ALL j of iou(a_i, b_j), b_best[j] = max over ALL i: class and
+ *     matched state ignored; starts at 0.0 and is raised by `iou > best`, so a NaN IoU
+ *     never raises it
+ * A NaN IoU never matches (NaN >= thr is false); thr = NaN matches nothing; with thr <= 0 a
+ * pair with empty intersection (IoU 0.0) is a candidate, as K2's and K9's.
+ * a_box4, b_box4: per box the two points as stored (p1x, p1y, p2x, p2y), 16-byte aligned [4*B]
+ * a_row_off, b_row_off: box offsets per image row                                 [n_rows+1]
+ * a_cls, b_cls: class id per box, 0..n_classes-1 (_dev: a box with another id matches like
+ *             any box but is left out of out_confusion)                               [B]
+ * out_a_match [n_a] i32, out_b_match [n_b] i32, out_b_iou [n_b] f64, out_a_best [n_a] f64,
+ * out_b_best [n_b] f64: as above
+ * out_row_counts: per row matched with equal class, matched with different class, A
+ *             unmatched, B unmatched                                        [4*n_rows] i32
+ * out_confusion: (C+1) x (C+1) row-major, C = n_classes: a matched pair counts in
+ *             [a_cls][b_cls], an unmatched A box in [a_cls][C], an unmatched B box in
+ *             [C][b_cls]; [C][C] stays 0.  Zeroed by the entry.          [(C+1)*(C+1)] u64 */
+int dyd_compare_boxes(const double *a_box4, const int32_t *a_row_off, const int32_t *a_cls,
+                      const double *b_box4, const int32_t *b_row_off, const int32_t *b_cls,
+                      int64_t n_rows, int32_t n_classes, double thr, int by_label,
+                      int32_t *out_a_match, int32_t *out_b_match, double *out_b_iou,
+                      double *out_a_best, double *out_b_best, int32_t *out_row_counts,
+                      uint64_t *out_confusion);
+/* device pointers; n_a = a_row_off[n_rows], n_b = b_row_off[n_rows] (required: they size the
+ * list of rows that leave the tile kernel); n_rows == 0 returns at once, otherwise every
+ * output is written (out_row_counts and out_confusion also when no row holds a box) */
+int dyd_compare_boxes_dev(const double *a_box4, const int32_t *a_row_off, const int32_t *a_cls,
+                          const double *b_box4, const int32_t *b_row_off, const int32_t *b_cls,
+                          int64_t n_rows, int64_t n_a, int64_t n_b, int32_t n_classes, double thr,
+                          int by_label, int32_t *out_a_match, int32_t *out_b_match,
+                          double *out_b_iou, double *out_a_best, double *out_b_best,
+                          int32_t *out_row_counts, uint64_t *out_confusion, void *stream);
+
 /* ---- K1+K2 fused: poly -> bbox -> IoU flag in one pass ---------------------------
  * One launch that produces K1's outputs and K2's flag for rows whose boxes all come
  * from K1 (processing.py:580-598 runs the two steps back to back on the same rows).

@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmarks on one MI355X (device-resident inputs, HIP-event timing,
 interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant.
 
-    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k13: segmentation lines beside K7;
+    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k18: box comparison beside K2 and K9; k13: segmentation lines beside K7;
      k14: polygon audit; k14tier: its in-lane / wave threshold; k16: COCO annotation objects beside K13; k17: oriented-box lines beside K13)
 """
 import argparse
@@ -253,6 +253,60 @@ def main():
                           **{a: int(cc[:, k].sum().item()) for k, a in enumerate(
                               ("keep", "clip", "no_size", "bad_coords", "degenerate", "outside", "low_visibility", "small"))}}),
               flush=True)
+
+    if "k18" in only:
+        # K18 (box comparison) beside K2 alone and K9 on the same device buffers, interleaved rounds.  A = the K1 boxes with 20
+        # classes; B = a copy with 10 % of the boxes dropped, 10 % jittered and 5 % put into another class.
+        ck(L.dyd_bbox_minmax_dev(xy.data_ptr(), pt_off.data_ptr(), B, P, out_box.data_ptr(), out_arg.data_ptr(), sp), "k1")
+        g = torch.Generator(device=dev).manual_seed(18)
+        cls20 = (labels.to(torch.int64) % 20).to(torch.int32).contiguous()
+        u = torch.rand(B, generator=g, device=dev)
+        kept = u >= 0.10
+        b_box = out_box[kept].clone()
+        ub = u[kept]
+        b_box[:, 3] += torch.where(ub < 0.20, 2.0, 0.0).to(torch.float64)
+        b_cls = torch.where(ub >= 0.95, (cls20[kept] + 1) % 20, cls20[kept]).to(torch.int32).contiguous()
+        row = torch.repeat_interleave(torch.arange(N, device=dev), nbox.to(torch.int64))
+        b_off = torch.zeros(N + 1, dtype=torch.int32, device=dev)
+        b_off[1:] = torch.cumsum(torch.bincount(row[kept], minlength=N), 0).to(torch.int32)
+        Bb = b_box.shape[0]
+        del u, ub, row
+        keep = torch.empty(B, dtype=torch.uint8, device=dev)
+        partner = torch.empty(B, dtype=torch.int32, device=dev)
+        a_match = torch.empty(B, dtype=torch.int32, device=dev)
+        a_best = torch.empty(B, dtype=torch.float64, device=dev)
+        b_match = torch.empty(Bb, dtype=torch.int32, device=dev)
+        b_iou = torch.empty(Bb, dtype=torch.float64, device=dev)
+        b_best = torch.empty(Bb, dtype=torch.float64, device=dev)
+        crow = torch.empty((N, 4), dtype=torch.int32, device=dev)
+        conf = torch.empty((21, 21), dtype=torch.int64, device=dev)
+
+        def k18(by_label):
+            return lambda: ck(L.dyd_compare_boxes_dev(
+                out_box.data_ptr(), box_off.data_ptr(), cls20.data_ptr(), b_box.data_ptr(), b_off.data_ptr(), b_cls.data_ptr(), N, B,
+                Bb, 20, 0.5, by_label, a_match.data_ptr(), b_match.data_ptr(), b_iou.data_ptr(), a_best.data_ptr(),
+                b_best.data_ptr(), crow.data_ptr(), conf.data_ptr(), sp), "k18")
+
+        # bytes K18 needs: per box 32 + 4 class in; 12 out per A box, 20 per B box; two offsets in and 16 out per row
+        k18_bytes = 36 * (B + Bb) + 12 * B + 20 * Bb + 8 * (N + 1) + 16 * N
+        legs = {"k2 auto (dyd_iou_any_ge_dev)": (32 * B + 4 * (N + 1) + N, lambda: ck(L.dyd_iou_any_ge_dev(
+                    out_box.data_ptr(), box_off.data_ptr(), N, B, 2, 0.98, out_high.data_ptr(), None, sp), "k2")),
+                "k9_suppress": (32 * B + 4 * (N + 1) + 5 * B, lambda: ck(L.dyd_suppress_boxes_dev(
+                    out_box.data_ptr(), box_off.data_ptr(), N, B, None, 0.98, keep.data_ptr(), partner.data_ptr(), sp), "k9")),
+                "k18_compare": (k18_bytes, k18(0)),
+                "k18_compare by_label": (k18_bytes, k18(1))}
+        res = {}
+        for rnd in range(2):
+            for nm, (_, fn) in legs.items():
+                res.setdefault(nm, []).append(timeit(fn))
+        for nm, (nbytes, _) in legs.items():
+            med = float(np.median([r[0] for r in res[nm]])); mn = min(r[1] for r in res[nm])
+            report(nm, nbytes, med, mn, rows_per_s=round(N / med * 1e3))
+        legs["k18_compare"][1]()
+        torch.cuda.synchronize()
+        print(json.dumps({"kernel": "k18_compare", "a_boxes": B, "b_boxes": Bb, "matched": int((b_match >= 0).sum().item()),
+                          "agree": int(conf[:20, :20].diagonal().sum().item()), "missing": int(conf[:20, 20].sum().item()),
+                          "extra": int(conf[20, :20].sum().item())}), flush=True)
 
     if "k12" in only:
         k12_bytes = 16 * P + 4 * (B + 1) + 48 * B + 4 * (N + 1) + N
