@@ -85,6 +85,8 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dyd_json_emit_repaired": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_void_p)]),
+    "dyd_json_emit_simplified": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_void_p)]),
     "dyd_json_scan_named_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "dyd_json_scan_named_boxes_v": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "dyd_scan_names": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
@@ -141,6 +143,9 @@ SIGNATURES = {
     "dyd_audit_polygons_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dyd_simplify_polygons": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dyd_simplify_polygons_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "dyd_coco_annotations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                                        C.POINTER(C.c_int64)]),
@@ -456,6 +461,21 @@ def audit_polygons(xy, pt_off, row_off, cls, width, height, size_status, n_class
                                    _ptr(height), _ptr(size_status), n, n_classes, min_area, _ptr(cat), _ptr(dfc), _ptr(area),
                                    _ptr(cc), _ptr(hist)), "dyd_audit_polygons")
     return cat, dfc, area, cc, hist
+
+
+def simplify_polygons(xy, pt_off, tolerance: float = 1.0):
+    """K19 over host arrays -> (keep u8 [P], action u8 [B], kept i32 [B], dev2 f64 [B]).  Rule and codes: include/dyd.h."""
+    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1)
+    pt_off = np.ascontiguousarray(pt_off, dtype=np.int32)
+    nb = len(pt_off) - 1
+    if nb < 0 or (nb and 2 * int(pt_off[-1]) != len(xy)):
+        raise ValueError("pt_off must hold one entry per polygon plus one and end at the number of points")
+    keep, action = np.zeros(len(xy) // 2, np.uint8), np.zeros(nb, np.uint8)
+    kept, dev2 = np.zeros(nb, np.int32), np.zeros(nb, np.float64)
+    check(lib().dyd_simplify_polygons(_ptr(xy) if xy.size else None, _ptr(pt_off), nb, float(tolerance),
+                                      _ptr(keep) if keep.size else None, _ptr(action), _ptr(kept), _ptr(dev2)),
+          "dyd_simplify_polygons")
+    return keep, action, kept, dev2
 
 
 COCO_SEGMENTATION = 1   # K16 flags bit 0: print the polygon into "segmentation" (clear: the detect flavour, an empty list)

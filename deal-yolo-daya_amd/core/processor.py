@@ -3248,37 +3248,49 @@ def _poly_min_area(min_area) -> float:
     return v
 
 
-def _poly_chunk(cells) -> tuple:
-    """one chunk of cells -> (row_off int64 [n+1], xy f64 [2P], pt_off int32 [B+1], obj int32 [B], cls int32 [B] (-1: the name
-    is no str), names, number of cells scanned by CPython): the native scan's polygons with the CPython ones of the irregular
-    cells (flatten.seg_cell_polygons) spliced in at their rows (_splice_items), and their points"""
+def _poly_chunk_open(cells) -> tuple:
+    """one chunk of cells -> (scan, row_off int64 [n+1], xy f64 [2P], pt_off int32 [B+1], obj int32 [B], cls int32 [B] (-1: the
+    name is no str), names, odd_names, irregular, dest, pdest): the native scan's polygons with the CPython ones of the irregular
+    cells (flatten.seg_cell_polygons) spliced in at their rows (_splice_items), and their points.  scan: the NamedPolygonScan,
+    still open (None without one): the caller closes it; dest / pdest: native polygon -> polygon and native point -> point
+    (None when nothing was spliced)"""
     scan = _native_scan(_nj.scan_named_polygons, cells)
     try:
-        row_off, dest, obj, cls, names, _, irregular, py = _splice_items(cells, scan, _fl.seg_cell_polygons, "polygons")
+        row_off, dest, obj, cls, names, odd_names, irregular, py = _splice_items(cells, scan, _fl.seg_cell_polygons, "polygons")
         xy, pt_off = (scan.xy, scan.pt_off) if scan is not None else (np.zeros(0), np.zeros(1, np.int32))
-    finally:
+        pdest = None
+        if py:
+            nb = int(row_off[-1])
+            nat_npts = np.diff(pt_off.astype(np.int64))
+            npts = np.zeros(nb, np.int64)
+            npts[dest] = nat_npts
+            for i, polys in py.items():
+                npts[row_off[i]:row_off[i] + len(polys)] = [len(pts) for _, _, pts in polys]
+            off = np.zeros(nb + 1, np.int64)
+            np.cumsum(npts, out=off[1:])
+            if off[-1] >= (1 << 31):
+                raise ValueError("a chunk holds 2^31 points or more")
+            xy2 = np.empty((int(off[-1]), 2))
+            pdest = np.repeat(off[dest] - pt_off[:-1].astype(np.int64), nat_npts) + np.arange(len(xy) // 2, dtype=np.int64)
+            xy2[pdest] = np.asarray(xy, np.float64).reshape(-1, 2)
+            for i, polys in py.items():
+                p = int(row_off[i])
+                for k, (_, _, pts) in enumerate(polys):
+                    if pts:
+                        xy2[off[p + k]:off[p + k + 1]] = [(_audit_number(x), _audit_number(y)) for x, y in pts]
+            xy, pt_off = xy2.reshape(-1), off.astype(np.int32)
+    except BaseException:
         if scan is not None:
             scan.close()
-    if py:
-        nb = int(row_off[-1])
-        nat_npts = np.diff(pt_off.astype(np.int64))
-        npts = np.zeros(nb, np.int64)
-        npts[dest] = nat_npts
-        for i, polys in py.items():
-            npts[row_off[i]:row_off[i] + len(polys)] = [len(pts) for _, _, pts in polys]
-        off = np.zeros(nb + 1, np.int64)
-        np.cumsum(npts, out=off[1:])
-        if off[-1] >= (1 << 31):
-            raise ValueError("a chunk holds 2^31 points or more")
-        xy2 = np.empty((int(off[-1]), 2))
-        pdest = np.repeat(off[dest] - pt_off[:-1].astype(np.int64), nat_npts) + np.arange(len(xy) // 2, dtype=np.int64)
-        xy2[pdest] = np.asarray(xy, np.float64).reshape(-1, 2)
-        for i, polys in py.items():
-            p = int(row_off[i])
-            for k, (_, _, pts) in enumerate(polys):
-                if pts:
-                    xy2[off[p + k]:off[p + k + 1]] = [(_audit_number(x), _audit_number(y)) for x, y in pts]
-        xy, pt_off = xy2.reshape(-1), off.astype(np.int32)
+        raise
+    return scan, row_off, xy, pt_off, obj, cls, names, odd_names, irregular, dest, pdest
+
+
+def _poly_chunk(cells) -> tuple:
+    """_poly_chunk_open with the scan closed -> (row_off, xy, pt_off, obj, cls, names, number of cells scanned by CPython)"""
+    scan, row_off, xy, pt_off, obj, cls, names, _, irregular, _, _ = _poly_chunk_open(cells)
+    if scan is not None:
+        scan.close()
     return row_off, xy, pt_off, obj, cls, names, len(irregular)
 
 
@@ -3376,6 +3388,190 @@ def audit_polygons_csv(input_csv_path, output_dir, json_col: str = ANNOTATION_CO
     audit = _csv_route("polygon_audit", input_csv_path, json_col, native,
                        lambda df: audit_polygons_frame(df, json_col, min_area=min_area, backend=backend))
     return None if audit is None else {**audit.totals, "paths": _write_poly_audit(audit, output_dir)}
+
+
+# =============================================================================== f7b'  polygon simplification
+# The fix the polygon audit points at (hist_vertices' long tail, duplicate_vertices), applied to the polygon column before any
+# export reads it: Douglas-Peucker with segment distance on every polygon of the audit (_poly_chunk_open), decided by K19
+# (csrc/k19_simplify.hip, rule in include/dyd.h and DESIGN §5q) in IEEE f64.  Only vertices are removed, so every coordinate
+# that stays is spelled from the value already in the cell.  A cell is re-spelled only when a polygon of it loses a vertex:
+# json.dumps(doc, ensure_ascii=False) with those ptList entries left out.  Every other cell is returned as the same object.
+# Native scan -> K19 -> native emit (NamedPolygonScan.emit_simplified); the cells the scanner leaves to CPython are scanned by
+# flatten.seg_cell_polygons, spliced into the same K19 launch and re-spelled by flatten.simplify_cell.
+SIMPLIFY_ACTIONS = ("kept", "simplified", "bad_coords", "too_few_points")           # K19 codes 0..3
+_SIMPLIFY_LIMIT = 2.0 ** 43
+
+
+def _simplify_tolerance(tolerance) -> float:
+    msg = f"tolerance must be a finite number >= 0 and < 2^43, got {tolerance!r}"
+    if isinstance(tolerance, bool) or not isinstance(tolerance, _NUMBER_TYPES):
+        raise ValueError(msg)
+    try:
+        v = float(tolerance)
+    except OverflowError:
+        raise ValueError(msg) from None
+    if not (np.isfinite(v) and 0.0 <= v < _SIMPLIFY_LIMIT):
+        raise ValueError(msg)
+    return v
+
+
+class _SimplifyTotals:
+    """class-keyed counts over the chunks (one per action, points in, points out), changes per chunk, totals"""
+
+    def __init__(self):
+        self.classes = _ClassSums((len(SIMPLIFY_ACTIONS) + 2,))
+        self.changes = []
+        self.rows_changed = self.polygons = self.simplified = self.points = self.removed = self.python_cells = 0
+
+
+def _simplify_chunk(cells, be, acc: _SimplifyTotals, start: int, tol: float) -> tuple:
+    """one chunk of rows: polygon table (_poly_chunk_open) -> K19 -> emit -> (rows in the chunk, their new texts) as int64 and
+    object arrays; the class counts and the simplified polygons go to acc"""
+    scan, row_off, xy, pt_off, obj, cls, names, odd_names, irregular, dest, pdest = _poly_chunk_open(cells)
+    acc.python_cells += len(irregular)
+    try:
+        keep, action, kept, dev2 = be.simplify_polygons(xy, pt_off, tol)
+        keep, action = np.asarray(keep, np.uint8), np.asarray(action, np.uint8)
+        kept, dev2 = np.asarray(kept, np.int64), np.asarray(dev2, np.float64)
+        simp = action == 1
+        idx, strs, redo = np.zeros(0, np.int64), np.zeros(0, object), []
+        if scan is not None and scan.n_boxes and simp.any():
+            changed, strs = scan.emit_simplified(keep if pdest is None else keep[pdest])
+            idx = np.flatnonzero(changed == 1)
+            redo = np.flatnonzero(changed == 2).tolist()
+    finally:
+        if scan is not None:
+            scan.close()
+    off = pt_off.astype(np.int64)
+    npts = np.diff(off)
+    py_idx, py_strs = [], []
+    for i in redo + irregular:                           # decided by K19 above, re-spelled by CPython
+        b0, b1 = int(row_off[i]), int(row_off[i + 1])
+        if simp[b0:b1].any():
+            py_idx.append(i)
+            py_strs.append(_fl.simplify_cell(cells[i], {int(obj[b]): keep[off[b]:off[b + 1]].tolist()
+                                                        for b in range(b0, b1) if simp[b]}))
+    if py_idx:
+        idx = np.concatenate([idx, np.asarray(py_idx, np.int64)])
+        strs = np.concatenate([np.asarray(strs, object), np.fromiter(py_strs, object, len(py_strs))])
+    nc = len(names)
+    cl = np.asarray(cls, np.int64)
+    named = cl >= 0
+    counts = np.zeros((nc, len(SIMPLIFY_ACTIONS) + 2), np.int64)
+    if nc:
+        counts[:, :4] = np.bincount(cl[named] * 4 + action[named], minlength=4 * nc).reshape(nc, 4)
+        counts[:, 4] = np.bincount(cl[named], weights=npts[named], minlength=nc).astype(np.int64)
+        counts[:, 5] = np.bincount(cl[named], weights=kept[named], minlength=nc).astype(np.int64)
+    acc.classes.add(names, counts)
+    acc.polygons += len(action)
+    acc.points += int(npts.sum())
+    acc.rows_changed += len(idx)
+    sel = np.flatnonzero(simp)
+    if len(sel):
+        acc.simplified += len(sel)
+        acc.removed += int((npts[sel] - kept[sel]).sum())
+        name_arr = np.asarray(names + [None], object)    # class id -1 -> the trailing None, then the odd names
+        nm = name_arr[cl[sel]]
+        if odd_names:
+            pos = np.searchsorted(sel, np.fromiter(odd_names, np.int64, len(odd_names)))
+            for p, b in zip(pos.tolist(), odd_names):
+                if p < len(sel) and sel[p] == b:
+                    nm[p] = odd_names[b]
+        acc.changes.append((start + np.searchsorted(row_off, sel, side="right") - 1, np.asarray(obj, np.int64)[sel], nm,
+                            npts[sel], kept[sel], np.sqrt(dev2[sel])))
+    return idx, strs
+
+
+def _simplify_result(acc: _SimplifyTotals, n: int, sources, tol: float) -> tuple:
+    """-> (changes frame, per_class frame, totals)"""
+    changes = _parts_frame(acc.changes, (("row", np.int64), ("object", np.int64), ("name", object), ("points", np.int64),
+                                         ("kept", np.int64), ("max_deviation", np.float64)), sources)
+    classes, (cc,) = acc.classes.sorted()
+    per_class = pd.DataFrame({"class": pd.Series(classes, dtype=object), "polygons": cc[:, :4].sum(axis=1),
+                              **{k: cc[:, j] for j, k in enumerate(SIMPLIFY_ACTIONS)},
+                              "points_in": cc[:, 4], "points_out": cc[:, 5]})
+    totals = {"rows": n, "rows_changed": acc.rows_changed, "polygons": acc.polygons, "polygons_simplified": acc.simplified,
+              "points": acc.points, "points_removed": acc.removed, "python_cells": acc.python_cells, "tolerance": tol}
+    return changes, per_class, totals
+
+
+def _simplify_rows(cells, n, tol, be, sources, cells_of=None) -> tuple:
+    """-> ([(changed rows, their new texts) per chunk], changes frame, per_class frame, totals)"""
+    acc = _SimplifyTotals()
+    texts = []
+    for s0, _, chunk in _chunks(n, cells, cells_of):
+        idx, strs = _simplify_chunk(chunk, be, acc, s0, tol)
+        texts.append((s0 + idx, strs))
+    return (texts, *_simplify_result(acc, n, sources, tol))
+
+
+def _simplify_cells_array(cells, tolerance, backend, stats, sources) -> tuple:
+    """simplify_polygons_cells with the cells as an object array"""
+    tol = _simplify_tolerance(tolerance)
+    be = _step_backend(backend, "simplify_polygons")
+    cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
+    texts, changes, per_class, totals = _simplify_rows(cells, len(cells), tol, be, sources)
+    out = np.fromiter(cells, object, len(cells))         # the same objects; only the changed rows are replaced
+    for idx, strs in texts:
+        out[idx] = strs
+    if stats is not None:
+        stats.update(totals)
+    return out, changes, per_class
+
+
+def simplify_polygons_cells(cells, tolerance: float = 1.0, backend=None, stats: Optional[dict] = None, sources=None) -> tuple:
+    """Polygon simplification of the annotation cells of a table (see the section comment) -> (cells with only the changed ones
+    replaced, changes frame, per_class frame).  ``changes``: [source,] row, object, name, points, kept, max_deviation per
+    simplified polygon (max_deviation = the largest distance of a removed vertex from the segment that replaced it, <=
+    tolerance); ``per_class``: class, polygons, one count per action, points_in, points_out.  ``stats`` receives the totals."""
+    out, changes, per_class = _simplify_cells_array(cells, tolerance, backend, stats, sources)
+    return out.tolist(), changes, per_class
+
+
+def simplify_polygons_frame(df: pd.DataFrame, json_col: str = ANNOTATION_COL, tolerance: float = 1.0, backend=None,
+                            stats: Optional[dict] = None) -> tuple:
+    """Polygon simplification of a table's polygon column (before a polygon-first split and the segment, COCO and OBB exports)
+    -> (copy of df in which only json_col differs, changes, per_class).  changes["row"] is the position in df."""
+    cells = df[json_col].to_numpy()
+    sources = df["source"].to_numpy() if "source" in df.columns else None
+    cells, changes, per_class = _simplify_cells_array(cells, tolerance, backend, stats, sources)
+    out = df.copy()
+    if len(changes):
+        out[json_col] = pd.Series(cells, index=out.index, dtype=object)
+    return out, changes, per_class
+
+
+def simplify_polygons_csv(input_csv_path, output_csv_path="simplified_polygons.csv", changes_csv=None, classes_csv=None,
+                          json_col: str = ANNOTATION_COL, tolerance: float = 1.0, backend=None):
+    """CSV -> CSV twin of simplify_polygons_frame, in the box repair's conventions (repair_boxes_csv): read as utf-8-sig; a
+    read failure prints 读取失败：... and a missing column 错误：缺少必要列 ..., both returning None.  The output holds the
+    input's rows with json_col rewritten; `changes_csv` / `classes_csv` (optional) receive the two frames.  -> {"rows",
+    "rows_changed", "polygons", "polygons_simplified", "points", "points_removed", "python_cells", "tolerance", "output",
+    "changes_output", "classes_output"}"""
+    tol = _simplify_tolerance(tolerance)
+
+    def native(table):                                   # NotImplemented (nothing written) when the native writer declines
+        n, _, _, sources, cells_of = _table_rows(table, json_col)
+        texts, *res = _simplify_rows(None, n, tol, _step_backend(backend, "simplify_polygons"), sources, cells_of)
+        texts = {i: t for idx, strs in texts for i, t in zip(idx.tolist(), strs)}
+        return res if _csv_write_spliced(output_csv_path, table, json_col, texts) else NotImplemented
+
+    def pandas(df):
+        totals = {}
+        out, changes, per_class = simplify_polygons_frame(df, json_col, tolerance=tol, backend=backend, stats=totals)
+        Path(output_csv_path).parent.mkdir(parents=True, exist_ok=True)
+        out.to_csv(output_csv_path, index=False, encoding="utf-8-sig")
+        return changes, per_class, totals
+
+    res = _csv_route("simplify", input_csv_path, json_col, native, pandas)
+    if res is None:
+        return None
+    changes, per_class, totals = res
+    for path, frame in ((changes_csv, changes), (classes_csv, per_class)):
+        if path is not None:
+            Path(path).parent.mkdir(parents=True, exist_ok=True)
+            frame.to_csv(path, index=False, encoding="utf-8-sig")
+    return {**totals, "output": output_csv_path, "changes_output": changes_csv, "classes_output": classes_csv}
 
 
 # =============================================================================== f7c  COCO export

@@ -1957,6 +1957,173 @@ void emit_repaired_cell(Span cell, const std::vector<uint8_t> &mode, const std::
     out += '}';
 }
 
+// one "objects" element (p at '{') whose polygon.ptList loses the vertices with keep[v] == 0; the vertices are the ptList dicts
+// holding both "x" and "y", in order (the named-polygon scan's points), n_vert of them; every other entry stays
+void emit_simplified_object(Parser &ps, const uint8_t *keep, size_t n_vert, std::string &out) {
+    ++ps.p;
+    out += '{';
+    KeySet ks;
+    bool first = true;
+    size_t v = 0;
+    if (ps.peek() == '}') { ++ps.p; out += '}'; if (n_vert) ps.irregular(); return; }
+    while (true) {
+        ps.ws();
+        const Span k = ps.string_token();
+        ks.add(ps, k);
+        if (!first) out += ", ";
+        first = false;
+        ps.emit_string(out, k);
+        out += ": ";
+        ps.ws();
+        if (ps.p >= ps.end || *ps.p != ':') ps.bad();
+        ++ps.p;
+        if (Parser::span_is(k, "polygon") && ps.peek() == '{') {
+            ++ps.p;
+            out += '{';
+            KeySet pks;
+            bool pfirst = true;
+            if (ps.peek() == '}') {
+                ++ps.p;
+            } else {
+                while (true) {
+                    ps.ws();
+                    const Span pk = ps.string_token();
+                    pks.add(ps, pk);
+                    if (!pfirst) out += ", ";
+                    pfirst = false;
+                    ps.emit_string(out, pk);
+                    out += ": ";
+                    ps.ws();
+                    if (ps.p >= ps.end || *ps.p != ':') ps.bad();
+                    ++ps.p;
+                    if (Parser::span_is(pk, "ptList") && ps.peek() == '[') {
+                        ++ps.p;
+                        out += '[';
+                        bool qfirst = true;
+                        if (ps.peek() == ']') {
+                            ++ps.p;
+                        } else {
+                            while (true) {
+                                bool stays = true;
+                                if (ps.peek() == '{') {       // a vertex when it holds both keys: read ahead, then come back
+                                    const char *at = ps.p;
+                                    ++ps.p;
+                                    KeySet qks;
+                                    bool has_x = false, has_y = false;
+                                    if (ps.peek() == '}') {
+                                        ++ps.p;
+                                    } else {
+                                        while (true) {
+                                            ps.ws();
+                                            const Span qk = ps.string_token();
+                                            qks.add(ps, qk);
+                                            ps.ws();
+                                            if (ps.p >= ps.end || *ps.p != ':') ps.bad();
+                                            ++ps.p;
+                                            ps.value(nullptr);
+                                            if (Parser::span_is(qk, "x")) has_x = true;
+                                            else if (Parser::span_is(qk, "y")) has_y = true;
+                                            const char d = ps.peek();
+                                            if (d == ',') { ++ps.p; continue; }
+                                            if (d == '}') { ++ps.p; break; }
+                                            ps.bad();
+                                        }
+                                    }
+                                    if (has_x && has_y) {
+                                        if (v >= n_vert) ps.irregular();
+                                        stays = keep[v++] != 0;
+                                    }
+                                    if (stays) ps.p = at;
+                                }
+                                if (stays) {
+                                    if (!qfirst) out += ", ";
+                                    qfirst = false;
+                                    ps.value(&out);
+                                }
+                                const char d = ps.peek();
+                                if (d == ',') { ++ps.p; continue; }
+                                if (d == ']') { ++ps.p; break; }
+                                ps.bad();
+                            }
+                        }
+                        out += ']';
+                    } else {
+                        ps.value(&out);
+                    }
+                    const char d = ps.peek();
+                    if (d == ',') { ++ps.p; continue; }
+                    if (d == '}') { ++ps.p; break; }
+                    ps.bad();
+                }
+            }
+            out += '}';
+        } else {
+            ps.value(&out);
+        }
+        const char d = ps.peek();
+        if (d == ',') { ++ps.p; continue; }
+        if (d == '}') { ++ps.p; break; }
+        ps.bad();
+    }
+    if (v != n_vert) ps.irregular();          // not the points the scan saw: the caller re-spells the cell
+    out += '}';
+}
+
+// the whole document of one cell with the objects k that have keep[k] != nullptr simplified (emit_simplified_object)
+void emit_simplified_cell(Span cell, const std::vector<const uint8_t *> &keep, const std::vector<size_t> &n_vert, std::string &out) {
+    Parser ps{cell.b, cell.e};
+    ps.ws();
+    if (ps.p >= ps.end || *ps.p != '{') ps.irregular();
+    ++ps.p;
+    out += '{';
+    KeySet ks;
+    bool first = true;
+    if (ps.peek() == '}') { ++ps.p; out += '}'; return; }
+    while (true) {
+        ps.ws();
+        const Span k = ps.string_token();
+        ks.add(ps, k);
+        if (!first) out += ", ";
+        first = false;
+        ps.emit_string(out, k);
+        out += ": ";
+        ps.ws();
+        if (ps.p >= ps.end || *ps.p != ':') ps.bad();
+        ++ps.p;
+        if (Parser::span_is(k, "objects") && ps.peek() == '[') {
+            ++ps.p;
+            out += '[';
+            if (ps.peek() == ']') {
+                ++ps.p;
+            } else {
+                for (size_t ko = 0;; ++ko) {
+                    if (ko) out += ", ";
+                    if (ko < keep.size() && keep[ko]) {
+                        if (ps.peek() != '{') ps.irregular();
+                        emit_simplified_object(ps, keep[ko], n_vert[ko], out);
+                    } else {
+                        ps.value(&out);
+                    }
+                    const char d = ps.peek();
+                    if (d == ',') { ++ps.p; continue; }
+                    if (d == ']') { ++ps.p; break; }
+                    ps.bad();
+                }
+            }
+            out += ']';
+        } else {
+            ps.value(&out);
+        }
+        const char d = ps.peek();
+        if (d == ',') { ++ps.p; continue; }
+        if (d == '}') { ++ps.p; break; }
+        ps.bad();
+    }
+    ps.ws();
+    if (ps.p != ps.end) ps.bad();
+    out += '}';
+}
+
 }  // namespace
 
 extern "C" {
@@ -2018,6 +2185,36 @@ int dyd_json_emit_repaired(dyd_scan *h, const uint8_t *action_per_box, const dou
             clip[k] = box4 + 4 * (int64_t)b;
         }
         emit_repaired_cell(h->src.get(i), mode, clip, buf);
+        return true;
+    });
+}
+
+int dyd_json_emit_simplified(dyd_scan *h, const uint8_t *keep_per_point, int n_threads, uint8_t *out_changed, const uint8_t **out_text,
+                             const int64_t **out_off) {
+    if (!h || !out_changed || !out_text || !out_off) return DYD_ERR_INVALID;
+    const int64_t nb = h->cell_box_off.empty() ? 0 : h->cell_box_off[(size_t)h->n_cells];
+    if (nb > 0 && ((int64_t)h->box_obj.size() != nb || (int64_t)h->pt_off.size() != nb + 1)) return DYD_ERR_INVALID;
+    if (nb > 0 && h->pt_off[(size_t)nb] > 0 && !keep_per_point) return DYD_ERR_INVALID;
+    return emit_changed_cells(h, n_threads, out_changed, out_text, out_off,
+                              [&](int64_t i, std::string &buf, std::vector<uint8_t> &) {
+        const int32_t b0 = h->cell_box_off[(size_t)i], b1 = h->cell_box_off[(size_t)i + 1];
+        auto loses = [&](int32_t b) {
+            for (int64_t q = h->pt_off[(size_t)b]; q < h->pt_off[(size_t)b + 1]; ++q)
+                if (!keep_per_point[q]) return true;
+            return false;
+        };
+        bool any = false;
+        for (int32_t b = b0; b < b1 && !any; ++b) any = loses(b);
+        if (!any) return false;
+        std::vector<const uint8_t *> keep((size_t)h->box_obj[(size_t)b1 - 1] + 1, nullptr);
+        std::vector<size_t> n_vert(keep.size(), 0);
+        for (int32_t b = b0; b < b1; ++b) {
+            if (!loses(b)) continue;
+            const size_t k = (size_t)h->box_obj[(size_t)b];
+            keep[k] = keep_per_point + h->pt_off[(size_t)b];
+            n_vert[k] = (size_t)(h->pt_off[(size_t)b + 1] - h->pt_off[(size_t)b]);
+        }
+        emit_simplified_cell(h->src.get(i), keep, n_vert, buf);
         return true;
     });
 }

@@ -227,6 +227,8 @@ void set_k1_variant(int v);
 void set_k2_variant(int v);
 void set_k7_variant(int v);
 void set_k14_lane_edges(int v);
+void set_k19_lane_points(int v);
+void set_k19_lds_points(int v);
 void set_k6_variant(int v);
 void set_k4_capacity_shift(int v);
 void set_k8_band(int v);
@@ -446,6 +448,14 @@ int dyd_set_option(const char *key, int64_t value) {
     }
     if (!strcmp(key, "k14_lane_edges")) {   // K14's in-lane / wave tier threshold (A/B)
         set_k14_lane_edges((int)value);
+        return DYD_OK;
+    }
+    if (!strcmp(key, "k19_lane_points")) {   // K19's tier limits (tests reach every tier at small shapes; A/B)
+        set_k19_lane_points((int)value);
+        return DYD_OK;
+    }
+    if (!strcmp(key, "k19_lds_points")) {
+        set_k19_lds_points((int)value);
         return DYD_OK;
     }
     if (!strcmp(key, "k7_trace_ptr")) {   // device buffer of 8 x n_tiles u64 (0 = off)

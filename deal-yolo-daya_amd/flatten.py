@@ -333,6 +333,21 @@ def repair_cell(cell, decisions) -> str:
     return json.dumps(doc, ensure_ascii=False)
 
 
+def simplify_cell(cell, decisions) -> str:
+    """One cell re-spelled by the polygon simplify step from decisions already made (K19): ``decisions`` maps the index of an
+    object in "objects" to its keep list, one flag per vertex (the ptList dicts holding both "x" and "y", in order).  The ptList
+    entries of the vertices whose flag is 0 are left out; every other entry and every other object stays as json.loads read it.
+    -> json.dumps(doc, ensure_ascii=False)"""
+    doc = json.loads(cell)
+    objs = doc["objects"]
+    for k, keep in decisions.items():
+        poly = objs[k]["polygon"]
+        flags = iter(keep)
+        poly["ptList"] = [pt for pt in poly["ptList"]
+                          if not (isinstance(pt, dict) and "x" in pt and "y" in pt) or next(flags)]
+    return json.dumps(doc, ensure_ascii=False)
+
+
 # ------------------------------------------------------------------------------------------
 # a1 / a2  key column -> flat bytes + offsets for K3
 # ------------------------------------------------------------------------------------------

@@ -520,6 +520,26 @@ class NamedPolygonScan(NamedBoxScan):
     def emit_repaired(self, *args, **kwargs):
         raise TypeError("a polygon scan holds no boxes to repair")
 
+    def emit_simplified(self, keep: np.ndarray, n_threads: int = 0) -> tuple:
+        """K19's out_keep over the scan's points -> (changed u8 [n_cells]: 0 unchanged, 1 re-spelled here, 2 left to the caller;
+        str per changed == 1 cell, in order): the cells holding a polygon that loses a vertex, with those ptList entries left out."""
+        L = _native.load_library()
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if keep.size != int(self.pt_off[-1]):
+            raise ValueError("keep must hold one flag per point")
+        changed = np.zeros(self.n_cells, np.uint8)
+        tp, op = C.c_void_p(), C.c_void_p()
+        _native.check(L.dyd_json_emit_simplified(self._h, keep.ctypes.data if keep.size else None, n_threads,
+                                                 changed.ctypes.data if self.n_cells else None, C.byref(tp), C.byref(op)),
+                      "dyd_json_emit_simplified")
+        idx = np.flatnonzero(changed == 1)
+        if not len(idx):
+            return changed, np.empty(0, object)
+        off = _view(op.value, np.int64, self.n_cells + 1)
+        sub = np.append(off[idx], off[idx[-1] + 1])           # unchanged cells have no text: the changed ones are contiguous
+        text = _view(tp.value, np.uint8, max(int(off[-1]), 1))
+        return changed, strings_from_buffers(text, sub, None, n_threads)
+
 
 def scan_named_polygons(cells, n_threads: int = 0) -> NamedPolygonScan:
     """cells -> NamedPolygonScan (the polygon audit's objects).  Raises UnicodeEncodeError for a cell holding a lone surrogate

@@ -545,6 +545,41 @@ int dyd_yolo_obb_lines_dev(const double *xy, const int32_t *pt_off, const int32_
                            uint8_t *out_clamped, double *out_corners_or_null, uint8_t *out_text_or_null, int64_t text_cap,
                            int64_t *out_total, void *stream);
 
+/* ---- K19: polygon simplification — Douglas-Peucker with segment distance (the polygon simplify step) ----
+ * Polygons are K14's: every object the YOLO step keeps, V = (float(x), float(y)) of every ptList dict holding both keys, a
+ * value that is no number NaN.  m = len(V), e2 = tolerance * tolerance.  All arithmetic is IEEE f64, operation by operation,
+ * without contraction; the division is the correctly rounded one.  Only vertices are removed: no coordinate changes.
+ * Action, the first that applies:
+ *   2 bad_coords      a coordinate is not finite or |v| >= 2^43 (K13's bound): untouched;
+ *   3 too_few_points  m < 4: untouched (a triangle cannot lose a point, two points are a box);
+ *   otherwise the polygon is simplified as below: 1 simplified when some vertex is removed, else 0 kept.
+ * Anchors: vertex 0, and b = the k maximising (x_k-x_0)*(x_k-x_0) + (y_k-y_0)*(y_k-y_0), ties to the lowest k.  When that
+ * maximum is 0.0 (all points coincide) the polygon is kept, untouched.  The root segments are (0, b) and (b, m), index m
+ * standing for vertex 0 (the closing chain).
+ * Squared distance s(k; i, j), with P = V[i], Q = V[j mod m], dx = Q.x - P.x, dy = Q.y - P.y, ex = x_k - P.x, ey = y_k - P.y,
+ * L2 = dx*dx + dy*dy:
+ *   if L2 == 0.0, or t = dx*ex + dy*ey <= 0.0:  s = ex*ex + ey*ey
+ *   else if t >= L2:                            fx = x_k - Q.x, fy = y_k - Q.y, s = fx*fx + fy*fy
+ *   else                                        c = dx*ey - dy*ex, s = (c*c) / L2
+ * For a segment with interior vertices (i < k < j), k* = the interior k with the largest s, ties to the lowest k, s* = that s.
+ * The segment splits at k* when s* > e2: k* is kept and (i, k*), (k*, j) are treated the same way.  When neither root splits,
+ * the root with the larger s* splits at its k* anyway (ties to (0, b); a root without interior vertices does not count): no
+ * polygon drops below three vertices, and below that forced split the rule is plain Douglas-Peucker.  A split depends on its
+ * segment alone, so every evaluation order (recursive, or in rounds over all current segments) gives the same bits.
+ * Out: out_keep u8 [n_points] (1 = the vertex stays; all 1 for an untouched polygon), out_action u8 [n_polys], out_kept int32
+ * [n_polys] (vertices that stay), out_dev2 f64 [n_polys] = the largest s* over the segments that ended without a split, 0.0
+ * when nothing was removed: the largest squared distance of a removed vertex from the segment that replaced it, always <= e2.
+ * Work: O(m * depth) distance evaluations per polygon, depth = the depth of the splits: O(m log m) for a round outline, O(m^2)
+ * for a comb (like K14's pair test).  Polygons are tiered by m (a lane, a workgroup with the points in LDS, a workgroup
+ * streaming from HBM; dyd_set_option "k19_lane_points", "k19_lds_points"); any m is exact.
+ * xy [2*n_points] (16-B aligned), pt_off [n_polys+1].  tolerance finite, >= 0 and < 2^43, else DYD_ERR_INVALID.
+ * dyd_simplify_polygons     : host pointers (n_points = pt_off[n_polys]);
+ * dyd_simplify_polygons_dev : device pointers, enqueued on stream (NULL: the library's stream); every output is written. */
+int dyd_simplify_polygons(const double *xy, const int32_t *pt_off, int64_t n_polys, double tolerance, uint8_t *out_keep,
+                          uint8_t *out_action, int32_t *out_kept, double *out_dev2);
+int dyd_simplify_polygons_dev(const double *xy, const int32_t *pt_off, int64_t n_polys, int64_t n_points, double tolerance,
+                              uint8_t *out_keep, uint8_t *out_action, int32_t *out_kept, double *out_dev2, void *stream);
+
 /* ---- native flatten / emit (HOST code, multithreaded) ------------------------------
  * Schema-specialised JSON scanner + canonical re-emitter that replaces json.loads / json.dumps inside
  * parse_and_replace_ptlist (processor.py:262-281), extract_width_height (:285-292) and extract_boxes
@@ -634,6 +669,13 @@ int dyd_json_scan_named_polygons_v(const uint8_t *const *cell_ptr, const int64_t
  * offsets as dyd_json_emit_dropping. */
 int dyd_json_emit_repaired(dyd_scan *scan, const uint8_t *action_per_box, const double *box4, int n_threads,
                            uint8_t *out_changed, const uint8_t **out_text, const int64_t **out_off);
+/* Polygon simplification, after dyd_json_scan_named_polygons(_v): keep_per_point [n_points] is K19's out_keep over the scan's
+ * points.  For every cell holding a polygon with a vertex that is not kept, the whole document as json.dumps(...,
+ * ensure_ascii=False) writes it, with each such object's polygon.ptList lacking the entries of those vertices; ptList entries
+ * that are no vertices (non-dicts, dicts lacking "x" or "y") stay in place.  out_changed, text and offsets as
+ * dyd_json_emit_dropping (2: the caller re-spells the cell, flatten.simplify_cell). */
+int dyd_json_emit_simplified(dyd_scan *scan, const uint8_t *keep_per_point, int n_threads, uint8_t *out_changed,
+                             const uint8_t **out_text, const int64_t **out_off);
 /* The replace step and the IoU step in ONE native pass (processor.py:262-281 then :341-376; ui/pages/processing.py:580-598 runs them
  * back to back): cells as flat text + offsets, or as one (pointer, length) pair per cell (text == cell_off == NULL).  Every worker
  * thread holds one staging slot (dyd_stage_acquire) and takes its share of the cells through scan -> dyd_bbox_iou_fused_staged -> emit
@@ -768,7 +810,9 @@ void dyd_host_free(void *p);
  * 4 up to 32 boxes per image on average, 10 beyond, 6 / 9 for polygons of 20..48 points), 4 = wave kernel, 10 = its dense
  * instantiation (rows of 40..256 boxes sorted and swept), 6 / 9 = workgroup tilings, 1 = two launches;
  * "k2_variant": -1 by shape, 4 = the wave kernel's pair stage, 0..3 / 5 = tile kernels (2 / 3 / 5 with the f32 filter and the sweep);
- * "k14_lane_edges": the largest number of edges of U whose self-intersection test K14 runs in one lane (<= 0: the default). */
+ * "k14_lane_edges": the largest number of edges of U whose self-intersection test K14 runs in one lane (<= 0: the default);
+ * "k19_lane_points": the largest polygon (points) K19 simplifies in one lane (default 32, at most 64), "k19_lds_points": the
+ * largest one a workgroup stages in LDS (default and at most 1024; beyond it the points stream from HBM); <= 0: the default. */
 int dyd_set_option(const char *key, int64_t value);
 /* measurement aid: plain streaming kernel (mode 0 copy, 1 read-only, 2 write-only, 3-5 the same non-temporal, 16 B per
  * lane) used to record the box's HBM ceiling next to the kernels' achieved GB/s; modes 6 / 7 / 8: one 8-byte word per lane

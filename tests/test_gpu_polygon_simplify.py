@@ -1,0 +1,252 @@
+"""K19 (polygon simplification, csrc/k19_simplify.hip) through both C-ABI entries and simplify_polygons_csv, against the
+restatement in tests/polygon_simplify_ref.py.  Bit-exact: keep, action, kept and the bits of dev2.  Needs a real MI355X."""
+import json
+import math
+
+import numpy as np
+import pandas as pd
+import pytest
+
+import polygon_simplify_ref as R
+from deal_yolo_daya_amd.core import processor as P
+
+pytestmark = pytest.mark.gpu
+
+TOLERANCES = (0, 0.5, 1, 2.5, 7, 100)
+LANE_POINTS, LDS_POINTS = 32, 1024                     # K19_LANE_POINTS, K19_LDS_POINTS: the default tier limits
+
+
+def random_table(rng, n_rows, max_polys=6, max_pts=45):
+    """K14's generator style: small integer grids (repeats, collinear runs, coincident points) with special values; a few
+    polygons of some hundred points as the tail"""
+    xy, pt_off = [], [0]
+    for _ in range(n_rows):
+        for _ in range(int(rng.integers(0, max_polys + 1))):
+            n = int(rng.integers(0, max_pts + 1)) if rng.random() < 0.3 else int(rng.integers(0, 9))
+            if rng.random() < 0.004:
+                n = int(rng.integers(100, 400))
+            span = rng.choice([3, 10, 30, 60])
+            pts = rng.integers(-5, span, size=(n, 2)).astype(np.float64)
+            if n and rng.random() < 0.3:
+                j = rng.integers(0, n)
+                pts[j] = pts[j - 1]                                       # a repeat (cyclic)
+            if n and rng.random() < 0.1:
+                pts[-1] = pts[0]                                          # a closing repeat
+            if n > 3 and rng.random() < 0.1:
+                j = int(rng.integers(0, n - 3))
+                pts[j:j + 4, 1] = pts[j, 1]                               # a run on one line
+            if n and rng.random() < 0.03:
+                pts[:] = pts[0]                                           # all points coincide
+            if n and rng.random() < 0.08:
+                pts[rng.integers(0, n), rng.integers(0, 2)] = rng.choice([np.nan, np.inf, -np.inf, 2.0 ** 43, -0.0])
+            xy.append(pts.reshape(-1))
+            pt_off.append(pt_off[-1] + n)
+    xy = np.concatenate(xy) if xy else np.zeros(0)
+    return xy, np.asarray(pt_off, np.int32)
+
+
+def same(got, want):
+    for g, w, what in zip(got[:3], want[:3], ("keep", "action", "kept")):
+        assert np.array_equal(g, w), what
+    assert np.array_equal(np.asarray(got[3]).view(np.uint64), np.asarray(want[3]).view(np.uint64)), "dev2"
+
+
+def run_dev(xy, pt_off, tol, offset=1):
+    """the _dev entry on torch tensors, every output at an odd offset inside a guarded buffer"""
+    import torch
+    from deal_yolo_daya_amd import _native
+
+    dev = torch.device("cuda", 0)
+    xy = np.ascontiguousarray(xy, np.float64).reshape(-1)
+    xy_buf = torch.zeros(len(xy) + 4, dtype=torch.float64, device=dev)
+    xy_buf[2:2 + len(xy)] = torch.from_numpy(xy).to(dev)                  # 16-B aligned, not at the allocation's start
+    pt = torch.from_numpy(np.ascontiguousarray(pt_off, np.int32)).to(dev)
+    nb, npnt = len(pt_off) - 1, len(xy) // 2
+    guard = 0xA5
+    keep = torch.full((npnt + 2 * offset,), guard, dtype=torch.uint8, device=dev)
+    act = torch.full((nb + 2 * offset,), guard, dtype=torch.uint8, device=dev)
+    kept = torch.full((nb + 2 * offset,), -7, dtype=torch.int32, device=dev)
+    dev2 = torch.full((nb + 2 * offset,), -7.0, dtype=torch.float64, device=dev)
+    L, sp = _native.lib(), torch.cuda.current_stream().cuda_stream
+    _native.check(L.dyd_simplify_polygons_dev(xy_buf.data_ptr() + 16, pt.data_ptr(), nb, npnt, float(tol),
+                                              keep.data_ptr() + offset, act.data_ptr() + offset, kept.data_ptr() + 4 * offset,
+                                              dev2.data_ptr() + 8 * offset, sp), "dyd_simplify_polygons_dev")
+    torch.cuda.synchronize()
+    out = [a.cpu().numpy() for a in (keep, act, kept, dev2)]
+    for a, fill in zip(out, (guard, guard, -7, -7.0)):
+        assert (a[:offset] == fill).all() and (a[len(a) - offset:] == fill).all(), "write outside the outputs"
+    return tuple(a[offset:len(a) - offset] for a in out)
+
+
+def both(native, xy, pt_off, tol, want=None):
+    """both entries against the restatement -> the restatement's answer"""
+    want = R.simplify_arrays(xy, pt_off, tol) if want is None else want
+    same(native.simplify_polygons(xy, pt_off, tol), want)
+    same(run_dev(xy, pt_off, tol), want)
+    return want
+
+
+def forced(xy, pt_off, want, tol):
+    """polygons whose roots both stay within the tolerance: the forced split happened"""
+    n, e2 = 0, tol * tol
+    pts = np.asarray(xy).reshape(-1, 2)
+    for p in np.flatnonzero(want[1] == 1).tolist():
+        V = [tuple(v) for v in pts[pt_off[p]:pt_off[p + 1]].tolist()]
+        b = R._anchor(V)[1]
+        s = [R.farthest(V, 0, b)[0], R.farthest(V, b, len(V))[0]]
+        n += all(v is None or v <= e2 for v in s)
+    return n
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_random_tables(native, seed):
+    xy, pt_off = random_table(np.random.default_rng(seed), 700)
+    actions, n_forced = set(), 0
+    for tol in TOLERANCES:
+        want = both(native, xy, pt_off, tol)
+        actions |= set(want[1].tolist())
+        n_forced += forced(xy, pt_off, want, tol)
+        assert (want[3] <= tol * tol).all()
+    assert actions == {0, 1, 2, 3} and n_forced > 0
+    assert (np.diff(pt_off) > LANE_POINTS).any()
+
+
+def _ring(rng, m, r=40.0):
+    """m vertices round a circle, rounded to the integer grid: repeats and collinear runs when m is large against r"""
+    th = 2 * np.pi * np.arange(m) / m + rng.random()
+    pts = np.stack([np.round(r * np.cos(th) + rng.integers(-1, 2, m)), np.round(r * np.sin(th) + rng.integers(-1, 2, m))], 1)
+    return pts.astype(np.float64)
+
+
+def _set_tiers(native, lane, lds):
+    native.check(native.lib().dyd_set_option(b"k19_lane_points", lane), "opt")
+    native.check(native.lib().dyd_set_option(b"k19_lds_points", lds), "opt")
+
+
+TIER_SETTINGS = [(0, 0), (8, 64), (64, 8), (8, 8), (64, 64), (8, 0), (64, 0)]
+
+
+def test_tier_limits(native):
+    rng = np.random.default_rng(11)
+    sizes = [lim + d for lim in (8, 64, LANE_POINTS, LDS_POINTS) for d in (-1, 0, 1)] + [3, 4, 5]
+    polys = [_ring(rng, m, r) for m in sizes for r in (6.0, 40.0)]
+    bad = _ring(rng, 65)
+    bad[40, 1] = np.nan                                                    # bad_coords decided by a block tier
+    polys += [bad, np.full((70, 2), 3.0)]                                  # and all points coincident there
+    xy = np.concatenate([p.reshape(-1) for p in polys])
+    pt_off = np.concatenate([[0], np.cumsum([len(p) for p in polys])]).astype(np.int32)
+    rxy, rpt = random_table(np.random.default_rng(12), 300, max_pts=90)
+    want = {tol: (R.simplify_arrays(xy, pt_off, tol), R.simplify_arrays(rxy, rpt, tol)) for tol in (0, 1, 7)}
+    assert {0, 1, 2} <= set(want[1][0][1].tolist())
+    try:
+        for lane, lds in TIER_SETTINGS:
+            _set_tiers(native, lane, lds)
+            for tol, (w_sizes, w_random) in want.items():
+                both(native, xy, pt_off, tol, w_sizes)
+                both(native, rxy, rpt, tol, w_random)
+    finally:
+        _set_tiers(native, 0, 0)
+
+
+def _comb(n_teeth):
+    """teeth of growing height on a base line: every split peels one or two vertices off the end, so the depth is ~m"""
+    pts = [(0.0, 0.0)]
+    for k in range(n_teeth):
+        pts += [(k + 0.5, 1.0 + 0.01 * k), (k + 1.0, 0.0)]
+    pts.append((float(n_teeth), -1.0))
+    return np.asarray(pts)
+
+
+def test_comb_of_2000_points_has_no_fixed_depth(native):
+    comb = _comb(999)
+    assert len(comb) == 2000
+    xy, pt_off = comb.reshape(-1), np.asarray([0, len(comb)], np.int32)
+    V = [tuple(p) for p in comb.tolist()]
+    want = R.simplify_arrays(xy, pt_off, 3.0)
+    assert R.simplify_rounds(V, 3.0)[:3] == (want[0].tolist(), 1, int(want[2][0])) and R.LAST_ROUNDS > 400
+    try:
+        for lane, lds in ((0, 0), (8, 8)):                                # the HBM tier by default; forced there as well
+            _set_tiers(native, lane, lds)
+            both(native, xy, pt_off, 3.0, want)
+        small = _comb(400)                                                # 802 points: the LDS tier
+        _set_tiers(native, 0, 0)
+        both(native, small.reshape(-1), np.asarray([0, len(small)], np.int32), 3.0)
+    finally:
+        _set_tiers(native, 0, 0)
+
+
+def test_circle_of_100000_points(native):
+    th = 2 * np.pi * np.arange(100_000) / 100_000
+    pts = np.stack([5000.0 + 5000.0 * np.cos(th), 5000.0 + 5000.0 * np.sin(th)], 1)
+    want = both(native, pts.reshape(-1), np.asarray([0, len(pts)], np.int32), 1.0)
+    assert want[1][0] == 1 and 100 < want[2][0] < 1000 and 0 < want[3][0] <= 1.0
+
+
+def test_long_polygons_first_and_last(native):
+    rng = np.random.default_rng(5)
+    polys = [_ring(rng, 3000, 900.0)] + [_ring(rng, int(m)) for m in rng.integers(0, 40, 500)] + [_ring(rng, 1500, 300.0)]
+    xy = np.concatenate([p.reshape(-1) for p in polys])
+    pt_off = np.concatenate([[0], np.cumsum([len(p) for p in polys])]).astype(np.int32)
+    want = both(native, xy, pt_off, 2.5)
+    assert want[1][0] == 1 and want[1][-1] == 1
+
+
+def test_empty_tables_and_empty_polygons(native):
+    none = (np.zeros(0, np.uint8), np.zeros(0, np.uint8), np.zeros(0, np.int32), np.zeros(0))
+    same(native.simplify_polygons(np.zeros(0), np.zeros(1, np.int32), 1.0), none)
+    same(run_dev(np.zeros(0), np.zeros(1, np.int32), 1.0), none)
+    both(native, np.zeros(0), np.zeros(4, np.int32), 1.0)                 # three polygons without points
+    rng = np.random.default_rng(2)
+    polys = [np.zeros((0, 2)), _ring(rng, 30), np.zeros((0, 2)), np.zeros((0, 2)), _ring(rng, 70), np.zeros((0, 2)),
+             _ring(rng, 1100, 300.0), np.zeros((0, 2))]
+    xy = np.concatenate([p.reshape(-1) for p in polys])
+    pt_off = np.concatenate([[0], np.cumsum([len(p) for p in polys])]).astype(np.int32)
+    want = both(native, xy, pt_off, 1.0)
+    assert want[1].tolist() == [3, 1, 3, 3, 1, 3, 1, 3]
+    # rows without polygons through the step
+    cells = [None, "{}", json.dumps({"objects": []}), json.dumps({"objects": [{"name": "a"}]})]
+    out, ch, pc = P.simplify_polygons_cells(cells, 1.0)
+    assert all(a is b for a, b in zip(out, cells)) and len(ch) == 0 and len(pc) == 0
+
+
+def test_invalid_tolerance(native):
+    from deal_yolo_daya_amd import _native
+
+    for tol in (-1.0, math.nan, math.inf, 2.0 ** 43):
+        with pytest.raises(Exception, match="tolerance"):
+            native.simplify_polygons(np.zeros(8), np.asarray([0, 4], np.int32), tol)
+        rc = _native.lib().dyd_simplify_polygons_dev(None, None, 0, 0, tol, None, None, None, None, None)
+        assert rc != 0
+
+
+def test_simplify_polygons_csv_end_to_end(native, tmp_path):
+    rng = np.random.default_rng(8)
+    cells = []
+    for i in range(300):
+        pts = _ring(rng, int(rng.integers(3, 120)), float(rng.choice([8.0, 40.0]))) + 100.0
+        cells.append(json.dumps({"objects": [{"name": "a", "polygon": {"ptList": [{"x": x, "y": y} for x, y in pts.tolist()]}}]}))
+    df = pd.DataFrame({"source": [f"s{i}.jpg" for i in range(len(cells))], P.ANNOTATION_COL: cells, "width": 640, "height": 480})
+    src = tmp_path / "in.csv"
+    df.to_csv(src, index=False, encoding="utf-8-sig")
+    res = P.simplify_polygons_csv(src, tmp_path / "out.csv", tmp_path / "ch.csv", tmp_path / "cl.csv", tolerance=1.0)
+    ref = R.simplify_table(cells, 1.0)
+    back = pd.read_csv(tmp_path / "out.csv", encoding="utf-8-sig")
+    assert back[P.ANNOTATION_COL].tolist() == ref["cells"]
+    for k, v in ref["totals"].items():
+        assert res[k] == v, k
+    # the file spells each float with repr; pandas' default parser may be an ulp off, so read it back exactly
+    ch = pd.read_csv(tmp_path / "ch.csv", encoding="utf-8-sig", float_precision="round_trip")
+    assert list(zip(ch["row"], ch["object"], ch["points"], ch["kept"])) == [(c[0], c[1], c[3], c[4]) for c in ref["changes"]]
+    want_dev = np.asarray([c[5] for c in ref["changes"]], np.float64)
+    assert np.array_equal(ch["max_deviation"].to_numpy(np.float64).view(np.uint64), want_dev.view(np.uint64))
+    assert res["polygons_simplified"] > 100
+    # the segment step on both tables: what was written is written, with no more vertices
+    n = len(cells)
+    args = (["a"] * n, [0] * n, [640] * n, [480] * n)
+    st0, st1 = {}, {}
+    before, _ = P.yolo_seg_label_texts(cells, *args, stats=st0)
+    after, _ = P.yolo_seg_label_texts(back[P.ANNOTATION_COL].tolist(), *args, stats=st1)
+    assert st0["written"] > 250 and st1["written"] >= st0["written"]
+    for a, b in zip(before, after):
+        if a is not None:
+            assert b is not None and len(b.split()) <= len(a.split())

@@ -3,7 +3,7 @@
 interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant.
 
     python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k18: box comparison beside K2 and K9; k13: segmentation lines beside K7;
-     k14: polygon audit; k14tier: its in-lane / wave threshold; k16: COCO annotation objects beside K13; k17: oriented-box lines beside K13)
+     k14: polygon audit; k14tier: its in-lane / wave threshold; simplify: polygon simplification (K19) beside K14 on rings of 8, 64 and 1024 points; k16: COCO annotation objects beside K13; k17: oriented-box lines beside K13)
 """
 import argparse
 import json
@@ -697,6 +697,45 @@ def main():
                        selfx=int(cc[:, 9].sum()))
             del xl
         ck(L.dyd_set_option(b"k14_lane_edges", 0), "opt")
+    if "simplify" in only:
+        # K19 beside K14 (which reads the same bytes) on rings of m jittered vertices, 2^24 points per table, tolerance 1
+        nc, total_pts = 20, 1 << 24
+        g = torch.Generator(device=dev).manual_seed(19)
+        for m in (8, 64, 1024):
+            nl = total_pts // m
+            th = torch.arange(m, dtype=torch.float64, device=dev) * (2 * np.pi / m)
+            rad = 400.0 + 1.4 * (torch.rand((nl, m), generator=g, device=dev, dtype=torch.float64) - 0.5)
+            xl = torch.stack([500.0 + rad * torch.cos(th), 500.0 + rad * torch.sin(th)], 2).reshape(-1, 2).contiguous()
+            del rad
+            one = torch.arange(nl + 1, dtype=torch.int32, device=dev)
+            ptl = (one * m).contiguous()
+            keep = torch.empty(nl * m, dtype=torch.uint8, device=dev); act = torch.empty(nl, dtype=torch.uint8, device=dev)
+            kept = torch.empty(nl, dtype=torch.int32, device=dev); dev2 = torch.empty(nl, dtype=torch.float64, device=dev)
+            cat = torch.empty(nl, dtype=torch.uint8, device=dev); dfc = torch.empty(nl, dtype=torch.uint8, device=dev)
+            area = torch.empty(nl, dtype=torch.float64, device=dev)
+            cc = torch.empty((nc, 14), dtype=torch.int64, device=dev); hist = torch.empty((nc, 11), dtype=torch.int64, device=dev)
+            w = torch.full((nl,), 1920.0, dtype=torch.float64, device=dev); h = torch.full((nl,), 1080.0, dtype=torch.float64, device=dev)
+            st = torch.zeros(nl, dtype=torch.uint8, device=dev)
+            cls = (torch.arange(nl, device=dev, dtype=torch.int32) % nc).contiguous()
+            a19 = (xl.data_ptr(), ptl.data_ptr(), nl, nl * m, 1.0, keep.data_ptr(), act.data_ptr(), kept.data_ptr(), dev2.data_ptr(), sp)
+            a14 = (xl.data_ptr(), ptl.data_ptr(), one.data_ptr(), cls.data_ptr(), w.data_ptr(), h.data_ptr(), st.data_ptr(), nl, nl,
+                   nl * m, nc, 1.0, cat.data_ptr(), dfc.data_ptr(), area.data_ptr(), cc.data_ptr(), hist.data_ptr(), sp)
+            res = {}
+            for rnd in range(2):                      # interleaved rounds
+                res.setdefault("k19", []).append(timeit(lambda: ck(L.dyd_simplify_polygons_dev(*a19), "k19"), iters=5))
+                res.setdefault("k14", []).append(timeit(lambda: ck(L.dyd_audit_polygons_dev(*a14), "k14"), iters=5))
+            nbytes = 16 * nl * m + 4 * (nl + 1) + nl * m + 13 * nl
+            med19, mn19 = min(res["k19"])
+            med14, mn14 = min(res["k14"])
+            report(f"k14_audit_polygons_ring{m}", nbytes, med14, mn14, polygons=nl, vertices=m)
+            if m == 64:                               # the same table with the lane tier raised to take it (default: LDS tier)
+                ck(L.dyd_set_option(b"k19_lane_points", 64), "opt")
+                medl, mnl = timeit(lambda: ck(L.dyd_simplify_polygons_dev(*a19), "k19"), iters=5)
+                ck(L.dyd_set_option(b"k19_lane_points", 0), "opt")
+                report("k19_simplify_polygons_ring64_in_lane", nbytes, medl, mnl, polygons=nl, vertices=m)
+            report(f"k19_simplify_polygons_ring{m}", nbytes, med19, mn19, polygons=nl, vertices=m, tolerance=1.0,
+                   kept_points=int(kept.sum().item()), simplified=int((act == 1).sum().item()), ms_vs_k14=round(med19 / med14, 3))
+            del xl, keep
     if "k7mix" in only:
         # where the box-tiled kernel overtakes the row kernels: rows of one box with a share of two-box rows mixed in
         import ctypes as C
