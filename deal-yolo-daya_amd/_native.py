@@ -146,6 +146,15 @@ SIGNATURES = {
     "dyd_simplify_polygons": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dyd_simplify_polygons_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dyd_yolo_tile_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                      C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "dyd_yolo_tile_lines_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int32,
+                                          C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
+                                          C.POINTER(C.c_int64), C.c_void_p]),
     "dyd_coco_annotations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                                        C.POINTER(C.c_int64)]),
@@ -494,6 +503,32 @@ def coco_annotations(xy, pt_off, row_off, cat_id, width, height, size_status, im
                                      int(flags), _ptr(action) if nb else None, _ptr(area) if nb else None, _ptr(kept), C.byref(text),
                                      C.byref(total)), "dyd_coco_annotations")
     return action, area, kept, _take_text(text, total)
+
+
+def yolo_tile_lines(xy, pt_off, row_off, cls, width, height, tile_w: int, tile_h: int, step_x: int, step_y: int,
+                    min_visibility: float = 0.1, mode: int = 0, max_tiles_per_row: int = 4096):
+    """K20 over host arrays -> (row_status u8 [n], tile_off i64 [n+1], tile_line_count i32 [T], text_off i64 [T+1], action u8 [B],
+    tiles_written / tiles_cut / tiles_dropped i32 [B], text bytes).  mode 0 segment, 1 detect.  Rule and codes: include/dyd.h."""
+    from .flatten import tile_grid
+
+    xy, pt_off, row_off, width, height, _, cls, n, nb = _poly_table(xy, pt_off, row_off, width, height,   # no row column of its own
+                                                                    ("width", width, np.float64), ("cls", cls, np.int32))
+    args = tuple(int(v) for v in (tile_w, tile_h, step_x, step_y))
+    T = 0
+    if n and all(1 <= v <= 1 << 20 for v in args) and 1 <= int(max_tiles_per_row) <= 1 << 20:   # else the entry rejects the call
+        _, nx, ny = tile_grid(width, height, *args, int(max_tiles_per_row))
+        T = int((nx * ny).sum())
+    status, tile_off = np.zeros(n, np.uint8), np.zeros(n + 1, np.int64)
+    lines, text_off = np.zeros(T, np.int32), np.zeros(T + 1, np.int64)
+    action = np.zeros(nb, np.uint8)
+    written, cut, dropped = np.zeros(nb, np.int32), np.zeros(nb, np.int32), np.zeros(nb, np.int32)
+    text, total, n_tiles = C.c_void_p(), C.c_int64(), C.c_int64()
+    opt = lambda a: _ptr(a) if a.size else None          # noqa: E731
+    check(lib().dyd_yolo_tile_lines(opt(xy), _ptr(pt_off), _ptr(row_off), opt(cls), _ptr(width), _ptr(height), n, *args,
+                                    float(min_visibility), int(mode), int(max_tiles_per_row), T, _ptr(status), _ptr(tile_off),
+                                    opt(lines), _ptr(text_off), opt(action), opt(written), opt(cut), opt(dropped),
+                                    C.byref(n_tiles), C.byref(text), C.byref(total)), "dyd_yolo_tile_lines")
+    return status, tile_off, lines, text_off, action, written, cut, dropped, _take_text(text, total)
 
 
 REPAIR_ACTIONS = 8   # action codes of K11: keep, clip, no_size, bad_coords, degenerate, outside, low_visibility, small

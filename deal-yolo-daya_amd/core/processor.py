@@ -3806,6 +3806,291 @@ def export_coco_from_excels(category_excels: list, output_dir: str, source_col: 
     return {"outputs": outputs, "stats": all_stats, "dataset_name_map": dataset_name_map}
 
 
+# =============================================================================== f8b  tiled YOLO labels
+# Slicing before training on large images: every image row is cut into a grid of overlapping tiles and every tile gets the label
+# lines of the polygons that reach into it, from the f64 coordinates of the annotation cells (no label file is read back).  The
+# rule is K20's (include/dyd.h): the grid in integers, the last tile moved back to the image's edge; per tile K13's
+# clip and printer on the polygon moved to the tile's origin; a polygon is written in a tile when at least min_visibility of its
+# image-clipped area lies inside.  Native named-polygon scan (_poly_chunk) -> K20 (csrc/k20_tile.hip) -> one text per tile.
+TILE_STATUS = _fl.TILE_STATUS                              # K20 row status codes 0..3
+TILE_TASKS = ("segment", "detect")                         # K20 modes 0, 1
+_TILE_MAX = 1 << 20
+_TILE_POLY_SPEC = (("row", np.int64), ("object", np.int64), ("name", object), ("class_id", np.int64), ("action", object),
+                   (("tiles_written", "tiles_cut", "tiles_dropped"), np.int64))
+_TILE_TABLE_SPEC = (("row", np.int64), (("tile", "x0", "y0", "w", "h", "lines"), np.int64), ("text", object))
+
+
+class TileLabels:
+    """Result of yolo_tile_label_texts: tiles (row, tile, x0, y0, w, h, lines, text: one row per tile of the grid), polygons (one
+    row per selected polygon: row, object, name, class_id, action, tiles_written, tiles_cut, tiles_dropped), per_class (class,
+    polygons, tiles_written, tiles_cut, tiles_dropped, lost), row_status (a TILE_STATUS entry per row), classes (names, the class
+    id is the position) and totals."""
+
+    def __init__(self, tiles, polygons, per_class, row_status, classes, totals):
+        self.tiles = tiles
+        self.polygons = polygons
+        self.per_class = per_class
+        self.row_status = row_status
+        self.classes = classes
+        self.totals = totals
+
+    def __repr__(self):
+        return f"TileLabels({len(self.tiles)} tiles, {self.totals})"
+
+
+def _tile_pair(v, what: str) -> tuple:
+    pair = tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    if len(pair) != 2 or not all(isinstance(t, (int, np.integer)) and not isinstance(t, bool) and 1 <= t <= _TILE_MAX for t in pair):
+        raise ValueError(f"{what} must be an int or (w, h) of ints in 1..2^20, got {v!r}")
+    return int(pair[0]), int(pair[1])
+
+
+def _tile_params(tile, overlap, step, min_visibility, task, max_tiles_per_row) -> tuple:
+    """-> (tile_w, tile_h, step_x, step_y, min_visibility, mode, max_tiles_per_row) as K20 takes them"""
+    tw, th = _tile_pair(tile, "tile")
+    if step is None:
+        if isinstance(overlap, bool) or not isinstance(overlap, _NUMBER_TYPES) or not 0.0 <= float(overlap) < 1.0:
+            raise ValueError(f"overlap must be a number in [0, 1), got {overlap!r}")
+        sx, sy = (max(1, t - int(np.floor(t * float(overlap)))) for t in (tw, th))
+    else:
+        sx, sy = _tile_pair(step, "step")
+        if sx > tw or sy > th:
+            raise ValueError(f"step {step!r} is larger than tile {tile!r}")
+    if isinstance(min_visibility, bool) or not isinstance(min_visibility, _NUMBER_TYPES) or not 0.0 <= float(min_visibility) <= 1.0:
+        raise ValueError(f"min_visibility must be a number in [0, 1], got {min_visibility!r}")
+    if task not in TILE_TASKS:
+        raise ValueError(f"task must be one of {TILE_TASKS}, got {task!r}")
+    if isinstance(max_tiles_per_row, bool) or not isinstance(max_tiles_per_row, (int, np.integer)) or not 1 <= max_tiles_per_row <= _TILE_MAX:
+        raise ValueError(f"max_tiles_per_row must be an int in 1..2^20, got {max_tiles_per_row!r}")
+    return tw, th, sx, sy, float(min_visibility), TILE_TASKS.index(task), int(max_tiles_per_row)
+
+
+class _TileTotals:
+    def __init__(self, classes):
+        self.given = classes is not None
+        self.id_of = {name: k for k, name in enumerate(classes)} if self.given else {}
+        self.polygons = self.unmatchable = self.unknown = self.python_cells = 0
+        self.tiles, self.polys, self.status = [], [], []
+
+
+def _tile_chunk(cells, labels, W, H, be, acc: _TileTotals, start: int, params: tuple):
+    """one chunk of rows: polygon table (_poly_chunk) -> class ids (export_coco_frame's selection, 0-based) -> K20 -> tile and
+    polygon tables"""
+    row_off, xy, pt_off, obj, cls, names, n_py = _poly_chunk(cells)
+    acc.python_cells += n_py
+    n, nb = len(cells), len(cls)
+    sel = cls >= 0
+    acc.polygons += nb
+    acc.unmatchable += int(nb - sel.sum())
+    if labels is not None and nb:                        # the dataset step's rule: the polygon's name is the row's label
+        ids = {nm: k for k, nm in enumerate(names)}
+        want = np.fromiter((ids.get(str(v), -2) for v in labels), np.int64, count=n)
+        sel &= cls == np.repeat(want, np.diff(row_off))
+    lut = np.full(len(names) + 1, -1, np.int32)          # local name id -> class id (-1: none); the last entry serves cls -1
+    if acc.given:
+        for k, nm in enumerate(names):
+            lut[k] = acc.id_of.get(nm, -1)
+    elif nb:
+        used, first = np.unique(cls[sel], return_index=True)
+        for k in used[np.argsort(first, kind="stable")].tolist():
+            lut[k] = acc.id_of.setdefault(names[k], len(acc.id_of))
+    cid = np.where(sel, lut[cls], -1).astype(np.int32) if nb else np.zeros(0, np.int32)
+    acc.unknown += int((sel & (cid < 0)).sum()) if nb else 0
+    tw, th, sx, sy, min_vis, mode, max_tiles = params
+    status, tile_off, lines, text_off, action, written, cut, dropped, text = be.yolo_tile_lines(
+        xy, pt_off, row_off.astype(np.int32), cid, W, H, tw, th, sx, sy, min_vis, mode, max_tiles)
+    status = np.asarray(status, np.uint8)
+    grid_status, nx, ny = _fl.tile_grid(W, H, tw, th, sx, sy, max_tiles)
+    if not np.array_equal(grid_status, status) or not np.array_equal(np.diff(np.asarray(tile_off, np.int64)), nx * ny):
+        raise RuntimeError("the device's tile grid differs from the host's")
+    row, tile, x0, y0, w, h = _fl.tile_boxes(W, H, nx, ny, tw, th, sx, sy)
+    text_off = np.asarray(text_off, np.int64)
+    raw = bytes(text).decode("ascii")
+    texts = np.empty(len(tile), object)
+    texts[:] = [raw[a:b] for a, b in zip(text_off[:-1].tolist(), text_off[1:].tolist())]
+    acc.status.append(status)
+    acc.tiles.append((start + row, np.stack([tile, x0, y0, w, h, np.asarray(lines, np.int64)], axis=1), texts))
+    chosen = np.flatnonzero(cid >= 0)
+    if len(chosen):
+        counts = np.stack([np.asarray(a, np.int64)[chosen] for a in (written, cut, dropped)], axis=1)
+        acc.polys.append((start + np.searchsorted(row_off, chosen, side="right") - 1, obj[chosen].astype(np.int64),
+                          np.asarray(names, object)[cls[chosen]], cid[chosen].astype(np.int64),
+                          np.asarray(SEG_ACTIONS, object)[np.asarray(action, np.uint8)[chosen]], counts))
+
+
+def _tile_rows(cells, n, widths, heights, sources, labels, classes, params, be, stats, cells_of=None) -> TileLabels:
+    if classes is not None:
+        classes = list(classes)
+        if len(set(classes)) != len(classes) or not all(isinstance(c, str) for c in classes):
+            raise ValueError("classes must be distinct strings")
+    if labels is not None and len(labels) != n:
+        raise ValueError("one label per row")
+    _, W, H = _audit_sizes(widths, heights, n)
+    acc = _TileTotals(classes)
+    for s0, s1, chunk in _chunks(n, cells, cells_of):
+        _tile_chunk(chunk, None if labels is None else labels[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, params)
+    tiles = _parts_frame(acc.tiles, _TILE_TABLE_SPEC)
+    polygons = _parts_frame(acc.polys, _TILE_POLY_SPEC, sources)
+    status = np.concatenate(acc.status) if acc.status else np.zeros(0, np.uint8)
+    names = list(acc.id_of)
+    k = polygons["class_id"].to_numpy()
+    live = np.isin(polygons["action"].to_numpy(), SEG_ACTIONS[:2])
+    lost = live & (polygons["tiles_written"].to_numpy() == 0)
+    count = lambda wt=None: np.bincount(k, weights=wt, minlength=len(names)).astype(np.int64)   # noqa: E731
+    per_class = pd.DataFrame({"class": pd.Series(names, dtype=object), "polygons": count(),
+                              **{c: count(polygons[c].to_numpy()) for c in ("tiles_written", "tiles_cut", "tiles_dropped")},
+                              "lost": count(lost.astype(np.int64))})
+    totals = {"rows": n, **{f"rows_{s}": int((status == c).sum()) for c, s in enumerate(TILE_STATUS)}, "tiles": len(tiles),
+              "tiles_with_lines": int((tiles["lines"] > 0).sum()), "lines": int(tiles["lines"].sum()), "polygons": acc.polygons,
+              "selected": len(polygons), "unmatchable_name_polygons": acc.unmatchable, "unknown_class": acc.unknown,
+              **{a: int((polygons["action"] == a).sum()) for a in SEG_ACTIONS},
+              **{c: int(polygons[c].sum()) for c in ("tiles_written", "tiles_cut", "tiles_dropped")}, "lost": int(lost.sum()),
+              "python_cells": acc.python_cells, "tile": params[:2], "step": params[2:4], "min_visibility": params[4],
+              "task": TILE_TASKS[params[5]]}
+    if stats is not None:
+        stats.update(totals)
+    return TileLabels(tiles, polygons, per_class, np.asarray(TILE_STATUS, object)[status], names, totals)
+
+
+def yolo_tile_label_texts(cells, widths, heights, classes=None, labels=None, tile=640, overlap: float = 0.2, step=None,
+                          min_visibility: float = 0.1, task: str = "segment", max_tiles_per_row: int = 4096, backend=None,
+                          stats: Optional[dict] = None, sources=None) -> TileLabels:
+    """The label text of every tile of every row (see the section comment).  Polygons and classes are export_coco_frame's: every
+    polygon with a str name is selected, with ``labels`` (one per row) only those whose name is str(labels[i]); ``classes``
+    fixes the ids (id = position; a selected polygon with another name is deselected and counted as unknown_class), without it
+    they are numbered from 0 by first appearance.  ``tile`` and ``step`` are an int or (w, h); without ``step`` it is
+    max(1, tile - floor(tile * overlap)) per axis, overlap in [0, 1).  task "segment" prints K13's polygon lines, "detect"
+    K7's box line of the part inside the tile.  A row is tiled only when its size is usable and whole and its grid has at most
+    max_tiles_per_row tiles (TileLabels.row_status says why not).  -> TileLabels."""
+    be = _step_backend(backend, "yolo_tile_lines")
+    params = _tile_params(tile, overlap, step, min_visibility, task, max_tiles_per_row)
+    cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
+    return _tile_rows(cells, len(cells), widths, heights, sources, labels, classes, params, be, stats)
+
+
+def _tile_write(res: TileLabels, sources, output_dir, split: str, keep_empty_tiles: bool, crop_images: bool, lost_csv) -> dict:
+    """TileLabels -> labels/<split>/<stem>__x<x0>_y<y0>.txt, tiles_<split>.csv, data.yaml, the lost objects and the crops"""
+    import yaml
+
+    out = Path(output_dir)
+    labels_dir, images_dir = out / "labels" / split, out / "images" / split
+    labels_dir.mkdir(parents=True, exist_ok=True)
+    tiles = res.tiles
+    n = len(res.row_status)
+    source_of = (lambda i: sources[i]) if sources is not None else (lambda i: None)          # noqa: E731
+    keep = (tiles["lines"].to_numpy() > 0) | bool(keep_empty_tiles)
+    rows, x0s, y0s = tiles["row"].to_numpy(), tiles["x0"].to_numpy(), tiles["y0"].to_numpy()
+    stems = {int(i): _safe_image_stem(source_of(int(i)), int(i)) for i in np.unique(rows[keep]).tolist()}
+    label_files = np.full(len(tiles), "", object)
+    image_files = np.full(len(tiles), "", object)
+    texts = tiles["text"].to_numpy()
+    for g in np.flatnonzero(keep).tolist():
+        name = f"{stems[int(rows[g])]}__x{int(x0s[g])}_y{int(y0s[g])}"
+        (labels_dir / f"{name}.txt").write_text(texts[g], encoding="utf-8")
+        label_files[g] = f"labels/{split}/{name}.txt"
+    images_missing = images_written = 0
+    if crop_images:
+        try:
+            from PIL import Image
+        except ImportError:
+            Image = None
+        ws, hs = tiles["w"].to_numpy(), tiles["h"].to_numpy()
+        for i in np.unique(rows[keep]).tolist():
+            src = source_of(i)
+            path = Path(str(src)) if isinstance(src, str) and src else None
+            if Image is None or path is None or not path.is_file():          # nothing is downloaded
+                images_missing += 1
+                continue
+            try:
+                with Image.open(path) as im:
+                    im.load()
+                    images_dir.mkdir(parents=True, exist_ok=True)
+                    for g in np.flatnonzero(keep & (rows == i)).tolist():
+                        name = f"{stems[i]}__x{int(x0s[g])}_y{int(y0s[g])}{path.suffix}"
+                        im.crop((int(x0s[g]), int(y0s[g]), int(x0s[g] + ws[g]), int(y0s[g] + hs[g]))).save(images_dir / name)
+                        image_files[g] = f"images/{split}/{name}"
+                        images_written += 1
+            except Exception:                                                # noqa: BLE001  an unreadable image: labels only
+                images_missing += 1
+    manifest = tiles.drop(columns="text").assign(status="tiled", label_file=label_files, image_file=image_files)
+    idle = np.flatnonzero(res.row_status != "tiled")
+    if len(idle):
+        blank = pd.DataFrame({"row": idle, **{c: -1 for c in ("tile", "x0", "y0", "w", "h")}, "lines": 0,
+                              "status": res.row_status[idle], "label_file": "", "image_file": ""})
+        manifest = pd.concat([manifest, blank], ignore_index=True).sort_values(["row", "tile"], kind="stable", ignore_index=True)
+    if sources is not None:
+        manifest.insert(0, "source", np.asarray(sources, object)[manifest["row"].to_numpy()] if n else np.zeros(0, object))
+    manifest_path = out / f"tiles_{split}.csv"
+    manifest.to_csv(manifest_path, index=False, encoding="utf-8-sig")
+    (out / "data.yaml").write_text(yaml.dump({"path": str(out), "train": "images/train", "val": "images/val", "test": "images/test",
+                                              "nc": len(res.classes), "names": list(res.classes)}, sort_keys=False,
+                                             allow_unicode=True), encoding="utf-8")
+    if lost_csv:
+        poly = res.polygons
+        lost = poly[poly["action"].isin(SEG_ACTIONS[:2]) & (poly["tiles_written"] == 0)]
+        lost.to_csv(lost_csv, index=False, encoding="utf-8-sig")
+    return {**res.totals, "classes": list(res.classes), "label_files": int(keep.sum()), "images_written": images_written,
+            "images_missing": images_missing, "output_dir": str(out), "manifest": str(manifest_path),
+            "lost_output": str(lost_csv) if lost_csv else None}
+
+
+def tile_yolo_frame(df: pd.DataFrame, output_dir, split: str = "train", json_col: str = ANNOTATION_COL, width_col: str = "width",
+                    height_col: str = "height", source_col: str = "source", label_col: Optional[str] = None, classes=None,
+                    tile=640, overlap: float = 0.2, step=None, min_visibility: float = 0.1, task: str = "segment",
+                    max_tiles_per_row: int = 4096, keep_empty_tiles: bool = False, crop_images: bool = False, lost_csv=None,
+                    backend=None, stats: Optional[dict] = None) -> dict:
+    """A table's annotation polygons as a tiled YOLO dataset under output_dir (yolo_tile_label_texts has the rule and the
+    arguments): labels/<split>/<stem>__x<x0>_y<y0>.txt per tile with lines (every tile with keep_empty_tiles), the stem from
+    _safe_image_stem(source, position); tiles_<split>.csv, one line per tile and one per row that is not tiled, with its status;
+    data.yaml with the classes; ``lost_csv``: the selected polygons that are written or clipped in the image but written in no
+    tile.  crop_images=True also writes the Pillow crop (x0, y0, x0 + w, y0 + h) of every such tile under images/<split>/ with
+    the source's suffix when the source is an existing local file; a row whose image is missing or unreadable, or every row
+    when Pillow is missing, is counted in images_missing and its labels are still written.  Nothing is downloaded.
+    -> dict(the totals, classes, label_files, images_written, images_missing, output_dir, manifest, lost_output)."""
+    be = _step_backend(backend, "yolo_tile_lines")
+    params = _tile_params(tile, overlap, step, min_visibility, task, max_tiles_per_row)
+    if label_col is not None and label_col not in df.columns:
+        raise ValueError(f"no column {label_col!r}")
+    cells = df[json_col].to_numpy()
+    widths, heights, _ = _size_columns(df, width_col, height_col)
+    sources = df[source_col].to_numpy() if source_col in df.columns else None
+    labels = df[label_col].to_numpy() if label_col is not None else None
+    res = _tile_rows(cells, len(cells), widths, heights, sources, labels, classes, params, be, None)
+    result = _tile_write(res, sources, output_dir, split, keep_empty_tiles, crop_images, lost_csv)
+    if stats is not None:
+        stats.update(result)
+    return result
+
+
+def tile_yolo_csv(input_csv_path, output_dir, split: str = "train", json_col: str = ANNOTATION_COL, width_col: str = "width",
+                  height_col: str = "height", source_col: str = "source", label_col: Optional[str] = None, classes=None,
+                  tile=640, overlap: float = 0.2, step=None, min_visibility: float = 0.1, task: str = "segment",
+                  max_tiles_per_row: int = 4096, keep_empty_tiles: bool = False, crop_images: bool = False, lost_csv=None,
+                  backend=None, stats: Optional[dict] = None):
+    """CSV -> tiled YOLO dataset, tile_yolo_frame on the native CSV hand-off (the polygon column is never parsed by pandas).
+    -> tile_yolo_frame's dict, or None when the file cannot be read or lacks the column."""
+    be = _step_backend(backend, "yolo_tile_lines")
+    params = _tile_params(tile, overlap, step, min_visibility, task, max_tiles_per_row)
+
+    def native(table):
+        light = table.light
+        if label_col is not None and label_col not in light.columns:
+            return NotImplemented                        # the pandas route raises tile_yolo_frame's error
+        n, widths, heights, _, cells_of = _table_rows(table, json_col, width_col, height_col)
+        sources = light[source_col].to_numpy() if source_col in light.columns else None
+        labels = light[label_col].to_numpy() if label_col is not None else None
+        res = _tile_rows(None, n, widths, heights, sources, labels, classes, params, be, None, cells_of)
+        result = _tile_write(res, sources, output_dir, split, keep_empty_tiles, crop_images, lost_csv)
+        if stats is not None:
+            stats.update(result)
+        return result
+
+    return _csv_route("tile_yolo", input_csv_path, json_col, native,
+                      lambda df: tile_yolo_frame(df, output_dir, split, json_col, width_col, height_col, source_col, label_col,
+                                                 classes, tile, overlap, step, min_visibility, task, max_tiles_per_row,
+                                                 keep_empty_tiles, crop_images, lost_csv, be, stats))
+
+
 def _dataset_dir_name(excel_path: Path, idx_excel: int, used_dir_names: set) -> tuple:
     """-> (category name, directory name) of one category workbook: safe_filename of the stem, with _1, _2, ... when an earlier
     workbook took the name (reference processor.py:931-936); the name is added to used_dir_names"""

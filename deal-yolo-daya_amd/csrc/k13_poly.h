@@ -1,7 +1,8 @@
 // k13_poly.h — the polygon handling K13 (k13_seg.hip), K14 (k14_poly_audit.hip) and K16 (k16_coco.hip) share: a polygon's
 // checks before clipping, its vertex list V, the Sutherland-Hodgman pipeline that clips it to the image (include/dyd.h, DESIGN
 // §5l) and the walk over the clipped vertices that decides `empty` and gives the area; the search of an offsets array and a
-// polygon tile's row range.  K14 and K16 give every polygon the action K13 would give it by calling this same code.
+// polygon tile's row range.  K14 and K16 give every polygon the action K13 would give it by calling this same code; K20
+// (k20_tile.hip) runs the same clip and walk once per tile on the polygon moved to the tile's origin.
 //
 // Two pieces stay written out in their kernels, because sharing them changed a kernel's registers (the rule of box_table.h:
 // a helper has to cost nothing).  K14 keeps its own copy of ClipWalk's walk: through the struct k14_poly_kernel takes 105 VGPRs
@@ -111,9 +112,10 @@ struct Clip {
     }
 };
 
-// the polygon's vertices after clipping, in order, to out(x, y); out returns false to stop early
-template <class Out>
-__device__ __forceinline__ void k13_vertices(const Poly &pg, bool needs_clip, double W, double H, Out &out) {
+// the polygon's vertices after clipping, in order, to out(x, y); out returns false to stop early.  P: Poly, or K20's polygon
+// seen from a tile (its each() hands out the translated vertices)
+template <class P, class Out>
+__device__ __forceinline__ void k13_vertices(const P &pg, bool needs_clip, double W, double H, Out &out) {
     if (!needs_clip) {
         pg.each(out);
         return;
@@ -148,7 +150,8 @@ __device__ __forceinline__ uint8_t k13_prepare(const double *xy, int32_t a, int3
     return 0xff;
 }
 
-__device__ __forceinline__ bool k13_outside(const Poly &pg, double W, double H) {
+template <class P>
+__device__ __forceinline__ bool k13_outside(const P &pg, double W, double H) {
     return pg.x1 < 0.0 || pg.x2 > W || pg.y1 < 0.0 || pg.y2 > H;
 }
 

@@ -5,8 +5,9 @@
 //
 // A polygon table: xy = P x (x, y) f64, pt_off = B+1 int32, row_off = N+1 int32, width / height = N f64, and per step one or
 // two columns of its own (K13 and K17: sel = B u8, class_id = N int32; K14: cls = B int32, size_status = N u8; K16: cat_id = B int32,
-// size_status = N u8), which each entry checks for NULL and uploads itself.  K19 (k19_simplify.hip) has no rows: it passes one
-// row that holds every polygon through the same checks and stages xy and pt_off with poly_column.
+// size_status = N u8; K20 (k20_tile.hip): cls = B int32), which each entry checks for NULL and uploads itself.
+// K19 (k19_simplify.hip) has no rows: it passes one row that holds every polygon through the same checks and stages xy and
+// pt_off with poly_column.
 #pragma once
 
 #include "dyd_common.h"

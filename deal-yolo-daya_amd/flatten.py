@@ -455,3 +455,39 @@ def column_str_bytes(col: pd.Series, drop_na: bool = False) -> tuple:
             return flat
     data, off = _strings_to_bytes(col.astype(str).tolist())
     return data, off
+
+
+# ---- the tile step's grid (K20; include/dyd.h has the rule) -------------------------------------------------------
+TILE_STATUS = ("tiled", "no_size", "fractional_size", "too_many_tiles")   # K20 row status codes 0..3
+_TILE_LIMIT = float(1 << 43)
+
+
+def tile_grid(width, height, tile_w: int, tile_h: int, step_x: int, step_y: int, max_tiles_per_row: int = 4096) -> tuple:
+    """K20's grid from the same integer rule as the kernel -> (status u8 [n], nx int64 [n], ny int64 [n]); nx = ny = 0 for a
+    row that is not tiled"""
+    W, H = np.asarray(width, np.float64), np.asarray(height, np.float64)
+    with np.errstate(invalid="ignore"):
+        ok = (W > 0) & (W < _TILE_LIMIT) & (H > 0) & (H < _TILE_LIMIT)
+        whole = ok & (W == np.floor(W)) & (H == np.floor(H))
+    Lx, Ly = np.where(whole, W, 0).astype(np.int64), np.where(whole, H, 0).astype(np.int64)
+    nx = np.where(Lx <= tile_w, 1, -((tile_w - Lx) // step_x) + 1)
+    ny = np.where(Ly <= tile_h, 1, -((tile_h - Ly) // step_y) + 1)
+    cap = max_tiles_per_row + 1                          # the product of the clipped counts stays below 2^42
+    many = whole & (np.minimum(nx, cap) * np.minimum(ny, cap) > max_tiles_per_row)
+    status = np.where(~ok, 1, np.where(~whole, 2, np.where(many, 3, 0))).astype(np.uint8)
+    tiled = status == 0
+    return status, np.where(tiled, nx, 0).astype(np.int64), np.where(tiled, ny, 0).astype(np.int64)
+
+
+def tile_boxes(width, height, nx, ny, tile_w: int, tile_h: int, step_x: int, step_y: int) -> tuple:
+    """the tiles of tile_grid's rows in K20's order (row by row, ty * nx + tx) -> (row, tile, x0, y0, w, h), int64 each"""
+    nx, ny = np.asarray(nx, np.int64), np.asarray(ny, np.int64)
+    count = nx * ny
+    row = np.repeat(np.arange(len(count), dtype=np.int64), count)
+    first = np.cumsum(count) - count
+    tile = np.arange(int(count.sum()), dtype=np.int64) - first[row]
+    Lx, Ly = np.asarray(width, np.float64)[row].astype(np.int64), np.asarray(height, np.float64)[row].astype(np.int64)
+    tx, ty = tile % np.maximum(nx[row], 1), tile // np.maximum(nx[row], 1)
+    x0 = np.where(Lx <= tile_w, 0, np.minimum(tx * step_x, Lx - tile_w))
+    y0 = np.where(Ly <= tile_h, 0, np.minimum(ty * step_y, Ly - tile_h))
+    return row, tile, x0, y0, np.minimum(Lx, tile_w), np.minimum(Ly, tile_h)

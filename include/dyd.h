@@ -580,6 +580,66 @@ int dyd_simplify_polygons(const double *xy, const int32_t *pt_off, int64_t n_pol
 int dyd_simplify_polygons_dev(const double *xy, const int32_t *pt_off, int64_t n_polys, int64_t n_points, double tolerance,
                               uint8_t *out_keep, uint8_t *out_action, int32_t *out_kept, double *out_dev2, void *stream);
 
+/* ---- K20: tiled YOLO label lines — every image row sliced into overlapping tiles (the tile step) ----
+ * All arithmetic is IEEE f64, operation by operation, without contraction, as in K13.  The table is K16's: xy, pt_off, row_off,
+ * width / height per row, and cls[p], the polygon's class id; cls[p] < 0: the polygon is not selected (action 255).
+ * Parameters: integers tile_w, tile_h, step_x, step_y with 1 <= step <= tile <= 2^20; min_visibility finite and in [0, 1];
+ * mode 0 segment, 1 detect; max_tiles_per_row in 1..2^20.  Anything else is DYD_ERR_INVALID.
+ * Row status, the first rule that applies:
+ *   1 no_size          K13's size test fails for W or H (not finite, not in (0, 2^43));
+ *   2 fractional_size  W or H is not a whole number;
+ *   3 too_many_tiles   nx * ny > max_tiles_per_row;
+ *   0 tiled            otherwise.  Only rows of status 0 have tiles.
+ * Grid, per axis, in int64, for a length L, tile T and step S: L <= T gives one tile, origin 0, extent L; otherwise
+ * n = ceil((L - T) / S) + 1 tiles, tile j with origin min(j * S, L - T) and extent T (the last tile is moved back to end at the
+ * image's edge: no tile leaves the image, nothing is padded).  A row's tiles are numbered ty * nx + tx; tile_off[i] is the
+ * exclusive sum of the rows' tile counts, T = tile_off[n_rows] the number of tiles; T > 2^31 - 1 is DYD_ERR_RANGE.
+ * Per polygon: action = exactly K13's on the row's W and H (codes 0..5, the same device code; 255 not selected).  Only written
+ * and clipped polygons go on; A_img = K14's area of the image-clipped polygon.
+ * Per tile (origin (ox, oy), extent (tw, th), taken as f64) and polygon, V = K13's vertex list (two points: the four corners):
+ *   1. every vertex of V becomes (x - ox, y - oy);
+ *   2. K13's clip, unchanged, with W = tw and H = th; 3. K13's walk over the clipped vertices C;
+ *   4. `empty` (fewer than 3 vertices, or an extent of C that is not > 0): the polygon has no part in the tile;
+ *   5. otherwise A_tile = the area of C (K14's);
+ *   6. written in the tile when A_tile >= min_visibility * A_img (a product, so A_img == 0 always passes), 7. else dropped;
+ *   8. a written polygon is cut when a moved vertex lies outside [0, tw] x [0, th].
+ * So a tile's segment lines are exactly what K13 prints for the moved polygon in an image of tw x th.
+ * Lines: segment "{cls}" then " {n(x/tw):.6f} {n(y/th):.6f}" per vertex of C (n and the printer K13's: digits(cls) + 18 * m
+ * bytes); detect K7's line "{cls} {(x1+x2)/2/tw:.6f} {(y1+y2)/2/th:.6f} {(x2-x1)/tw:.6f} {(y2-y1)/th:.6f}" with (x1, y1, x2, y2)
+ * the extent of C (every value lies in [0, 1 + 2^-50), DESIGN 5r has the argument, so it is 8 bytes, K13's printer prints it
+ * as "%.6f" does, and the line is digits(cls) + 36 bytes).  A tile's lines are
+ * its written polygons in polygon order joined with "\n"; the text is the tiles' texts one after the other, nothing between.
+ * xy [2*n_points] (16-B aligned), pt_off [n_polys+1], row_off [n_rows+1], cls [n_polys], width / height [n_rows].
+ * tiles_cap            : entries the caller provides in out_tile_line_count (out_text_off: one more).  T > tiles_cap is
+ *                        DYD_ERR_RANGE with *out_n_tiles = T and out_row_status / out_tile_off written: size and call again
+ *                        (or compute T from the rule above, as the origin and extent of tile g are computed).
+ * out_row_status       : the codes above                                              u8  [n_rows]
+ * out_tile_off         : tiles of row i are [off[i], off[i+1])                        i64 [n_rows+1]
+ * out_tile_line_count  : lines of tile g                                              i32 [T]
+ * out_text_off         : byte range of tile g in the text = [off[g], off[g+1])        i64 [T+1]
+ * out_action           : K13's codes, 255                                             u8  [n_polys]
+ * out_tiles_written / _cut / _dropped : tiles in which the polygon is written / written and cut / dropped   i32 [n_polys]
+ * *out_n_tiles         : T (a HOST int64)
+ * dyd_yolo_tile_lines     : host pointers; *out_text is allocated by the library (release with dyd_host_free).
+ * dyd_yolo_tile_lines_dev : device pointers; out_text_or_null == NULL only measures (everything but the text);
+ *                           otherwise text_cap bytes are available and DYD_ERR_RANGE is returned, with the needed size in
+ *                           *out_total, when that is too little.  *out_total is a HOST int64.
+ *                           n_polys = row_off[n_rows], n_points = pt_off[n_polys].
+ * n_rows, n_polys, n_points and tiles_cap stay below 2^31 (DYD_ERR_INVALID otherwise). */
+int dyd_yolo_tile_lines(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *cls, const double *width,
+                        const double *height, int64_t n_rows, int64_t tile_w, int64_t tile_h, int64_t step_x, int64_t step_y,
+                        double min_visibility, int32_t mode, int64_t max_tiles_per_row, int64_t tiles_cap, uint8_t *out_row_status,
+                        int64_t *out_tile_off, int32_t *out_tile_line_count, int64_t *out_text_off, uint8_t *out_action,
+                        int32_t *out_tiles_written, int32_t *out_tiles_cut, int32_t *out_tiles_dropped, int64_t *out_n_tiles,
+                        uint8_t **out_text, int64_t *out_text_len);
+int dyd_yolo_tile_lines_dev(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *cls, const double *width,
+                            const double *height, int64_t n_rows, int64_t n_polys, int64_t n_points, int64_t tile_w, int64_t tile_h,
+                            int64_t step_x, int64_t step_y, double min_visibility, int32_t mode, int64_t max_tiles_per_row,
+                            int64_t tiles_cap, uint8_t *out_row_status, int64_t *out_tile_off, int32_t *out_tile_line_count,
+                            int64_t *out_text_off, uint8_t *out_action, int32_t *out_tiles_written, int32_t *out_tiles_cut,
+                            int32_t *out_tiles_dropped, int64_t *out_n_tiles, uint8_t *out_text_or_null, int64_t text_cap,
+                            int64_t *out_total, void *stream);
+
 /* ---- native flatten / emit (HOST code, multithreaded) ------------------------------
  * Schema-specialised JSON scanner + canonical re-emitter that replaces json.loads / json.dumps inside
  * parse_and_replace_ptlist (processor.py:262-281), extract_width_height (:285-292) and extract_boxes

@@ -3,7 +3,7 @@
 interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant.
 
     python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k18: box comparison beside K2 and K9; k13: segmentation lines beside K7;
-     k14: polygon audit; k14tier: its in-lane / wave threshold; simplify: polygon simplification (K19) beside K14 on rings of 8, 64 and 1024 points; k16: COCO annotation objects beside K13; k17: oriented-box lines beside K13)
+     k14: polygon audit; k14tier: its in-lane / wave threshold; simplify: polygon simplification (K19) beside K14 on rings of 8, 64 and 1024 points; k16: COCO annotation objects beside K13; k17: oriented-box lines beside K13; tile: tiled label lines (K20) beside K13)
 """
 import argparse
 import json
@@ -21,6 +21,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--only", default="k1,k2,k3,k4,k5,k6")
     ap.add_argument("--bpr", type=int, default=0, help="fixed boxes per row (0 = U{1..32})")
+    ap.add_argument("--tile", type=int, default=640, help="tile size of the `tile` entry")
+    ap.add_argument("--overlap", type=float, default=0.2, help="tile overlap of the `tile` entry")
     args = ap.parse_args()
     only = set(args.only.split(","))
 
@@ -547,6 +549,58 @@ def main():
                med, mn, rows=B, text_bytes=T13,
                actions=dict(zip(("written", "clipped", "bad_coords", "too_few_points", "empty", "no_size"), counts)))
         del xs, text
+    if "tile" in only:
+        import ctypes as C
+        # K20 (tiled label lines) beside K13 on the same device buffers: the synthetic rows as they are, every image 1920 x 1080,
+        # tile 640 with overlap 0.2 (step 512): a grid of 4 x 2 tiles per row.  K13 reads the same polygons once and prints each
+        # once; K20 clips a polygon once per tile it reaches and prints it in each.  pairs = tile-polygon pairs with a part in the tile.
+        tile, step = args.tile, max(1, args.tile - int(args.tile * args.overlap))
+        total, n_tiles = C.c_int64(), C.c_int64()
+        w = torch.full((N,), 1920.0, dtype=torch.float64, device=dev); h = torch.full((N,), 1080.0, dtype=torch.float64, device=dev)
+        cid = (torch.arange(N, device=dev, dtype=torch.int32) % 20).contiguous()
+        cls = (torch.arange(B, device=dev, dtype=torch.int32) % 20).contiguous()
+        toff = torch.empty(N + 1, dtype=torch.int64, device=dev); flag = torch.empty(N, dtype=torch.uint8, device=dev)
+        act = torch.empty(B, dtype=torch.uint8, device=dev)
+        seg_args = (xy.data_ptr(), pt_off.data_ptr(), box_off.data_ptr(), None, w.data_ptr(), h.data_ptr(), cid.data_ptr(), N, B, P,
+                    toff.data_ptr(), flag.data_ptr(), act.data_ptr())
+        ck(L.dyd_yolo_seg_lines_dev(*seg_args, None, 0, C.byref(total), sp), "k13 measure")
+        T13 = total.value
+        text13 = torch.empty(T13, dtype=torch.uint8, device=dev)
+        nx = 1 if 1920 <= tile else -((tile - 1920) // step) + 1
+        ny = 1 if 1080 <= tile else -((tile - 1080) // step) + 1
+        cap = N * nx * ny
+        status = torch.empty(N, dtype=torch.uint8, device=dev); tile_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
+        lines = torch.empty(cap, dtype=torch.int32, device=dev); xoff = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+        act20 = torch.empty(B, dtype=torch.uint8, device=dev)
+        wr, cut, drop = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+        for mode, task in ((0, "segment"), (1, "detect")):
+            a20 = (xy.data_ptr(), pt_off.data_ptr(), box_off.data_ptr(), cls.data_ptr(), w.data_ptr(), h.data_ptr(), N, B, P, tile, tile,
+                   step, step, 0.1, mode, 4096, cap, status.data_ptr(), tile_off.data_ptr(), lines.data_ptr(), xoff.data_ptr(),
+                   act20.data_ptr(), wr.data_ptr(), cut.data_ptr(), drop.data_ptr(), C.byref(n_tiles))
+            ck(L.dyd_yolo_tile_lines_dev(*a20, None, 0, C.byref(total), sp), "k20 measure")
+            T20 = total.value
+            text20 = torch.empty(T20, dtype=torch.uint8, device=dev)
+            res = {}
+            for rnd in range(2):                      # interleaved rounds
+                res.setdefault("k13", []).append(timeit(lambda: ck(L.dyd_yolo_seg_lines_dev(*seg_args, text13.data_ptr(), T13,
+                                                                                            C.byref(total), sp), "k13")))
+                res.setdefault("k20m", []).append(timeit(lambda: ck(L.dyd_yolo_tile_lines_dev(*a20, None, 0, C.byref(total), sp),
+                                                                    "k20 measure")))
+                res.setdefault("k20", []).append(timeit(lambda: ck(L.dyd_yolo_tile_lines_dev(*a20, text20.data_ptr(), T20,
+                                                                                             C.byref(total), sp), "k20")))
+            pairs = int(wr.sum().item() + drop.sum().item())
+            k13_bytes = 16 * P + 4 * (B + 1) + B + 4 * (N + 1) + 20 * N + 8 * (N + 1) + N + B + T13
+            k20_bytes = 16 * P + 4 * (B + 1) + 4 * B + 4 * (N + 1) + 16 * N + N + 8 * (N + 1) + 12 * n_tiles.value + 13 * B + T20
+            med13, mn13 = min(res["k13"])
+            med20, mn20 = min(res["k20"])
+            medm, mnm = min(res["k20m"])
+            report("k13_yolo_seg_lines_rows", k13_bytes, med13, mn13, rows=N, polygons=B, points=P, text_bytes=T13)
+            report(f"k20_yolo_tile_lines_{task}_measure_only", k20_bytes - T20, medm, mnm, rows=N, tiles=n_tiles.value)
+            report(f"k20_yolo_tile_lines_{task}", k20_bytes, med20, mn20, rows=N, polygons=B, points=P, tile=tile, step=step,
+                   tiles=n_tiles.value, pairs=pairs, lines=int(wr.sum().item()), lines_cut=int(cut.sum().item()), text_bytes=T20,
+                   ms_vs_k13=round(med20 / med13, 3), pairs_per_polygon=round(pairs / B, 3), text_vs_k13=round(T20 / max(T13, 1), 3))
+            del text20
+        del text13
     if "k14" in only:
         import ctypes as C
         # K14 (polygon audit) on K13's two shapes, and long polygons (convex rings of 256 vertices: no crossing, so the wave
