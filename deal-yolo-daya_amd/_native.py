@@ -155,6 +155,12 @@ SIGNATURES = {
                                           C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
                                           C.POINTER(C.c_int64), C.c_void_p]),
+    "dyd_rasterize_polygons": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_int64)]),
+    "dyd_rasterize_polygons_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                             C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
     "dyd_coco_annotations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                                        C.POINTER(C.c_int64)]),
@@ -529,6 +535,21 @@ def yolo_tile_lines(xy, pt_off, row_off, cls, width, height, tile_w: int, tile_h
                                     opt(lines), _ptr(text_off), opt(action), opt(written), opt(cut), opt(dropped),
                                     C.byref(n_tiles), C.byref(text), C.byref(total)), "dyd_yolo_tile_lines")
     return status, tile_off, lines, text_off, action, written, cut, dropped, _take_text(text, total)
+
+
+def rasterize_polygons(xy, pt_off, row_off, val, width, height, background: int = 0, max_pixels_per_row: int = 1 << 26):
+    """K21 over host arrays -> (row_status u8 [n], pix_off i64 [n+1], action u8 [B], covered i64 [B], owned i64 [B], pixels u8
+    [pix_off[n]]): the mask of row i is pixels[pix_off[i]:pix_off[i+1]] as H lines of W bytes.  Rule and codes: include/dyd.h."""
+    xy, pt_off, row_off, width, height, _, val, n, nb = _poly_table(xy, pt_off, row_off, width, height,   # no row column of its own
+                                                                    ("width", width, np.float64), ("val", val, np.int32))
+    status, pix_off = np.zeros(n, np.uint8), np.zeros(n + 1, np.int64)
+    action, covered, owned = np.zeros(nb, np.uint8), np.zeros(nb, np.int64), np.zeros(nb, np.int64)
+    pixels, total = C.c_void_p(), C.c_int64()
+    opt = lambda a: _ptr(a) if a.size else None          # noqa: E731
+    check(lib().dyd_rasterize_polygons(opt(xy), _ptr(pt_off), _ptr(row_off), opt(val), _ptr(width), _ptr(height), n, int(background),
+                                       int(max_pixels_per_row), _ptr(status), _ptr(pix_off), opt(action), opt(covered), opt(owned),
+                                       C.byref(pixels), C.byref(total)), "dyd_rasterize_polygons")
+    return status, pix_off, action, covered, owned, np.frombuffer(_take_text(pixels, total), np.uint8)
 
 
 REPAIR_ACTIONS = 8   # action codes of K11: keep, clip, no_size, bad_coords, degenerate, outside, low_visibility, small

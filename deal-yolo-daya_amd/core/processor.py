@@ -3873,9 +3873,10 @@ class _TileTotals:
         self.tiles, self.polys, self.status = [], [], []
 
 
-def _tile_chunk(cells, labels, W, H, be, acc: _TileTotals, start: int, params: tuple):
-    """one chunk of rows: polygon table (_poly_chunk) -> class ids (export_coco_frame's selection, 0-based) -> K20 -> tile and
-    polygon tables"""
+def _tile_class_ids(cells, labels, acc) -> tuple:
+    """one chunk of rows: polygon table (_poly_chunk) and the class id of every polygon (export_coco_frame's selection, 0-based;
+    -1: not selected) -> (row_off, xy, pt_off, obj, cls, names, cid).  acc (a _TileTotals) takes the counts and, without given
+    classes, numbers the names by first appearance."""
     row_off, xy, pt_off, obj, cls, names, n_py = _poly_chunk(cells)
     acc.python_cells += n_py
     n, nb = len(cells), len(cls)
@@ -3896,6 +3897,12 @@ def _tile_chunk(cells, labels, W, H, be, acc: _TileTotals, start: int, params: t
             lut[k] = acc.id_of.setdefault(names[k], len(acc.id_of))
     cid = np.where(sel, lut[cls], -1).astype(np.int32) if nb else np.zeros(0, np.int32)
     acc.unknown += int((sel & (cid < 0)).sum()) if nb else 0
+    return row_off, xy, pt_off, obj, cls, names, cid
+
+
+def _tile_chunk(cells, labels, W, H, be, acc: _TileTotals, start: int, params: tuple):
+    """one chunk of rows: polygon table and class ids (_tile_class_ids) -> K20 -> tile and polygon tables"""
+    row_off, xy, pt_off, obj, cls, names, cid = _tile_class_ids(cells, labels, acc)
     tw, th, sx, sy, min_vis, mode, max_tiles = params
     status, tile_off, lines, text_off, action, written, cut, dropped, text = be.yolo_tile_lines(
         xy, pt_off, row_off.astype(np.int32), cid, W, H, tw, th, sx, sy, min_vis, mode, max_tiles)
@@ -4089,6 +4096,319 @@ def tile_yolo_csv(input_csv_path, output_dir, split: str = "train", json_col: st
                       lambda df: tile_yolo_frame(df, output_dir, split, json_col, width_col, height_col, source_col, label_col,
                                                  classes, tile, overlap, step, min_visibility, task, max_tiles_per_row,
                                                  keep_empty_tiles, crop_images, lost_csv, be, stats))
+
+
+# =============================================================================== f8c  label masks
+# Pixels from the polygons: every image row becomes one uint8 mask, H lines of W bytes, in which a pixel holds the value of the
+# last polygon that covers its centre, or the background.  The rule is K21's (include/dyd.h): the even-odd rule on
+# the f64 coordinates, an edge in its canonical direction, so that polygons with a shared edge neither overlap nor leave a gap.
+# Native named-polygon scan (_poly_chunk) -> K21 (csrc/k21_raster.hip) -> masks, and per polygon how many pixels it covers and
+# how many it still owns at the end.
+MASK_STATUS = _fl.MASK_STATUS                              # K21 row status codes 0..3
+MASK_MODES = ("semantic", "instance")
+MASK_ORDERS = ("annotation", "large_first")
+MASK_ACTIONS = {0: "rasterised", 2: "bad_coords", 3: "too_few_points", 5: "no_raster", 255: "too_many_instances"}
+MASK_RESULTS = ("painted", "hidden", "empty", "bad_coords", "too_few_points", "no_raster", "too_many_instances")
+_MASK_MAX_PIXELS = 1 << 30
+_MASK_POLY_SPEC = (("row", np.int64), ("object", np.int64), ("name", object), ("class_id", np.int64), ("value", np.int64),
+                   ("action", object), (("covered", "owned"), np.int64), ("result", object))
+_MASK_ROW_SPEC = (("row", np.int64), (("width", "height"), np.float64), ("status", object),
+                  (("polygons", "painted", "hidden", "empty"), np.int64))
+
+
+class PolygonMasks:
+    """Result of polygon_masks: masks (per row a 2-D uint8 array [H, W], or None for a row that is not rasterised; all None
+    with keep_masks=False), rows (row, width, height, status, polygons, painted, hidden, empty), polygons (one row per selected
+    polygon: row, object, name, class_id, value, action, covered, owned, result), per_class (class, value, polygons, painted, hidden,
+    empty, bad_coords, too_few_points, pixels, share), classes (names, the class id is the position) and totals."""
+
+    def __init__(self, masks, rows, polygons, per_class, classes, totals):
+        self.masks = masks
+        self.rows = rows
+        self.polygons = polygons
+        self.per_class = per_class
+        self.classes = classes
+        self.totals = totals
+
+    def __repr__(self):
+        return f"PolygonMasks({len(self.rows)} rows, {self.totals})"
+
+
+def _mask_int(v, what: str, lo: int, hi: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise ValueError(f"{what} must be an int in {lo}..{hi}, got {v!r}")
+    return int(v)
+
+
+def _mask_params(mode, background, class_offset, order, max_pixels_per_row, batch_pixels) -> tuple:
+    """-> (mode, background, class_offset, order, max_pixels_per_row, batch_pixels), checked"""
+    if mode not in MASK_MODES:
+        raise ValueError(f"mode must be one of {MASK_MODES}, got {mode!r}")
+    if order not in MASK_ORDERS:
+        raise ValueError(f"order must be one of {MASK_ORDERS}, got {order!r}")
+    return (mode, _mask_int(background, "background", 0, 255), _mask_int(class_offset, "class_offset", 0, 255), order,
+            _mask_int(max_pixels_per_row, "max_pixels_per_row", 1, _MASK_MAX_PIXELS), _mask_int(batch_pixels, "batch_pixels", 1, 1 << 40))
+
+
+def _mask_values(cid, background: int, class_offset: int) -> np.ndarray:
+    """semantic values of class ids (-1 stays -1); a value past 255 or equal to the background is an error"""
+    val = np.where(cid >= 0, cid + class_offset, -1).astype(np.int32)
+    if (val > 255).any():
+        raise ValueError(f"class id {int(cid.max())} + class_offset {class_offset} does not fit a uint8 mask (16-bit masks are not written)")
+    if (val == background).any():
+        raise ValueError(f"class id {background - class_offset} would be painted with the background value {background}")
+    return val
+
+
+def _mask_instances(cid, row_off) -> tuple:
+    """instance values: 1 + the polygon's position among its row's selected polygons (-1: not selected, or a row of more than
+    255 of them) -> (val int32 [B], too_many bool [n])"""
+    sel = cid >= 0
+    before = np.concatenate([[0], np.cumsum(sel)])
+    count = before[row_off[1:]] - before[row_off[:-1]]
+    row = np.repeat(np.arange(len(row_off) - 1), np.diff(row_off))
+    too_many = count > 255
+    val = np.where(sel & ~too_many[row], before[1:] - before[row_off[:-1]][row], -1).astype(np.int32)
+    return val, too_many
+
+
+def _mask_action_names(codes) -> np.ndarray:
+    """K21 action codes -> their names"""
+    return np.asarray([MASK_ACTIONS[int(c)] for c in codes], object) if len(codes) else np.zeros(0, object)
+
+
+def _mask_chunk(cells, labels, W, H, be, acc, start: int, params: tuple, on_masks):
+    """one chunk of rows: polygon table and class ids (_tile_class_ids) -> values and paint order -> K21 per batch of rows ->
+    on_masks(first row, [mask or None per row of the batch]) and the row and polygon tables"""
+    mode, background, class_offset, order, max_pixels, batch_pixels = params
+    row_off, xy, pt_off, obj, cls, names, cid = _tile_class_ids(cells, labels, acc)
+    n, nb = len(cells), len(cid)
+    row_off = np.asarray(row_off, np.int64)
+    too_many = np.zeros(n, bool)
+    if mode == "semantic":
+        val = _mask_values(cid, background, class_offset)
+    else:
+        val, too_many = _mask_instances(cid, row_off)
+    perm = None
+    if order == "large_first" and nb:                    # paint in another order: permute the table, permute the results back
+        perm = _fl.large_first_order(xy, pt_off, row_off)
+        xy, pt_off = _fl.permute_polygons(xy, pt_off, perm)
+        val_dev = val[perm]
+    else:
+        val_dev = val
+    pt_off = np.asarray(pt_off, np.int64)
+    xy = np.asarray(xy, np.float64).reshape(-1)
+    host_status, host_pixels = _fl.mask_rows(W, H, max_pixels)
+    action, covered, owned = np.zeros(nb, np.uint8), np.zeros(nb, np.int64), np.zeros(nb, np.int64)
+    for a, b in _fl.mask_batches(host_pixels, batch_pixels):
+        p0, p1 = int(row_off[a]), int(row_off[b])
+        q0, q1 = int(pt_off[p0]), int(pt_off[p1])
+        status, pix_off, act, cov, own, pixels = be.rasterize_polygons(
+            xy[2 * q0:2 * q1], (pt_off[p0:p1 + 1] - q0).astype(np.int32), (row_off[a:b + 1] - p0).astype(np.int32),
+            val_dev[p0:p1], W[a:b], H[a:b], background, max_pixels)
+        pix_off = np.asarray(pix_off, np.int64)
+        if not np.array_equal(np.asarray(status, np.uint8), host_status[a:b]) or not np.array_equal(np.diff(pix_off), host_pixels[a:b]):
+            raise RuntimeError("the device's mask sizes differ from the host's")
+        action[p0:p1], covered[p0:p1], owned[p0:p1] = act, cov, own
+        pixels = np.asarray(pixels, np.uint8)
+        masks = [pixels[pix_off[k]:pix_off[k + 1]].reshape(int(H[a + k]), int(W[a + k]))
+                 if host_status[a + k] == 0 and not too_many[a + k] else None for k in range(b - a)]
+        on_masks(start + a, masks)
+    if perm is not None:
+        back = np.empty(nb, np.int64)
+        back[perm] = np.arange(nb)
+        action, covered, owned = action[back], covered[back], owned[back]
+    chosen = np.flatnonzero(cid >= 0)
+    prow = np.searchsorted(row_off, chosen, side="right") - 1
+    act_c, cov_c, own_c = action[chosen], covered[chosen], owned[chosen]
+    result = _mask_action_names(act_c)
+    done = act_c == 0
+    result[done & (own_c > 0)] = "painted"
+    result[done & (own_c == 0) & (cov_c > 0)] = "hidden"
+    result[done & (cov_c == 0)] = "empty"
+    status_names = np.asarray(MASK_STATUS, object)[host_status]
+    status_names[too_many & (host_status == 0)] = "too_many_instances"
+    count = lambda what: np.bincount(prow[result == what], minlength=n).astype(np.int64)   # noqa: E731
+    acc.rows.append((start + np.arange(n, dtype=np.int64), np.stack([W, H], axis=1), status_names,
+                     np.stack([np.bincount(prow, minlength=n).astype(np.int64), count("painted"), count("hidden"), count("empty")], axis=1)))
+    acc.pixels += int(host_pixels[~too_many].sum())
+    if len(chosen):
+        acc.polys.append((start + prow, obj[chosen].astype(np.int64), np.asarray(names, object)[cls[chosen]], cid[chosen].astype(np.int64),
+                          val[chosen].astype(np.int64), _mask_action_names(act_c), np.stack([cov_c, own_c], axis=1), result))
+
+
+def _mask_rows(cells, n, widths, heights, sources, labels, classes, params, be, stats, on_masks, cells_of=None) -> PolygonMasks:
+    """the chunks of n rows through _mask_chunk -> PolygonMasks without masks (on_masks receives them as they arrive)"""
+    mode, background, class_offset = params[:3]
+    if classes is not None:
+        classes = list(classes)
+        if len(set(classes)) != len(classes) or not all(isinstance(c, str) for c in classes):
+            raise ValueError("classes must be distinct strings")
+        if mode == "semantic" and classes:
+            _mask_values(np.arange(len(classes)), background, class_offset)
+    if labels is not None and len(labels) != n:
+        raise ValueError("one label per row")
+    _, W, H = _audit_sizes(widths, heights, n)
+    acc = _TileTotals(classes)
+    acc.rows, acc.pixels = [], 0
+    for s0, s1, chunk in _chunks(n, cells, cells_of):
+        _mask_chunk(chunk, None if labels is None else labels[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, params, on_masks)
+    rows = _parts_frame(acc.rows, _MASK_ROW_SPEC)
+    polygons = _parts_frame(acc.polys, _MASK_POLY_SPEC, sources)
+    names = list(acc.id_of)
+    k, result = polygons["class_id"].to_numpy(), polygons["result"].to_numpy()
+    count = lambda what: np.bincount(k[result == what], minlength=len(names)).astype(np.int64)   # noqa: E731
+    pixels = np.bincount(k, weights=polygons["owned"].to_numpy(), minlength=len(names)).astype(np.int64)
+    per_class = pd.DataFrame({"class": pd.Series(names, dtype=object),
+                              "value": np.arange(len(names), dtype=np.int64) + class_offset if mode == "semantic" else np.full(len(names), -1, np.int64),
+                              "polygons": np.bincount(k, minlength=len(names)).astype(np.int64),
+                              **{c: count(c) for c in ("painted", "hidden", "empty", "bad_coords", "too_few_points")},
+                              "pixels": pixels, "share": pixels / acc.pixels if acc.pixels else np.zeros(len(names))})
+    status = rows["status"].to_numpy()
+    totals = {"rows": n, **{f"rows_{s}": int((status == s).sum()) for s in (*MASK_STATUS, "too_many_instances")},
+              "polygons": acc.polygons, "selected": len(polygons), "unmatchable_name_polygons": acc.unmatchable,
+              "unknown_class": acc.unknown, **{r: int((result == r).sum()) for r in MASK_RESULTS}, "pixels": acc.pixels,
+              "background_pixels": acc.pixels - int(pixels.sum()), "python_cells": acc.python_cells, "mode": mode,
+              "order": params[3], "background": background, "class_offset": class_offset}
+    if stats is not None:
+        stats.update(totals)
+    return PolygonMasks([None] * n, rows, polygons, per_class, names, totals)
+
+
+def polygon_masks(cells, widths, heights, classes=None, labels=None, mode: str = "semantic", background: int = 0,
+                  class_offset: int = 1, order: str = "annotation", max_pixels_per_row: int = 1 << 26, batch_pixels: int = 1 << 28,
+                  keep_masks: bool = True, backend=None, stats: Optional[dict] = None, sources=None) -> PolygonMasks:
+    """One label mask per row (see the section comment).  Polygons and classes are yolo_tile_label_texts': every polygon with a
+    str name is selected, with ``labels`` (one per row) only those whose name is str(labels[i]); ``classes`` fixes the ids,
+    without it they are numbered from 0 by first appearance.  mode "semantic" paints class id + class_offset (ValueError when
+    a value passes 255 or equals ``background``: up front with ``classes``, else at the chunk where it first happens); mode
+    "instance" paints 1 + the polygon's position among its row's selected polygons, and a row with more than 255 of them is
+    not painted (status too_many_instances).  order "large_first" paints, within a row, the polygons with the larger box of
+    points first, so that small objects stay visible; "annotation" keeps their order.  A row is rasterised only when its size
+    is usable and whole and it has at most max_pixels_per_row pixels.  Rows reach the device in batches of at most
+    batch_pixels pixels (a single larger row goes alone).  -> PolygonMasks."""
+    be = _step_backend(backend, "rasterize_polygons")
+    params = _mask_params(mode, background, class_offset, order, max_pixels_per_row, batch_pixels)
+    cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
+    kept = [None] * len(cells)
+
+    def on_masks(first, masks):
+        if keep_masks:
+            kept[first:first + len(masks)] = [None if m is None else m.copy() for m in masks]
+
+    res = _mask_rows(cells, len(cells), widths, heights, sources, labels, classes, params, be, stats, on_masks)
+    res.masks = kept
+    return res
+
+
+def mask_palette() -> np.ndarray:
+    """the fixed palette of png_mode "P", uint8 [256, 3]: value v gets the colour whose red, green and blue bytes take the bits
+    3k, 3k + 1 and 3k + 2 of v as their bit 7 - k (the colour map of the PASCAL VOC segmentation masks); 0 is black"""
+    v = np.arange(256, dtype=np.uint8)
+    pal = np.zeros((256, 3), np.uint8)
+    for bit in range(8):
+        pal[:, bit % 3] |= ((v >> bit) & 1) << (7 - bit // 3)
+    return pal
+
+
+def _mask_export(run, n: int, sources, output_dir, split: str, png_mode: str, problems_csv, keep_empty_masks: bool, background: int) -> dict:
+    """run(on_masks) -> PolygonMasks; the masks are written as they arrive: masks/<split>/<stem>.png, then masks_<split>.csv,
+    mask_classes.csv and the problems"""
+    from PIL import Image
+
+    out = Path(output_dir)
+    masks_dir = out / "masks" / split
+    masks_dir.mkdir(parents=True, exist_ok=True)
+    palette = mask_palette().reshape(-1).tolist() if png_mode == "P" else None
+    files = np.full(n, "", object)
+
+    def on_masks(first, masks):
+        for k, m in enumerate(masks):
+            if m is None or (not keep_empty_masks and (m == background).all()):
+                continue
+            i = first + k
+            name = _safe_image_stem(sources[i] if sources is not None else None, i) + ".png"
+            im = Image.frombytes(png_mode, (m.shape[1], m.shape[0]), m.tobytes())
+            if palette is not None:
+                im.putpalette(palette)
+            im.save(masks_dir / name)
+            files[i] = f"masks/{split}/{name}"
+
+    res = run(on_masks)
+    manifest = res.rows.assign(mask_file=files)
+    if sources is not None:
+        manifest.insert(0, "source", np.asarray(sources, object) if n else np.zeros(0, object))
+    manifest_path, classes_path = out / f"masks_{split}.csv", out / "mask_classes.csv"
+    manifest.to_csv(manifest_path, index=False, encoding="utf-8-sig")
+    res.per_class.to_csv(classes_path, index=False, encoding="utf-8-sig")
+    if problems_csv:
+        poly = res.polygons
+        poly[poly["result"].isin(("hidden", "empty", "bad_coords", "too_few_points"))].to_csv(problems_csv, index=False, encoding="utf-8-sig")
+    return {**res.totals, "classes": list(res.classes), "mask_files": int((files != "").sum()), "output_dir": str(out),
+            "paths": {"masks": str(masks_dir), "manifest": str(manifest_path), "classes": str(classes_path),
+                      "problems": str(problems_csv) if problems_csv else None}}
+
+
+def _mask_export_params(png_mode, mode, background, class_offset, order, max_pixels_per_row, batch_pixels) -> tuple:
+    if png_mode not in ("L", "P"):
+        raise ValueError(f"png_mode must be 'L' or 'P', got {png_mode!r}")
+    return _mask_params(mode, background, class_offset, order, max_pixels_per_row, batch_pixels)
+
+
+def export_masks_frame(df: pd.DataFrame, output_dir, split: str = "train", json_col: str = ANNOTATION_COL, width_col: str = "width",
+                       height_col: str = "height", source_col: str = "source", label_col: Optional[str] = None, classes=None,
+                       mode: str = "semantic", background: int = 0, class_offset: int = 1, order: str = "annotation",
+                       max_pixels_per_row: int = 1 << 26, batch_pixels: int = 1 << 28, png_mode: str = "L", problems_csv=None,
+                       keep_empty_masks: bool = True, backend=None, stats: Optional[dict] = None) -> dict:
+    """A table's annotation polygons as label masks under output_dir (polygon_masks has the rule and the arguments):
+    masks/<split>/<stem>.png per rasterised row, written with Pillow as each batch arrives (the masks are never all alive at
+    once), the stem from _safe_image_stem(source, position); png_mode "L" writes grey values, "P" the same bytes with
+    mask_palette() attached for viewing; keep_empty_masks=False leaves out the masks that are all background.
+    masks_<split>.csv: one line per row (PolygonMasks.rows plus mask_file); mask_classes.csv: PolygonMasks.per_class;
+    ``problems_csv``: the hidden, empty, bad_coords and too_few_points polygons.
+    -> dict(the totals, classes, mask_files, output_dir, paths)."""
+    be = _step_backend(backend, "rasterize_polygons")
+    params = _mask_export_params(png_mode, mode, background, class_offset, order, max_pixels_per_row, batch_pixels)
+    if label_col is not None and label_col not in df.columns:
+        raise ValueError(f"no column {label_col!r}")
+    cells = df[json_col].to_numpy()
+    widths, heights, _ = _size_columns(df, width_col, height_col)
+    sources = df[source_col].to_numpy() if source_col in df.columns else None
+    labels = df[label_col].to_numpy() if label_col is not None else None
+    run = lambda on_masks: _mask_rows(cells, len(cells), widths, heights, sources, labels, classes, params, be, None, on_masks)   # noqa: E731
+    result = _mask_export(run, len(cells), sources, output_dir, split, png_mode, problems_csv, keep_empty_masks, params[1])
+    if stats is not None:
+        stats.update(result)
+    return result
+
+
+def export_masks_csv(input_csv_path, output_dir, split: str = "train", json_col: str = ANNOTATION_COL, width_col: str = "width",
+                     height_col: str = "height", source_col: str = "source", label_col: Optional[str] = None, classes=None,
+                     mode: str = "semantic", background: int = 0, class_offset: int = 1, order: str = "annotation",
+                     max_pixels_per_row: int = 1 << 26, batch_pixels: int = 1 << 28, png_mode: str = "L", problems_csv=None,
+                     keep_empty_masks: bool = True, backend=None, stats: Optional[dict] = None):
+    """CSV -> label masks, export_masks_frame on the native CSV hand-off (the polygon column is never parsed by pandas).
+    -> export_masks_frame's dict, or None when the file cannot be read or lacks the column."""
+    be = _step_backend(backend, "rasterize_polygons")
+    params = _mask_export_params(png_mode, mode, background, class_offset, order, max_pixels_per_row, batch_pixels)
+
+    def native(table):
+        light = table.light
+        if label_col is not None and label_col not in light.columns:
+            return NotImplemented                        # the pandas route raises export_masks_frame's error
+        n, widths, heights, _, cells_of = _table_rows(table, json_col, width_col, height_col)
+        sources = light[source_col].to_numpy() if source_col in light.columns else None
+        labels = light[label_col].to_numpy() if label_col is not None else None
+        run = lambda on_masks: _mask_rows(None, n, widths, heights, sources, labels, classes, params, be, None, on_masks, cells_of)   # noqa: E731
+        result = _mask_export(run, n, sources, output_dir, split, png_mode, problems_csv, keep_empty_masks, params[1])
+        if stats is not None:
+            stats.update(result)
+        return result
+
+    return _csv_route("export_masks", input_csv_path, json_col, native,
+                      lambda df: export_masks_frame(df, output_dir, split, json_col, width_col, height_col, source_col, label_col,
+                                                    classes, mode, background, class_offset, order, max_pixels_per_row, batch_pixels,
+                                                    png_mode, problems_csv, keep_empty_masks, be, stats))
 
 
 def _dataset_dir_name(excel_path: Path, idx_excel: int, used_dir_names: set) -> tuple:

@@ -229,6 +229,8 @@ void set_k7_variant(int v);
 void set_k14_lane_edges(int v);
 void set_k19_lane_points(int v);
 void set_k19_lds_points(int v);
+void set_k21_strip(int v);
+void set_k21_crossings(int v);
 void set_k6_variant(int v);
 void set_k4_capacity_shift(int v);
 void set_k8_band(int v);
@@ -456,6 +458,14 @@ int dyd_set_option(const char *key, int64_t value) {
     }
     if (!strcmp(key, "k19_lds_points")) {
         set_k19_lds_points((int)value);
+        return DYD_OK;
+    }
+    if (!strcmp(key, "k21_strip")) {   // K21's strip width and crossing-list capacity (tests reach their boundaries at small shapes)
+        set_k21_strip((int)value);
+        return DYD_OK;
+    }
+    if (!strcmp(key, "k21_crossings")) {
+        set_k21_crossings((int)value);
         return DYD_OK;
     }
     if (!strcmp(key, "k7_trace_ptr")) {   // device buffer of 8 x n_tiles u64 (0 = off)

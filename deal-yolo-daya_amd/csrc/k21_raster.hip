@@ -1,0 +1,402 @@
+// k21_raster.hip — K21: label masks, the annotation polygons of every image row scan-converted into one byte per pixel.
+//
+// A pixel is covered by a polygon when an odd number of the polygon's edges cross the pixel's scanline to the right of the
+// pixel's centre (include/dyd.h has the rule, DESIGN §5s the mapping and its cost); it holds the value of the last polygon of
+// its row that covers it, or the background.  The polygon code is K13's: k13_size_ok for the sizes, Poly / k13_prepare for the
+// action and the box of a two-point polygon, k13_scan_inclusive for both offset arrays, last_le for the row search.
+//
+// Layout in HBM: xy = P x (x, y) f64, pt_off = B+1 int32, row_off = N+1 int32, val = B int32, width / height = N f64.
+// Outputs: row_status = N u8, pix_off = N+1 int64, action = B u8, covered / owned = B int64, pixels.  Scratch: 32 bytes per
+// polygon (the bounding box of V), the rows' item offsets and the scan's partial sums.
+//
+// Steps (no hand-off between workgroups inside a launch):
+//   1. rows, a lane per row: status, pixel count and item count; two scans give pix_off and item_off;
+//   2. polygons, a lane per polygon: the action and the bounding box; the host reads the pixel total and the item count;
+//   3. paint, a wave (one workgroup) per item = (row, scanline, strip of `strip` columns), items taken grid-stride.  The wave
+//      keeps the strip's owner per pixel (a polygon index), a parity byte per pixel and a list of crossings in LDS.  Per polygon
+//      of the row, in order, culled by its box: lanes take edges in chunks of 64 and compute xs for the crossing ones (one
+//      division per edge and scanline), a ballot and a popcount compact them into the list, lanes then take pixels and XOR in
+//      xs > xc for the listed crossings.  A full list is applied and emptied: parity is linear, so any edge count is exact.
+//      After the polygon's last edge the pixels of parity 1 take it as owner; their count goes to covered and owned, every
+//      overwritten owner is decremented (aggregated by old owner inside the wave), all by integer atomics, so no result
+//      depends on the schedule.  At the end of the item the owners are translated to val / background in LDS and stream out in
+//      16-byte stores, byte by byte where the destination's alignment cuts a chunk.
+#include "k13_poly.h"
+#include "k13_scan.h"
+#include "poly_table.h"
+
+namespace dyd {
+
+constexpr int K21_BLOCK = 256;
+constexpr int K21_STRIP = 1024;              // columns per item (default and most); 4 + 1 + 1 bytes of LDS per column
+constexpr int K21_CROSSINGS = 256;           // capacity of the crossing list (default and most)
+constexpr int64_t K21_MAX_PIXELS = 1LL << 30;
+constexpr int64_t K21_MAX_GRID = 1 << 20;    // paint workgroups; the items beyond are taken grid-stride
+enum : uint8_t { RASTER_DONE = 0, RASTER_NO_RASTER = 5 };   // the other actions are K13's codes
+
+// row status (0 rasterised, 1 no_size, 2 fractional_size, 3 too_large); for status 0 the image's width and height
+__device__ __forceinline__ uint8_t k21_row_size(double W, double H, int64_t max_pixels, int64_t *w, int64_t *h) {
+    *w = *h = 0;
+    if (!k13_size_ok(W) || !k13_size_ok(H)) return 1;
+    if (W != floor(W) || H != floor(H)) return 2;
+    const int64_t iw = (int64_t)W, ih = (int64_t)H;
+    if (iw > max_pixels || ih > max_pixels || iw * ih > max_pixels) return 3;   // the product stays at or below 2^60
+    *w = iw;
+    *h = ih;
+    return 0;
+}
+
+// ---- 1. rows: a lane per row -----------------------------------------------------------------------------------
+__global__ __launch_bounds__(K21_BLOCK) void k21_rows_kernel(const double *__restrict__ width, const double *__restrict__ height,
+                                                             int64_t n_rows, int64_t max_pixels, int strip,
+                                                             uint8_t *__restrict__ row_status, int64_t *__restrict__ pix_off,
+                                                             int64_t *__restrict__ item_off) {
+    const int64_t i = (int64_t)blockIdx.x * K21_BLOCK + threadIdx.x;
+    if (i >= n_rows) return;
+    int64_t w, h;
+    row_status[i] = k21_row_size(width[i], height[i], max_pixels, &w, &h);
+    pix_off[i + 1] = w * h;
+    item_off[i + 1] = h * ((w + strip - 1) / strip);
+    if (i == 0) pix_off[0] = item_off[0] = 0;
+}
+
+// ---- 2. polygons: a lane per polygon ---------------------------------------------------------------------------
+// action (255: val < 0); info[4p .. 4p+3] = x1, y1, x2, y2 of the points, which is the box of V
+__global__ __launch_bounds__(K21_BLOCK) void k21_poly_kernel(const double *__restrict__ xy, const int32_t *__restrict__ pt_off,
+                                                             const int32_t *__restrict__ row_off, const int32_t *__restrict__ val,
+                                                             const uint8_t *__restrict__ row_status, int64_t n_rows, int64_t n_polys,
+                                                             int64_t n_points, uint8_t *__restrict__ action, double *__restrict__ info) {
+    __shared__ int32_t rows[2];
+    const int64_t p0 = (int64_t)blockIdx.x * K21_BLOCK, p1 = min(p0 + K21_BLOCK, n_polys);
+    poly_tile_rows(row_off, n_rows, p0, p1, rows);
+    const int64_t p = p0 + threadIdx.x;
+    if (p >= p1) return;
+    const int64_t r = last_le(row_off, rows[0], rows[1], p);
+    uint8_t act;
+    double x1 = 0.0, y1 = 0.0, x2 = 0.0, y2 = 0.0;
+    if (val[p] < 0) {
+        act = SEG_UNSELECTED;
+    } else if (row_status[r] != 0) {
+        act = RASTER_NO_RASTER;
+    } else {
+        const int32_t a = max(pt_off[p], 0), b = (int32_t)min((int64_t)max(pt_off[p + 1], a), n_points);
+        Poly pg;
+        act = k13_prepare(xy, a, b, pg);
+        if (act == 0xff) {
+            act = RASTER_DONE;
+            x1 = pg.x1; y1 = pg.y1; x2 = pg.x2; y2 = pg.y2;
+        }
+    }
+    action[p] = act;
+    double *q = info + 4 * p;
+    q[0] = x1; q[1] = y1; q[2] = x2; q[3] = y2;
+}
+
+// ---- 3. paint: a wave per item ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(kWave) void k21_paint_kernel(const double *__restrict__ xy, const int32_t *__restrict__ pt_off,
+                                                          const int32_t *__restrict__ row_off, const int32_t *__restrict__ val,
+                                                          const double *__restrict__ width, const double *__restrict__ height,
+                                                          int64_t n_rows, int64_t n_polys, int64_t n_points, int background,
+                                                          int strip, int cap, const uint8_t *__restrict__ row_status,
+                                                          const int64_t *__restrict__ pix_off, const int64_t *__restrict__ item_off,
+                                                          int64_t n_items, const uint8_t *__restrict__ action,
+                                                          const double *__restrict__ info, unsigned long long *__restrict__ covered,
+                                                          unsigned long long *__restrict__ owned, uint8_t *__restrict__ pixels) {
+    __shared__ int32_t owner[K21_STRIP];
+    __shared__ uint8_t parity[K21_STRIP];
+    __shared__ double list[K21_CROSSINGS];
+    __shared__ __attribute__((aligned(16))) uint8_t img[K21_STRIP + 16];
+    const int lane = threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const int64_t r = last_le(item_off, 0, n_rows - 1, item);
+        const int64_t local = item - item_off[r];
+        const int64_t W = (int64_t)width[r], H = (int64_t)height[r];
+        const int64_t n_strips = (W + strip - 1) / strip;
+        if (row_status[r] != 0 || local < 0 || local >= H * n_strips) continue;   // never for a sound item_off
+        const int64_t j = local / n_strips, x0 = (local - j * n_strips) * strip;
+        const int npx = (int)min((int64_t)strip, W - x0);
+        const double yc = (double)j + 0.5, xc_first = (double)x0 + 0.5, xc_last = (double)(x0 + npx - 1) + 0.5;
+        for (int px = lane; px < npx; px += kWave) {
+            owner[px] = -1;
+            parity[px] = 0;
+        }
+        __syncthreads();
+        // the crossings listed so far, XORed into the parity of every pixel of the strip
+        auto apply = [&](int n_listed) __attribute__((always_inline)) {
+            __syncthreads();
+            for (int px = lane; px < npx; px += kWave) {
+                const double xc = (double)(x0 + px) + 0.5;
+                uint8_t par = parity[px];
+                for (int c = 0; c < n_listed; ++c) par ^= (uint8_t)(list[c] > xc);
+                parity[px] = par;
+            }
+            __syncthreads();
+        };
+        const int64_t pa = max((int64_t)row_off[r], (int64_t)0), pb = min((int64_t)row_off[r + 1], n_polys);
+        for (int64_t p = pa; p < pb; ++p) {
+            if (action[p] != RASTER_DONE) continue;
+            const double *q = info + 4 * p;
+            const double bx1 = q[0], by1 = q[1], bx2 = q[2], by2 = q[3];
+            // The cull.  No edge crosses the scanline unless by1 <= yc < by2.  A crossing lies within an ulp of [bx1, bx2]:
+            // to the right of the box (with a pixel to spare) no crossing has xs > xc; to the left every one has, and a closed
+            // outline crosses a scanline an even number of times, so the parity stays 0.
+            if (!(by1 <= yc) || !(yc < by2) || xc_first >= bx2 + 1.0 || xc_last <= bx1 - 1.0) continue;
+            const int32_t a = max(pt_off[p], 0), b = (int32_t)min((int64_t)max(pt_off[p + 1], a), n_points);
+            const double2 *pts = reinterpret_cast<const double2 *>(xy) + a;
+            const bool two = b - a == 2;
+            const int m = two ? 4 : b - a;
+            int n_listed = 0;
+            for (int k0 = 0; k0 < m; k0 += kWave) {
+                const int k = k0 + lane;
+                bool cross = false;
+                double xs = 0.0;
+                if (k < m) {
+                    const int kn = k + 1 == m ? 0 : k + 1;
+                    double ax, ay, bx, by;
+                    if (two) {   // the corners (x1, y1), (x2, y1), (x2, y2), (x1, y2) of the box
+                        ax = k == 0 || k == 3 ? bx1 : bx2;
+                        ay = k < 2 ? by1 : by2;
+                        bx = kn == 0 || kn == 3 ? bx1 : bx2;
+                        by = kn < 2 ? by1 : by2;
+                    } else {
+                        const double2 A = pts[k], B = pts[kn];
+                        ax = A.x; ay = A.y; bx = B.x; by = B.y;
+                    }
+                    const bool swap = ay > by || (ay == by && ax > bx);   // the canonical direction
+                    const double Px = swap ? bx : ax, Py = swap ? by : ay, Qx = swap ? ax : bx, Qy = swap ? ay : by;
+                    if (Py != Qy && Py <= yc && yc < Qy) {
+                        cross = true;
+                        const double t = yc - Py, d = Qx - Px;
+                        const double n = t * d;
+                        xs = Px + n / (Qy - Py);
+                    }
+                }
+                const unsigned long long mask = __ballot(cross);
+                const int rank = __popcll(mask & below), count = __popcll(mask);
+                for (int done = 0; done < count;) {
+                    const int take = min(cap - n_listed, count - done);
+                    if (cross && rank >= done && rank < done + take) list[n_listed + rank - done] = xs;
+                    n_listed += take;
+                    done += take;
+                    if (n_listed == cap) {
+                        apply(n_listed);
+                        n_listed = 0;
+                    }
+                }
+            }
+            apply(n_listed);
+            // the covered pixels change hands
+            int n_covered = 0;
+            for (int base = 0; base < npx; base += kWave) {
+                const int px = base + lane;
+                const bool cov = px < npx && parity[px] != 0;
+                int32_t old = -1;
+                if (cov) {
+                    old = owner[px];
+                    owner[px] = (int32_t)p;
+                    parity[px] = 0;
+                }
+                n_covered += __popcll(__ballot(cov));
+                const bool lost = cov && old >= 0;
+                unsigned long long todo = __ballot(lost);
+                while (todo) {   // one atomic per distinct old owner among these 64 pixels
+                    const int leader = __ffsll((long long)todo) - 1;
+                    const int32_t o = __shfl(old, leader);
+                    const unsigned long long same = __ballot(lost && old == o);
+                    if (lane == leader) atomicAdd(owned + o, 0ull - (unsigned long long)__popcll(same));
+                    todo &= ~same;
+                }
+            }
+            if (lane == 0 && n_covered > 0) {
+                atomicAdd(covered + p, (unsigned long long)n_covered);
+                atomicAdd(owned + p, (unsigned long long)n_covered);
+            }
+        }
+        // owners -> bytes.  img[0] stands for the 16-byte aligned address at or below the strip's first pixel.
+        uint8_t *dst = pixels + pix_off[r] + j * W + x0;
+        const int phase = (int)(reinterpret_cast<uintptr_t>(dst) & 15u);
+        __syncthreads();
+        for (int px = lane; px < npx; px += kWave) {
+            const int32_t o = owner[px];
+            img[phase + px] = (uint8_t)(o < 0 ? background : val[o]);
+        }
+        __syncthreads();
+        const int lo = phase, hi = phase + npx;
+        for (int c = lane; 16 * c < hi; c += kWave) {
+            const int at = 16 * c;
+            if (at >= lo && at + 16 <= hi) {
+                *reinterpret_cast<uint4 *>(dst - phase + at) = *reinterpret_cast<const uint4 *>(img + at);
+            } else {
+                for (int k = max(at, lo); k < min(at + 16, hi); ++k) dst[k - phase] = img[k];
+            }
+        }
+        __syncthreads();   // img, owner and parity are written again by the next item
+    }
+}
+
+// dyd_set_option("k21_strip" / "k21_crossings", n): the strip's width and the list's capacity; <= 0 restores the default, larger
+// values are capped
+static int g_k21_strip = K21_STRIP, g_k21_crossings = K21_CROSSINGS;
+
+void set_k21_strip(int v) { g_k21_strip = v > 0 ? (v < K21_STRIP ? v : K21_STRIP) : K21_STRIP; }
+void set_k21_crossings(int v) { g_k21_crossings = v > 0 ? (v < K21_CROSSINGS ? v : K21_CROSSINGS) : K21_CROSSINGS; }
+
+struct RasterOut {
+    uint8_t *row_status;
+    int64_t *pix_off;
+    uint8_t *action;
+    int64_t *covered, *owned;
+};
+
+static int raster_params(int32_t background, int64_t max_pixels) {
+    DYD_REQUIRE(background >= 0 && background <= 255, "background must lie in 0..255");
+    DYD_REQUIRE(max_pixels >= 1 && max_pixels <= K21_MAX_PIXELS, "max_pixels_per_row must lie in 1..2^30");
+    return DYD_OK;
+}
+
+// Steps 1 to 3 on device pointers.  get_pixels(total, &pixels, &cap) is asked for the pixel buffer once its size is known
+// (pixels NULL: measure only).  *total_out is a host value.
+template <class GetPixels>
+static int raster_launch(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *val, const double *width,
+                         const double *height, int64_t n_rows, int64_t n_polys, int64_t n_points, int32_t background,
+                         int64_t max_pixels, const RasterOut &o, int64_t *total_out, GetPixels get_pixels, hipStream_t st) {
+    const int strip = g_k21_strip, cap = g_k21_crossings;
+    const size_t info_bytes = 32 * (size_t)max(n_polys, (int64_t)1), item_bytes = 8 * (size_t)(n_rows + 1);
+    void *scr = nullptr;
+    int rc = get_scratch(info_bytes + item_bytes + 8 * (size_t)k13_scan_parts(n_rows), &scr, st);
+    if (rc) return rc;
+    double *info = static_cast<double *>(scr);
+    int64_t *item_off = reinterpret_cast<int64_t *>(info + info_bytes / 8), *part = item_off + n_rows + 1;
+    auto fail = [&](int code) {
+        release_scratch(st);
+        return code;
+    };
+    hipLaunchKernelGGL(k21_rows_kernel, dim3((unsigned)ceil_div(n_rows, (int64_t)K21_BLOCK)), dim3(K21_BLOCK), 0, st, width, height,
+                       n_rows, max_pixels, strip, o.row_status, o.pix_off, item_off);
+    k13_scan_inclusive(o.pix_off + 1, n_rows, part, st);
+    k13_scan_inclusive(item_off + 1, n_rows, part, st);   // after the first scan in the stream, so the partial sums are free again
+    if (n_polys > 0)
+        hipLaunchKernelGGL(k21_poly_kernel, dim3((unsigned)ceil_div(n_polys, (int64_t)K21_BLOCK)), dim3(K21_BLOCK), 0, st, xy, pt_off,
+                           row_off, val, o.row_status, n_rows, n_polys, n_points, o.action, info);
+    int64_t total = 0, n_items = 0;
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipMemcpyAsync(&total, o.pix_off + n_rows, 8, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipMemcpyAsync(&n_items, item_off + n_rows, 8, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) {
+        set_error("K21: the row and polygon steps failed: %s", hipGetErrorString(err));
+        return fail(err == hipErrorOutOfMemory ? DYD_ERR_OOM : DYD_ERR_HIP);
+    }
+    *total_out = total;
+    uint8_t *pixels = nullptr;
+    int64_t pix_cap = 0;
+    if ((rc = get_pixels(total, &pixels, &pix_cap))) return fail(rc);
+    if (!pixels) return fail(DYD_OK);
+    if (total > pix_cap) {
+        set_error("K21: pixel buffer too small (%lld bytes needed, %lld given)", (long long)total, (long long)pix_cap);
+        return fail(DYD_ERR_RANGE);
+    }
+    if (n_polys > 0) {
+        hipError_t e = hipMemsetAsync(o.covered, 0, 8 * (size_t)n_polys, st);
+        if (e == hipSuccess) e = hipMemsetAsync(o.owned, 0, 8 * (size_t)n_polys, st);
+        if (e != hipSuccess) {
+            set_error("K21: clearing the counters failed: %s", hipGetErrorString(e));
+            return fail(DYD_ERR_HIP);
+        }
+    }
+    if (n_items > 0)
+        hipLaunchKernelGGL(k21_paint_kernel, dim3((unsigned)(n_items < K21_MAX_GRID ? n_items : K21_MAX_GRID)), dim3(kWave), 0, st, xy, pt_off, row_off, val,
+                           width, height, n_rows, n_polys, n_points, (int)background, strip, cap, o.row_status, o.pix_off, item_off,
+                           n_items, o.action, info, reinterpret_cast<unsigned long long *>(o.covered),
+                           reinterpret_cast<unsigned long long *>(o.owned), pixels);
+    release_scratch(st);
+    DYD_HIP(hipGetLastError());
+    return DYD_OK;
+}
+
+}  // namespace dyd
+
+using namespace dyd;
+
+extern "C" {
+
+int dyd_rasterize_polygons_dev(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *val, const double *width,
+                               const double *height, int64_t n_rows, int64_t n_polys, int64_t n_points, int32_t background,
+                               int64_t max_pixels_per_row, uint8_t *out_row_status, int64_t *out_pix_off, uint8_t *out_action,
+                               int64_t *out_covered, int64_t *out_owned, uint8_t *out_pixels_or_null, int64_t pix_cap,
+                               int64_t *out_total, void *stream) {
+    DYD_API_ENTER();
+    int rc = raster_params(background, max_pixels_per_row);
+    if (rc) return rc;
+    DYD_REQUIRE(n_rows >= 0 && n_polys >= 0 && n_points >= 0 && pix_cap >= 0, "negative size");
+    DYD_REQUIRE(n_polys < (1LL << 31) && n_points < (1LL << 31) && n_rows < (1LL << 31), "size too large");
+    DYD_REQUIRE(out_pix_off && out_total, "null pointer");
+    hipStream_t st = pick_stream(stream);
+    if (n_rows == 0) {
+        DYD_HIP(hipMemsetAsync(out_pix_off, 0, 8, st));
+        *out_total = 0;
+        return DYD_OK;
+    }
+    DYD_REQUIRE(row_off && width && height && out_row_status, "null pointer");
+    DYD_REQUIRE(n_polys == 0 || (pt_off && val && out_action), "null pointer");
+    DYD_REQUIRE(n_polys == 0 || !out_pixels_or_null || (out_covered && out_owned), "null pointer");
+    DYD_REQUIRE(n_points == 0 || xy, "null pointer");
+    const RasterOut o{out_row_status, out_pix_off, out_action, out_covered, out_owned};
+    auto get_pixels = [&](int64_t, uint8_t **pixels, int64_t *cap) {
+        *pixels = out_pixels_or_null;
+        *cap = pix_cap;
+        return DYD_OK;
+    };
+    return raster_launch(xy, pt_off, row_off, val, width, height, n_rows, n_polys, n_points, background, max_pixels_per_row, o,
+                         out_total, get_pixels, st);
+}
+
+int dyd_rasterize_polygons(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *val, const double *width,
+                           const double *height, int64_t n_rows, int32_t background, int64_t max_pixels_per_row,
+                           uint8_t *out_row_status, int64_t *out_pix_off, uint8_t *out_action, int64_t *out_covered,
+                           int64_t *out_owned, uint8_t **out_pixels, int64_t *out_pixels_len) {
+    DYD_API_ENTER();
+    int rc = raster_params(background, max_pixels_per_row);
+    if (rc) return rc;
+    DYD_REQUIRE(n_rows >= 0, "negative size");
+    DYD_REQUIRE(n_rows < (1LL << 31), "size too large");
+    DYD_REQUIRE(out_pix_off && out_pixels && out_pixels_len, "null pointer");
+    *out_pixels = nullptr;
+    *out_pixels_len = 0;
+    out_pix_off[0] = 0;
+    if (n_rows == 0) return DYD_OK;
+    int64_t n_polys = 0, n_points = 0;
+    rc = poly_table_check(xy, pt_off, row_off, n_rows, width, height, out_row_status != nullptr,
+                          val && out_action && out_covered && out_owned, nullptr, 0, &n_polys, &n_points);
+    if (rc) return rc;
+    for (int64_t p = 0; p < n_polys; ++p) DYD_REQUIRE(val[p] <= 255, "val above 255");
+    hipStream_t st = ctx().stream;
+    PolyTableDev t;
+    DevBuf d_val, d_status, d_poff, d_act, d_cov, d_own, d_pix;
+    const size_t nb8 = 8 * (size_t)n_polys;
+    if ((rc = t.upload(xy, pt_off, row_off, width, height, n_rows, n_polys, n_points)) ||
+        (rc = poly_column(d_val, val, 4 * (size_t)n_polys)) || (rc = d_status.alloc((size_t)n_rows)) ||
+        (rc = d_poff.alloc(8 * (size_t)(n_rows + 1))) || (rc = d_act.alloc((size_t)n_polys)) || (rc = d_cov.alloc(nb8)) ||
+        (rc = d_own.alloc(nb8)))
+        return rc;
+    const RasterOut o{d_status.as<uint8_t>(), d_poff.as<int64_t>(), d_act.as<uint8_t>(), d_cov.as<int64_t>(), d_own.as<int64_t>()};
+    auto get_pixels = [&](int64_t total, uint8_t **pixels, int64_t *cap) {
+        const int r = d_pix.alloc((size_t)total);
+        *pixels = d_pix.as<uint8_t>();
+        *cap = total;
+        return r;
+    };
+    int64_t total = 0;
+    KernelTimer timer(st);
+    rc = raster_launch(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), d_val.as<int32_t>(), t.w.as<double>(),
+                       t.h.as<double>(), n_rows, n_polys, n_points, background, max_pixels_per_row, o, &total, get_pixels, st);
+    if (rc) return rc;
+    timer.finish();
+    return hand_back_text(d_pix.p, total,
+                          {{out_row_status, d_status.p, (size_t)n_rows}, {out_pix_off, d_poff.p, 8 * (size_t)(n_rows + 1)},
+                           {out_action, d_act.p, (size_t)n_polys}, {out_covered, d_cov.p, nb8}, {out_owned, d_own.p, nb8}},
+                          st, out_pixels, out_pixels_len);
+}
+
+}  // extern "C"

@@ -491,3 +491,60 @@ def tile_boxes(width, height, nx, ny, tile_w: int, tile_h: int, step_x: int, ste
     x0 = np.where(Lx <= tile_w, 0, np.minimum(tx * step_x, Lx - tile_w))
     y0 = np.where(Ly <= tile_h, 0, np.minimum(ty * step_y, Ly - tile_h))
     return row, tile, x0, y0, np.minimum(Lx, tile_w), np.minimum(Ly, tile_h)
+
+
+# ---- the mask step's rows, order and batches (K21; include/dyd.h has the rule) ------------------------------------
+MASK_STATUS = ("rasterised", "no_size", "fractional_size", "too_large")   # K21 row status codes 0..3
+
+
+def mask_rows(width, height, max_pixels_per_row: int = 1 << 26) -> tuple:
+    """K21's row rule from the same tests as the kernel -> (status u8 [n], pixels int64 [n]); pixels = W * H for a row that is
+    rasterised, else 0"""
+    W, H = np.asarray(width, np.float64), np.asarray(height, np.float64)
+    with np.errstate(invalid="ignore"):
+        ok = (W > 0) & (W < _TILE_LIMIT) & (H > 0) & (H < _TILE_LIMIT)
+        whole = ok & (W == np.floor(W)) & (H == np.floor(H))
+    w, h = np.where(whole, W, 0).astype(np.int64), np.where(whole, H, 0).astype(np.int64)
+    cap = max_pixels_per_row + 1                         # the product of the clipped sizes stays below 2^62
+    large = whole & (np.minimum(w, cap) * np.minimum(h, cap) > max_pixels_per_row)
+    status = np.where(~ok, 1, np.where(~whole, 2, np.where(large, 3, 0))).astype(np.uint8)
+    return status, np.where(status == 0, w * h, 0).astype(np.int64)
+
+
+def mask_batches(pixels, batch_pixels: int) -> list:
+    """consecutive row ranges [(a, b)] whose pixel totals stay within batch_pixels; a single larger row goes alone"""
+    out, a, total = [], 0, 0
+    for i, v in enumerate(np.asarray(pixels, np.int64).tolist()):
+        if i > a and total + v > batch_pixels:
+            out.append((a, i))
+            a, total = i, 0
+        total += v
+    if len(pixels) > a:
+        out.append((a, len(pixels)))
+    return out
+
+
+def large_first_order(xy, pt_off, row_off) -> np.ndarray:
+    """the polygons of a table, within each row stably sorted by decreasing (max x - min x) * (max y - min y) of their points
+    (NaN and a polygon without points sort as 0) -> perm int64 [B]: the polygon at new position k is the old perm[k]"""
+    pt_off, row_off = np.asarray(pt_off, np.int64), np.asarray(row_off, np.int64)
+    nb = len(pt_off) - 1
+    pts = np.asarray(xy, np.float64).reshape(-1, 2)
+    area = np.zeros(nb)
+    full = np.flatnonzero(np.diff(pt_off) > 0)
+    if len(full):
+        first = pt_off[:-1][full]                        # polygons without points own no entry, so these delimit the others'
+        with np.errstate(invalid="ignore", over="ignore"):
+            ext = [np.maximum.reduceat(pts[:, c], first) - np.minimum.reduceat(pts[:, c], first) for c in (0, 1)]
+            area[full] = np.nan_to_num(ext[0] * ext[1], nan=0.0)
+    row = np.repeat(np.arange(len(row_off) - 1, dtype=np.int64), np.diff(row_off))
+    return np.lexsort((-area, row)).astype(np.int64)     # lexsort is stable
+
+
+def permute_polygons(xy, pt_off, perm) -> tuple:
+    """-> (xy, pt_off int32) of the table whose polygon k is the given table's polygon perm[k]"""
+    pt_off, perm = np.asarray(pt_off, np.int64), np.asarray(perm, np.int64)
+    count = np.diff(pt_off)[perm]
+    new_off = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
+    src = np.repeat(pt_off[:-1][perm] - new_off[:-1], count) + np.arange(int(new_off[-1]), dtype=np.int64)
+    return np.asarray(xy, np.float64).reshape(-1, 2)[src].reshape(-1), new_off.astype(np.int32)

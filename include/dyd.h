@@ -640,6 +640,59 @@ int dyd_yolo_tile_lines_dev(const double *xy, const int32_t *pt_off, const int32
                             int32_t *out_tiles_dropped, int64_t *out_n_tiles, uint8_t *out_text_or_null, int64_t text_cap,
                             int64_t *out_total, void *stream);
 
+/* ---- K21: label masks — the annotation polygons of every image row rasterised into one byte per pixel (the mask step) ----
+ * All arithmetic is IEEE f64, operation by operation, without contraction, as in K13; the division is the correctly rounded one.
+ * The table is K20's: xy, pt_off, row_off, width / height per row, and val[p] (int32), the byte painted for polygon p:
+ * val[p] < 0: the polygon is not selected (action 255); val[p] > 255 is DYD_ERR_INVALID in the host entry and the caller's
+ * duty in the _dev entry (the low byte is painted).
+ * Parameters: background in 0..255; max_pixels_per_row in 1..2^30.  Anything else is DYD_ERR_INVALID.
+ * Row status, the first rule that applies:
+ *   1 no_size          K13's size test fails for W or H (not finite, not in (0, 2^43));
+ *   2 fractional_size  W or H is not a whole number;
+ *   3 too_large        W > max_pixels_per_row or H > max_pixels_per_row or W * H > max_pixels_per_row, tested in that order
+ *                      (so nothing overflows);
+ *   0 rasterised       otherwise.
+ * pix_off[i] is the exclusive sum of W * H over the rows of status 0 (other rows add 0); total = pix_off[n_rows].  A row's mask
+ * is H lines of W bytes at pix_off[i], row-major, no padding.
+ * Polygon action, the first rule that applies:
+ *   255 not selected    val[p] < 0;
+ *   5 no_raster         the row's status is not 0;
+ *   2 bad_coords        K13's rule: a coordinate is not finite or |v| >= 2^43;
+ *   3 too_few_points    fewer than 2 points;
+ *   0 rasterised        otherwise.  Only action 0 paints.
+ * V is K13's vertex list (two points: the four corners (x1, y1), (x2, y1), (x2, y2), (x1, y2) of their box).
+ * Coverage.  Pixel (i, j) has the centre xc = i + 0.5, yc = j + 0.5.  For each cyclic edge A = V[k], B = V[(k + 1) % m]:
+ *   - canonical direction: if A.y > B.y, or A.y == B.y and A.x > B.x, the endpoints are swapped, giving P (the first) and Q;
+ *   - an edge with P.y == Q.y never crosses; the edge crosses scanline j when P.y <= yc and yc < Q.y;
+ *   - then t = yc - P.y, d = Q.x - P.x, n = t * d, q = n / (Q.y - P.y), xs = P.x + q.
+ * The polygon covers the pixel when the number of crossing edges with xs > xc is odd (the even-odd rule; a centre on a left or
+ * top edge is in, on a right or bottom edge out).  The canonical direction makes an edge shared by two polygons give the same
+ * bits in both, so adjacent polygons neither overlap nor leave a gap.
+ * Paint.  A pixel holds val[p] of the last polygon in table order (within its row) that covers it, background when none does.
+ * Counters, i64 per polygon: covered[p] = the pixels of the image that p covers; owned[p] = the pixels that hold p's paint at the
+ * end (ownership is by polygon: an equal val does not merge two polygons); both 0 unless the action is 0.
+ * xy [2*n_points] (16-B aligned), pt_off [n_polys+1], row_off [n_rows+1], val [n_polys], width / height [n_rows].
+ * out_row_status : the codes above                                  u8  [n_rows]
+ * out_pix_off    : the mask of row i is bytes [off[i], off[i+1])    i64 [n_rows+1]
+ * out_action     : the codes above                                  u8  [n_polys]
+ * out_covered / out_owned                                           i64 [n_polys]
+ * dyd_rasterize_polygons     : host pointers; *out_pixels is allocated by the library (release with dyd_host_free).
+ * dyd_rasterize_polygons_dev : device pointers, enqueued on stream.  out_pixels_or_null == NULL only measures: status, pix_off,
+ *                              action and *out_total (a HOST int64); the counters are not touched.  Otherwise pix_cap bytes are
+ *                              available, and DYD_ERR_RANGE is returned, with the needed size in *out_total and no pixel or
+ *                              counter written, when that is too little.  The pixel pointer may have any byte alignment.
+ *                              n_polys = row_off[n_rows], n_points = pt_off[n_polys].
+ * n_rows, n_polys and n_points stay below 2^31 (DYD_ERR_INVALID otherwise). */
+int dyd_rasterize_polygons(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *val, const double *width,
+                           const double *height, int64_t n_rows, int32_t background, int64_t max_pixels_per_row,
+                           uint8_t *out_row_status, int64_t *out_pix_off, uint8_t *out_action, int64_t *out_covered,
+                           int64_t *out_owned, uint8_t **out_pixels, int64_t *out_pixels_len);
+int dyd_rasterize_polygons_dev(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *val, const double *width,
+                               const double *height, int64_t n_rows, int64_t n_polys, int64_t n_points, int32_t background,
+                               int64_t max_pixels_per_row, uint8_t *out_row_status, int64_t *out_pix_off, uint8_t *out_action,
+                               int64_t *out_covered, int64_t *out_owned, uint8_t *out_pixels_or_null, int64_t pix_cap,
+                               int64_t *out_total, void *stream);
+
 /* ---- native flatten / emit (HOST code, multithreaded) ------------------------------
  * Schema-specialised JSON scanner + canonical re-emitter that replaces json.loads / json.dumps inside
  * parse_and_replace_ptlist (processor.py:262-281), extract_width_height (:285-292) and extract_boxes

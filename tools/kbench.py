@@ -3,7 +3,8 @@
 interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant.
 
     python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k18: box comparison beside K2 and K9; k13: segmentation lines beside K7;
-     k14: polygon audit; k14tier: its in-lane / wave threshold; simplify: polygon simplification (K19) beside K14 on rings of 8, 64 and 1024 points; k16: COCO annotation objects beside K13; k17: oriented-box lines beside K13; tile: tiled label lines (K20) beside K13)
+     k14: polygon audit; k14tier: its in-lane / wave threshold; simplify: polygon simplification (K19) beside K14 on rings of 8, 64 and 1024 points; k16: COCO annotation objects beside K13; k17: oriented-box lines beside K13; tile: tiled label lines (K20) beside K13;
+     k21: label masks (K21) on many small and few large images, beside Pillow on one core)
 """
 import argparse
 import json
@@ -601,6 +602,68 @@ def main():
                    ms_vs_k13=round(med20 / med13, 3), pairs_per_polygon=round(pairs / B, 3), text_vs_k13=round(T20 / max(T13, 1), 3))
             del text20
         del text13
+    if "k21" in only:
+        import ctypes as C
+        import time
+        # K21 (label masks): measure-only and full, ms, pixels/s and bytes moved (1 byte written per pixel, the table read once,
+        # the small outputs), on two tables: many small images (the first rows of the synthetic table, the k20 leg's polygon mix,
+        # scaled from 1920 x 1080 to 256 x 144) and few large images (8 of 4096 x 4096 with 4 outlines of 2000 vertices each).
+        # Beside them, as a yardstick of time only (its fill rule differs, so its pixels are not compared), Pillow's
+        # ImageDraw.polygon over the same tables on one core.
+        total = C.c_int64()
+
+        def k21_leg(name, xy_, pt_, roff, nr, nb, npts, W, H):
+            w = torch.full((nr,), float(W), dtype=torch.float64, device=dev); h = torch.full((nr,), float(H), dtype=torch.float64, device=dev)
+            val = (torch.arange(nb, device=dev, dtype=torch.int32) % 20 + 1).contiguous()
+            status = torch.empty(nr, dtype=torch.uint8, device=dev); poff = torch.empty(nr + 1, dtype=torch.int64, device=dev)
+            act = torch.empty(nb, dtype=torch.uint8, device=dev)
+            cov = torch.empty(nb, dtype=torch.int64, device=dev); own = torch.empty(nb, dtype=torch.int64, device=dev)
+            a21 = (xy_.data_ptr(), pt_.data_ptr(), roff.data_ptr(), val.data_ptr(), w.data_ptr(), h.data_ptr(), nr, nb, npts, 0, 1 << 26,
+                   status.data_ptr(), poff.data_ptr(), act.data_ptr(), cov.data_ptr(), own.data_ptr())
+            ck(L.dyd_rasterize_polygons_dev(*a21, None, 0, C.byref(total), sp), "k21 measure")
+            T = total.value
+            pix = torch.empty(T, dtype=torch.uint8, device=dev)
+            medm, mnm = timeit(lambda: ck(L.dyd_rasterize_polygons_dev(*a21, None, 0, C.byref(total), sp), "k21 measure"))
+            med, mn = timeit(lambda: ck(L.dyd_rasterize_polygons_dev(*a21, pix.data_ptr(), T, C.byref(total), sp), "k21"))
+            table_bytes = 16 * npts + 4 * (nb + 1) + 4 * nb + 4 * (nr + 1) + 16 * nr
+            small_out = nr + 8 * (nr + 1) + nb
+            report(f"k21_rasterize_{name}_measure_only", table_bytes + small_out, medm, mnm, rows=nr, pixels=T)
+            painted = int((pix != 0).sum().item())
+            # Pillow on one core over the same table
+            from PIL import Image, ImageDraw
+            hx, hp, hr, hv = xy_.cpu().numpy(), pt_.cpu().numpy(), roff.cpu().numpy(), val.cpu().numpy()
+            t0 = time.perf_counter()
+            for i in range(nr):
+                im = Image.new("L", (W, H), 0)
+                draw = ImageDraw.Draw(im)
+                for q in range(hr[i], hr[i + 1]):
+                    pts = hx[hp[q]:hp[q + 1]]
+                    if len(pts) == 2:
+                        draw.rectangle([tuple(pts.min(0)), tuple(pts.max(0))], fill=int(hv[q]))
+                    elif len(pts) > 2:
+                        draw.polygon(pts.reshape(-1).tolist(), fill=int(hv[q]))
+            pillow_ms = (time.perf_counter() - t0) * 1e3
+            report(f"k21_rasterize_{name}", table_bytes + small_out + 16 * nb + T, med, mn, rows=nr, polygons=nb, points=npts, width=W,
+                   height=H, pixels=T, painted_pixels=painted, covered_pixels=int(cov.sum().item()), Gpixels_per_s=round(T / med / 1e6, 2),
+                   byte_floor_GB=round((table_bytes + T) / 1e9, 4), pillow_one_core_ms=round(pillow_ms, 1),
+                   pillow_over_k21=round(pillow_ms / med, 1))
+
+        nr = min(N, 8192)
+        nb_s = int(box_off[nr].item()); np_s = int(pt_off[nb_s].item())
+        xs = (xy[:np_s] * torch.tensor([256.0 / 1920.0, 144.0 / 1080.0], dtype=torch.float64, device=dev)).contiguous()
+        k21_leg("small_images", xs, pt_off[:nb_s + 1].contiguous(), box_off[:nr + 1].contiguous(), nr, nb_s, np_s, 256, 144)
+        del xs
+        rng = np.random.default_rng(21)
+        m, rings = 2000, []
+        for q in range(32):
+            ang = np.sort(rng.uniform(0, 2 * np.pi, m))
+            rad = rng.uniform(600, 1800, 1) * (1 + 0.3 * np.sin(ang * rng.integers(3, 40)) + rng.uniform(-0.05, 0.05, m))
+            c = rng.uniform(1000, 3096, 2)
+            rings.append(np.stack([c[0] + rad * np.cos(ang), c[1] + rad * np.sin(ang)], axis=1))
+        xl = torch.from_numpy(np.concatenate(rings)).to(dev)
+        ptl = torch.arange(0, 32 * m + 1, m, dtype=torch.int32, device=dev)
+        rol = torch.arange(0, 33, 4, dtype=torch.int32, device=dev)
+        k21_leg("large_images", xl, ptl, rol, 8, 32, 32 * m, 4096, 4096)
     if "k14" in only:
         import ctypes as C
         # K14 (polygon audit) on K13's two shapes, and long polygons (convex rings of 256 vertices: no crossing, so the wave
