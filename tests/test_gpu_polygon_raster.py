@@ -281,6 +281,91 @@ def test_random_table(native):
     same(native.rasterize_polygons(*t, 255, 96 * 96), want)
 
 
+# ----------------------------------------------------------------------------------------------- the compiled limits
+# All at the default options: strips of 1,024 columns (K21_STRIP), a list of 256 crossings (K21_CROSSINGS), 2^20 paint workgroups
+# (K21_MAX_GRID).  tests/test_polygon_raster_cpu.py runs the first two tables through the mapping's transliteration.
+STRIP, CROSSINGS, MAX_GRID = 1024, 256, 1 << 20
+
+
+def full_strip_rows(widths=(1023, 1024, 1025, 2049)):
+    """rows of height 3: a blob across the whole width, a box on the last three columns, a box across the first strip's end"""
+    rng = np.random.default_rng(12)
+    return [(w, 3, [(1, blob(rng, w / 2, 1.5, w / 2, 9)), (2, [(w - 3.0, 0.0), (float(w), 3.0)]), (3, [(1020.0, 1.0), (1030.0, 3.0)])])
+            for w in widths]
+
+
+def full_list_rows(n_teeth=150):
+    """a comb of n_teeth teeth: 3 * n_teeth + 2 vertices, 2 * n_teeth crossings on the scanlines 1 to 9, and a blob on top"""
+    comb = [(0.0, 0.0)]
+    for k in range(n_teeth):
+        comb += [(3.0 * k + 0.5, 10.0), (3.0 * k + 1.5, 1.0), (3.0 * k + 2.5, 10.0)]
+    w = 3 * n_teeth + 5
+    comb.append((float(w), 0.0))
+    return [(w, 12, [(1, comb), (2, blob(np.random.default_rng(13), w / 2, 6, 100, 9))])]
+
+
+def test_default_strip_widths(native):
+    want = both(native, table(full_strip_rows()), background=5)
+    assert (want[3] > 0).all() and (want[4] < want[3]).any() and len(want[-1]) == 3 * (1023 + 1024 + 1025 + 2049)
+    for w in (STRIP, STRIP + 1):                             # a full strip, and a second strip of one pixel, at every phase
+        t = table(full_strip_rows((w,)))
+        want = R.raster_arrays(*t, 5)
+        assert (want[3] > 0).all()
+        for phase in range(16):
+            got, rc, total = run_dev(t, 5, phase=phase)
+            assert rc == 0 and total == 3 * w, phase
+            same(got, want)
+
+
+def test_more_crossings_than_the_default_list_holds(native):
+    rows = full_list_rows()
+    assert len(rows[0][2][0][1]) == 452 and rows[0][0] == 455
+    want = both(native, table(rows))
+    assert want[3][0] > 3000 and want[4][0] < want[3][0] and 2 * 150 > CROSSINGS
+
+
+def test_more_items_than_paint_workgroups(native):
+    H = 2 ** 20 - 3
+    rng = np.random.default_rng(14)
+    t = table([(1, H, [(1, [(0.0, 10.0), (1.0, H - 10.0)]), (2, [(0.0, 100.0), (1.0, 500000.25), (0.2, 900000.0)])]),
+               (70, 40, [(3, blob(rng, 35, 20, 30, 9)), (4, [(60.0, 2.0), (70.0, 39.0)])])])
+    n_items = sum(int(h) * -(-int(w) // STRIP) for w, h in zip(t[4], t[5]))
+    assert n_items == MAX_GRID + 37                          # workgroups 0 to 36 take a scanline of each row
+    want = both(native, t, background=7, max_pixels=1 << 26)
+    assert set(np.unique(want[-1]).tolist()) == {1, 2, 3, 4, 7} and len(want[-1]) == H + 2800
+    assert want[3][0] == 2 ** 20 - 23 and want[4][0] < want[3][0]
+
+
+def test_no_row_is_rasterised(native):
+    box, tri = [(1.0, 1.0), (4.0, 4.0)], [(0.0, 0.0), (3.0, 1.0), (2.0, 4.0)]
+    polys = [(1, box), (-1, box), (2, tri)]
+    t = table([(0, 5, polys), (4.5, 4, polys), (5000, 5000, polys)])
+    want = both(native, t, background=3, max_pixels=1 << 20)
+    assert want[0].tolist() == [1, 2, 3] and want[1].tolist() == [0, 0, 0, 0] and len(want[-1]) == 0
+    assert want[2].tolist() == [5, 255, 5] * 3 and not want[3].any() and not want[4].any()
+    got = native.rasterize_polygons(*t, 3, 1 << 20)
+    assert not got[3].any() and not got[4].any() and len(got[5]) == 0
+    got, rc, total = run_dev(t, 3, 1 << 20, pix_cap=0)       # a pixel pointer that is not NULL and no room behind it
+    assert rc == 0 and total == 0
+    same(got, want)
+
+
+BIG = 2.0 ** 40
+SKEWED = [[(-BIG, -BIG + 1), (BIG + 3, BIG), (7.0, 2 * BIG)], [(-2 * BIG + 5, 3.0), (2 * BIG, -BIG + 11), (BIG + 1, 4 * BIG)],
+          [(-4 * BIG, 2 * BIG + 7), (4 * BIG - 9, -2 * BIG), (13.0, -4 * BIG + 1)], [(BIG + 20, -BIG), (-BIG, BIG + 45), (-2 * BIG - 3, -2 * BIG)],
+          [(-BIG, -3 * BIG), (3 * BIG + 1, BIG + 17), (-BIG - 30, BIG)], [(2 * BIG, 2 * BIG + 1), (-2 * BIG + 60, -2 * BIG), (4 * BIG, -BIG + 25)]]
+
+
+def test_large_skewed_polygons(native):
+    """vertices of 2^40 to 2^42 whose edges cross a 50 x 50 image at a slant: xs is a rounded quotient on every scanline"""
+    polys = [(k + 1, tri) for k, tri in enumerate(SKEWED)] + [(9, blob(np.random.default_rng(15), 25, 25, 20, 9))]
+    want = both(native, table([(50, 50, polys)]))
+    cov = want[3][:len(SKEWED)]
+    assert ((cov > 0) & (cov < 2500)).sum() >= 2 and (cov == 2500).any() and want[3][-1] > 0
+    for k, tri in enumerate(SKEWED):                         # and each alone, where nothing hides it
+        both(native, table([(50, 50, [(k + 1, tri)])]))
+
+
 # ----------------------------------------------------------------------------------------------- end to end
 @pytest.mark.parametrize("mode, order", [("semantic", "annotation"), ("semantic", "large_first"), ("instance", "annotation"),
                                          ("instance", "large_first")])

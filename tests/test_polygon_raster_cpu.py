@@ -321,3 +321,27 @@ def test_the_kernels_mapping_changes_nothing(strip, capacity):
     assert (want[3] > want[4]).any() and len(want[-1]) > 5000
     for g, w_, what in zip(got, want, ("row_status", "pix_off", "action", "covered", "owned", "pixels")):
         assert np.array_equal(g, w_), what
+
+
+def _mapping_at_the_defaults(t, background):
+    want = R.raster_arrays(*t, background)
+    got = R.paint_by_items(*t, background, strip=1024, capacity=256)
+    for g, w_, what in zip(got, want, ("row_status", "pix_off", "action", "covered", "owned", "pixels")):
+        assert np.array_equal(g, w_), what
+    return want
+
+
+def test_the_mapping_on_full_default_strips():
+    """the table of test_gpu_polygon_raster.test_default_strip_widths: rows of 1023, 1024, 1025 and 2049 columns"""
+    from test_gpu_polygon_raster import full_strip_rows, table
+
+    want = _mapping_at_the_defaults(table(full_strip_rows()), 5)
+    assert (want[3] > 0).all() and (want[4] < want[3]).any() and want[1][-1] == 3 * (1023 + 1024 + 1025 + 2049)
+
+
+def test_the_mapping_on_more_crossings_than_the_default_list_holds():
+    """the table of test_gpu_polygon_raster.test_more_crossings_than_the_default_list_holds: 300 crossings per scanline"""
+    from test_gpu_polygon_raster import full_list_rows, table
+
+    want = _mapping_at_the_defaults(table(full_list_rows()), 0)
+    assert want[3][0] > 3000 and want[4][0] < want[3][0]
