@@ -161,6 +161,10 @@ SIGNATURES = {
     "dyd_rasterize_polygons_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                              C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+    "dyd_compare_polygons": (C.c_int, [C.c_void_p] * 10 + [C.c_int64, C.c_int32, C.c_double, C.c_int, C.c_int64, C.c_int64]
+                             + [C.c_void_p] * 15),
+    "dyd_compare_polygons_dev": (C.c_int, [C.c_void_p] * 10 + [C.c_int64] * 5 + [C.c_int32, C.c_double, C.c_int, C.c_int64, C.c_int64]
+                                 + [C.c_void_p] * 16 + [C.c_int64, C.c_void_p]),
     "dyd_coco_annotations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                                        C.POINTER(C.c_int64)]),
@@ -550,6 +554,34 @@ def rasterize_polygons(xy, pt_off, row_off, val, width, height, background: int 
                                        int(max_pixels_per_row), _ptr(status), _ptr(pix_off), opt(action), opt(covered), opt(owned),
                                        C.byref(pixels), C.byref(total)), "dyd_rasterize_polygons")
     return status, pix_off, action, covered, owned, np.frombuffer(_take_text(pixels, total), np.uint8)
+
+
+def compare_polygons(a_xy, a_pt_off, a_row_off, a_cls, b_xy, b_pt_off, b_row_off, b_cls, width, height, n_classes: int,
+                     thr: float = 0.5, by_label: bool = False, max_pixels_per_row: int = 1 << 26, max_pairs_per_row: int = 1 << 20):
+    """K22 over host arrays: two polygon tables of the same rows -> (row_status u8 [n], pair_off i64 [n+1], a_action u8 [A],
+    b_action u8 [B], a_pixels i64 [A], b_pixels i64 [B], a_match i32 [A], b_match i32 [B], b_iou f64 [B], a_best f64 [A], b_best
+    f64 [B], row_counts i32 [n, 4], confusion u64 [C+1, C+1], pixel_confusion u64 [C+1, C+1], row_pixels i64 [n, 2]).  Rule and
+    codes: include/dyd.h."""
+    a_xy, a_pt_off, a_row_off, width, height, _, a_cls, n, na = _poly_table(a_xy, a_pt_off, a_row_off, width, height,
+                                                                            ("width", width, np.float64), ("a_cls", a_cls, np.int32))
+    b_xy, b_pt_off, b_row_off, _, _, _, b_cls, _, nb = _poly_table(b_xy, b_pt_off, b_row_off, width, height,
+                                                                   ("width", width, np.float64), ("b_cls", b_cls, np.int32))
+    C_ = int(n_classes)
+    cells = max(C_, 0) + 1
+    status, pair_off = np.zeros(n, np.uint8), np.zeros(n + 1, np.int64)
+    a_act, b_act = np.zeros(na, np.uint8), np.zeros(nb, np.uint8)
+    a_pix, b_pix = np.zeros(na, np.int64), np.zeros(nb, np.int64)
+    a_match, b_match = np.full(na, -1, np.int32), np.full(nb, -1, np.int32)
+    b_iou, a_best, b_best = np.zeros(nb, np.float64), np.zeros(na, np.float64), np.zeros(nb, np.float64)
+    rows, row_pixels = np.zeros((n, 4), np.int32), np.zeros((n, 2), np.int64)
+    conf, pconf = np.zeros((cells, cells), np.uint64), np.zeros((cells, cells), np.uint64)
+    opt = lambda a: _ptr(a) if a.size else None          # noqa: E731
+    check(lib().dyd_compare_polygons(opt(a_xy), _ptr(a_pt_off), _ptr(a_row_off), opt(a_cls), opt(b_xy), _ptr(b_pt_off),
+                                     _ptr(b_row_off), opt(b_cls), _ptr(width), _ptr(height), n, C_, float(thr), int(bool(by_label)),
+                                     int(max_pixels_per_row), int(max_pairs_per_row), _ptr(status), _ptr(pair_off), opt(a_act),
+                                     opt(b_act), opt(a_pix), opt(b_pix), opt(a_match), opt(b_match), opt(b_iou), opt(a_best),
+                                     opt(b_best), _ptr(rows), _ptr(conf), _ptr(pconf), _ptr(row_pixels)), "dyd_compare_polygons")
+    return status, pair_off, a_act, b_act, a_pix, b_pix, a_match, b_match, b_iou, a_best, b_best, rows, conf, pconf, row_pixels
 
 
 REPAIR_ACTIONS = 8   # action codes of K11: keep, clip, no_size, bad_coords, degenerate, outside, low_visibility, small

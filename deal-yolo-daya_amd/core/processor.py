@@ -2832,8 +2832,9 @@ def compare_boxes_cells(cells_a, cells_b, iou_threshold: float = 0.5, by_label: 
     return _compare_result(acc, n, sources, thr, by_label, stats)
 
 
-def _compare_keyed(cells_a, keys_a, sources_a, cells_b, keys_b, key, thr, by_label, backend, stats) -> BoxComparison:
-    """the comparison of the rows of A whose key is also in B (each key at most once per side); rows are positions in A"""
+def _compare_align(keys_a, keys_b, key) -> tuple:
+    """two key columns (each key at most once per side) -> (rows_a, rows_b, only_a, only_b): the positions in A and in B of the
+    rows found in both, in A's order, and the positions of the rows found on one side only"""
     ia, ib = pd.Index(keys_a), pd.Index(keys_b)
     for side, idx in (("the base", ia), ("the other", ib)):
         if idx.has_duplicates:
@@ -2845,10 +2846,11 @@ def _compare_keyed(cells_a, keys_a, sources_a, cells_b, keys_b, key, thr, by_lab
     only_a = np.flatnonzero(at < 0)
     seen = np.zeros(len(ib), bool)
     seen[rows_b] = True
-    only_b = np.flatnonzero(~seen)
-    cells_a, cells_b = np.asarray(cells_a, object), np.asarray(cells_b, object)
-    res = compare_boxes_cells(cells_a[rows_a], cells_b[rows_b], thr, by_label, backend, None,
-                              None if sources_a is None else np.asarray(sources_a, object)[rows_a])
+    return rows_a, rows_b, only_a, np.flatnonzero(~seen)
+
+
+def _compare_aligned(res, rows_a, keys_a, only_a, keys_b, only_b, stats):
+    """a comparison of the aligned rows, reported in positions of A, with the rows found on one side only"""
     res.per_row["row"] = rows_a[res.per_row["row"].to_numpy()]
     res.differences["row"] = rows_a[res.differences["row"].to_numpy()]
     res.unpaired = pd.DataFrame({"key": np.concatenate([np.asarray(keys_a, object)[only_a], np.asarray(keys_b, object)[only_b]]),
@@ -2857,6 +2859,15 @@ def _compare_keyed(cells_a, keys_a, sources_a, cells_b, keys_b, key, thr, by_lab
     if stats is not None:
         stats.update(res.totals)
     return res
+
+
+def _compare_keyed(cells_a, keys_a, sources_a, cells_b, keys_b, key, thr, by_label, backend, stats) -> BoxComparison:
+    """the comparison of the rows of A whose key is also in B (each key at most once per side); rows are positions in A"""
+    rows_a, rows_b, only_a, only_b = _compare_align(keys_a, keys_b, key)
+    cells_a, cells_b = np.asarray(cells_a, object), np.asarray(cells_b, object)
+    res = compare_boxes_cells(cells_a[rows_a], cells_b[rows_b], thr, by_label, backend, None,
+                              None if sources_a is None else np.asarray(sources_a, object)[rows_a])
+    return _compare_aligned(res, rows_a, keys_a, only_a, keys_b, only_b, stats)
 
 
 def compare_boxes_frame(df_a: pd.DataFrame, df_b: Optional[pd.DataFrame] = None, json_col: str = BBOX_COL, other_col=None,
@@ -4409,6 +4420,369 @@ def export_masks_csv(input_csv_path, output_dir, split: str = "train", json_col:
                       lambda df: export_masks_frame(df, output_dir, split, json_col, width_col, height_col, source_col, label_col,
                                                     classes, mode, background, class_offset, order, max_pixels_per_row, batch_pixels,
                                                     png_mode, problems_csv, keep_empty_masks, be, stats))
+
+
+# =============================================================================== f8d  polygon comparison
+# How two sets of annotation polygons of the same images differ, in pixels: the polygon twin of the box comparison (f6a).  Per
+# image row K22 (csrc/k22_poly_compare.hip, rule in include/dyd.h and DESIGN §5t) rasterises both sides by K21's rule, counts per
+# pair of polygons the pixels both cover, and matches the B polygons, in annotation order, greedily to the A polygons by mask IoU
+# (the still free A polygon with the largest IoU >= iou_threshold that shares a pixel, ties to the lowest index).  A matched pair
+# of equal names agrees, one of different names is `relabelled`, an unmatched A polygon is `missing`, an unmatched B polygon
+# `extra`; polygons with bad coordinates or fewer than two points are `skipped`.  The same pass gives the pixel confusion matrix:
+# a pixel's class on a side is the name of the last polygon that covers it, else the background.  Polygons whose name is no str
+# share one class, reported as None and listed last.  Native scan of both sides (_poly_chunk) -> K22 per batch of rows -> frames.
+POLY_COMPARE_STATUS = _fl.COMPARE_STATUS                   # K22 row status codes 0..4
+COMPARE_BACKGROUND = "(background)"                        # the pixel confusion matrix's last row and column
+_POLY_COMPARE_MAX_PAIRS = 1 << 24
+_POLY_COMPARE_MAX_CLASSES = 1023
+_POLY_COMPARE_DIFF_SPEC = (("row", np.int64), ("kind", object), ("a_object", np.int64), ("b_object", np.int64), ("a_name", object),
+                           ("b_name", object), ("iou", np.float64), ("best_iou", np.float64), ("a_pixels", np.int64),
+                           ("b_pixels", np.int64))
+
+
+class PolygonComparison:
+    """Result of compare_polygons_*: classes (sorted as str, None last), confusion (frame of polygon counts, index = A class,
+    columns = B class, plus a last "(none)" row and column), pixel_confusion (the same shape in pixels, the last row and column
+    "(background)"), per_class, hist_iou (int64 [C, 20], the mask IoU of the agreeing pairs), per_row, differences (one line per
+    missing / extra / relabelled polygon), unpaired (key, side: rows found in one frame only) and totals."""
+
+    def __init__(self, classes, confusion, pixel_confusion, per_class, hist_iou, per_row, differences, unpaired, totals):
+        self.classes = classes
+        self.confusion = confusion
+        self.pixel_confusion = pixel_confusion
+        self.per_class = per_class
+        self.hist_iou = hist_iou
+        self.per_row = per_row
+        self.differences = differences
+        self.unpaired = unpaired
+        self.totals = totals
+
+    def __repr__(self):
+        return f"PolygonComparison({len(self.classes)} classes, {self.totals})"
+
+
+class _PolyCompareTotals(_CompareTotals):
+    """_CompareTotals plus the class-keyed pixel counts ([A class, B class], class against background either way), the skipped
+    polygons per class and side, and the rows' status and pixel counts per chunk"""
+
+    def __init__(self):
+        super().__init__()
+        self.pix = np.zeros((0, 0), np.int64)
+        self.pix_a = np.zeros(0, np.int64)               # A's class where B is background
+        self.pix_b = np.zeros(0, np.int64)
+        self.pix_none = 0                                # background on both sides
+        self.skipped = np.zeros((0, 2), np.int64)
+        self.status, self.row_pixels = [], []
+
+    def add_pixels(self, names, pconf, skipped):
+        """after add(names, ...): a chunk's (C+1) x (C+1) pixel counts and [C, 2] skipped polygons"""
+        g = np.asarray([self.index[nm] for nm in names], np.int64)
+        grow = len(self.index) - len(self.pix_a)
+        if grow:
+            self.pix = np.pad(self.pix, ((0, grow), (0, grow)))
+            self.pix_a, self.pix_b = np.pad(self.pix_a, (0, grow)), np.pad(self.pix_b, (0, grow))
+            self.skipped = np.pad(self.skipped, ((0, grow), (0, 0)))
+        c = len(names)
+        self.pix_none += int(pconf[c, c])
+        if c:
+            self.pix[np.ix_(g, g)] += pconf[:c, :c]
+            self.pix_a[g] += pconf[:c, c]
+            self.pix_b[g] += pconf[c, :c]
+            self.skipped[g] += skipped
+
+
+def _poly_compare_params(iou_threshold, by_label, max_pixels_per_row, max_pairs_per_row, batch_pixels, batch_pairs) -> tuple:
+    return (_compare_threshold(iou_threshold), bool(by_label), _mask_int(max_pixels_per_row, "max_pixels_per_row", 1, _MASK_MAX_PIXELS),
+            _mask_int(max_pairs_per_row, "max_pairs_per_row", 1, _POLY_COMPARE_MAX_PAIRS),
+            _mask_int(batch_pixels, "batch_pixels", 1, 1 << 40), _mask_int(batch_pairs, "batch_pairs", 1, 1 << 40))
+
+
+def _poly_compare_chunk(cells_a, cells_b, W, H, be, acc: _PolyCompareTotals, start: int, params: tuple):
+    """one chunk of rows: both polygon tables (_poly_chunk) on one class list -> K22 per batch of rows -> class-keyed sums,
+    per-row counts, differences"""
+    thr, by_label, max_pixels, max_pairs, batch_pixels, batch_pairs = params
+    n = len(cells_a)
+    sides = [_poly_chunk(cells) for cells in (cells_a, cells_b)]
+    acc.python_cells += sides[0][6] + sides[1][6]
+    ids, cls = {}, []
+    for t in sides:                                      # one class list for both sides, the names that are no str last
+        to = np.asarray([ids.setdefault(nm, len(ids)) for nm in t[5]] + [-1], np.int32)
+        cls.append(to[np.asarray(t[4], np.int64)])
+    names = list(ids)
+    if any((c < 0).any() for c in cls):
+        names.append(None)
+        cls = [np.where(c < 0, len(names) - 1, c).astype(np.int32) for c in cls]
+    C = max(len(names), 1)                               # K22 takes at least one class; a chunk without polygons uses none
+    if C > _POLY_COMPARE_MAX_CLASSES:
+        raise ValueError(f"a chunk holds {C} classes; the polygon comparison takes at most {_POLY_COMPARE_MAX_CLASSES}")
+    off = [np.asarray(t[0], np.int64) for t in sides]
+    xy = [np.asarray(t[1], np.float64).reshape(-1) for t in sides]
+    pt = [np.asarray(t[2], np.int64) for t in sides]
+    obj = [np.asarray(t[3], np.int64) for t in sides]
+    count = [np.diff(o) for o in off]
+    host_status, host_pixels, host_pairs = _fl.compare_rows(W, H, count[0], count[1], max_pixels, max_pairs)
+    act = [np.zeros(len(c), np.uint8) for c in cls]
+    pix = [np.zeros(len(c), np.int64) for c in cls]
+    match = [np.full(len(c), -1, np.int64) for c in cls]
+    best = [np.zeros(len(c)) for c in cls]
+    b_iou = np.zeros(len(cls[1]))
+    rows, row_pixels = np.zeros((n, 4), np.int64), np.zeros((n, 2), np.int64)
+    conf, pconf = np.zeros((C + 1, C + 1), np.int64), np.zeros((C + 1, C + 1), np.int64)
+    for a, b in _fl.compare_batches(host_pixels, host_pairs, batch_pixels, batch_pairs):
+        tabs, span = [], []
+        for k in (0, 1):
+            p0, p1 = int(off[k][a]), int(off[k][b])
+            q0, q1 = int(pt[k][p0]), int(pt[k][p1])
+            span.append((p0, p1))
+            tabs += [xy[k][2 * q0:2 * q1], (pt[k][p0:p1 + 1] - q0).astype(np.int32), (off[k][a:b + 1] - p0).astype(np.int32),
+                     cls[k][p0:p1]]
+        out = be.compare_polygons(*tabs, W[a:b], H[a:b], C, thr, by_label, max_pixels, max_pairs)
+        status, pair_off = np.asarray(out[0], np.uint8), np.asarray(out[1], np.int64)
+        if not np.array_equal(status, host_status[a:b]) or not np.array_equal(np.diff(pair_off), host_pairs[a:b]):
+            raise RuntimeError("the device's row status or pair counts differ from the host's")
+        for k in (0, 1):
+            p0, p1 = span[k]
+            act[k][p0:p1], pix[k][p0:p1], match[k][p0:p1], best[k][p0:p1] = out[2 + k], out[4 + k], out[6 + k], out[9 + k]
+        b_iou[span[1][0]:span[1][1]] = out[8]
+        rows[a:b], row_pixels[a:b] = np.asarray(out[11], np.int64).reshape(b - a, 4), np.asarray(out[14], np.int64).reshape(b - a, 2)
+        conf += np.asarray(out[12]).astype(np.int64).reshape(C + 1, C + 1)
+        pconf += np.asarray(out[13]).astype(np.int64).reshape(C + 1, C + 1)
+    (off_a, off_b), (a_match, b_match), (a_best, b_best) = off, match, best
+    row_a = np.repeat(np.arange(n, dtype=np.int64), count[0])
+    row_b = np.repeat(np.arange(n, dtype=np.int64), count[1])
+    hit = np.flatnonzero(b_match >= 0)                   # matched B polygons and their A polygons
+    hit_a = off_a[row_b[hit]] + b_match[hit]
+    same = cls[0][hit_a] == cls[1][hit]
+    Cn = len(names)
+    hist = np.zeros((Cn, COMPARE_HIST_BINS), np.int64)
+    np.add.at(hist, (cls[1][hit[same]], np.minimum((b_iou[hit[same]] * COMPARE_HIST_BINS).astype(np.int64),
+                                                   COMPARE_HIST_BINS - 1)), 1)
+    skipped = np.stack([np.bincount(c[(x == 2) | (x == 3)], minlength=Cn)[:Cn] for c, x in zip(cls, act)], axis=1) if Cn \
+        else np.zeros((0, 2), np.int64)
+    keep = np.r_[np.arange(Cn), C].astype(np.int64)       # without the stand-in class of a chunk that has none
+    acc.add(names, conf[np.ix_(keep, keep)], hist)
+    acc.add_pixels(names, pconf[np.ix_(keep, keep)], skipped)
+    acc.rows.append(rows)
+    acc.n_a.append(count[0])
+    acc.n_b.append(count[1])
+    acc.status.append(host_status)
+    acc.row_pixels.append(np.concatenate([row_pixels, host_pixels[:, None]], axis=1))
+    miss, extra, rel_b = np.flatnonzero((act[0] == 0) & (a_match < 0)), np.flatnonzero((act[1] == 0) & (b_match < 0)), hit[~same]
+    rel_a = hit_a[~same]
+    k = (len(miss), len(extra), len(rel_b))
+    if sum(k):
+        absent = lambda m: np.full(m, -1, np.int64)      # noqa: E731
+        none = lambda m: np.full(m, None, object)        # noqa: E731
+        name_of = np.asarray(names + [None], object)
+        row = np.concatenate([row_a[miss], row_b[extra], row_b[rel_b]])
+        kind = np.repeat(np.arange(3), k)
+        at = np.concatenate([miss - off_a[row_a[miss]], extra - off_b[row_b[extra]], rel_a - off_a[row_b[rel_b]]])
+        order = np.lexsort((at, kind, row))
+        cols = (start + row, np.asarray(COMPARE_KINDS, object)[kind],
+                np.concatenate([obj[0][miss], absent(k[1]), obj[0][rel_a]]),
+                np.concatenate([absent(k[0]), obj[1][extra], obj[1][rel_b]]),
+                np.concatenate([name_of[cls[0][miss]], none(k[1]), name_of[cls[0][rel_a]]]),
+                np.concatenate([none(k[0]), name_of[cls[1][extra]], name_of[cls[1][rel_b]]]),
+                np.concatenate([np.zeros(k[0] + k[1]), b_iou[rel_b]]),
+                np.concatenate([a_best[miss], b_best[extra], b_iou[rel_b]]),
+                np.concatenate([pix[0][miss], absent(k[1]), pix[0][rel_a]]),
+                np.concatenate([absent(k[0]), pix[1][extra], pix[1][rel_b]]))
+        acc.diffs.append(tuple(c[order] for c in cols))
+
+
+def _poly_compare_result(acc: _PolyCompareTotals, n: int, sources, params: tuple, mismatch, stats) -> PolygonComparison:
+    thr, by_label, max_pixels, max_pairs = params[:4]
+    classes = sorted(acc.index, key=lambda c: (c is None, str(c)))
+    perm = np.asarray([acc.index[c] for c in classes], np.int64)
+    pairs, missing, extra, hist = acc.pairs[np.ix_(perm, perm)], acc.missing[perm], acc.extra[perm], acc.hist[perm]
+    C = len(classes)
+    full, pfull = np.zeros((C + 1, C + 1), np.int64), np.zeros((C + 1, C + 1), np.int64)
+    full[:C, :C], full[:C, C], full[C, :C] = pairs, missing, extra
+    pfull[:C, :C], pfull[:C, C], pfull[C, :C], pfull[C, C] = acc.pix[np.ix_(perm, perm)], acc.pix_a[perm], acc.pix_b[perm], acc.pix_none
+    labels = pd.Index(classes + [COMPARE_NONE], dtype=object)
+    confusion = pd.DataFrame(full, index=labels, columns=labels)
+    plabels = pd.Index(classes + [COMPARE_BACKGROUND], dtype=object)
+    pixel_confusion = pd.DataFrame(pfull, index=plabels, columns=plabels)
+    agree = np.diagonal(pairs).copy() if C else np.zeros(0, np.int64)
+    both = np.diagonal(pfull)[:C].copy()
+    a_px, b_px = pfull[:C].sum(axis=1), pfull[:, :C].sum(axis=0)
+    union = a_px + b_px - both
+    with np.errstate(invalid="ignore", divide="ignore"):
+        pixel_iou = np.where(union > 0, both / np.where(union > 0, union, 1), np.nan)
+    skipped = acc.skipped[perm] if C else np.zeros((0, 2), np.int64)
+    per_class = pd.DataFrame({"class": pd.Series(classes, dtype=object), "a_polygons": full[:C].sum(axis=1),
+                              "b_polygons": full[:, :C].sum(axis=0), "agree": agree,
+                              "relabelled_to_other": pairs.sum(axis=1) - agree, "relabelled_from_other": pairs.sum(axis=0) - agree,
+                              "missing": missing, "extra": extra, "a_skipped": skipped[:, 0], "b_skipped": skipped[:, 1],
+                              "a_pixels": a_px, "b_pixels": b_px, "pixels_both": both, "pixel_iou": pixel_iou})
+    rows = np.concatenate(acc.rows) if acc.rows else np.zeros((0, 4), np.int64)
+    rpix = np.concatenate(acc.row_pixels) if acc.row_pixels else np.zeros((0, 3), np.int64)
+    status = np.asarray(POLY_COMPARE_STATUS, object)[np.concatenate(acc.status) if acc.status else np.zeros(0, np.uint8)]
+    if mismatch is not None:
+        status[mismatch] = "size_mismatch"
+    pr = {"row": np.arange(n, dtype=np.int64)}
+    if sources is not None:
+        pr["source"] = np.asarray(sources, object)
+    pr["status"] = status
+    pr["a_polygons"] = np.concatenate(acc.n_a) if acc.n_a else np.zeros(0, np.int64)
+    pr["b_polygons"] = np.concatenate(acc.n_b) if acc.n_b else np.zeros(0, np.int64)
+    pr.update({k: rows[:, j] for j, k in enumerate(_COMPARE_ROW_COLS)})
+    pr["pixels_agree_fg"], pr["pixels_fg"] = rpix[:, 0], rpix[:, 1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        pr["fg_iou"] = np.where(rpix[:, 1] > 0, rpix[:, 0] / np.where(rpix[:, 1] > 0, rpix[:, 1], 1), np.nan)
+    differences = _parts_frame(acc.diffs, _POLY_COMPARE_DIFF_SPEC, sources)
+    if sources is not None:                              # row first, as in per_row
+        differences = differences[["row", "source", *differences.columns[2:]]]
+    n_pixels = int(rpix[:, 2].sum())
+    seen = union > 0
+    totals = {"rows": n, "a_polygons": int(pr["a_polygons"].sum()), "b_polygons": int(pr["b_polygons"].sum()),
+              "matched": int(rows[:, :2].sum()), "agree": int(rows[:, 0].sum()), "relabelled": int(rows[:, 1].sum()),
+              "missing": int(rows[:, 2].sum()), "extra": int(rows[:, 3].sum()), "a_skipped": int(skipped[:, 0].sum()),
+              "b_skipped": int(skipped[:, 1].sum()),
+              **{f"rows_{s}": int((status == s).sum()) for s in (*POLY_COMPARE_STATUS, "size_mismatch")}, "pixels": n_pixels,
+              "pixel_accuracy": float(np.trace(pfull)) / n_pixels if n_pixels else float("nan"),
+              "mean_pixel_iou": float(pixel_iou[seen].mean()) if seen.any() else float("nan"),
+              "python_cells": acc.python_cells, "iou_threshold": thr, "by_label": by_label, "max_pixels_per_row": max_pixels,
+              "max_pairs_per_row": max_pairs}
+    if stats is not None:
+        stats.update(totals)
+    unpaired = pd.DataFrame({"key": np.zeros(0, object), "side": np.zeros(0, object)})
+    return PolygonComparison(classes, confusion, pixel_confusion, per_class, hist, pd.DataFrame(pr), differences, unpaired, totals)
+
+
+def _poly_compare_rows(cells_a, cells_b, n, widths, heights, mismatch, params, be, stats, sources) -> PolygonComparison:
+    """the chunks of n aligned rows through _poly_compare_chunk; mismatch (bool [n] or None): rows whose two sizes differ, which
+    reach the device without a size"""
+    _, W, H = _audit_sizes(widths, heights, n)
+    if mismatch is not None:
+        W, H = np.where(mismatch, np.nan, W), np.where(mismatch, np.nan, H)
+    acc = _PolyCompareTotals()
+    for s0, s1, chunk in _chunks(n, cells_a):
+        _poly_compare_chunk(chunk, cells_b[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, params)
+    return _poly_compare_result(acc, n, sources, params, mismatch, stats)
+
+
+def compare_polygons_cells(cells_a, cells_b, widths, heights, iou_threshold: float = 0.5, by_label: bool = False,
+                           max_pixels_per_row: int = 1 << 26, max_pairs_per_row: int = 1 << 20, batch_pixels: int = 1 << 28,
+                           batch_pairs: int = 1 << 26, backend=None, stats: Optional[dict] = None, sources=None) -> PolygonComparison:
+    """Polygon comparison of two lists of annotation cells of the same images, row by row (see the section comment): cells_a is
+    the base, cells_b the other set, widths / heights the images' sizes.  A row is compared only when its size is usable and
+    whole, it has at most max_pixels_per_row pixels and at most max_pairs_per_row pairs of polygons (per_row["status"] says
+    which).  Rows reach the device in batches of at most batch_pixels pixels and batch_pairs pairs (a single larger row goes
+    alone).  ``sources`` (optional) adds a source column to per_row and differences.  by_label=True matches polygons of equal
+    names only, so it reports no `relabelled` line.  -> PolygonComparison."""
+    params = _poly_compare_params(iou_threshold, by_label, max_pixels_per_row, max_pairs_per_row, batch_pixels, batch_pairs)
+    be = _step_backend(backend, "compare_polygons")
+    cells_a = cells_a.to_numpy() if hasattr(cells_a, "to_numpy") else cells_a
+    cells_b = cells_b.to_numpy() if hasattr(cells_b, "to_numpy") else cells_b
+    n = len(cells_a)
+    if len(cells_b) != n:
+        raise ValueError(f"the two lists must hold one cell per image each: {n} against {len(cells_b)} cells")
+    return _poly_compare_rows(cells_a, cells_b, n, widths, heights, None, params, be, stats, sources)
+
+
+def _poly_compare_mismatch(sizes_a, sizes_b, rows_a, rows_b):
+    """bool per aligned row: both sides carry a usable size and the two differ; None when B carries no size columns"""
+    if sizes_a[0] is None or sizes_b[0] is None:
+        return None
+    sa, Wa, Ha = _audit_sizes(sizes_a[0], sizes_a[1], len(sizes_a[0]))
+    sb, Wb, Hb = _audit_sizes(sizes_b[0], sizes_b[1], len(sizes_b[0]))
+    return (sa[rows_a] == 0) & (sb[rows_b] == 0) & ((Wa[rows_a] != Wb[rows_b]) | (Ha[rows_a] != Hb[rows_b]))
+
+
+def _poly_compare_tables(cells_a, sizes_a, keys_a, sources, cells_b, sizes_b, keys_b, key, params, be, stats) -> PolygonComparison:
+    """two tables (cells, (widths, heights), keys or None) -> the comparison of their aligned rows: by position without keys,
+    else on the keys (_compare_align, the box comparison's); sizes from A, a row whose two usable sizes differ is size_mismatch"""
+    cells_a, cells_b = np.asarray(cells_a, object), np.asarray(cells_b, object)
+    if keys_a is None:
+        rows_a = rows_b = np.arange(len(cells_a), dtype=np.int64)
+        only_a = only_b = np.zeros(0, np.int64)
+        keys_a = keys_b = np.zeros(0, object)
+    else:
+        rows_a, rows_b, only_a, only_b = _compare_align(keys_a, keys_b, key)
+    mismatch = _poly_compare_mismatch(sizes_a, sizes_b, rows_a, rows_b)
+    widths, heights = (None if v is None else np.asarray(v)[rows_a] for v in sizes_a)
+    res = _poly_compare_rows(cells_a[rows_a], cells_b[rows_b], len(rows_a), widths, heights, mismatch, params, be, None,
+                             None if sources is None else np.asarray(sources, object)[rows_a])
+    return _compare_aligned(res, rows_a, keys_a, only_a, keys_b, only_b, stats)
+
+
+def compare_polygons_frame(df_a: pd.DataFrame, df_b: Optional[pd.DataFrame] = None, json_col: str = ANNOTATION_COL, other_col=None,
+                           key="source", width_col: str = "width", height_col: str = "height", iou_threshold: float = 0.5,
+                           by_label: bool = False, max_pixels_per_row: int = 1 << 26, max_pairs_per_row: int = 1 << 20,
+                           batch_pixels: int = 1 << 28, batch_pairs: int = 1 << 26, backend=None,
+                           stats: Optional[dict] = None) -> PolygonComparison:
+    """Polygon comparison of two annotation columns, aligned as compare_boxes_frame aligns them.  With df_b=None: json_col
+    against other_col of df_a, row by row.  With two frames and key=None: by position (equal lengths).  Otherwise on the column
+    `key`; rows found in one frame only are not compared (totals rows_only_a / rows_only_b, ``unpaired``).  The sizes come from
+    df_a's width_col / height_col; when df_b carries them too, an aligned row whose two usable sizes differ is reported as
+    size_mismatch and not compared.  per_row["row"] / differences["row"] are positions in df_a."""
+    params = _poly_compare_params(iou_threshold, by_label, max_pixels_per_row, max_pairs_per_row, batch_pixels, batch_pairs)
+    be = _step_backend(backend, "compare_polygons")
+    wa, ha, sources = _size_columns(df_a, width_col, height_col)
+    if df_b is None:
+        if other_col is None:
+            raise ValueError("with one frame, other_col names the column to compare json_col against")
+        return _poly_compare_tables(df_a[json_col].to_numpy(), (wa, ha), None, sources, df_a[other_col].to_numpy(), (None, None),
+                                    None, None, params, be, stats)
+    col_b = other_col if other_col is not None else json_col
+    wb, hb, _ = _size_columns(df_b, width_col, height_col)
+    if key is None:
+        if len(df_b) != len(df_a):
+            raise ValueError(f"without a key the frames are compared by position: {len(df_a)} against {len(df_b)} rows")
+        return _poly_compare_tables(df_a[json_col].to_numpy(), (wa, ha), None, sources, df_b[col_b].to_numpy(), (wb, hb), None, None,
+                                    params, be, stats)
+    return _poly_compare_tables(df_a[json_col].to_numpy(), (wa, ha), df_a[key].to_numpy(), sources, df_b[col_b].to_numpy(), (wb, hb),
+                                df_b[key].to_numpy(), key, params, be, stats)
+
+
+def _write_polygon_comparison(res: PolygonComparison, output_dir) -> dict:
+    out = Path(output_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    paths = {k: str(out / f"polygon_compare_{k}.csv") for k in ("confusion", "pixels", "classes", "differences", "rows")}
+    paths["hist"] = str(out / "polygon_compare_hist.npz")
+    res.confusion.to_csv(paths["confusion"], index_label="a_class", encoding="utf-8-sig")
+    res.pixel_confusion.to_csv(paths["pixels"], index_label="a_class", encoding="utf-8-sig")
+    res.per_class.to_csv(paths["classes"], index=False, encoding="utf-8-sig")
+    res.differences.to_csv(paths["differences"], index=False, encoding="utf-8-sig")
+    res.per_row.to_csv(paths["rows"], index=False, encoding="utf-8-sig")
+    np.savez(paths["hist"], classes=np.asarray([COMPARE_NONE if c is None else c for c in res.classes], dtype=str),
+             hist_iou=res.hist_iou)
+    return paths
+
+
+def compare_polygons_csv(a_csv, b_csv, output_dir, json_col: str = ANNOTATION_COL, key="source", width_col: str = "width",
+                         height_col: str = "height", iou_threshold: float = 0.5, by_label: bool = False,
+                         max_pixels_per_row: int = 1 << 26, max_pairs_per_row: int = 1 << 20, batch_pixels: int = 1 << 28,
+                         batch_pairs: int = 1 << 26, backend=None):
+    """Two CSVs -> polygon_compare_confusion.csv, polygon_compare_pixels.csv, polygon_compare_classes.csv,
+    polygon_compare_differences.csv, polygon_compare_rows.csv and polygon_compare_hist.npz (classes, hist_iou) under output_dir,
+    in compare_boxes_csv's conventions: read as utf-8-sig; a read failure prints 读取失败：... and a missing column 错误：缺少必要列
+    ..., both returning None.  key=None compares by position.  -> dict(totals, paths=...)"""
+    params = _poly_compare_params(iou_threshold, by_label, max_pixels_per_row, max_pairs_per_row, batch_pixels, batch_pairs)
+    be = _step_backend(backend, "compare_polygons")
+    sides, routes = [], []
+    for path in (a_csv, b_csv):
+        side = _csv_route(
+            "compare_polygons", path, json_col,
+            lambda table: (table.light, _fc_cells(table.heavy[json_col], 0, table.n_rows)),
+            lambda df: (df, df[json_col].to_numpy()))
+        if side is None:
+            return None
+        routes.append(LAST_IO_PATH["compare_polygons"])
+        if key is not None and key not in side[0].columns:
+            print(f"错误：缺少必要列 {key}")
+            return None
+        sides.append(side)
+    LAST_IO_PATH["compare_polygons"] = "native" if routes == ["native", "native"] else "pandas"
+    (light_a, cells_a), (light_b, cells_b) = sides
+    wa, ha, sources = _size_columns(light_a, width_col, height_col)
+    wb, hb, _ = _size_columns(light_b, width_col, height_col)
+    if key is None and len(cells_a) != len(cells_b):
+        raise ValueError(f"without a key the files are compared by position: {len(cells_a)} against {len(cells_b)} rows")
+    res = _poly_compare_tables(cells_a, (wa, ha), None if key is None else light_a[key].to_numpy(), sources, cells_b, (wb, hb),
+                               None if key is None else light_b[key].to_numpy(), key, params, be, None)
+    return {**res.totals, "paths": _write_polygon_comparison(res, output_dir)}
 
 
 def _dataset_dir_name(excel_path: Path, idx_excel: int, used_dir_names: set) -> tuple:

@@ -231,6 +231,10 @@ void set_k19_lane_points(int v);
 void set_k19_lds_points(int v);
 void set_k21_strip(int v);
 void set_k21_crossings(int v);
+void set_k22_strip(int v);
+void set_k22_crossings(int v);
+void set_k22_chunk(int v);
+void set_k22_grid(int v);
 void set_k6_variant(int v);
 void set_k4_capacity_shift(int v);
 void set_k8_band(int v);
@@ -466,6 +470,22 @@ int dyd_set_option(const char *key, int64_t value) {
     }
     if (!strcmp(key, "k21_crossings")) {
         set_k21_crossings((int)value);
+        return DYD_OK;
+    }
+    if (!strcmp(key, "k22_strip")) {   // K22's strip width, list capacity, chunk of B bitmaps and paint grid (tests reach every limit at small shapes)
+        set_k22_strip((int)value);
+        return DYD_OK;
+    }
+    if (!strcmp(key, "k22_crossings")) {
+        set_k22_crossings((int)value);
+        return DYD_OK;
+    }
+    if (!strcmp(key, "k22_chunk")) {
+        set_k22_chunk((int)value);
+        return DYD_OK;
+    }
+    if (!strcmp(key, "k22_grid")) {
+        set_k22_grid((int)value);
         return DYD_OK;
     }
     if (!strcmp(key, "k7_trace_ptr")) {   // device buffer of 8 x n_tiles u64 (0 = off)

@@ -1,5 +1,5 @@
 // poly_table.h — what the host-pointer entries of the polygon steps K13 (k13_seg.hip), K14 (k14_poly_audit.hip), K16
-// (k16_coco.hip), K17 (k17_obb.hip), K20 (k20_tile.hip) and K21 (k21_raster.hip) share: the checks of a polygon table in host memory and its staging in device memory.  The polygon twin of
+// (k16_coco.hip), K17 (k17_obb.hip), K20 (k20_tile.hip), K21 (k21_raster.hip) and K22 (k22_poly_compare.hip, two tables) share: the checks of a polygon table in host memory and its staging in device memory.  The polygon twin of
 // box_table.h; the device code the three kernels share is in k13_poly.h (polygon, clip, walk, row search) and k13_scan.h (scan,
 // print window).
 //

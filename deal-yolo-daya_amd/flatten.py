@@ -548,3 +548,31 @@ def permute_polygons(xy, pt_off, perm) -> tuple:
     new_off = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
     src = np.repeat(pt_off[:-1][perm] - new_off[:-1], count) + np.arange(int(new_off[-1]), dtype=np.int64)
     return np.asarray(xy, np.float64).reshape(-1, 2)[src].reshape(-1), new_off.astype(np.int32)
+
+
+# ---- the polygon comparison's rows and batches (K22; include/dyd.h has the rule) ----------------------------------
+COMPARE_STATUS = ("compared", *MASK_STATUS[1:], "too_many_pairs")   # K22 row status codes 0..4
+
+
+def compare_rows(width, height, n_a, n_b, max_pixels_per_row: int = 1 << 26, max_pairs_per_row: int = 1 << 20) -> tuple:
+    """K22's row rule: K21's sizes (mask_rows), then 4 for a row of more than max_pairs_per_row pairs of polygons -> (status u8
+    [n], pixels int64 [n], pairs int64 [n]); pixels = W * H and pairs = n_a * n_b for a row that is compared, else 0"""
+    status, pixels = mask_rows(width, height, max_pixels_per_row)
+    pairs = np.asarray(n_a, np.int64) * np.asarray(n_b, np.int64)
+    status = np.where((status == 0) & (pairs > max_pairs_per_row), 4, status).astype(np.uint8)
+    return status, np.where(status == 0, pixels, 0).astype(np.int64), np.where(status == 0, pairs, 0).astype(np.int64)
+
+
+def compare_batches(pixels, pairs, batch_pixels: int, batch_pairs: int) -> list:
+    """consecutive row ranges [(a, b)] whose pixel totals stay within batch_pixels and whose pair totals within batch_pairs; a
+    single larger row goes alone"""
+    out, a, tot_px, tot_pr = [], 0, 0, 0
+    for i, (v, w) in enumerate(zip(np.asarray(pixels, np.int64).tolist(), np.asarray(pairs, np.int64).tolist())):
+        if i > a and (tot_px + v > batch_pixels or tot_pr + w > batch_pairs):
+            out.append((a, i))
+            a, tot_px, tot_pr = i, 0, 0
+        tot_px += v
+        tot_pr += w
+    if len(pixels) > a:
+        out.append((a, len(pixels)))
+    return out

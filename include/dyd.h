@@ -693,6 +693,70 @@ int dyd_rasterize_polygons_dev(const double *xy, const int32_t *pt_off, const in
                                int64_t *out_covered, int64_t *out_owned, uint8_t *out_pixels_or_null, int64_t pix_cap,
                                int64_t *out_total, void *stream);
 
+/* ---- K22: polygon comparison — two polygon tables of the same image rows matched by mask IoU ----------------------------
+ * Tables A ("base") and B ("other") are polygon tables in K21's layout: xy [2*P] f64 (16-B aligned), pt_off [B+1] i32, row_off
+ * [n_rows+1] i32, and cls [B] i32: cls[p] < 0: the polygon is not selected, otherwise a class id in 0..n_classes-1 (a larger id is
+ * DYD_ERR_INVALID in the host entry and the caller's duty in the _dev entry, where such a polygon takes part in everything but
+ * the two matrices).  Both tables cover the same n_rows rows and share width / height [n_rows] f64.
+ * Parameters: n_classes in 1..1023; max_pixels_per_row in 1..2^30; max_pairs_per_row in 1..2^24.  Anything else is
+ * DYD_ERR_INVALID.  Offsets are clamped as K13 and K21 clamp them.
+ * Row status, the first rule that applies:
+ *   1 no_size, 2 fractional_size, 3 too_large   exactly K21's rules on W, H and max_pixels_per_row;
+ *   4 too_many_pairs   na * nb > max_pairs_per_row, na and nb the row's polygon counts in A and B, selected or not;
+ *   0 compared         otherwise.
+ * Action per polygon, on either side, the first rule that applies (K21's codes): 255 not selected (cls < 0); 5 the row is not
+ * compared; 2 bad_coords; 3 too_few_points; 0 compared.  Only polygons of action 0 take part in anything below.
+ * Coverage.  cover(p) is K21's set of pixels: centre sampling, the canonical edge direction, P.y <= yc < Q.y,
+ * xs = P.x + ((yc - P.y) * (Q.x - P.x)) / (Q.y - P.y) rounded operation by operation without contraction, the even-odd rule, a
+ * two-point polygon taken as its box.
+ * Pixel counts and IoU.  pixels[p] = |cover(p)|; inter(a, b) = |cover(a) & cover(b)|;
+ *   iou(a, b) = (double)inter / (double)(pixels[a] + pixels[b] - inter) when inter > 0, else exactly 0.0.  There is no NaN IoU.
+ * Matching, per row, indices in-row: K18's rule on that IoU with one difference: a pair is a candidate only when inter > 0 AND
+ * iou >= thr, so a threshold <= 0 never matches disjoint polygons; thr = NaN matches nothing.
+ *   for j in 0 .. nb-1 (compared B polygons in annotation order):
+ *     cand = { i : A polygon i compared and not matched yet, (not by_label or a_cls[i] == b_cls[j]), inter(a_i, b_j) > 0,
+ *              iou(a_i, b_j) >= thr }
+ *     cand not empty: i* = the i of cand with the largest iou, ties -> lowest i; b_match[j] = i*, a_match[i*] = j, b_iou[j] = iou
+ *     else:           b_match[j] = -1, b_iou[j] = 0.0
+ *   a_match / b_match are -1 and b_iou 0.0 for every polygon never taken, compared or not.
+ *   a_best[i] / b_best[j]: the largest iou with ANY compared polygon of the other side, class and matched state ignored; from 0.0.
+ * out_confusion: K18's meaning over compared polygons: a matched pair in [a_cls][b_cls], an unmatched compared A polygon in
+ *   [a_cls][C], an unmatched compared B polygon in [C][b_cls], C = n_classes.  out_row_counts: K18's four counts per row (matched
+ *   with equal class, matched with different class, compared A unmatched, compared B unmatched).
+ * Pixel classes.  On each side a pixel's class is the cls of the last compared polygon of the row, in table order, that covers it
+ *   (K21's ownership), C (the background) when none does.  out_pixel_confusion[ca][cb] counts the pixels of all rows of status 0;
+ *   its sum is the sum of W * H over those rows.  out_row_pixels: per row the pixels where both sides are foreground with the
+ *   same class, then the pixels where either side is foreground.
+ * Pair table.  pair_off[i] is the exclusive sum of na * nb over the rows of status 0 (other rows add 0).  inter(a_i, b_j) of row
+ *   r is the u32 at pair_off[r] + i * nb + j (a row has at most 2^30 pixels).
+ * out_row_status u8 [n_rows]; out_pair_off i64 [n_rows+1]; out_a_action / out_b_action u8 [B]; out_a_pixels / out_b_pixels i64
+ * [B]; out_a_match / out_b_match i32 [B]; out_b_iou f64 [n_b]; out_a_best / out_b_best f64 [B]; out_row_counts i32 [4*n_rows];
+ * out_confusion / out_pixel_confusion u64 [(C+1)*(C+1)], zeroed by the entry; out_row_pixels i64 [2*n_rows].
+ * n_rows == 0 returns at once; otherwise every output is written, also when no row holds a polygon.
+ * dyd_compare_polygons     : host pointers; the pair counts stay inside.
+ * dyd_compare_polygons_dev : device pointers, enqueued on stream.  n_a = a_row_off[n_rows], n_a_points = a_pt_off[n_a], and the
+ *                            same for B.  out_pairs_or_null: pair_cap u32 elements for the pair counts, left there for the
+ *                            caller; NULL: the library keeps them in a buffer of its own.  DYD_ERR_RANGE when pair_off[n_rows]
+ *                            exceeds pair_cap, DYD_ERR_OOM when the library's buffer cannot be had: in both cases nothing but
+ *                            out_row_status and out_pair_off has been written.
+ * n_rows, n_a, n_b and the point counts stay below 2^31 (DYD_ERR_INVALID otherwise). */
+int dyd_compare_polygons(const double *a_xy, const int32_t *a_pt_off, const int32_t *a_row_off, const int32_t *a_cls,
+                         const double *b_xy, const int32_t *b_pt_off, const int32_t *b_row_off, const int32_t *b_cls,
+                         const double *width, const double *height, int64_t n_rows, int32_t n_classes, double thr, int by_label,
+                         int64_t max_pixels_per_row, int64_t max_pairs_per_row, uint8_t *out_row_status, int64_t *out_pair_off,
+                         uint8_t *out_a_action, uint8_t *out_b_action, int64_t *out_a_pixels, int64_t *out_b_pixels,
+                         int32_t *out_a_match, int32_t *out_b_match, double *out_b_iou, double *out_a_best, double *out_b_best,
+                         int32_t *out_row_counts, uint64_t *out_confusion, uint64_t *out_pixel_confusion, int64_t *out_row_pixels);
+int dyd_compare_polygons_dev(const double *a_xy, const int32_t *a_pt_off, const int32_t *a_row_off, const int32_t *a_cls,
+                             const double *b_xy, const int32_t *b_pt_off, const int32_t *b_row_off, const int32_t *b_cls,
+                             const double *width, const double *height, int64_t n_rows, int64_t n_a, int64_t n_a_points, int64_t n_b,
+                             int64_t n_b_points, int32_t n_classes, double thr, int by_label, int64_t max_pixels_per_row,
+                             int64_t max_pairs_per_row, uint8_t *out_row_status, int64_t *out_pair_off, uint8_t *out_a_action,
+                             uint8_t *out_b_action, int64_t *out_a_pixels, int64_t *out_b_pixels, int32_t *out_a_match,
+                             int32_t *out_b_match, double *out_b_iou, double *out_a_best, double *out_b_best,
+                             int32_t *out_row_counts, uint64_t *out_confusion, uint64_t *out_pixel_confusion, int64_t *out_row_pixels,
+                             uint32_t *out_pairs_or_null, int64_t pair_cap, void *stream);
+
 /* ---- native flatten / emit (HOST code, multithreaded) ------------------------------
  * Schema-specialised JSON scanner + canonical re-emitter that replaces json.loads / json.dumps inside
  * parse_and_replace_ptlist (processor.py:262-281), extract_width_height (:285-292) and extract_boxes
@@ -925,7 +989,10 @@ void dyd_host_free(void *p);
  * "k2_variant": -1 by shape, 4 = the wave kernel's pair stage, 0..3 / 5 = tile kernels (2 / 3 / 5 with the f32 filter and the sweep);
  * "k14_lane_edges": the largest number of edges of U whose self-intersection test K14 runs in one lane (<= 0: the default);
  * "k19_lane_points": the largest polygon (points) K19 simplifies in one lane (default 32, at most 64), "k19_lds_points": the
- * largest one a workgroup stages in LDS (default and at most 1024; beyond it the points stream from HBM); <= 0: the default. */
+ * largest one a workgroup stages in LDS (default and at most 1024; beyond it the points stream from HBM); <= 0: the default;
+ * "k21_strip" / "k21_crossings" and "k22_strip" / "k22_crossings": the strip width (default and at most 1024) and the capacity of
+ * the crossing list (256) of K21 and of K22, "k22_chunk": the B bitmaps K22 holds at a time (32), "k22_grid": a cap on K22's paint
+ * workgroups (2^20); <= 0: the default, larger values are capped. */
 int dyd_set_option(const char *key, int64_t value);
 /* measurement aid: plain streaming kernel (mode 0 copy, 1 read-only, 2 write-only, 3-5 the same non-temporal, 16 B per
  * lane) used to record the box's HBM ceiling next to the kernels' achieved GB/s; modes 6 / 7 / 8: one 8-byte word per lane

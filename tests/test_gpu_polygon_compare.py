@@ -1,0 +1,348 @@
+"""K22 (polygon comparison by mask IoU, csrc/k22_poly_compare.hip) through both C-ABI entries and compare_polygons_csv, against
+the restatement in tests/polygon_compare_ref.py.  Exact: every output array with np.array_equal and equal dtypes, guard values
+round the outputs of the _dev entry.  The shapes are the smallest at which each compiled capacity (strip, crossing list, chunk of
+B bitmaps, paint grid) is reached.  Needs a real MI355X."""
+import json
+import math
+
+import numpy as np
+import pandas as pd
+import pytest
+
+import polygon_compare_ref as R
+from polygon_compare_tables import RANDOM, blob, box, random_rows, random_table, random_want, table
+from deal_yolo_daya_amd.core import processor as P
+
+pytestmark = pytest.mark.gpu
+
+NAMES = R.NAMES
+STRIP, CROSSINGS, CHUNK = 1024, 256, 32
+ERR_RANGE = -5
+
+
+def same(got, want, names=NAMES):
+    for g, w, what in zip(got, want, names):
+        g, w = np.asarray(g), np.asarray(w)
+        assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w), what
+
+
+FILLS = {np.uint8: 0xA5, np.int32: -77, np.int64: -7, np.float64: -3.5, np.uint64: 0xDEADBEEF12345678, np.uint32: 0xABCDEF01}
+
+
+def run_dev(t, n_classes, thr=0.5, by_label=False, max_pixels_per_row=1 << 26, max_pairs_per_row=1 << 20, pairs="own",
+            pair_cap=None, n_pairs=None):
+    """the _dev entry on torch tensors: every output one element into a guarded buffer filled with a sentinel -> (the sixteen
+    outputs, return code).  pairs="null" passes no pair buffer (the last output is then empty)."""
+    import torch
+    from deal_yolo_daya_amd import _native
+
+    a_xy, a_pt, a_row, a_cls, b_xy, b_pt, b_row, b_cls, W, H = t
+    dev = torch.device("cuda", 0)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)     # noqa: E731
+
+    def up_xy(xy):                                                       # 16 bytes into its buffer: still 16-byte aligned
+        d = torch.zeros(len(xy) + 4, dtype=torch.float64, device=dev)
+        d[2:2 + len(xy)] = up(xy)
+        return d
+
+    d_axy, d_bxy = up_xy(a_xy), up_xy(b_xy)
+    ins = [up(v) for v in (a_pt, a_row, a_cls, b_pt, b_row, b_cls, W, H)]
+    n, na, nb, Cc = len(W), len(a_cls), len(b_cls), n_classes + 1
+    if n_pairs is None:                                                  # the size of the pair table, from the row rule
+        n_pairs = R.compare_arrays(*t, n_classes, thr, by_label, max_pixels_per_row, max_pairs_per_row)[1][-1] if n else 0
+    want_pairs = int(n_pairs)
+    spec = [(np.uint8, n), (np.int64, n + 1), (np.uint8, na), (np.uint8, nb), (np.int64, na), (np.int64, nb), (np.int32, na),
+            (np.int32, nb), (np.float64, nb), (np.float64, na), (np.float64, nb), (np.int32, 4 * n), (np.uint64, Cc * Cc),
+            (np.uint64, Cc * Cc), (np.int64, 2 * n), (np.uint32, int(want_pairs))]
+    bufs = [up(np.full(size + 2, FILLS[dt], dt)) for dt, size in spec]
+    ptrs = [b.data_ptr() + b.element_size() for b in bufs]
+    if pairs == "null":
+        ptrs[-1] = None
+    cap = int(want_pairs) if pair_cap is None else pair_cap
+    L, sp = _native.lib(), torch.cuda.current_stream().cuda_stream
+    rc = L.dyd_compare_polygons_dev(d_axy.data_ptr() + 16, ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(),
+                                    d_bxy.data_ptr() + 16, ins[3].data_ptr(), ins[4].data_ptr(), ins[5].data_ptr(),
+                                    ins[6].data_ptr(), ins[7].data_ptr(), n, na, len(a_xy) // 2, nb, len(b_xy) // 2, n_classes,
+                                    float(thr), int(by_label), max_pixels_per_row, max_pairs_per_row, *ptrs, cap, sp)
+    torch.cuda.synchronize()
+    out = []
+    for k, (b, (dt, size)) in enumerate(zip(bufs, spec)):
+        a = b.cpu().numpy()
+        assert a[0] == FILLS[dt] and a[-1] == FILLS[dt], f"write outside {NAMES[k]}"
+        out.append(a[1:-1])
+    if pairs == "null":
+        assert (out[-1] == FILLS[np.uint32]).all()
+        out[-1] = np.zeros(0, np.uint32)
+    out[11], out[14] = out[11].reshape(n, 4), out[14].reshape(n, 2)
+    out[12], out[13] = out[12].reshape(Cc, Cc), out[13].reshape(Cc, Cc)
+    return out, rc
+
+
+def both(native, t, n_classes, want=None, **kw):
+    want = R.compare_arrays(*t, n_classes, **kw) if want is None else want
+    same(native.compare_polygons(*t, n_classes, **kw), want[:15])
+    got, rc = run_dev(t, n_classes, n_pairs=want[1][-1], **kw)
+    assert rc == 0, native.lib().dyd_last_error()
+    same(got, want)
+    return want
+
+
+def option(native, strip=0, crossings=0, chunk=0, grid=0):
+    for key, v in ((b"k22_strip", strip), (b"k22_crossings", crossings), (b"k22_chunk", chunk), (b"k22_grid", grid)):
+        native.check(native.lib().dyd_set_option(key, v), "opt")
+
+
+@pytest.fixture(autouse=True)
+def default_options(native):
+    yield
+    option(native)
+
+
+# ----------------------------------------------------------------------------------------------- random tables
+def test_the_random_table_holds_every_case():
+    want = random_want()
+    assert want[11].sum(axis=0).min() > 0, "agree, relabelled, missing, extra"
+    assert {0, 1, 2, 3, 4} <= set(want[0].tolist())
+    assert {0, 2, 3, 5, 255} <= set(want[2].tolist()) | set(want[3].tolist())
+    between = np.flatnonzero(want[0] != 0)
+    assert (want[0][between - 1] == 0).any() and (want[0][np.minimum(between + 1, len(want[0]) - 1)] == 0).any()
+    assert ((want[4] > 0).sum() > 20) and len(want[15]) > 200 and (want[15] > 0).sum() > 30
+
+
+@pytest.mark.parametrize("by_label", [False, True])
+@pytest.mark.parametrize("thr", [0.5, 0.9])
+def test_random_table(native, thr, by_label):
+    want = random_want(thr, by_label)
+    assert want[11][:, 0].sum() > 0 and want[11][:, 2].sum() > 0 and want[11][:, 3].sum() > 0
+    assert (want[11][:, 1].sum() > 0) != by_label
+    both(native, random_table(), want=want, thr=thr, by_label=by_label, **RANDOM)
+
+
+def test_grid_stride_and_determinism(native):
+    """three paint workgroups over a few thousand items; and the same bytes from every run"""
+    t = random_table()
+    n_items = sum(int(h) for s, h in zip(random_want()[0], t[9]) if s == 0)
+    assert n_items > 300
+    runs = []
+    for grid in (0, 0, 3, 3):
+        option(native, grid=grid)
+        got, rc = run_dev(t, **RANDOM)
+        assert rc == 0
+        same(got, random_want())
+        runs.append(b"".join(np.ascontiguousarray(g).tobytes() for g in got))
+    assert runs[0] == runs[1] == runs[2] == runs[3]
+    option(native, strip=17, crossings=3, chunk=2, grid=5)                      # every capacity small at once
+    same(native.compare_polygons(*t, **RANDOM), random_want()[:15])
+
+
+# ----------------------------------------------------------------------------------------------- strips
+def strip_rows(widths, h=5):
+    rng = np.random.default_rng(31)
+    rows = []
+    for w in widths:
+        a = [(0, blob(rng, w / 2, h / 2, w / 2 + 1, 9)), (1, box(w - 3, 0, w, h)), (2, box(-5, 1, w + 5, 2.2))]
+        b = [(0, blob(rng, w / 2 + 1, h / 2, w / 2, 7)), (2, box(w - 4, 1, w - 1, h)), (1, box(0, 0, w, 1.7)), (1, box(60, 1, 70, 4))]
+        rows.append((w, h, a, b))
+    return rows
+
+
+@pytest.mark.parametrize("strip", [64, 17])
+def test_strips(native, strip):
+    option(native, strip=strip)
+    want = both(native, table(strip_rows((63, 64, 65, 130))), 3)
+    assert (want[4] > 0).all() and (want[15] > 0).sum() >= 16
+
+
+def test_the_default_strip(native):
+    w = STRIP + 37
+    rng = np.random.default_rng(32)
+    a = [(0, blob(rng, w / 2, 1.5, w / 2, 9)), (1, box(1000, 0, 1050, 3)), (2, box(w - 3, 0, w, 3))]
+    b = [(0, blob(rng, w / 2 + 3, 1.5, w / 2, 9)), (1, box(1020, 1, 1030, 3)), (2, box(w - 5, 0, w - 1, 2)), (0, box(3, 0, 1024, 1))]
+    want = both(native, table([(w, 3, a, b)]), 3)
+    assert (want[4] > 0).all() and (want[5] > 0).all() and (want[15] > 0).sum() >= 5 and want[13].sum() == 3 * w
+
+
+# ----------------------------------------------------------------------------------------------- the crossing list
+def comb(n_teeth):
+    pts = [(0.0, 0.0)]
+    for k in range(n_teeth):
+        pts += [(3.0 * k + 0.5, 10.0), (3.0 * k + 1.5, 1.0), (3.0 * k + 2.5, 10.0)]
+    return pts + [(3.0 * n_teeth + 5.0, 0.0)]
+
+
+@pytest.mark.parametrize("crossings", [3, 1])
+def test_a_full_crossing_list_is_applied_and_emptied(native, crossings):
+    option(native, crossings=crossings)
+    rng = np.random.default_rng(33)
+    shifted = [(x + 1.0, y) for x, y in comb(40)]
+    want = both(native, table([(125, 12, [(0, comb(40)), (1, blob(rng, 60, 6, 30, 9))], [(0, shifted), (1, blob(rng, 62, 6, 30, 9))])]), 2)
+    assert want[4][0] > 300 and want[5][0] > 300 and (want[15] > 0).all()
+
+
+def test_more_crossings_than_the_default_list_holds(native):
+    a, b = comb(150), [(x + 1.0, y) for x, y in comb(150)]
+    assert 2 * 150 > CROSSINGS
+    want = both(native, table([(640, 4, [(0, a)], [(0, b), (1, box(100, 0, 300, 4))])]), 2)
+    assert want[4][0] > 600 and (want[15] > 0).all()
+
+
+# ----------------------------------------------------------------------------------------------- chunks of B bitmaps
+def overlapping(n, w, h, n_classes, seed):
+    rng = np.random.default_rng(seed)
+    return [(int(rng.integers(0, n_classes)), blob(rng, w / 2 + rng.uniform(-2, 2), h / 2 + rng.uniform(-1, 1), w / 2, 6)) for _ in range(n)]
+
+
+@pytest.mark.parametrize("chunk", [1, 2, 3])
+def test_chunks(native, chunk):
+    option(native, chunk=chunk)
+    rows = [(20, 10, overlapping(3, 20, 10, 2, 40 + k), overlapping(7, 20, 10, 2, 50 + k)) for k in range(3)]
+    rows.append((20, 10, [], overlapping(7, 20, 10, 2, 60)))
+    want = both(native, table(rows), 2)
+    assert (want[15] > 0).sum() >= 50
+
+
+def test_one_more_b_polygon_than_the_default_chunk(native):
+    want = both(native, table([(16, 8, overlapping(3, 16, 8, 2, 70), overlapping(CHUNK + 1, 16, 8, 2, 71))]), 2)
+    assert len(want[15]) == 3 * (CHUNK + 1) and (want[15] > 0).sum() > 90 and want[15][CHUNK] > 0 and want[15][-1] > 0
+
+
+# ----------------------------------------------------------------------------------------------- the match step
+def pixel_boxes(n):
+    return [(k % 2, box(k % 32, k // 32, k % 32 + 1, k // 32 + 1)) for k in range(n)]
+
+
+def test_rows_longer_than_a_wave(native):
+    few = [(0, box(0, 0, 32, 1)), (1, box(5, 0, 6, 1)), (0, box(3, 2, 6, 3))]
+    rows = [(32, 32, pixel_boxes(70), few), (32, 32, few, pixel_boxes(70)), (32, 32, pixel_boxes(70), pixel_boxes(70)[::-1])]
+    for thr in (0.5, 0.02):
+        want = both(native, table(rows), 2, thr=thr)
+        assert want[11][:, :2].sum() > (2 if thr == 0.5 else 70)
+
+
+def test_rows_without_polygons(native):
+    a = [(0, box(0, 0, 4, 4)), (1, box(2, 2, 6, 6))]
+    want = both(native, table([(8, 8, a, []), (8, 8, [], a), (8, 8, [], []), (8, 8, a, a)]), 2)
+    assert want[11].tolist() == [[0, 0, 2, 0], [0, 0, 0, 2], [0, 0, 0, 0], [2, 0, 0, 0]]
+    assert want[14].tolist() == [[0, 28], [0, 28], [0, 0], [28, 28]] and want[13].sum() == 4 * 64
+
+
+@pytest.mark.parametrize("n_classes", [1, 31, 32, 1023])
+def test_class_counts(native, n_classes):
+    rng = np.random.default_rng(31)
+    top = n_classes - 1
+    a = [(top, box(0, 0, 10, 10)), (0, box(12, 0, 20, 8)), (top // 2, blob(rng, 10, 14, 6, 7)), (top, box(22, 12, 24, 20))]
+    b = [(0, box(1, 0, 10, 10)), (top, box(12, 1, 20, 8)), (top // 2, blob(rng, 11, 14, 6, 7)), (top, box(0, 18, 3, 20))]
+    want = both(native, table([(24, 20, a, b)]), n_classes)
+    assert want[12].sum() == 6 and want[11][0, :2].sum() == 2 and want[13].sum() == 480 and want[13][top, 0] > 50 and want[13][0, top] > 50
+
+
+# ----------------------------------------------------------------------------------------------- pairs
+def pair_rows():
+    a = [(0, box(0, 0, 4, 4)), (1, box(3, 3, 8, 8))]
+    b = [(0, box(1, 1, 5, 5)), (1, box(4, 4, 8, 8)), (0, box(0, 6, 2, 8)), (1, box(6, 0, 8, 2))]
+    return [(8, 8, a, b[:3]), (8, 8, a, b), (8, 8, a[:1], b)]
+
+
+def test_too_many_pairs(native):
+    want = both(native, table(pair_rows()), 2, max_pairs_per_row=6)
+    assert want[0].tolist() == [0, 4, 0] and want[1].tolist() == [0, 6, 6, 10]
+    assert want[2].tolist() == [0, 0, 5, 5, 0] and want[3].tolist() == [0, 0, 0, 5, 5, 5, 5, 0, 0, 0, 0]
+    assert want[13].sum() == 128
+
+
+def test_a_pair_buffer_one_short_and_none_at_all(native):
+    t = table(pair_rows())
+    want = R.compare_arrays(*t, 2, max_pairs_per_row=6)
+    got, rc = run_dev(t, 2, max_pairs_per_row=6, pair_cap=9)
+    assert rc == ERR_RANGE and b"too small" in native.lib().dyd_last_error()
+    same(got[:2], want[:2])
+    for g in got[2:]:                                                          # nothing else was written
+        assert (g == FILLS[g.dtype.type]).all()
+    got, rc = run_dev(t, 2, max_pairs_per_row=6, pairs="null")
+    assert rc == 0
+    same(got[:15], want[:15])
+
+
+# ----------------------------------------------------------------------------------------------- degenerate tables
+def test_degenerate_tables(native):
+    none = tuple(np.zeros(k, d) for k, d in ((0, np.float64), (1, np.int32), (1, np.int32), (0, np.int32)) * 2) + (np.zeros(0), np.zeros(0))
+    got = native.compare_polygons(*none, 2)                                    # n_rows == 0 returns at once
+    assert all(len(g) == 0 for g in got[:1] + got[2:12]) and not got[12].any() and not got[13].any()
+    got, rc = run_dev(none, 2)
+    assert rc == 0 and all((g == FILLS[g.dtype.type]).all() for g in got)      # and writes nothing
+    want = both(native, table([(5, 4, [], []), (2, 2, [], [])]), 2)            # no polygons: the matrices are still zeroed
+    assert want[13].tolist() == [[0, 0, 0], [0, 0, 0], [0, 0, 24]] and not want[12].any()
+    a = [(0, box(0, 0, 3, 3)), (-1, box(0, 0, 3, 3))]
+    want = both(native, table([(0, 5, a, a), (4.5, 4, a, a), (5000, 5000, a, a)]), 2, max_pixels_per_row=1 << 20)   # a pixel total of 0
+    assert want[0].tolist() == [1, 2, 3] and want[2].tolist() == [5, 255] * 3 and not want[13].any() and len(want[15]) == 0
+
+
+BIG = 2.0 ** 40
+SKEWED = [[(-BIG, -BIG + 1), (BIG + 3, BIG), (7.0, 2 * BIG)], [(-2 * BIG + 5, 3.0), (2 * BIG, -BIG + 11), (BIG + 1, 4 * BIG)],
+          [(-4 * BIG, 2 * BIG + 7), (4 * BIG - 9, -2 * BIG), (13.0, -4 * BIG + 1)], [(BIG + 20, -BIG), (-BIG, BIG + 45), (-2 * BIG - 3, -2 * BIG)]]
+
+
+def test_large_coordinates(native):
+    a = [(k % 2, tri) for k, tri in enumerate(SKEWED)] + [(0, [(1.0, 1.0), (2.0 ** 43, 5.0), (3.0, 9.0)])]
+    b = [(k % 2, tri) for k, tri in enumerate(SKEWED[::-1])] + [(1, blob(np.random.default_rng(80), 25, 25, 20, 9))]
+    want = both(native, table([(50, 50, a, b)]), 2, thr=0.3)
+    assert want[2].tolist() == [0, 0, 0, 0, 2] and ((want[4] > 0) & (want[4] < 2500)).sum() >= 2 and (want[8] == 1.0).sum() >= 2
+
+
+@pytest.mark.parametrize("bad", [dict(n_classes=0), dict(n_classes=1024), dict(max_pixels_per_row=0), dict(max_pixels_per_row=2 ** 30 + 1),
+                                 dict(max_pairs_per_row=0), dict(max_pairs_per_row=2 ** 24 + 1), dict(cls=2)])
+def test_invalid_arguments_are_the_argument_error(native, bad):
+    t = list(table([(8, 8, [(bad.get("cls", 0), box(0, 0, 4, 4))], [(0, box(1, 1, 5, 5))])]))
+    kw = dict(n_classes=2, max_pixels_per_row=1 << 20, max_pairs_per_row=1 << 10)
+    kw.update({k: v for k, v in bad.items() if k != "cls"})
+    with pytest.raises(Exception, match="invalid argument"):
+        native.compare_polygons(*t, **kw)
+    if "cls" not in bad:
+        got, rc = run_dev(tuple(t), kw["n_classes"], max_pixels_per_row=kw["max_pixels_per_row"], max_pairs_per_row=kw["max_pairs_per_row"],
+                          pair_cap=1) if kw["n_classes"] > 0 else (None, -1)
+        assert rc == -1
+
+
+# ----------------------------------------------------------------------------------------------- the long sparse table
+def test_long_sparse_table(native):
+    """tests/long_tables.py as A, the same polygons moved by (0.5, 0) as B: 6,000 rows and 2,986 polygons a side, so every scan
+    runs over more than one part; one row of 700 x 700 pairs"""
+    import long_tables as LT
+
+    xy, pt_off, row_off, W, H = LT.long_sparse()
+    cls = LT.k14_cls(len(pt_off) - 1)
+    moved = xy.copy()
+    moved[0::2] += 0.5
+    t = (xy, pt_off, row_off, cls, moved, pt_off, row_off, cls, W, H)
+    want = both(native, t, 4)
+    assert want[1][-1] > 490000 and {0, 1, 2} <= set(want[0].tolist()) and want[11][:, 0].sum() > 500 and want[11][:, 2].sum() > 100
+
+
+# ----------------------------------------------------------------------------------------------- through the product
+def test_compare_polygons_csv_end_to_end(native, tmp_path):
+    from helpers import OracleBackend
+
+    names = ["a", "b", "c"]
+    rows = random_rows(21, n_rows=30, max_polys=5, max_size=60)
+
+    def cells(k):
+        return [json.dumps({"objects": [{"name": names[c] if c >= 0 else 7, "polygon": {"ptList": [{"x": x, "y": y} for x, y in pts]}}
+                                        for c, pts in row[k] if all(map(math.isfinite, sum(pts, ())))]}) for row in rows]
+
+    src = [f"im{k}.jpg" for k in range(30)]
+    sizes = {"width": [r[0] for r in rows], "height": [r[1] for r in rows]}
+    pa, pb = tmp_path / "a.csv", tmp_path / "b.csv"
+    pd.DataFrame({"source": src, P.ANNOTATION_COL: cells(2), **sizes}).to_csv(pa, index=False, encoding="utf-8-sig")
+    pd.DataFrame({"source": src[::-1], P.ANNOTATION_COL: cells(3)[::-1]}).to_csv(pb, index=False, encoding="utf-8-sig")
+    kw = dict(iou_threshold=0.4, max_pairs_per_row=20, batch_pixels=5000, batch_pairs=40)
+    res = P.compare_polygons_csv(pa, pb, tmp_path / "gpu", **kw)
+    ref_be = type("RefBackend", (OracleBackend,), {"compare_polygons": staticmethod(lambda *a, **k: R.compare_arrays(*a, **k)[:15])})()
+    want = P.compare_polygons_csv(pa, pb, tmp_path / "ref", backend=ref_be, **kw)
+    assert {k: v for k, v in res.items() if k not in ("paths", "python_cells")} == \
+        {k: v for k, v in want.items() if k not in ("paths", "python_cells")}
+    assert res["agree"] > 10 and res["missing"] > 0 and res["extra"] > 0 and res["rows_compared"] > 20 and res["pixels"] > 15000
+    for key in ("confusion", "pixels", "classes", "differences", "rows"):
+        got_text, want_text = (open(r["paths"][key], encoding="utf-8-sig").read() for r in (res, want))
+        assert got_text == want_text and len(got_text) > 20, key
+    g, w = np.load(res["paths"]["hist"]), np.load(want["paths"]["hist"])
+    assert g["classes"].tolist() == w["classes"].tolist() and np.array_equal(g["hist_iou"], w["hist_iou"]) and g["hist_iou"].sum() > 10

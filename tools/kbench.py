@@ -4,7 +4,8 @@ interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant
 
     python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k18: box comparison beside K2 and K9; k13: segmentation lines beside K7;
      k14: polygon audit; k14tier: its in-lane / wave threshold; simplify: polygon simplification (K19) beside K14 on rings of 8, 64 and 1024 points; k16: COCO annotation objects beside K13; k17: oriented-box lines beside K13; tile: tiled label lines (K20) beside K13;
-     k21: label masks (K21) on many small and few large images, beside Pillow on one core)
+     k21: label masks (K21) on many small and few large images, beside Pillow on one core; k22: polygon comparison (K22) on the same
+     two tables, interleaved with K21 over either side)
 """
 import argparse
 import json
@@ -602,6 +603,25 @@ def main():
                    ms_vs_k13=round(med20 / med13, 3), pairs_per_polygon=round(pairs / B, 3), text_vs_k13=round(T20 / max(T13, 1), 3))
             del text20
         del text13
+    def raster_shapes():
+        """the two tables of the k21 and k22 legs -> (name, xy, pt_off, row_off, rows, polygons, points, W, H)"""
+        nr = min(N, 8192)
+        nb_s = int(box_off[nr].item()); np_s = int(pt_off[nb_s].item())
+        xs = (xy[:np_s] * torch.tensor([256.0 / 1920.0, 144.0 / 1080.0], dtype=torch.float64, device=dev)).contiguous()
+        yield "small_images", xs, pt_off[:nb_s + 1].contiguous(), box_off[:nr + 1].contiguous(), nr, nb_s, np_s, 256, 144
+        del xs
+        rng = np.random.default_rng(21)
+        m, rings = 2000, []
+        for q in range(32):
+            ang = np.sort(rng.uniform(0, 2 * np.pi, m))
+            rad = rng.uniform(600, 1800, 1) * (1 + 0.3 * np.sin(ang * rng.integers(3, 40)) + rng.uniform(-0.05, 0.05, m))
+            c = rng.uniform(1000, 3096, 2)
+            rings.append(np.stack([c[0] + rad * np.cos(ang), c[1] + rad * np.sin(ang)], axis=1))
+        xl = torch.from_numpy(np.concatenate(rings)).to(dev)
+        ptl = torch.arange(0, 32 * m + 1, m, dtype=torch.int32, device=dev)
+        rol = torch.arange(0, 33, 4, dtype=torch.int32, device=dev)
+        yield "large_images", xl, ptl, rol, 8, 32, 32 * m, 4096, 4096
+
     if "k21" in only:
         import ctypes as C
         import time
@@ -648,22 +668,85 @@ def main():
                    byte_floor_GB=round((table_bytes + T) / 1e9, 4), pillow_one_core_ms=round(pillow_ms, 1),
                    pillow_over_k21=round(pillow_ms / med, 1))
 
-        nr = min(N, 8192)
-        nb_s = int(box_off[nr].item()); np_s = int(pt_off[nb_s].item())
-        xs = (xy[:np_s] * torch.tensor([256.0 / 1920.0, 144.0 / 1080.0], dtype=torch.float64, device=dev)).contiguous()
-        k21_leg("small_images", xs, pt_off[:nb_s + 1].contiguous(), box_off[:nr + 1].contiguous(), nr, nb_s, np_s, 256, 144)
-        del xs
-        rng = np.random.default_rng(21)
-        m, rings = 2000, []
-        for q in range(32):
-            ang = np.sort(rng.uniform(0, 2 * np.pi, m))
-            rad = rng.uniform(600, 1800, 1) * (1 + 0.3 * np.sin(ang * rng.integers(3, 40)) + rng.uniform(-0.05, 0.05, m))
-            c = rng.uniform(1000, 3096, 2)
-            rings.append(np.stack([c[0] + rad * np.cos(ang), c[1] + rad * np.sin(ang)], axis=1))
-        xl = torch.from_numpy(np.concatenate(rings)).to(dev)
-        ptl = torch.arange(0, 32 * m + 1, m, dtype=torch.int32, device=dev)
-        rol = torch.arange(0, 33, 4, dtype=torch.int32, device=dev)
-        k21_leg("large_images", xl, ptl, rol, 8, 32, 32 * m, 4096, 4096)
+        for shape in raster_shapes():
+            k21_leg(*shape)
+    if "k22" in only:
+        import ctypes as C
+        # K22 (polygon comparison by mask IoU) on the k21 leg's two tables.  B is A with 10 % of the polygons dropped, 10 % with
+        # jittered vertices and 5 % put into another class (the k18 leg's proportions).  K22 runs interleaved with K21 over A and
+        # K21 over B on the same device buffers, which is what the comparison would cost by two mask exports; the two mask
+        # downloads that route also needs are timed beside them.  Byte floor: both tables read once, the pair table written.
+        total = C.c_int64()
+        nc = 20
+
+        def k22_leg(name, xy_, pt_, roff, nr, nb, npts, W, H):
+            rng = np.random.default_rng(22)
+            hx, hp, hr = xy_.cpu().numpy().reshape(-1, 2), pt_.cpu().numpy().astype(np.int64), roff.cpu().numpy().astype(np.int64)
+            u = rng.random(nb)
+            keep = np.flatnonzero(u >= 0.10)
+            cls_a = (np.arange(nb) % nc).astype(np.int32)
+            cls_b = np.where(u[keep] >= 0.95, (cls_a[keep] + 1) % nc, cls_a[keep]).astype(np.int32)
+            cnt = np.diff(hp)[keep]
+            pb = np.concatenate([[0], np.cumsum(cnt)])
+            src = np.repeat(hp[:-1][keep] - pb[:-1], cnt) + np.arange(int(pb[-1]))
+            xb = hx[src].copy()
+            jit = np.repeat((u[keep] >= 0.10) & (u[keep] < 0.20), cnt)
+            xb[jit] += rng.uniform(-2.0, 2.0, (int(jit.sum()), 2))
+            rb = np.concatenate([[0], np.cumsum(np.bincount(np.searchsorted(hr, keep, side="right") - 1, minlength=nr))])
+            nbb, npb = len(keep), int(pb[-1])
+            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)   # noqa: E731
+            b_xy, b_pt, b_row, d_ca, d_cb = up(xb.reshape(-1), np.float64), up(pb, np.int32), up(rb, np.int32), up(cls_a, np.int32), up(cls_b, np.int32)
+            w = torch.full((nr,), float(W), dtype=torch.float64, device=dev); h = torch.full((nr,), float(H), dtype=torch.float64, device=dev)
+            e = lambda n_, dt: torch.empty(max(n_, 1), dtype=dt, device=dev)                   # noqa: E731
+            status, poff = e(nr, torch.uint8), e(nr + 1, torch.int64)
+            outs_a = (e(nb, torch.uint8), e(nb, torch.int64), e(nb, torch.int32), e(nb, torch.float64))
+            outs_b = (e(nbb, torch.uint8), e(nbb, torch.int64), e(nbb, torch.int32), e(nbb, torch.float64))
+            b_iou, rows_, rpix = e(nbb, torch.float64), e(4 * nr, torch.int32), e(2 * nr, torch.int64)
+            conf, pconf = e((nc + 1) ** 2, torch.int64), e((nc + 1) ** 2, torch.int64)
+            n_pairs = int((np.diff(hr) * np.diff(rb)).sum())
+            pairs = e(n_pairs, torch.int32)
+            a22 = (xy_.data_ptr(), pt_.data_ptr(), roff.data_ptr(), d_ca.data_ptr(), b_xy.data_ptr(), b_pt.data_ptr(), b_row.data_ptr(),
+                   d_cb.data_ptr(), w.data_ptr(), h.data_ptr(), nr, nb, npts, nbb, npb, nc, 0.5, 0, 1 << 26, 1 << 20, status.data_ptr(),
+                   poff.data_ptr(), outs_a[0].data_ptr(), outs_b[0].data_ptr(), outs_a[1].data_ptr(), outs_b[1].data_ptr(),
+                   outs_a[2].data_ptr(), outs_b[2].data_ptr(), b_iou.data_ptr(), outs_a[3].data_ptr(), outs_b[3].data_ptr(),
+                   rows_.data_ptr(), conf.data_ptr(), pconf.data_ptr(), rpix.data_ptr(), pairs.data_ptr(), n_pairs, sp)
+            T = nr * W * H
+            pix = torch.empty(T, dtype=torch.uint8, device=dev)
+            s21, p21 = torch.empty(nr, dtype=torch.uint8, device=dev), torch.empty(nr + 1, dtype=torch.int64, device=dev)
+            val_a, val_b = d_ca + 1, d_cb + 1
+
+            keepalive = []
+
+            def k21_call(x, p, r, v, n_, np_):
+                act_, own_ = e(n_, torch.uint8), e(n_, torch.int64)
+                cov_ = e(n_, torch.int64)
+                keepalive.extend([act_, own_, cov_])
+                args21 = (x.data_ptr(), p.data_ptr(), r.data_ptr(), v.data_ptr(), w.data_ptr(), h.data_ptr(), nr, n_, np_, 0, 1 << 26,
+                          s21.data_ptr(), p21.data_ptr(), act_.data_ptr(), cov_.data_ptr(), own_.data_ptr(), pix.data_ptr(), T,
+                          C.byref(total), sp)
+                return lambda: ck(L.dyd_rasterize_polygons_dev(*args21), "k21")
+
+            legs = {"k21_a": k21_call(xy_, pt_, roff, val_a, nb, npts), "k21_b": k21_call(b_xy, b_pt, b_row, val_b, nbb, npb),
+                    "k22": lambda: ck(L.dyd_compare_polygons_dev(*a22), "k22")}
+            res = {}
+            for rnd in range(2):                  # interleaved rounds (guide rule 24)
+                for key, fn in legs.items():
+                    res.setdefault(key, []).append(timeit(fn))
+            med = {k: float(np.median([r[0] for r in v])) for k, v in res.items()}
+            mn = {k: min(r[1] for r in v) for k, v in res.items()}
+            host = torch.empty(T, dtype=torch.uint8).pin_memory()
+            dl, _ = timeit(lambda: host.copy_(pix, non_blocking=True), iters=5, warm=1)
+            table_bytes = 16 * (npts + npb) + 4 * (nb + nbb + 2) + 4 * (nb + nbb) + 8 * (nr + 1) + 16 * nr
+            report(f"k22_compare_polygons_{name}", table_bytes + 4 * n_pairs + 29 * (nb + nbb) + 41 * nr, med["k22"], mn["k22"], rows=nr,
+                   a_polygons=nb, b_polygons=nbb, a_points=npts, b_points=npb, width=W, height=H, pixels=T, pairs=n_pairs,
+                   pairs_hit=int((pairs[:n_pairs] != 0).sum().item()) if n_pairs else 0, matched=int((outs_b[2][:nbb] >= 0).sum().item()),
+                   Gpixels_per_s=round(T / med["k22"] / 1e6, 2), byte_floor_GB=round((table_bytes + 4 * n_pairs) / 1e9, 4),
+                   k21_a_ms=round(med["k21_a"], 4), k21_b_ms=round(med["k21_b"], 4), mask_download_ms=round(dl, 4),
+                   k22_over_two_k21=round(med["k22"] / (med["k21_a"] + med["k21_b"]), 3),
+                   k22_over_two_k21_and_downloads=round(med["k22"] / (med["k21_a"] + med["k21_b"] + 2 * dl), 3))
+
+        for shape in raster_shapes():
+            k22_leg(*shape)
     if "k14" in only:
         import ctypes as C
         # K14 (polygon audit) on K13's two shapes, and long polygons (convex rings of 256 vertices: no crossing, so the wave
