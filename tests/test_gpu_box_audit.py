@@ -1,7 +1,6 @@
 """K10 (box audit) on the MI355X: both ABI entries against the numpy restatement of tests/box_audit_ref.py — row lengths
 around the 64-box chunk and past 1024, special values, 20 and 5,000 classes (LDS and global accumulation), nb in {1, 16, 64} —
 and the step functions on synthetic tables of 100k and 1M rows against the definition."""
-import ctypes as C
 
 import numpy as np
 import pandas as pd
@@ -64,8 +63,13 @@ def _sizes(rng, n=3000):
     return np.concatenate([SIZES, rng.integers(0, 40, n), [1025, 2049]])
 
 
-def _dev_call(box4, row_off, cls, W, H, status, n_classes, nb):
+def _dev_call(box4, row_off, cls, W, H, status, n_classes, nb, hz=None):
+    """dyd_box_audit_dev on a delayed side stream through the harness of tests/stream_contract.py (`hz`: the caller's own,
+    with its own decoys)"""
     import torch
+    from stream_contract import Harness, box_table_decoy
+
+    hz = hz or Harness(box_table_decoy(box4, row_off, cls, W, H, status, n_classes))
 
     dev = torch.device("cuda:0")
     n, B = len(row_off) - 1, len(cls)
@@ -77,15 +81,15 @@ def _dev_call(box4, row_off, cls, W, H, status, n_classes, nb):
     wh = torch.full((max(n_classes, 1) * nb * nb,), -7, dtype=torch.int64, device=dev)
     xy = torch.full_like(wh, -7)
     bpi = torch.full((257,), -7, dtype=torch.int64, device=dev)
-    s = torch.cuda.Stream()
-    torch.cuda.synchronize()
+    hz.arm([d_box, d_off, d_cls, d_w, d_h, d_st])
+    hz.watch(flag, rows, cc, wh, xy, bpi)
     L = _native.lib()
-    rc = L.dyd_box_audit_dev(d_box.data_ptr(), d_off.data_ptr(), n, B, d_cls.data_ptr(), d_w.data_ptr(), d_h.data_ptr(),
-                             d_st.data_ptr(), n_classes, nb, flag.data_ptr(), rows.data_ptr(), cc.data_ptr(), wh.data_ptr(),
-                             xy.data_ptr(), bpi.data_ptr(), C.c_void_p(s.cuda_stream))
-    assert s.cuda_stream != 0
+    rc = hz.call(L.dyd_box_audit_dev, d_box.data_ptr(), d_off.data_ptr(), n, B, d_cls.data_ptr(), d_w.data_ptr(), d_h.data_ptr(),
+                 d_st.data_ptr(), n_classes, nb, flag.data_ptr(), rows.data_ptr(), cc.data_ptr(), wh.data_ptr(),
+                 xy.data_ptr(), bpi.data_ptr())
+    assert hz.s.cuda_stream != 0
     _native.check(rc, "dyd_box_audit_dev")
-    s.synchronize()
+    hz.restore()
     C_ = n_classes
     return (flag.cpu().numpy()[:B], rows.cpu().numpy()[:n], cc.cpu().numpy()[:C_],
             wh.cpu().numpy()[:C_ * nb * nb].reshape(C_, nb, nb), xy.cpu().numpy()[:C_ * nb * nb].reshape(C_, nb, nb),

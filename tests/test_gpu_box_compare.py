@@ -1,6 +1,5 @@
 """K18 (box comparison) on the MI355X: both ABI entries against the restatement (tests/box_compare_ref.py) with all seven
 outputs equal, closed-form displacement chains across the 64-box tiles, and the step functions on synthetic tables."""
-import ctypes as C
 import json
 
 import numpy as np
@@ -61,9 +60,14 @@ def _tables(sizes, rng, special=True):
     return a, a_off, a_cls, b, b_off, b_cls, N_CLASSES
 
 
-def _dev_call(native, a_box4, a_off, a_cls, b_box4, b_off, b_cls, n_classes, thr, by_label):
-    """dyd_compare_boxes_dev on torch buffers, every output prefilled with a sentinel so that an unwritten element shows"""
+def _dev_call(native, a_box4, a_off, a_cls, b_box4, b_off, b_cls, n_classes, thr, by_label, hz=None):
+    """dyd_compare_boxes_dev on torch buffers, every output prefilled with a sentinel so that an unwritten element shows; on a
+    delayed side stream through the harness of tests/stream_contract.py (`hz`: the caller's own, with its own decoys)"""
     import torch
+    from stream_contract import Harness, moved, rev_off, rot_cls
+
+    hz = hz or Harness((moved(a_box4, 4), rev_off(a_off), rot_cls(a_cls, n_classes), moved(b_box4, 4), rev_off(b_off),
+                        rot_cls(b_cls, n_classes)))
 
     dev = torch.device("cuda:0")
     n, na, nb = len(a_off) - 1, int(a_off[-1]), int(b_off[-1])
@@ -74,11 +78,12 @@ def _dev_call(native, a_box4, a_off, a_cls, b_box4, b_off, b_cls, n_classes, thr
     cells = (n_classes + 1) ** 2
     outs = [full(na, -7, torch.int32), full(nb, -7, torch.int32), full(nb, -7.0, torch.float64), full(na, -7.0, torch.float64),
             full(nb, -7.0, torch.float64), full(4 * n, -7, torch.int32), full(cells, 77, torch.int64)]
-    s = torch.cuda.current_stream(dev)
-    rc = native.lib().dyd_compare_boxes_dev(*(t.data_ptr() for t in ins), n, na, nb, n_classes, float(thr), int(by_label),
-                                            *(t.data_ptr() for t in outs), C.c_void_p(s.cuda_stream))
+    hz.arm(ins)
+    hz.watch(*outs)
+    rc = hz.call(native.lib().dyd_compare_boxes_dev, *(t.data_ptr() for t in ins), n, na, nb, n_classes, float(thr), int(by_label),
+                 *(t.data_ptr() for t in outs))
     native.check(rc, "dyd_compare_boxes_dev")
-    torch.cuda.synchronize()
+    hz.restore()
     res = [t.cpu().numpy()[:m] for t, m in zip(outs, (na, nb, nb, na, nb, 4 * n, cells))]
     res[5] = res[5].reshape(n, 4)
     res[6] = res[6].reshape(n_classes + 1, n_classes + 1)

@@ -2,7 +2,6 @@
 around the 64-box chunk and past 1024, special values, boxes landing on the image edge, 20 and 5,000 classes (LDS and global
 class counters) — then the step functions on synthetic tables of 100k and 1M rows against the definition, and the invariants
 (idempotence, the audit after the repair, YOLO label lines in [0, 1])."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -42,8 +41,13 @@ def _with_edges(args, rng):
     return box4, row_off, cls, W, H, st
 
 
-def _dev_call(box4, row_off, cls, W, H, status, n_classes, mv, ms):
+def _dev_call(box4, row_off, cls, W, H, status, n_classes, mv, ms, hz=None):
+    """dyd_repair_boxes_dev on a delayed side stream through the harness of tests/stream_contract.py (`hz`: the caller's own,
+    with its own decoys)"""
     import torch
+    from stream_contract import Harness, box_table_decoy
+
+    hz = hz or Harness(box_table_decoy(box4, row_off, cls, W, H, status, n_classes))
 
     dev = torch.device("cuda:0")
     n, B = len(row_off) - 1, len(cls)
@@ -53,13 +57,13 @@ def _dev_call(box4, row_off, cls, W, H, status, n_classes, mv, ms):
     obox = torch.full((max(B, 1), 4), -7.0, dtype=torch.float64, device=dev)
     rows = torch.full((max(n, 1), 8), -7, dtype=torch.int32, device=dev)
     cc = torch.full((max(n_classes, 1), 8), -7, dtype=torch.int64, device=dev)
-    s = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    rc = _native.lib().dyd_repair_boxes_dev(d_box.data_ptr(), d_off.data_ptr(), n, B, d_cls.data_ptr(), d_w.data_ptr(),
-                                            d_h.data_ptr(), d_st.data_ptr(), n_classes, mv, ms, act.data_ptr(),
-                                            obox.data_ptr(), rows.data_ptr(), cc.data_ptr(), C.c_void_p(s.cuda_stream))
+    hz.arm([d_box, d_off, d_cls, d_w, d_h, d_st])
+    hz.watch(act, obox, rows, cc)
+    rc = hz.call(_native.lib().dyd_repair_boxes_dev, d_box.data_ptr(), d_off.data_ptr(), n, B, d_cls.data_ptr(), d_w.data_ptr(),
+                 d_h.data_ptr(), d_st.data_ptr(), n_classes, mv, ms, act.data_ptr(), obox.data_ptr(), rows.data_ptr(),
+                 cc.data_ptr())
     _native.check(rc, "dyd_repair_boxes_dev")
-    s.synchronize()
+    hz.restore()
     return act.cpu().numpy()[:B], obox.cpu().numpy()[:B], rows.cpu().numpy()[:n], cc.cpu().numpy()[:n_classes]
 
 

@@ -1,6 +1,5 @@
 """K9 (duplicate-box suppression) on the MI355X: both ABI entries against the restatement, adversarial chains across the
 64-box blocks, and the step functions on synthetic tables (replace step -> suppression)."""
-import ctypes as C
 import io
 
 import numpy as np
@@ -45,8 +44,13 @@ def _rows_table(sizes, rng, special=False):
     return box4, row_off, names
 
 
-def _dev_call(native, box4, row_off, thr, name):
+def _dev_call(native, box4, row_off, thr, name, hz=None):
+    """dyd_suppress_boxes_dev on a delayed side stream through the harness of tests/stream_contract.py (`hz`: the caller's own,
+    with its own decoys)"""
     import torch
+    from stream_contract import Harness, moved, rev, rev_off
+
+    hz = hz or Harness((moved(box4, 4), rev_off(row_off), rev(name)))
 
     dev = torch.device("cuda:0")
     b = torch.from_numpy(np.ascontiguousarray(box4, np.float64)).to(dev)
@@ -55,12 +59,12 @@ def _dev_call(native, box4, row_off, thr, name):
     nm = torch.from_numpy(name).to(dev) if name is not None else None
     keep = torch.full((max(nb, 1),), 7, dtype=torch.uint8, device=dev)
     partner = torch.full((max(nb, 1),), -7, dtype=torch.int32, device=dev)
-    s = torch.cuda.current_stream(dev)
-    rc = native.lib().dyd_suppress_boxes_dev(b.data_ptr(), o.data_ptr(), len(row_off) - 1, nb,
-                                             nm.data_ptr() if nm is not None else None, float(thr), keep.data_ptr(),
-                                             partner.data_ptr(), C.c_void_p(s.cuda_stream))
+    hz.arm([b, o, nm])
+    hz.watch(keep, partner)
+    rc = hz.call(native.lib().dyd_suppress_boxes_dev, b.data_ptr(), o.data_ptr(), len(row_off) - 1, nb,
+                 nm.data_ptr() if nm is not None else None, float(thr), keep.data_ptr(), partner.data_ptr())
     native.check(rc, "dyd_suppress_boxes_dev")
-    torch.cuda.synchronize()
+    hz.restore()
     return keep.cpu().numpy()[:nb], partner.cpu().numpy()[:nb]
 
 

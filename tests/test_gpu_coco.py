@@ -48,21 +48,25 @@ def same(got, want):
     assert bytes(text) == want[3]
 
 
-def run_dev(t, img_base=1, ann_base=1, flags=1, offset=3):
+def run_dev(t, img_base=1, ann_base=1, flags=1, offset=3, hz=None):
     """the _dev entry on torch tensors: measure only, a buffer one byte too small, then the text at an odd address inside a guarded
-    buffer with the other outputs at guarded offsets"""
+    buffer with the other outputs at guarded offsets.  hz: the harness of tests/stream_contract.py (its decoys in the table's
+    order), armed anew for every one of the calls; without one the calls go to torch's current stream"""
     import torch
     from deal_yolo_daya_amd import _native
+    from stream_contract import PLAIN
 
+    hz = hz or PLAIN
     xy, pt_off, row_off, cat, W, H, st = t
     dev = torch.device("cuda", 0)
-    L, sp = _native.lib(), torch.cuda.current_stream().cuda_stream
+    L = _native.lib()
     tt = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)   # noqa: E731
     n, nb, npnt = len(row_off) - 1, len(cat), len(xy) // 2
     xy_buf = torch.zeros(len(xy) + 4, dtype=torch.float64, device=dev)
     xy_buf[2:2 + len(xy)] = tt(xy, np.float64)                                  # 16-B aligned, not at the allocation's start
     keep = [tt(pt_off, np.int32), tt(row_off, np.int32), tt(cat if nb else np.zeros(1), np.int32), tt(W if n else np.zeros(1), np.float64),
             tt(H if n else np.zeros(1), np.float64), tt(st if n else np.zeros(1), np.uint8)]
+    hz.arm([xy_buf[2:2 + len(xy)]] + keep)
     guard = 0xA5
     outs = lambda: (torch.full((nb + 2 * offset,), guard, dtype=torch.uint8, device=dev),          # noqa: E731
                     torch.full((nb + 2 * offset,), -7.0, dtype=torch.float64, device=dev),
@@ -70,12 +74,13 @@ def run_dev(t, img_base=1, ann_base=1, flags=1, offset=3):
     total = CT.c_int64(-1)
 
     def call(o, text, cap):
-        return L.dyd_coco_annotations_dev(xy_buf.data_ptr() + 16, *(a.data_ptr() for a in keep), n, nb, npnt, img_base, ann_base, flags,
-                                          o[0].data_ptr() + offset, o[1].data_ptr() + 8 * offset, o[2].data_ptr() + 4 * offset,
-                                          text, cap, CT.byref(total), sp)
+        hz.watch(*o)
+        return hz.call(L.dyd_coco_annotations_dev, xy_buf.data_ptr() + 16, *(a.data_ptr() for a in keep), n, nb, npnt, img_base,
+                       ann_base, flags, o[0].data_ptr() + offset, o[1].data_ptr() + 8 * offset, o[2].data_ptr() + 4 * offset,
+                       text, cap, CT.byref(total))
 
     def unpack(o):
-        torch.cuda.synchronize()
+        hz.restore()
         h = [a.cpu().numpy() for a in o]
         for a, fill in zip(h, (guard, -7.0, -7)):
             assert (a[:offset] == fill).all() and (a[len(a) - offset:] == fill).all(), "write outside the outputs"
@@ -90,6 +95,7 @@ def run_dev(t, img_base=1, ann_base=1, flags=1, offset=3):
         assert call(outs(), small.data_ptr(), T - 1) == ERR_RANGE and total.value == T
     o2 = outs()
     buf = torch.full((T + offset + 32,), 0xAB, dtype=torch.uint8, device=dev)
+    hz.watch(buf)
     _native.check(call(o2, buf.data_ptr() + offset, T), "print")
     printed = unpack(o2)
     b = buf.cpu().numpy()

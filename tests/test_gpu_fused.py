@@ -167,25 +167,29 @@ def test_fused_host_entry_edges(native):
 
 
 def test_dev_entry_points_on_a_side_stream(native):
-    """_dev twins launch on exactly the stream they are given (here a non-default torch stream)."""
+    """_dev twins launch on exactly the stream they are given: a side stream that is still busy with the delay of
+    tests/stream_contract.py when the entries are called, the inputs decoys and the outputs unfilled until the delay ends.
+    K2 reads the boxes K1 leaves on that stream."""
     import torch
+    from stream_contract import Harness, moved, rev_off
 
     rng = np.random.default_rng(2)
     xy, pt_off, box_off = _table(rng, 500, 20, 10, False)
     B = len(pt_off) - 1
     dev = torch.device("cuda:0")
     L = native.lib()
-    s = torch.cuda.Stream(dev)
-    with torch.cuda.stream(s):
-        t_xy, t_po, t_bo = (torch.from_numpy(a).to(dev) for a in (xy, pt_off, box_off))
-        t_box = torch.empty((B, 4), dtype=torch.float64, device=dev)
-        t_arg = torch.empty((B, 4), dtype=torch.int32, device=dev)
-        t_high = torch.empty(500, dtype=torch.uint8, device=dev)
-        native.check(L.dyd_bbox_minmax_dev(t_xy.data_ptr(), t_po.data_ptr(), B, int(t_xy.shape[0]), t_box.data_ptr(), t_arg.data_ptr(),
-                                           s.cuda_stream), "k1")
-        native.check(L.dyd_iou_any_ge_dev(t_box.data_ptr(), t_bo.data_ptr(), 500, B, 2, 0.9, t_high.data_ptr(), None,
-                                          s.cuda_stream), "k2")
-    s.synchronize()
+    hz = Harness()
+    t_xy, t_po, t_bo = hz.up(xy, moved(xy)), hz.up(pt_off, rev_off(pt_off)), hz.up(box_off, rev_off(box_off))
+    t_box = torch.full((B, 4), -7.0, dtype=torch.float64, device=dev)
+    t_arg = torch.full((B, 4), -7, dtype=torch.int32, device=dev)
+    t_high = torch.full((500,), 9, dtype=torch.uint8, device=dev)
+    hz.watch(t_box, t_arg, t_high)
+    native.check(hz.call(L.dyd_bbox_minmax_dev, t_xy.data_ptr(), t_po.data_ptr(), B, int(t_xy.shape[0]), t_box.data_ptr(),
+                         t_arg.data_ptr()), "k1")
+    assert hz.pending == [True]                                    # K1 only queues its kernel
+    native.check(L.dyd_iou_any_ge_dev(t_box.data_ptr(), t_bo.data_ptr(), 500, B, 2, 0.9, t_high.data_ptr(), None,
+                                      hz.s.cuda_stream), "k2")
+    hz.restore()
     obox, oarg = olib.bbox_minmax(xy, pt_off)
     assert np.array_equal(t_arg.cpu().numpy(), oarg)
     assert np.array_equal(t_high.cpu().numpy(), olib.iou_any_ge(obox, box_off, 2, 0.9))

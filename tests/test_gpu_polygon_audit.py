@@ -55,11 +55,15 @@ def same(got, want):
     assert np.array_equal(cc, want[3]) and np.array_equal(hist, want[4])
 
 
-def run_dev(table, min_area=1.0, offset=1):
-    """the _dev entry on torch tensors, every output at an odd offset inside a guarded buffer"""
+def run_dev(table, min_area=1.0, offset=1, hz=None):
+    """the _dev entry on torch tensors, every output at an odd offset inside a guarded buffer.
+    hz: the harness of tests/stream_contract.py (its decoys in the table's order, xy to size_status); without one the call goes
+    to torch's current stream"""
     import torch
     from deal_yolo_daya_amd import _native
+    from stream_contract import PLAIN
 
+    hz = hz or PLAIN
     xy, pt_off, row_off, cls, W, H, st, nc = table
     dev = torch.device("cuda", 0)
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)   # noqa: E731
@@ -73,12 +77,13 @@ def run_dev(table, min_area=1.0, offset=1):
     cc = torch.full((nc * 14 + 2 * offset,), -7, dtype=torch.int64, device=dev)
     hist = torch.full((nc * 11 + 2 * offset,), -7, dtype=torch.int64, device=dev)
     keep = [t(pt_off, np.int32), t(row_off, np.int32), t(cls, np.int32), t(W, np.float64), t(H, np.float64), t(st, np.uint8)]
-    L, sp = _native.lib(), torch.cuda.current_stream().cuda_stream
-    _native.check(L.dyd_audit_polygons_dev(xy_buf.data_ptr() + 16, *(a.data_ptr() for a in keep), n, nb, len(xy) // 2, nc,
-                                           float(min_area), cat.data_ptr() + offset, dfc.data_ptr() + offset,
-                                           area.data_ptr() + 8 * offset, cc.data_ptr() + 8 * offset,
-                                           hist.data_ptr() + 8 * offset, sp), "dyd_audit_polygons_dev")
-    torch.cuda.synchronize()
+    L = _native.lib()
+    hz.arm([xy_buf[2:2 + len(xy)]] + keep)
+    hz.watch(cat, dfc, area, cc, hist)
+    _native.check(hz.call(L.dyd_audit_polygons_dev, xy_buf.data_ptr() + 16, *(a.data_ptr() for a in keep), n, nb, len(xy) // 2, nc,
+                          float(min_area), cat.data_ptr() + offset, dfc.data_ptr() + offset, area.data_ptr() + 8 * offset,
+                          cc.data_ptr() + 8 * offset, hist.data_ptr() + 8 * offset), "dyd_audit_polygons_dev")
+    hz.restore()
     out = [a.cpu().numpy() for a in (cat, dfc, area, cc, hist)]
     for a, fill in zip(out, (guard, guard, -7.0, -7, -7)):
         assert (a[:offset] == fill).all() and (a[len(a) - offset:] == fill).all(), "write outside the outputs"

@@ -30,12 +30,15 @@ FILLS = {np.uint8: 0xA5, np.int32: -77, np.int64: -7, np.float64: -3.5, np.uint6
 
 
 def run_dev(t, n_classes, thr=0.5, by_label=False, max_pixels_per_row=1 << 26, max_pairs_per_row=1 << 20, pairs="own",
-            pair_cap=None, n_pairs=None):
+            pair_cap=None, n_pairs=None, hz=None):
     """the _dev entry on torch tensors: every output one element into a guarded buffer filled with a sentinel -> (the sixteen
-    outputs, return code).  pairs="null" passes no pair buffer (the last output is then empty)."""
+    outputs, return code).  pairs="null" passes no pair buffer (the last output is then empty).  hz: the harness of
+    tests/stream_contract.py (its decoys in the table's order); without one the call goes to torch's current stream"""
     import torch
     from deal_yolo_daya_amd import _native
+    from stream_contract import PLAIN
 
+    hz = hz or PLAIN
     a_xy, a_pt, a_row, a_cls, b_xy, b_pt, b_row, b_cls, W, H = t
     dev = torch.device("cuda", 0)
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)     # noqa: E731
@@ -59,12 +62,14 @@ def run_dev(t, n_classes, thr=0.5, by_label=False, max_pixels_per_row=1 << 26, m
     if pairs == "null":
         ptrs[-1] = None
     cap = int(want_pairs) if pair_cap is None else pair_cap
-    L, sp = _native.lib(), torch.cuda.current_stream().cuda_stream
-    rc = L.dyd_compare_polygons_dev(d_axy.data_ptr() + 16, ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(),
-                                    d_bxy.data_ptr() + 16, ins[3].data_ptr(), ins[4].data_ptr(), ins[5].data_ptr(),
-                                    ins[6].data_ptr(), ins[7].data_ptr(), n, na, len(a_xy) // 2, nb, len(b_xy) // 2, n_classes,
-                                    float(thr), int(by_label), max_pixels_per_row, max_pairs_per_row, *ptrs, cap, sp)
-    torch.cuda.synchronize()
+    L = _native.lib()
+    hz.arm([d_axy[2:2 + len(a_xy)]] + ins[:3] + [d_bxy[2:2 + len(b_xy)]] + ins[3:])
+    hz.watch(*bufs)
+    rc = hz.call(L.dyd_compare_polygons_dev, d_axy.data_ptr() + 16, ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(),
+                 d_bxy.data_ptr() + 16, ins[3].data_ptr(), ins[4].data_ptr(), ins[5].data_ptr(),
+                 ins[6].data_ptr(), ins[7].data_ptr(), n, na, len(a_xy) // 2, nb, len(b_xy) // 2, n_classes,
+                 float(thr), int(by_label), max_pixels_per_row, max_pairs_per_row, *ptrs, cap)
+    hz.restore()
     out = []
     for k, (b, (dt, size)) in enumerate(zip(bufs, spec)):
         a = b.cpu().numpy()

@@ -51,11 +51,14 @@ def same(got, want):
     assert np.array_equal(np.asarray(got[3]).view(np.uint64), np.asarray(want[3]).view(np.uint64)), "dev2"
 
 
-def run_dev(xy, pt_off, tol, offset=1):
-    """the _dev entry on torch tensors, every output at an odd offset inside a guarded buffer"""
+def run_dev(xy, pt_off, tol, offset=1, hz=None):
+    """the _dev entry on torch tensors, every output at an odd offset inside a guarded buffer.
+    hz: the harness of tests/stream_contract.py (its decoys: xy, pt_off); without one the call goes to torch's current stream"""
     import torch
     from deal_yolo_daya_amd import _native
+    from stream_contract import PLAIN
 
+    hz = hz or PLAIN
     dev = torch.device("cuda", 0)
     xy = np.ascontiguousarray(xy, np.float64).reshape(-1)
     xy_buf = torch.zeros(len(xy) + 4, dtype=torch.float64, device=dev)
@@ -67,11 +70,13 @@ def run_dev(xy, pt_off, tol, offset=1):
     act = torch.full((nb + 2 * offset,), guard, dtype=torch.uint8, device=dev)
     kept = torch.full((nb + 2 * offset,), -7, dtype=torch.int32, device=dev)
     dev2 = torch.full((nb + 2 * offset,), -7.0, dtype=torch.float64, device=dev)
-    L, sp = _native.lib(), torch.cuda.current_stream().cuda_stream
-    _native.check(L.dyd_simplify_polygons_dev(xy_buf.data_ptr() + 16, pt.data_ptr(), nb, npnt, float(tol),
-                                              keep.data_ptr() + offset, act.data_ptr() + offset, kept.data_ptr() + 4 * offset,
-                                              dev2.data_ptr() + 8 * offset, sp), "dyd_simplify_polygons_dev")
-    torch.cuda.synchronize()
+    L = _native.lib()
+    hz.arm([xy_buf[2:2 + len(xy)], pt])
+    hz.watch(keep, act, kept, dev2)
+    _native.check(hz.call(L.dyd_simplify_polygons_dev, xy_buf.data_ptr() + 16, pt.data_ptr(), nb, npnt, float(tol),
+                          keep.data_ptr() + offset, act.data_ptr() + offset, kept.data_ptr() + 4 * offset,
+                          dev2.data_ptr() + 8 * offset), "dyd_simplify_polygons_dev")
+    hz.restore()
     out = [a.cpu().numpy() for a in (keep, act, kept, dev2)]
     for a, fill in zip(out, (guard, guard, -7, -7.0)):
         assert (a[:offset] == fill).all() and (a[len(a) - offset:] == fill).all(), "write outside the outputs"

@@ -64,12 +64,15 @@ def same(got, want):
             assert np.asarray(g).dtype == np.asarray(w).dtype and np.array_equal(g, w), what
 
 
-def run_dev(t, params, phase=0, measure_only=False, text_cap=None):
+def run_dev(t, params, phase=0, measure_only=False, text_cap=None, hz=None):
     """the _dev entry on torch tensors: outputs at odd offsets inside guarded buffers, the text at `phase` bytes past a 16-byte
-    boundary -> (the nine outputs, return code, *out_total)"""
+    boundary -> (the nine outputs, return code, *out_total).  hz: the harness of tests/stream_contract.py (its decoys in the
+    table's order), armed anew for both calls; without one the calls go to torch's current stream"""
     import torch
     from deal_yolo_daya_amd import _native
+    from stream_contract import PLAIN
 
+    hz = hz or PLAIN
     xy, pt_off, row_off, cls, W, H = t
     tw, th, sx, sy, mv, mode, mx = params
     dev = torch.device("cuda", 0)
@@ -87,15 +90,17 @@ def run_dev(t, params, phase=0, measure_only=False, text_cap=None):
     text_off = torch.full((T + 3,), g64, dtype=torch.int64, device=dev)
     lines = torch.full((T + 2,), g32, dtype=torch.int32, device=dev)
     wr, cut, drop = (torch.full((nb + 2,), g32, dtype=torch.int32, device=dev) for _ in range(3))
-    L, sp = _native.lib(), torch.cuda.current_stream().cuda_stream
+    L = _native.lib()
     n_tiles, total = C.c_int64(-1), C.c_int64(-1)
+    hz.arm([d_xy[2:2 + len(xy)], d_pt, d_row, d_cls, d_w, d_h])
+    hz.watch(status, act, tile_off, text_off, lines, wr, cut, drop)
 
     def call(text_ptr, cap):
-        return L.dyd_yolo_tile_lines_dev(d_xy.data_ptr() + 16, d_pt.data_ptr(), d_row.data_ptr(), d_cls.data_ptr(), d_w.data_ptr(),
-                                         d_h.data_ptr(), n, nb, npnt, tw, th, sx, sy, float(mv), mode, mx, T, status.data_ptr() + 1,
-                                         tile_off.data_ptr() + 8, lines.data_ptr() + 4, text_off.data_ptr() + 8, act.data_ptr() + 1,
-                                         wr.data_ptr() + 4, cut.data_ptr() + 4, drop.data_ptr() + 4, C.byref(n_tiles), text_ptr, cap,
-                                         C.byref(total), sp)
+        return hz.call(L.dyd_yolo_tile_lines_dev, d_xy.data_ptr() + 16, d_pt.data_ptr(), d_row.data_ptr(), d_cls.data_ptr(),
+                       d_w.data_ptr(), d_h.data_ptr(), n, nb, npnt, tw, th, sx, sy, float(mv), mode, mx, T, status.data_ptr() + 1,
+                       tile_off.data_ptr() + 8, lines.data_ptr() + 4, text_off.data_ptr() + 8, act.data_ptr() + 1,
+                       wr.data_ptr() + 4, cut.data_ptr() + 4, drop.data_ptr() + 4, C.byref(n_tiles), text_ptr, cap,
+                       C.byref(total))
 
     rc = call(None, 0)
     assert rc == 0, L.dyd_last_error()
@@ -107,6 +112,7 @@ def run_dev(t, params, phase=0, measure_only=False, text_cap=None):
         buf = torch.full((64 + 16 + size + 64,), 0x7e, dtype=torch.uint8, device=dev)
         assert buf.data_ptr() % 16 == 0
         at = 64 + phase
+        hz.watch(buf)
         rc = call(buf.data_ptr() + at, cap)
         torch.cuda.synchronize()
         out = buf.cpu().numpy()
@@ -115,7 +121,7 @@ def run_dev(t, params, phase=0, measure_only=False, text_cap=None):
             assert (out[:at] == 0x7e).all() and (out[at + size:] == 0x7e).all(), "write outside the text"
         else:
             assert (out == 0x7e).all()
-    torch.cuda.synchronize()
+    hz.restore()
     arrays = []
     for a, off, fill in ((status, 1, g8), (tile_off, 1, g64), (lines, 1, g32), (text_off, 1, g64), (act, 1, g8), (wr, 1, g32),
                          (cut, 1, g32), (drop, 1, g32)):

@@ -33,14 +33,17 @@ def check(native, xy, pt_off, row_off, sel, W, H, cid):
     return got
 
 
-def check_dev(xy, pt_off, row_off, sel, W, H, cid, offset=3):
-    """the _dev entry on torch tensors: measure only, too small a buffer, then print into a buffer at an odd address"""
+def check_dev(xy, pt_off, row_off, sel, W, H, cid, offset=3, hz=None):
+    """the _dev entry on torch tensors: measure only, too small a buffer, then print into a buffer at an odd address.
+    hz: the harness of tests/stream_contract.py (its decoys in the order xy, pt_off, row_off, sel, W, H, cid), armed anew for
+    every one of the calls; without one the calls go to torch's current stream as they always did"""
     import torch
     from deal_yolo_daya_amd import _native
+    from stream_contract import PLAIN
 
+    hz = hz or PLAIN
     dev = torch.device("cuda", 0)
     L = _native.lib()
-    sp = torch.cuda.current_stream().cuda_stream
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)   # noqa: E731
     n, nb, npnt = len(row_off) - 1, int(row_off[-1]), int(pt_off[-1])
     d_xy, d_pt, d_row = t(xy if len(xy) else np.zeros(2), np.float64), t(pt_off, np.int32), t(row_off, np.int32)
@@ -54,15 +57,18 @@ def check_dev(xy, pt_off, row_off, sel, W, H, cid, offset=3):
     total = C.c_int64()
     args = (d_xy.data_ptr(), d_pt.data_ptr(), d_row.data_ptr(), d_sel.data_ptr() if d_sel is not None else None, d_w.data_ptr(),
             d_h.data_ptr(), d_cid.data_ptr(), n, nb, npnt, toff.data_ptr(), flag.data_ptr(), act.data_ptr(), clamped.data_ptr())
-    _native.check(L.dyd_yolo_obb_lines_dev(*args, None, None, 0, C.byref(total), sp), "measure")     # no corners, no text
+    hz.arm([d_xy, d_pt, d_row, d_sel, d_w, d_h, d_cid])
+    hz.watch(toff, flag, act, clamped, corners)
+    _native.check(hz.call(L.dyd_yolo_obb_lines_dev, *args, None, None, 0, C.byref(total)), "measure")     # no corners, no text
     T = total.value
     if T:
         small = torch.empty(T - 1 if T > 1 else 1, dtype=torch.uint8, device=dev)
-        rc = L.dyd_yolo_obb_lines_dev(*args, corners.data_ptr(), small.data_ptr(), T - 1, C.byref(total), sp)
+        rc = hz.call(L.dyd_yolo_obb_lines_dev, *args, corners.data_ptr(), small.data_ptr(), T - 1, C.byref(total))
         assert rc != 0 and total.value == T                                    # DYD_ERR_RANGE with the needed size
     buf = torch.full((T + offset + 32,), 0xAB, dtype=torch.uint8, device=dev)
-    _native.check(L.dyd_yolo_obb_lines_dev(*args, corners.data_ptr(), buf.data_ptr() + offset, T, C.byref(total), sp), "print")
-    torch.cuda.synchronize()
+    hz.watch(buf)
+    _native.check(hz.call(L.dyd_yolo_obb_lines_dev, *args, corners.data_ptr(), buf.data_ptr() + offset, T, C.byref(total)), "print")
+    hz.restore()
     b = buf.cpu().numpy()
     assert (b[:offset] == 0xAB).all() and (b[offset + T:] == 0xAB).all()      # nothing written outside the text
     return (toff.cpu().numpy(), flag.cpu().numpy()[:n], act.cpu().numpy()[:nb], b[offset:offset + T].tobytes(),
