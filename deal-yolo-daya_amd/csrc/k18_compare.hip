@@ -24,6 +24,7 @@
 //   Confusion counts: per workgroup in LDS (u32) while (C+1)^2 <= K18_CONF_LDS, flushed with one u64 atomic per non-zero cell;
 //   global u64 atomics otherwise and in the big-row kernel.  The counts do not depend on the order.
 //   The exact IoU of every candidate is needed, so K2's rejecting bound (thr_lo) is not used here.
+#include "k18_pick.h"
 #include "k2_wave.h"
 
 namespace dyd {
@@ -72,12 +73,7 @@ __device__ __forceinline__ double k18_iou(const Corners &a, const Corners &b, do
     return (uni != 0.0) ? inter / uni : 0.0;
 }
 
-// sort keys of an IoU: `best` key (0 for NaN and 0.0) and candidate key (bits + 1; 0 = no candidate)
-__device__ __forceinline__ unsigned long long k18_bits(double v) { return (unsigned long long)__double_as_longlong(v); }
-__device__ __forceinline__ double k18_value(unsigned long long k) { return __longlong_as_double((long long)k); }
-__device__ __forceinline__ unsigned long long k18_best_key(double iou) { return (iou > 0.0) ? k18_bits(iou) : 0ull; }
-
-// one count in confusion[a][b]; a, b in 0..C (C = none), anything else (a class id outside the list) is not counted
+// k18_count in the workgroup's LDS copy of the matrix when there is one
 __device__ __forceinline__ void k18_count(unsigned int *lds_conf, unsigned long long *conf, int32_t C, int32_t a, int32_t b) {
     if ((uint32_t)a > (uint32_t)C || (uint32_t)b > (uint32_t)C) return;
     const int64_t cell = (int64_t)a * (C + 1) + b;
@@ -187,7 +183,7 @@ __global__ __launch_bounds__(K18_BLOCK) void k18_tile_kernel(
                     const double iou = no_nan ? k18_iou<true>(me, o, me_ar) : k18_iou<false>(me, o, me_ar);
                     if (iou > best) best = iou;
                     bk = k18_best_key(iou);
-                    if (a_match < 0 && (!by_label || S.cls[k] == me_cls) && iou >= thr) mine = k18_bits(iou) + 1ull;
+                    if (a_match < 0 && (!by_label || S.cls[k] == me_cls) && iou >= thr) mine = k18_cand_key(iou);
                 }
                 // segmented suffix-max over the lanes of each row; the row's first lane ends with the row's maxima
                 unsigned long long ck = mine;
@@ -325,7 +321,7 @@ __global__ __launch_bounds__(K18_BLOCK) void k18_big_rows_kernel(
                     const unsigned long long b1 = k18_best_key(iou);
                     bk = (b1 > bk) ? b1 : bk;
                     if (out_a_match[a_base + i] < 0 && (!by_label || a_cls[a_base + i] == o_cls) && iou >= thr) {
-                        const unsigned long long c1 = k18_bits(iou) + 1ull;
+                        const unsigned long long c1 = k18_cand_key(iou);
                         if (c1 > key) {
                             key = c1;
                             idx = i;
@@ -367,18 +363,18 @@ __global__ __launch_bounds__(K18_BLOCK) void k18_big_rows_kernel(
                     out_a_match[a_base + gi] = j;
                     const int32_t mc = a_cls[a_base + gi];
                     if (mc == o_cls) ++same; else ++diff;
-                    k18_count(nullptr, out_conf, C, k18_class(mc, C), k18_class(o_cls, C));
+                    k18_count(out_conf, C, k18_class(mc, C), k18_class(o_cls, C));
                 }
                 if (threadIdx.x == 0) {
                     out_b_match[b_base + j] = hit ? gi : -1;
                     out_b_iou[b_base + j] = hit ? k18_value(gk - 1ull) : 0.0;
                     out_b_best[b_base + j] = k18_value(gb);
-                    if (!hit) k18_count(nullptr, out_conf, C, C, k18_class(o_cls, C));
+                    if (!hit) k18_count(out_conf, C, C, k18_class(o_cls, C));
                 }
             }
         }
         for (int32_t i = threadIdx.x; i < na; i += K18_BLOCK)
-            if (out_a_match[a_base + i] < 0) k18_count(nullptr, out_conf, C, k18_class(a_cls[a_base + i], C), C);
+            if (out_a_match[a_base + i] < 0) k18_count(out_conf, C, k18_class(a_cls[a_base + i], C), C);
         if (same) atomicAdd(&cnt[0], same);
         if (diff) atomicAdd(&cnt[1], diff);
         __syncthreads();

@@ -3,7 +3,10 @@
 // A pixel is covered by a polygon when an odd number of the polygon's edges cross the pixel's scanline to the right of the
 // pixel's centre (include/dyd.h has the rule, DESIGN §5s the mapping and its cost); it holds the value of the last polygon of
 // its row that covers it, or the background.  The polygon code is K13's: k13_size_ok for the sizes, Poly / k13_prepare for the
-// action and the box of a two-point polygon, k13_scan_inclusive for both offset arrays, last_le for the row search.
+// action and the box of a two-point polygon, k13_scan_inclusive for both offset arrays, last_le for the row search.  The pixel
+// rule itself is k21_cover.h, shared with K22 (k22_poly_compare.hip): the row rule, the polygons of a row, the box cull and the
+// edge step; the polygon kernel below also serves K22 through k21_polys.  This file keeps what a mask needs beyond coverage:
+// the owner per pixel, the covered / owned counters and the byte stream-out.
 //
 // Layout in HBM: xy = P x (x, y) f64, pt_off = B+1 int32, row_off = N+1 int32, val = B int32, width / height = N f64.
 // Outputs: row_status = N u8, pix_off = N+1 int64, action = B u8, covered / owned = B int64, pixels.  Scratch: 32 bytes per
@@ -14,15 +17,14 @@
 //   2. polygons, a lane per polygon: the action and the bounding box; the host reads the pixel total and the item count;
 //   3. paint, a wave (one workgroup) per item = (row, scanline, strip of `strip` columns), items taken grid-stride.  The wave
 //      keeps the strip's owner per pixel (a polygon index), a parity byte per pixel and a list of crossings in LDS.  Per polygon
-//      of the row, in order, culled by its box: lanes take edges in chunks of 64 and compute xs for the crossing ones (one
-//      division per edge and scanline), a ballot and a popcount compact them into the list, lanes then take pixels and XOR in
-//      xs > xc for the listed crossings.  A full list is applied and emptied: parity is linear, so any edge count is exact.
+//      of the row, in order, culled by its box (k21_reaches): k21_edges puts the crossings of the scanline into the list, lanes
+//      then take pixels and XOR in xs > xc for the listed crossings.
 //      After the polygon's last edge the pixels of parity 1 take it as owner; their count goes to covered and owned, every
 //      overwritten owner is decremented (aggregated by old owner inside the wave), all by integer atomics, so no result
 //      depends on the schedule.  At the end of the item the owners are translated to val / background in LDS and stream out in
 //      16-byte stores, byte by byte where the destination's alignment cuts a chunk.
-#include "k13_poly.h"
 #include "k13_scan.h"
+#include "k21_cover.h"
 #include "poly_table.h"
 
 namespace dyd {
@@ -32,19 +34,6 @@ constexpr int K21_STRIP = 1024;              // columns per item (default and mo
 constexpr int K21_CROSSINGS = 256;           // capacity of the crossing list (default and most)
 constexpr int64_t K21_MAX_PIXELS = 1LL << 30;
 constexpr int64_t K21_MAX_GRID = 1 << 20;    // paint workgroups; the items beyond are taken grid-stride
-enum : uint8_t { RASTER_DONE = 0, RASTER_NO_RASTER = 5 };   // the other actions are K13's codes
-
-// row status (0 rasterised, 1 no_size, 2 fractional_size, 3 too_large); for status 0 the image's width and height
-__device__ __forceinline__ uint8_t k21_row_size(double W, double H, int64_t max_pixels, int64_t *w, int64_t *h) {
-    *w = *h = 0;
-    if (!k13_size_ok(W) || !k13_size_ok(H)) return 1;
-    if (W != floor(W) || H != floor(H)) return 2;
-    const int64_t iw = (int64_t)W, ih = (int64_t)H;
-    if (iw > max_pixels || ih > max_pixels || iw * ih > max_pixels) return 3;   // the product stays at or below 2^60
-    *w = iw;
-    *h = ih;
-    return 0;
-}
 
 // ---- 1. rows: a lane per row -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(K21_BLOCK) void k21_rows_kernel(const double *__restrict__ width, const double *__restrict__ height,
@@ -61,7 +50,7 @@ __global__ __launch_bounds__(K21_BLOCK) void k21_rows_kernel(const double *__res
 }
 
 // ---- 2. polygons: a lane per polygon ---------------------------------------------------------------------------
-// action (255: val < 0); info[4p .. 4p+3] = x1, y1, x2, y2 of the points, which is the box of V
+// action and info as k21_cover.h says; K22 launches it too, once per table
 __global__ __launch_bounds__(K21_BLOCK) void k21_poly_kernel(const double *__restrict__ xy, const int32_t *__restrict__ pt_off,
                                                              const int32_t *__restrict__ row_off, const int32_t *__restrict__ val,
                                                              const uint8_t *__restrict__ row_status, int64_t n_rows, int64_t n_polys,
@@ -77,19 +66,26 @@ __global__ __launch_bounds__(K21_BLOCK) void k21_poly_kernel(const double *__res
     if (val[p] < 0) {
         act = SEG_UNSELECTED;
     } else if (row_status[r] != 0) {
-        act = RASTER_NO_RASTER;
+        act = COVER_NO_ROW;
     } else {
         const int32_t a = max(pt_off[p], 0), b = (int32_t)min((int64_t)max(pt_off[p + 1], a), n_points);
         Poly pg;
         act = k13_prepare(xy, a, b, pg);
         if (act == 0xff) {
-            act = RASTER_DONE;
+            act = COVER_DONE;
             x1 = pg.x1; y1 = pg.y1; x2 = pg.x2; y2 = pg.y2;
         }
     }
     action[p] = act;
     double *q = info + 4 * p;
     q[0] = x1; q[1] = y1; q[2] = x2; q[3] = y2;
+}
+
+void k21_polys(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *val, const uint8_t *row_status,
+               int64_t n_rows, int64_t n_polys, int64_t n_points, uint8_t *action, double *info, hipStream_t st) {
+    if (n_polys > 0)
+        hipLaunchKernelGGL(k21_poly_kernel, dim3((unsigned)ceil_div(n_polys, (int64_t)K21_BLOCK)), dim3(K21_BLOCK), 0, st, xy, pt_off,
+                           row_off, val, row_status, n_rows, n_polys, n_points, action, info);
 }
 
 // ---- 3. paint: a wave per item ---------------------------------------------------------------------------------
@@ -107,7 +103,6 @@ __global__ __launch_bounds__(kWave) void k21_paint_kernel(const double *__restri
     __shared__ double list[K21_CROSSINGS];
     __shared__ __attribute__((aligned(16))) uint8_t img[K21_STRIP + 16];
     const int lane = threadIdx.x;
-    const unsigned long long below = (1ull << lane) - 1ull;
     for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
         const int64_t r = last_le(item_off, 0, n_rows - 1, item);
         const int64_t local = item - item_off[r];
@@ -116,7 +111,7 @@ __global__ __launch_bounds__(kWave) void k21_paint_kernel(const double *__restri
         if (row_status[r] != 0 || local < 0 || local >= H * n_strips) continue;   // never for a sound item_off
         const int64_t j = local / n_strips, x0 = (local - j * n_strips) * strip;
         const int npx = (int)min((int64_t)strip, W - x0);
-        const double yc = (double)j + 0.5, xc_first = (double)x0 + 0.5, xc_last = (double)(x0 + npx - 1) + 0.5;
+        const K21Strip s{(double)j + 0.5, (double)x0 + 0.5, (double)(x0 + npx - 1) + 0.5, x0, npx, (npx + kWave - 1) / kWave};
         for (int px = lane; px < npx; px += kWave) {
             owner[px] = -1;
             parity[px] = 0;
@@ -133,59 +128,12 @@ __global__ __launch_bounds__(kWave) void k21_paint_kernel(const double *__restri
             }
             __syncthreads();
         };
-        const int64_t pa = max((int64_t)row_off[r], (int64_t)0), pb = min((int64_t)row_off[r + 1], n_polys);
+        int64_t pa, pb;
+        k21_row_polys(row_off, r, n_polys, &pa, &pb);
         for (int64_t p = pa; p < pb; ++p) {
-            if (action[p] != RASTER_DONE) continue;
-            const double *q = info + 4 * p;
-            const double bx1 = q[0], by1 = q[1], bx2 = q[2], by2 = q[3];
-            // The cull.  No edge crosses the scanline unless by1 <= yc < by2.  A crossing lies within an ulp of [bx1, bx2]:
-            // to the right of the box (with a pixel to spare) no crossing has xs > xc; to the left every one has, and a closed
-            // outline crosses a scanline an even number of times, so the parity stays 0.
-            if (!(by1 <= yc) || !(yc < by2) || xc_first >= bx2 + 1.0 || xc_last <= bx1 - 1.0) continue;
+            if (!k21_reaches(action, info, p, s)) continue;
             const int32_t a = max(pt_off[p], 0), b = (int32_t)min((int64_t)max(pt_off[p + 1], a), n_points);
-            const double2 *pts = reinterpret_cast<const double2 *>(xy) + a;
-            const bool two = b - a == 2;
-            const int m = two ? 4 : b - a;
-            int n_listed = 0;
-            for (int k0 = 0; k0 < m; k0 += kWave) {
-                const int k = k0 + lane;
-                bool cross = false;
-                double xs = 0.0;
-                if (k < m) {
-                    const int kn = k + 1 == m ? 0 : k + 1;
-                    double ax, ay, bx, by;
-                    if (two) {   // the corners (x1, y1), (x2, y1), (x2, y2), (x1, y2) of the box
-                        ax = k == 0 || k == 3 ? bx1 : bx2;
-                        ay = k < 2 ? by1 : by2;
-                        bx = kn == 0 || kn == 3 ? bx1 : bx2;
-                        by = kn < 2 ? by1 : by2;
-                    } else {
-                        const double2 A = pts[k], B = pts[kn];
-                        ax = A.x; ay = A.y; bx = B.x; by = B.y;
-                    }
-                    const bool swap = ay > by || (ay == by && ax > bx);   // the canonical direction
-                    const double Px = swap ? bx : ax, Py = swap ? by : ay, Qx = swap ? ax : bx, Qy = swap ? ay : by;
-                    if (Py != Qy && Py <= yc && yc < Qy) {
-                        cross = true;
-                        const double t = yc - Py, d = Qx - Px;
-                        const double n = t * d;
-                        xs = Px + n / (Qy - Py);
-                    }
-                }
-                const unsigned long long mask = __ballot(cross);
-                const int rank = __popcll(mask & below), count = __popcll(mask);
-                for (int done = 0; done < count;) {
-                    const int take = min(cap - n_listed, count - done);
-                    if (cross && rank >= done && rank < done + take) list[n_listed + rank - done] = xs;
-                    n_listed += take;
-                    done += take;
-                    if (n_listed == cap) {
-                        apply(n_listed);
-                        n_listed = 0;
-                    }
-                }
-            }
-            apply(n_listed);
+            k21_edges(reinterpret_cast<const double2 *>(xy) + a, b - a, info + 4 * p, s.yc, cap, list, apply);
             // the covered pixels change hands
             int n_covered = 0;
             for (int base = 0; base < npx; base += kWave) {
@@ -239,8 +187,8 @@ __global__ __launch_bounds__(kWave) void k21_paint_kernel(const double *__restri
 // values are capped
 static int g_k21_strip = K21_STRIP, g_k21_crossings = K21_CROSSINGS;
 
-void set_k21_strip(int v) { g_k21_strip = v > 0 ? (v < K21_STRIP ? v : K21_STRIP) : K21_STRIP; }
-void set_k21_crossings(int v) { g_k21_crossings = v > 0 ? (v < K21_CROSSINGS ? v : K21_CROSSINGS) : K21_CROSSINGS; }
+void set_k21_strip(int v) { g_k21_strip = k21_capped(v, K21_STRIP); }
+void set_k21_crossings(int v) { g_k21_crossings = k21_capped(v, K21_CROSSINGS); }
 
 struct RasterOut {
     uint8_t *row_status;
@@ -276,9 +224,7 @@ static int raster_launch(const double *xy, const int32_t *pt_off, const int32_t 
                        n_rows, max_pixels, strip, o.row_status, o.pix_off, item_off);
     k13_scan_inclusive(o.pix_off + 1, n_rows, part, st);
     k13_scan_inclusive(item_off + 1, n_rows, part, st);   // after the first scan in the stream, so the partial sums are free again
-    if (n_polys > 0)
-        hipLaunchKernelGGL(k21_poly_kernel, dim3((unsigned)ceil_div(n_polys, (int64_t)K21_BLOCK)), dim3(K21_BLOCK), 0, st, xy, pt_off,
-                           row_off, val, o.row_status, n_rows, n_polys, n_points, o.action, info);
+    k21_polys(xy, pt_off, row_off, val, o.row_status, n_rows, n_polys, n_points, o.action, info, st);
     int64_t total = 0, n_items = 0;
     hipError_t err = hipGetLastError();
     if (err == hipSuccess) err = hipMemcpyAsync(&total, o.pix_off + n_rows, 8, hipMemcpyDeviceToHost, st);

@@ -3,8 +3,9 @@
 // cover(p) is K21's pixel set (centre sampling, canonical edge direction, even-odd rule; include/dyd.h has the rule, DESIGN §5t
 // the mapping and its cost).  Per pair of polygons of a row the kernel counts |cover(a) & cover(b)|, per polygon |cover(p)|; K18's
 // greedy matching then runs on the quotient of those integers, and the pixel confusion matrix comes out of the same pass.  The
-// polygon code is K13's (k13_size_ok, Poly / k13_prepare, k13_scan_inclusive, last_le, poly_tile_rows); the edge -> crossing
-// list -> parity step is a copy of K21's (k21_raster.hip), kept apart until a later change merges the two.
+// polygon code is K13's (k13_scan_inclusive, last_le); the pixel rule is K21's own, from k21_cover.h: the row rule, the polygon
+// kernel (k21_polys, defined in k21_raster.hip), the polygons of a row, the box cull and the edge -> crossing list -> parity
+// step.  The greedy matcher's keys and confusion count are K18's, from k18_pick.h.
 //
 // Layout in HBM, per table: xy = P x (x, y) f64, pt_off = B+1 int32, row_off = N+1 int32, cls = B int32; width / height = N f64.
 // Scratch: 32 bytes per polygon (its box), the rows' item offsets, the scan's partial sums; the pair counts (u32 per pair of a
@@ -23,8 +24,9 @@
 //      the strip once and adds it with one u64 atomic.  Integer atomics only: no result depends on the schedule;
 //   4. match, a wave per row: K18's big-row scheme.  Lanes stride over the A polygons, the B polygons are taken in order, the
 //      arg-max (largest IoU, then lowest index) by shuffles; the matched state is out_a_match, which only the owning lane touches.
-#include "k13_poly.h"
 #include "k13_scan.h"
+#include "k18_pick.h"
+#include "k21_cover.h"
 #include "poly_table.h"
 
 namespace dyd {
@@ -38,27 +40,7 @@ constexpr int K22_PITCH = K22_WORDS + 1;     // words per stored B bitmap: lanes
 constexpr int64_t K22_MAX_PIXELS = 1LL << 30;
 constexpr int64_t K22_MAX_PAIRS = 1LL << 24;
 constexpr int64_t K22_MAX_GRID = 1 << 20;    // paint workgroups; the items beyond are taken grid-stride
-enum : uint8_t { CMP_DONE = 0, CMP_NO_ROW = 5, CMP_ROW_PAIRS = 4 };   // the other actions are K13's codes
-
-// row status 0..3: K21's rule (k21_raster.hip: k21_row_size), restated so that the file stands alone
-__device__ __forceinline__ uint8_t k22_row_size(double W, double H, int64_t max_pixels, int64_t *w, int64_t *h) {
-    *w = *h = 0;
-    if (!k13_size_ok(W) || !k13_size_ok(H)) return 1;
-    if (W != floor(W) || H != floor(H)) return 2;
-    const int64_t iw = (int64_t)W, ih = (int64_t)H;
-    if (iw > max_pixels || ih > max_pixels || iw * ih > max_pixels) return 3;   // the product stays at or below 2^60
-    *w = iw;
-    *h = ih;
-    return 0;
-}
-
-// the polygons [first, last) of row r, clamped as K13 clamps them
-__device__ __forceinline__ void k22_row_polys(const int32_t *__restrict__ row_off, int64_t r, int64_t n_polys, int64_t *first,
-                                              int64_t *last) {
-    const int64_t a = max((int64_t)row_off[r], (int64_t)0), b = min((int64_t)row_off[r + 1], n_polys);
-    *first = a;
-    *last = max(b, a);
-}
+constexpr uint8_t CMP_ROW_PAIRS = 4;         // row status: more pairs than max_pairs_per_row
 
 // ---- 1. rows: a lane per row -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(K22_BLOCK) void k22_rows_kernel(const double *__restrict__ width, const double *__restrict__ height,
@@ -69,9 +51,9 @@ __global__ __launch_bounds__(K22_BLOCK) void k22_rows_kernel(const double *__res
     const int64_t i = (int64_t)blockIdx.x * K22_BLOCK + threadIdx.x;
     if (i >= n_rows) return;
     int64_t w, h, a0, a1, b0, b1;
-    uint8_t st = k22_row_size(width[i], height[i], max_pixels, &w, &h);
-    k22_row_polys(a_row_off, i, n_a, &a0, &a1);
-    k22_row_polys(b_row_off, i, n_b, &b0, &b1);
+    uint8_t st = k21_row_size(width[i], height[i], max_pixels, &w, &h);
+    k21_row_polys(a_row_off, i, n_a, &a0, &a1);
+    k21_row_polys(b_row_off, i, n_b, &b0, &b1);
     const int64_t pairs = (a1 - a0) * (b1 - b0);   // both counts stay below 2^31
     if (st == 0 && pairs > max_pairs) st = CMP_ROW_PAIRS;
     row_status[i] = st;
@@ -80,37 +62,7 @@ __global__ __launch_bounds__(K22_BLOCK) void k22_rows_kernel(const double *__res
     if (i == 0) pair_off[0] = item_off[0] = 0;
 }
 
-// ---- 2. polygons: a lane per polygon ---------------------------------------------------------------------------
-// action (255: cls < 0); info[4p .. 4p+3] = x1, y1, x2, y2 of the points, which is the box of V
-__global__ __launch_bounds__(K22_BLOCK) void k22_poly_kernel(const double *__restrict__ xy, const int32_t *__restrict__ pt_off,
-                                                             const int32_t *__restrict__ row_off, const int32_t *__restrict__ cls,
-                                                             const uint8_t *__restrict__ row_status, int64_t n_rows, int64_t n_polys,
-                                                             int64_t n_points, uint8_t *__restrict__ action, double *__restrict__ info) {
-    __shared__ int32_t rows[2];
-    const int64_t p0 = (int64_t)blockIdx.x * K22_BLOCK, p1 = min(p0 + K22_BLOCK, n_polys);
-    poly_tile_rows(row_off, n_rows, p0, p1, rows);
-    const int64_t p = p0 + threadIdx.x;
-    if (p >= p1) return;
-    const int64_t r = last_le(row_off, rows[0], rows[1], p);
-    uint8_t act;
-    double x1 = 0.0, y1 = 0.0, x2 = 0.0, y2 = 0.0;
-    if (cls[p] < 0) {
-        act = SEG_UNSELECTED;
-    } else if (row_status[r] != 0) {
-        act = CMP_NO_ROW;
-    } else {
-        const int32_t a = max(pt_off[p], 0), b = (int32_t)min((int64_t)max(pt_off[p + 1], a), n_points);
-        Poly pg;
-        act = k13_prepare(xy, a, b, pg);
-        if (act == 0xff) {
-            act = CMP_DONE;
-            x1 = pg.x1; y1 = pg.y1; x2 = pg.x2; y2 = pg.y2;
-        }
-    }
-    action[p] = act;
-    double *q = info + 4 * p;
-    q[0] = x1; q[1] = y1; q[2] = x2; q[3] = y2;
-}
+// ---- 2. polygons: K21's kernel, launched through k21_polys (k21_cover.h), once per table ----------------------------
 
 // ---- 3. paint and intersect: a wave per item -------------------------------------------------------------------
 // one side of the comparison as the paint kernel reads it
@@ -123,36 +75,14 @@ struct K22Side {
     int64_t n_polys, n_points;
 };
 
-// the strip of an item
-struct K22Strip {
-    double yc, xc_first, xc_last;
-    int64_t x0;
-    int npx, n_words;
-};
-
-// K21's cull (k21_raster.hip has the argument): false when polygon p cannot cover a pixel centre of the strip
-__device__ __forceinline__ bool k22_reaches(const K22Side &t, int64_t p, const K22Strip &s) {
-    if (t.action[p] != CMP_DONE) return false;
-    const double *q = t.info + 4 * p;
-    const double bx1 = q[0], by1 = q[1], bx2 = q[2], by2 = q[3];
-    return by1 <= s.yc && s.yc < by2 && !(s.xc_first >= bx2 + 1.0) && !(s.xc_last <= bx1 - 1.0);
-}
-
 // The bitmap of polygon p over the strip: words[c] bit l = pixel 64 c + l covered, for c < n_words; -> the number of covered
-// pixels.  *par_out: the lane's own pixels, bit c = pixel 64 c + lane.  K21's step: lanes take edges in chunks of 64, the
-// crossings go through `list` (capacity cap), a full list is applied and emptied, parity being linear in the crossings.
-__device__ __forceinline__ int k22_bitmap(const K22Side &t, int64_t p, const K22Strip &s, int cap, double *list,
+// pixels.  *par_out: the lane's own pixels, bit c = pixel 64 c + lane.
+__device__ __forceinline__ int k22_bitmap(const K22Side &t, int64_t p, const K21Strip &s, int cap, double *list,
                                           unsigned long long *words, uint32_t *par_out) {
     const int lane = threadIdx.x;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const double *q = t.info + 4 * p;
-    const double bx1 = q[0], by1 = q[1], bx2 = q[2], by2 = q[3];
     const int32_t a = max(t.pt_off[p], 0), b = (int32_t)min((int64_t)max(t.pt_off[p + 1], a), t.n_points);
-    const double2 *pts = reinterpret_cast<const double2 *>(t.xy) + a;
-    const bool two = b - a == 2;
-    const int m = two ? 4 : b - a;
-    const double yc = s.yc;
     uint32_t par = 0;
+    // the crossings listed so far, XORed into the parity of the lane's pixels
     auto apply = [&](int n_listed) __attribute__((always_inline)) {
         __syncthreads();
         for (int c = 0; c < s.n_words; ++c) {
@@ -163,46 +93,7 @@ __device__ __forceinline__ int k22_bitmap(const K22Side &t, int64_t p, const K22
         }
         __syncthreads();
     };
-    int n_listed = 0;
-    for (int k0 = 0; k0 < m; k0 += kWave) {
-        const int k = k0 + lane;
-        bool cross = false;
-        double xs = 0.0;
-        if (k < m) {
-            const int kn = k + 1 == m ? 0 : k + 1;
-            double ax, ay, bx, by;
-            if (two) {   // the corners (x1, y1), (x2, y1), (x2, y2), (x1, y2) of the box
-                ax = k == 0 || k == 3 ? bx1 : bx2;
-                ay = k < 2 ? by1 : by2;
-                bx = kn == 0 || kn == 3 ? bx1 : bx2;
-                by = kn < 2 ? by1 : by2;
-            } else {
-                const double2 A = pts[k], B = pts[kn];
-                ax = A.x; ay = A.y; bx = B.x; by = B.y;
-            }
-            const bool swap = ay > by || (ay == by && ax > bx);   // the canonical direction
-            const double Px = swap ? bx : ax, Py = swap ? by : ay, Qx = swap ? ax : bx, Qy = swap ? ay : by;
-            if (Py != Qy && Py <= yc && yc < Qy) {
-                cross = true;
-                const double tt = yc - Py, d = Qx - Px;
-                const double n = tt * d;
-                xs = Px + n / (Qy - Py);
-            }
-        }
-        const unsigned long long mask = __ballot(cross);
-        const int rank = __popcll(mask & below), count = __popcll(mask);
-        for (int done = 0; done < count;) {
-            const int take = min(cap - n_listed, count - done);
-            if (cross && rank >= done && rank < done + take) list[n_listed + rank - done] = xs;
-            n_listed += take;
-            done += take;
-            if (n_listed == cap) {
-                apply(n_listed);
-                n_listed = 0;
-            }
-        }
-    }
-    apply(n_listed);
+    k21_edges(reinterpret_cast<const double2 *>(t.xy) + a, b - a, t.info + 4 * p, s.yc, cap, list, apply);
     int n_covered = 0;
     for (int c = 0; c < s.n_words; ++c) {
         const bool in = ((par >> c) & 1u) != 0 && c * kWave + lane < s.npx;
@@ -236,25 +127,20 @@ __global__ __launch_bounds__(kWave) void k22_paint_kernel(K22Side A, K22Side B, 
         const int64_t W = (int64_t)width[r], H = (int64_t)height[r];
         const int64_t n_strips = (W + strip - 1) / strip;
         if (row_status[r] != 0 || local < 0 || local >= H * n_strips) continue;   // never for a sound item_off
-        const int64_t j = local / n_strips;
-        K22Strip s;
-        s.x0 = (local - j * n_strips) * strip;
-        s.npx = (int)min((int64_t)strip, W - s.x0);
-        s.n_words = (s.npx + kWave - 1) / kWave;   // <= K22_WORDS: strip <= K22_STRIP
-        s.yc = (double)j + 0.5;
-        s.xc_first = (double)s.x0 + 0.5;
-        s.xc_last = (double)(s.x0 + s.npx - 1) + 0.5;
+        const int64_t j = local / n_strips, x0 = (local - j * n_strips) * strip;
+        const int npx = (int)min((int64_t)strip, W - x0);   // at most K22_WORDS words: strip <= K22_STRIP
+        const K21Strip s{(double)j + 0.5, (double)x0 + 0.5, (double)(x0 + npx - 1) + 0.5, x0, npx, (npx + kWave - 1) / kWave};
         for (int px = lane; px < s.npx; px += kWave) owner_a[px] = owner_b[px] = -1;
         int64_t a0, a1, b0, b1;
-        k22_row_polys(A.row_off, r, A.n_polys, &a0, &a1);
-        k22_row_polys(B.row_off, r, B.n_polys, &b0, &b1);
+        k21_row_polys(A.row_off, r, A.n_polys, &a0, &a1);
+        k21_row_polys(B.row_off, r, B.n_polys, &b0, &b1);
         const int64_t nb = b1 - b0, cell0 = pair_off[r];
         int64_t q = b0;
         for (bool first = true;; first = false) {
             // the next chunk of B bitmaps; B's ownership and pixel counts
             int n_chunk = 0;
             for (; q < b1 && n_chunk < chunk; ++q) {
-                if (!k22_reaches(B, q, s)) continue;
+                if (!k21_reaches(B.action, B.info, q, s)) continue;
                 uint32_t par;
                 const int n_cov = k22_bitmap(B, q, s, cap, list, bits_b + n_chunk * K22_PITCH, &par);
                 for (int c = 0; c < s.n_words; ++c)
@@ -268,7 +154,7 @@ __global__ __launch_bounds__(kWave) void k22_paint_kernel(K22Side A, K22Side B, 
             if (n_chunk == 0 && !first) break;
             __syncthreads();
             for (int64_t p = a0; p < a1; ++p) {
-                if (!k22_reaches(A, p, s)) continue;
+                if (!k21_reaches(A.action, A.info, p, s)) continue;
                 uint32_t par;
                 const int n_cov = k22_bitmap(A, p, s, cap, list, bits_a, &par);
                 if (first) {
@@ -330,13 +216,6 @@ __global__ __launch_bounds__(kWave) void k22_paint_kernel(K22Side A, K22Side B, 
 }
 
 // ---- 4. match: a wave per row ----------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long k22_bits(double v) { return (unsigned long long)__double_as_longlong(v); }
-__device__ __forceinline__ double k22_value(unsigned long long k) { return __longlong_as_double((long long)k); }
-__device__ __forceinline__ void k22_count(unsigned long long *conf, int32_t C, int32_t a, int32_t b) {
-    if ((uint32_t)a > (uint32_t)C || (uint32_t)b > (uint32_t)C) return;   // a class id outside the list is not counted
-    atomicAdd(conf + (int64_t)a * (C + 1) + b, 1ull);
-}
-
 __global__ __launch_bounds__(kWave) void k22_match_kernel(const int32_t *__restrict__ a_row_off, const int32_t *__restrict__ a_cls,
                                                           const uint8_t *__restrict__ a_action, const unsigned long long *__restrict__ a_pixels,
                                                           const int32_t *__restrict__ b_row_off, const int32_t *__restrict__ b_cls,
@@ -350,8 +229,8 @@ __global__ __launch_bounds__(kWave) void k22_match_kernel(const int32_t *__restr
     const int lane = threadIdx.x;
     for (int64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
         int64_t a0, a1, b0, b1;
-        k22_row_polys(a_row_off, r, n_a, &a0, &a1);
-        k22_row_polys(b_row_off, r, n_b, &b0, &b1);
+        k21_row_polys(a_row_off, r, n_a, &a0, &a1);
+        k21_row_polys(b_row_off, r, n_b, &b0, &b1);
         const int64_t na = a1 - a0, nb = b1 - b0;
         for (int64_t i = lane; i < na; i += kWave) {
             out_a_match[a0 + i] = -1;
@@ -361,7 +240,7 @@ __global__ __launch_bounds__(kWave) void k22_match_kernel(const int32_t *__restr
         const bool compared = row_status[r] == 0;
         const int64_t cell0 = pair_off[r];
         for (int64_t j = 0; j < nb; ++j) {   // wave-uniform
-            const bool b_ok = compared && b_action[b0 + j] == CMP_DONE;
+            const bool b_ok = compared && b_action[b0 + j] == COVER_DONE;
             unsigned long long key = 0ull, bk = 0ull;
             int64_t idx = INT64_MAX;
             if (b_ok) {
@@ -369,15 +248,15 @@ __global__ __launch_bounds__(kWave) void k22_match_kernel(const int32_t *__restr
                 const int32_t cb = b_cls[b0 + j];
                 const unsigned long long pb = b_pixels[b0 + j];
                 for (int64_t i = lane; i < na; i += kWave) {   // ascending: the first of equal keys stays
-                    if (a_action[a0 + i] != CMP_DONE) continue;
+                    if (a_action[a0 + i] != COVER_DONE) continue;
                     const uint32_t inter = pairs[cell0 + i * nb + j];
                     if (inter == 0) continue;
                     const double iou = (double)inter / (double)(a_pixels[a0 + i] + pb - inter);
                     if (iou > out_a_best[a0 + i]) out_a_best[a0 + i] = iou;
-                    const unsigned long long bits = k22_bits(iou);   // iou > 0: ordered like its bits
+                    const unsigned long long bits = k18_bits(iou), cand = k18_cand_key(iou);   // iou > 0: ordered like its bits
                     bk = bits > bk ? bits : bk;
-                    if (out_a_match[a0 + i] < 0 && (!by_label || a_cls[a0 + i] == cb) && iou >= thr && bits + 1ull > key) {
-                        key = bits + 1ull;
+                    if (out_a_match[a0 + i] < 0 && (!by_label || a_cls[a0 + i] == cb) && iou >= thr && cand > key) {
+                        key = cand;
                         idx = i;
                     }
                 }
@@ -398,20 +277,20 @@ __global__ __launch_bounds__(kWave) void k22_match_kernel(const int32_t *__restr
                 out_a_match[a0 + wi] = (int32_t)j;
                 const int32_t ca = a_cls[a0 + wi], cb = b_cls[b0 + j];
                 if (ca == cb) ++same; else ++diff;
-                k22_count(conf, C, ca, cb);
+                k18_count(conf, C, ca, cb);
             }
             if (lane == 0) {
                 out_b_match[b0 + j] = hit ? (int32_t)wi : -1;
-                out_b_iou[b0 + j] = hit ? k22_value(wk - 1ull) : 0.0;
-                out_b_best[b0 + j] = k22_value(wb);
-                if (b_ok && !hit) k22_count(conf, C, C, b_cls[b0 + j]);
+                out_b_iou[b0 + j] = hit ? k18_value(wk - 1ull) : 0.0;
+                out_b_best[b0 + j] = k18_value(wb);
+                if (b_ok && !hit) k18_count(conf, C, C, b_cls[b0 + j]);
             }
         }
         if (compared)
             for (int64_t i = lane; i < na; i += kWave)
-                if (a_action[a0 + i] == CMP_DONE) {
+                if (a_action[a0 + i] == COVER_DONE) {
                     ++a_live;
-                    if (out_a_match[a0 + i] < 0) k22_count(conf, C, a_cls[a0 + i], C);
+                    if (out_a_match[a0 + i] < 0) k18_count(conf, C, a_cls[a0 + i], C);
                 }
         for (int d = 32; d >= 1; d >>= 1) {
             same += __shfl_xor(same, d);
@@ -433,11 +312,10 @@ __global__ __launch_bounds__(kWave) void k22_match_kernel(const int32_t *__restr
 static int g_k22_strip = K22_STRIP, g_k22_crossings = K22_CROSSINGS, g_k22_chunk = K22_CHUNK;
 static int64_t g_k22_grid = K22_MAX_GRID;
 
-static int k22_capped(int v, int most) { return v > 0 ? (v < most ? v : most) : most; }
-void set_k22_strip(int v) { g_k22_strip = k22_capped(v, K22_STRIP); }
-void set_k22_crossings(int v) { g_k22_crossings = k22_capped(v, K22_CROSSINGS); }
-void set_k22_chunk(int v) { g_k22_chunk = k22_capped(v, K22_CHUNK); }
-void set_k22_grid(int v) { g_k22_grid = k22_capped(v, (int)K22_MAX_GRID); }
+void set_k22_strip(int v) { g_k22_strip = k21_capped(v, K22_STRIP); }
+void set_k22_crossings(int v) { g_k22_crossings = k21_capped(v, K22_CROSSINGS); }
+void set_k22_chunk(int v) { g_k22_chunk = k21_capped(v, K22_CHUNK); }
+void set_k22_grid(int v) { g_k22_grid = k21_capped(v, (int)K22_MAX_GRID); }
 
 // one table of a comparison in device memory with its outputs
 struct K22Table {
@@ -510,12 +388,8 @@ static int compare_launch(const K22Table &a, const K22Table &b, const double *wi
         set_error("K22: clearing the counters failed: %s", hipGetErrorString(e));
         return fail(DYD_ERR_HIP);
     }
-    if (a.n_polys > 0)
-        hipLaunchKernelGGL(k22_poly_kernel, dim3((unsigned)ceil_div(a.n_polys, (int64_t)K22_BLOCK)), dim3(K22_BLOCK), 0, st, a.xy,
-                           a.pt_off, a.row_off, a.cls, o.row_status, n_rows, a.n_polys, a.n_points, a.action, inf_a);
-    if (b.n_polys > 0)
-        hipLaunchKernelGGL(k22_poly_kernel, dim3((unsigned)ceil_div(b.n_polys, (int64_t)K22_BLOCK)), dim3(K22_BLOCK), 0, st, b.xy,
-                           b.pt_off, b.row_off, b.cls, o.row_status, n_rows, b.n_polys, b.n_points, b.action, inf_b);
+    k21_polys(a.xy, a.pt_off, a.row_off, a.cls, o.row_status, n_rows, a.n_polys, a.n_points, a.action, inf_a, st);
+    k21_polys(b.xy, b.pt_off, b.row_off, b.cls, o.row_status, n_rows, b.n_polys, b.n_points, b.action, inf_b, st);
     unsigned long long *a_pix = reinterpret_cast<unsigned long long *>(a.pixels);
     unsigned long long *b_pix = reinterpret_cast<unsigned long long *>(b.pixels);
     unsigned long long *conf = reinterpret_cast<unsigned long long *>(o.confusion);

@@ -1,5 +1,6 @@
 """Table builders shared by tests/test_polygon_compare_cpu.py and tests/test_gpu_polygon_compare.py: the ten input arrays of K22 from
-rows written out by hand, small shapes, and the random table both files compare on, with its expected outputs computed once."""
+rows written out by hand, small shapes, and the random table both files compare on, with its expected outputs computed once; and
+the identities that tie K22's outputs to K21's masks of the same two tables, with the table both files check them on."""
 import functools
 import math
 
@@ -90,3 +91,76 @@ def random_want(thr=0.5, by_label=False):
 
 def box(x1, y1, x2, y2):
     return [(float(x1), float(y1)), (float(x2), float(y2))]
+
+
+def strip_rows(widths, h=5):
+    rng = np.random.default_rng(31)
+    rows = []
+    for w in widths:
+        a = [(0, blob(rng, w / 2, h / 2, w / 2 + 1, 9)), (1, box(w - 3, 0, w, h)), (2, box(-5, 1, w + 5, 2.2))]
+        b = [(0, blob(rng, w / 2 + 1, h / 2, w / 2, 7)), (2, box(w - 4, 1, w - 1, h)), (1, box(0, 0, w, 1.7)), (1, box(60, 1, 70, 4))]
+        rows.append((w, h, a, b))
+    return rows
+
+
+def comb(n_teeth):
+    pts = [(0.0, 0.0)]
+    for k in range(n_teeth):
+        pts += [(3.0 * k + 0.5, 10.0), (3.0 * k + 1.5, 1.0), (3.0 * k + 2.5, 10.0)]
+    return pts + [(3.0 * n_teeth + 5.0, 0.0)]
+
+
+# ----------------------------------------------------------------------------------------------- K21 and K22 on the same tables
+def shared_rows():
+    """The smallest table that reaches what K21 and K22 share (csrc/k21_cover.h): strip edges at and around a wave with boxes
+    that overhang the image; about 80 crossings per scanline; a two-point polygon per side (the synthetic corners); polygons of
+    65 points (a second chunk of edges); unselected polygons; a row of fractional size between painted rows."""
+    rng = np.random.default_rng(34)
+    rows = strip_rows((63, 64, 65, 130))
+    shifted = [(x + 1.0, y) for x, y in comb(40)]
+    rows.append((125, 12, [(0, comb(40)), (1, box(3, 2, 90, 7))], [(0, shifted), (1, box(100, 9, 4, 1))]))
+    rows.append((40.5, 30, [(2, box(0, 0, 5, 5))], [(2, box(0, 0, 5, 5))]))
+    rows.append((40, 30, [(2, blob(rng, 20, 15, 18, 65)), (-1, box(0, 0, 40, 30)), (1, box(30, 2, 38, 20))],
+                 [(2, blob(rng, 21, 15, 18, 65)), (1, box(29, 2, 38, 21)), (-1, blob(rng, 10, 10, 9, 5))]))
+    return rows
+
+
+@functools.lru_cache(maxsize=None)
+def shared_table():
+    return table(shared_rows())
+
+
+@functools.lru_cache(maxsize=None)
+def shared_want():
+    """the restatements over shared_table(): K21's outputs over side A and over side B, K22's over both (3 classes)"""
+    import polygon_raster_ref as RR
+
+    t = shared_table()
+    return RR.raster_arrays(*raster_side(t, 0)), RR.raster_arrays(*raster_side(t, 1)), R.compare_arrays(*t, 3)
+
+
+def raster_side(t, k):
+    """side k (0: A, 1: B) of a comparison as K21's six inputs, with val = cls + 1 (background 0) and unselected polygons kept
+    unselected"""
+    xy, pt_off, row_off, cls = t[4 * k:4 * k + 4]
+    assert cls.max(initial=0) <= 254, "val must fit a byte"
+    return xy, pt_off, row_off, np.where(cls >= 0, cls + 1, -1).astype(np.int32), t[8], t[9]
+
+
+def assert_same_cover(t, mask_a, mask_b, cmp):
+    """mask_a / mask_b: K21's six outputs over raster_side(t, 0 / 1) with background 0; cmp: K22's outputs over t, under the same
+    max_pixels_per_row.  A row of pair status 4 is rasterised and not compared, so nothing is said about it."""
+    status, row_pixels = cmp[0], cmp[14]
+    rows = status != R.STATUS_PAIRS
+    for mask, row_off, action, pixels in ((mask_a, t[2], cmp[2], cmp[4]), (mask_b, t[6], cmp[3], cmp[5])):
+        polys = np.repeat(rows, np.diff(row_off))
+        assert np.array_equal(mask[0][rows], status[rows]), "row_status"
+        assert np.array_equal(mask[2][polys], action[polys]), "action"
+        assert mask[3].dtype == pixels.dtype and np.array_equal(mask[3][polys], pixels[polys]), "covered against a_pixels / b_pixels"
+    pix_off = mask_a[1]
+    assert np.array_equal(pix_off, mask_b[1])
+    want = np.zeros((len(status), 2), np.int64)
+    for r in np.flatnonzero(status == 0):
+        ma, mb = mask_a[5][pix_off[r]:pix_off[r + 1]], mask_b[5][pix_off[r]:pix_off[r + 1]]
+        want[r] = ((ma == mb) & (ma != 0)).sum(), ((ma != 0) | (mb != 0)).sum()
+    assert row_pixels.dtype == want.dtype and np.array_equal(row_pixels, want), "row_pixels"

@@ -10,7 +10,9 @@ import pandas as pd
 import pytest
 
 import polygon_compare_ref as R
-from polygon_compare_tables import RANDOM, blob, box, random_rows, random_table, random_want, table
+import test_gpu_polygon_raster as k21
+from polygon_compare_tables import (RANDOM, assert_same_cover, blob, box, comb, random_rows, random_table, random_want, raster_side,
+                                    shared_table, shared_want, strip_rows, table)
 from deal_yolo_daya_amd.core import processor as P
 
 pytestmark = pytest.mark.gpu
@@ -141,16 +143,6 @@ def test_grid_stride_and_determinism(native):
 
 
 # ----------------------------------------------------------------------------------------------- strips
-def strip_rows(widths, h=5):
-    rng = np.random.default_rng(31)
-    rows = []
-    for w in widths:
-        a = [(0, blob(rng, w / 2, h / 2, w / 2 + 1, 9)), (1, box(w - 3, 0, w, h)), (2, box(-5, 1, w + 5, 2.2))]
-        b = [(0, blob(rng, w / 2 + 1, h / 2, w / 2, 7)), (2, box(w - 4, 1, w - 1, h)), (1, box(0, 0, w, 1.7)), (1, box(60, 1, 70, 4))]
-        rows.append((w, h, a, b))
-    return rows
-
-
 @pytest.mark.parametrize("strip", [64, 17])
 def test_strips(native, strip):
     option(native, strip=strip)
@@ -168,13 +160,6 @@ def test_the_default_strip(native):
 
 
 # ----------------------------------------------------------------------------------------------- the crossing list
-def comb(n_teeth):
-    pts = [(0.0, 0.0)]
-    for k in range(n_teeth):
-        pts += [(3.0 * k + 0.5, 10.0), (3.0 * k + 1.5, 1.0), (3.0 * k + 2.5, 10.0)]
-    return pts + [(3.0 * n_teeth + 5.0, 0.0)]
-
-
 @pytest.mark.parametrize("crossings", [3, 1])
 def test_a_full_crossing_list_is_applied_and_emptied(native, crossings):
     option(native, crossings=crossings)
@@ -189,6 +174,32 @@ def test_more_crossings_than_the_default_list_holds(native):
     assert 2 * 150 > CROSSINGS
     want = both(native, table([(640, 4, [(0, a)], [(0, b), (1, box(100, 0, 300, 4))])]), 2)
     assert want[4][0] > 600 and (want[15] > 0).all()
+
+
+# ----------------------------------------------------------------------------------------------- K21 and K22 share one pixel rule
+@pytest.mark.parametrize("k21_small", [True, False])
+def test_masks_and_comparison_agree_with_the_options_crossed(native, k21_small):
+    """K21 over A, K21 over B and K22 over (A, B) through the _dev entries: each against its restatement, and the identities
+    of polygon_compare_tables.assert_same_cover between the devices' outputs.  One kernel's strip and list small while the
+    other's are not, then exchanged: the six options belong to their own kernel."""
+    small, other = dict(strip=17, crossings=3), dict(strip=64, crossings=1)
+    t, want = shared_table(), shared_want()
+    try:
+        k21.option(native, **(small if k21_small else other))
+        option(native, chunk=2, **(other if k21_small else small))
+        masks = []
+        for side in (0, 1):
+            ts = raster_side(t, side)
+            got, rc, total = k21.run_dev(ts)
+            assert rc == 0 and total == len(got[5])
+            k21.same(got, want[side])
+            masks.append(got)
+        cmp, rc = run_dev(t, 3, n_pairs=want[2][1][-1])
+        assert rc == 0, native.lib().dyd_last_error()
+        same(cmp, want[2])
+        assert_same_cover(t, masks[0], masks[1], cmp)
+    finally:
+        k21.option(native)
 
 
 # ----------------------------------------------------------------------------------------------- chunks of B bitmaps
