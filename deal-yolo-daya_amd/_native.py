@@ -165,6 +165,10 @@ SIGNATURES = {
                              + [C.c_void_p] * 15),
     "dyd_compare_polygons_dev": (C.c_int, [C.c_void_p] * 10 + [C.c_int64] * 5 + [C.c_int32, C.c_double, C.c_int, C.c_int64, C.c_int64]
                                  + [C.c_void_p] * 16 + [C.c_int64, C.c_void_p]),
+    "dyd_polygon_rle": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int64] + [C.c_void_p] * 6
+                        + [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "dyd_polygon_rle_dev": (C.c_int, [C.c_void_p] * 6 + [C.c_int64] * 4 + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                                                               C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "dyd_coco_annotations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                                        C.POINTER(C.c_int64)]),
@@ -554,6 +558,25 @@ def rasterize_polygons(xy, pt_off, row_off, val, width, height, background: int 
                                        int(max_pixels_per_row), _ptr(status), _ptr(pix_off), opt(action), opt(covered), opt(owned),
                                        C.byref(pixels), C.byref(total)), "dyd_rasterize_polygons")
     return status, pix_off, action, covered, owned, np.frombuffer(_take_text(pixels, total), np.uint8)
+
+
+def polygon_rle(xy, pt_off, row_off, sel, width, height, max_pixels_per_row: int = 1 << 26):
+    """K23 over host arrays -> (row_status u8 [n], action u8 [B], area i64 [B], bbox i32 [B, 4], run_off i64 [B+1], runs u32
+    [run_off[B]], text_off i64 [B+1], text bytes): the column-major run lengths of polygon p's own mask are
+    runs[run_off[p]:run_off[p+1]], their COCO "counts" string text[text_off[p]:text_off[p+1]].  Rule and codes: include/dyd.h."""
+    xy, pt_off, row_off, width, height, _, sel, n, nb = _poly_table(xy, pt_off, row_off, width, height,   # no row column of its own
+                                                                    ("width", width, np.float64), ("sel", sel, np.int32))
+    status, action = np.zeros(n, np.uint8), np.zeros(nb, np.uint8)
+    area, bbox = np.zeros(nb, np.int64), np.zeros((nb, 4), np.int32)
+    run_off, text_off = np.zeros(nb + 1, np.int64), np.zeros(nb + 1, np.int64)
+    runs, n_runs, text, total = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int64()
+    opt = lambda a: _ptr(a) if a.size else None          # noqa: E731
+    check(lib().dyd_polygon_rle(opt(xy), _ptr(pt_off), _ptr(row_off), opt(sel), _ptr(width), _ptr(height), n, int(max_pixels_per_row),
+                                _ptr(status), opt(action), opt(area), opt(bbox), _ptr(run_off), _ptr(text_off), C.byref(runs),
+                                C.byref(n_runs), C.byref(text), C.byref(total)), "dyd_polygon_rle")
+    n_bytes = C.c_int64(4 * n_runs.value)
+    return (status, action, area, bbox, run_off, np.frombuffer(_take_text(runs, n_bytes), np.uint32), text_off,
+            _take_text(text, total))
 
 
 def compare_polygons(a_xy, a_pt_off, a_row_off, a_cls, b_xy, b_pt_off, b_row_off, b_cls, width, height, n_classes: int,

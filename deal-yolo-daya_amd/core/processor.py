@@ -3618,8 +3618,9 @@ class _CocoTotals:
         self.wrote_text = False
 
 
-def _coco_chunk(cells, labels, status, W, H, names_of_rows, be, acc: _CocoTotals, start: int, flags: int, keep_empty: bool, out):
-    """one chunk of rows: polygon table (_poly_chunk) -> category ids -> K16 -> the annotation text to `out`, image entries"""
+def _coco_category_ids(cells, labels, acc: _CocoTotals) -> tuple:
+    """one chunk of rows: polygon table (_poly_chunk) and the category id of every polygon (0: not selected) -> (row_off, xy,
+    pt_off, obj, cls, names, cat); acc takes the counts and, without given classes, numbers the names by first appearance"""
     row_off, xy, pt_off, obj, cls, names, n_py = _poly_chunk(cells)
     acc.python_cells += n_py
     n, nb = len(cells), len(cls)
@@ -3639,6 +3640,13 @@ def _coco_chunk(cells, labels, status, W, H, names_of_rows, be, acc: _CocoTotals
             lut[k] = acc.cat_of.setdefault(names[k], len(acc.cat_of) + 1)
     cat = np.where(sel, lut[cls], 0).astype(np.int32) if nb else np.zeros(0, np.int32)
     acc.unknown += int((sel & (cat == 0)).sum()) if nb else 0
+    return row_off, xy, pt_off, obj, cls, names, cat
+
+
+def _coco_chunk(cells, labels, status, W, H, names_of_rows, be, acc: _CocoTotals, start: int, flags: int, keep_empty: bool, out):
+    """one chunk of rows: polygon table (_poly_chunk) -> category ids -> K16 -> the annotation text to `out`, image entries"""
+    row_off, xy, pt_off, obj, cls, names, cat = _coco_category_ids(cells, labels, acc)
+    n, nb = len(cells), len(cls)
     action, _, kept, text = be.coco_annotations(xy, pt_off, row_off.astype(np.int32), cat, W, H, status, start + 1,
                                                 1 + acc.polygons, flags)
     acc.polygons += nb
@@ -3659,8 +3667,68 @@ def _coco_chunk(cells, labels, status, W, H, names_of_rows, be, acc: _CocoTotals
     return int(n - usable.sum())
 
 
+_COCO_RLE_ACTION = np.asarray([0, 0, 2, 3, 4, 5], np.uint8)   # K23's action -> its COCO_ACTIONS entry (0 with area 0: empty)
+
+
+def _coco_rle_chunk(cells, labels, W, H, names_of_rows, be, acc: _CocoTotals, start: int, iscrowd: int, max_pixels: int,
+                    keep_empty: bool, out):
+    """_coco_chunk with "segmentation" as a run-length mask: category ids as there -> K23 (polygon_rle's device step) -> one
+    annotation object per selected polygon of action 0 that covers a pixel, its area and bbox the mask's, formatted here"""
+    import time as _time
+
+    row_off, xy, pt_off, obj, cls, names, cat = _coco_category_ids(cells, labels, acc)
+    n, nb = len(cells), len(cls)
+    chosen = cat > 0
+    row_off = np.asarray(row_off, np.int64)
+    t0 = _time.perf_counter()
+    status, act, area, bbox, _, text_off, text = _rle_device(be, xy, pt_off, row_off, np.where(chosen, cat, -1).astype(np.int32), W, H,
+                                                             max_pixels)
+    t1 = _time.perf_counter()
+    action = np.where(chosen, _COCO_RLE_ACTION[np.minimum(act, 5)], 0).astype(np.uint8)
+    action[chosen & (act == 0) & (area == 0)] = 4
+    acc.actions += np.bincount(action[chosen], minlength=len(COCO_ACTIONS))[:len(COCO_ACTIONS)]
+    printed = np.flatnonzero(chosen & (action == 0))
+    prow = np.searchsorted(row_off, printed, side="right") - 1
+    kept = np.bincount(prow, minlength=n)
+    parts = []
+    for p, r in zip(printed.tolist(), prow.tolist()):
+        x, y, w, h = bbox[p].tolist()
+        parts.append('{"id":%d,"image_id":%d,"category_id":%d,"bbox":[%d.00,%d.00,%d.00,%d.00],"area":%d.00,"iscrowd":%d,'
+                     '"segmentation":{"size":[%d,%d],"counts":%s}}'
+                     % (1 + acc.polygons + p, start + r + 1, cat[p], x, y, w, h, area[p], iscrowd, int(H[r]), int(W[r]),
+                        json.dumps(text[text_off[p]:text_off[p + 1]].decode("ascii"))))
+    if parts:
+        chunk_text = ",".join(parts).encode("ascii")
+        out.write(b"," + chunk_text if acc.wrote_text else chunk_text)
+        acc.wrote_text = True
+    acc.rle_seconds[0] += t1 - t0
+    acc.rle_seconds[1] += _time.perf_counter() - t1
+    acc.polygons += nb
+    usable = status == 0
+    for k in np.flatnonzero(usable & ((kept > 0) | keep_empty)).tolist():
+        acc.image_parts.append(_coco_json({"id": start + k + 1, "width": _coco_size(float(W[k])), "height": _coco_size(float(H[k])),
+                                           "file_name": names_of_rows(start + k)}))
+    bad = np.flatnonzero(chosen & (action >= 2))
+    if len(bad):
+        acc.skipped.append((start + np.searchsorted(row_off, bad, side="right") - 1, obj[bad].astype(np.int64),
+                            np.asarray(names, object)[cls[bad]], np.asarray(COCO_ACTIONS, object)[action[bad]]))
+    return int(n - usable.sum())
+
+
+def _coco_segmentation(segmentation, iscrowd, max_pixels_per_row) -> tuple:
+    """-> (run-length mode?, iscrowd, max_pixels_per_row), checked; anything but "rle" is the polygon-list export's flag"""
+    if not (isinstance(segmentation, str) and segmentation == "rle"):
+        if isinstance(segmentation, str):
+            raise ValueError(f'segmentation must be True, False or "rle", got {segmentation!r}')
+        return False, 0, 0
+    if isinstance(iscrowd, bool) or iscrowd not in (0, 1):
+        raise ValueError(f"iscrowd must be 0 or 1, got {iscrowd!r}")
+    return True, int(iscrowd), _mask_int(max_pixels_per_row, "max_pixels_per_row", 1, 1 << 30)
+
+
 def _coco_export_rows(cells, n, widths, heights, sources, labels, classes, segmentation, keep_empty_images, file_names,
-                      output_json, skipped_csv, be, stats, cells_of=None) -> dict:
+                      output_json, skipped_csv, be, stats, cells_of=None, iscrowd: int = 0, max_pixels_per_row: int = 1 << 26) -> dict:
+    rle, iscrowd, max_pixels = _coco_segmentation(segmentation, iscrowd, max_pixels_per_row)
     if classes is not None:
         classes = list(classes)
         if len(set(classes)) != len(classes) or not all(isinstance(c, str) for c in classes):
@@ -3677,6 +3745,7 @@ def _coco_export_rows(cells, n, widths, heights, sources, labels, classes, segme
     else:
         name_of = str
     acc = _CocoTotals(classes)
+    acc.rle_seconds = [0.0, 0.0]                         # run-length mode: the device step, the objects formatted in Python
     flags = 1 if segmentation else 0
     output_json = str(output_json)
     if os.path.dirname(output_json):
@@ -3686,6 +3755,10 @@ def _coco_export_rows(cells, n, widths, heights, sources, labels, classes, segme
     with open(tmp, "wb") as out:
         out.write(b'{"info":' + _coco_json(_COCO_INFO) + b',"licenses":[],"annotations":[')
         for s0, s1, chunk in _chunks(n, cells, cells_of):
+            if rle:
+                no_size += _coco_rle_chunk(chunk, None if labels is None else labels[s0:s1], W[s0:s1], H[s0:s1], name_of, be, acc, s0,
+                                           iscrowd, max_pixels, bool(keep_empty_images), out)
+                continue
             no_size += _coco_chunk(chunk, None if labels is None else labels[s0:s1], status[s0:s1], W[s0:s1], H[s0:s1], name_of, be,
                                    acc, s0, flags, bool(keep_empty_images), out)
         categories = [{"id": k, "name": nm, "supercategory": ""} for nm, k in acc.cat_of.items()]
@@ -3699,26 +3772,38 @@ def _coco_export_rows(cells, n, widths, heights, sources, labels, classes, segme
               **{a: int(acc.actions[k]) for k, a in enumerate(COCO_ACTIONS)}, "unmatchable_name_polygons": acc.unmatchable,
               "unknown_class": acc.unknown, "annotations": int(acc.actions[0] + acc.actions[1]), "categories": categories,
               "python_cells": acc.python_cells, "output": output_json, "skipped_output": skipped_csv}
+    if rle:
+        result.update(rle_device_seconds=acc.rle_seconds[0], rle_format_seconds=acc.rle_seconds[1])
     if stats is not None:
         stats.update(result)
     return result
 
 
+def _coco_entry(segmentation) -> str:
+    """the backend entry the export needs"""
+    return "polygon_rle" if isinstance(segmentation, str) and segmentation == "rle" else "coco_annotations"
+
+
 def export_coco_frame(df: pd.DataFrame, output_json, json_col: str = ANNOTATION_COL, width_col: str = "width",
                       height_col: str = "height", source_col: str = "source", label_col: Optional[str] = None, classes=None,
-                      segmentation: bool = True, keep_empty_images: bool = True, file_names=None, skipped_csv=None, backend=None,
-                      stats: Optional[dict] = None) -> dict:
+                      segmentation=True, keep_empty_images: bool = True, file_names=None, skipped_csv=None, backend=None,
+                      stats: Optional[dict] = None, iscrowd: int = 0, max_pixels_per_row: int = 1 << 26) -> dict:
     """A table's annotation polygons as one COCO instances file (see the section comment).  Every polygon with a str name is
     selected; with ``label_col`` only those whose name is str(row[label_col]) (the dataset step's rule).  ``classes`` fixes the
     categories (id = index + 1; a selected polygon with another name is deselected and counted as unknown_class); without it
     they are numbered by first appearance.  A row with a usable size gets an image entry (id = position + 1; file_name =
     file_names[i], else str(source), else the position) unless it has no annotation and keep_empty_images is False; a row
     without one gets none and its polygons are no_size.  segmentation=False leaves every "segmentation" empty (the detect
-    flavour).  ``skipped_csv``: [source,] row, object, name, action of every selected polygon that is not printed.  The file is
+    flavour).  segmentation="rle" writes every selected polygon's own mask as COCO's run-length encoding instead (K23, the
+    section "run-length masks"): "segmentation" is {"size":[H,W],"counts":"..."}, "area" and "bbox" are the mask's pixel area
+    and pixel box, "iscrowd" is ``iscrowd`` (0 or 1); a polygon that covers no pixel centre is `empty`, a polygon of a row that
+    is not rasterised (no usable, whole size of at most max_pixels_per_row pixels) is `no_size` and such a row gets no image
+    entry, nothing is `clipped`; the dict then also holds rle_device_seconds and rle_format_seconds (the objects are formatted
+    in Python).  ``skipped_csv``: [source,] row, object, name, action of every selected polygon that is not printed.  The file is
     written to output_json + ".tmp" and moved into place.  -> dict(rows, rows_no_size, images, polygons, one count per
     COCO_ACTIONS entry over the selected polygons, unmatchable_name_polygons, unknown_class, annotations, categories,
     python_cells, output, skipped_output)."""
-    be = _step_backend(backend, "coco_annotations")
+    be = _step_backend(backend, _coco_entry(segmentation))
     if label_col is not None and label_col not in df.columns:
         raise ValueError(f"no column {label_col!r}")
     cells = df[json_col].to_numpy()
@@ -3726,13 +3811,13 @@ def export_coco_frame(df: pd.DataFrame, output_json, json_col: str = ANNOTATION_
     sources = df[source_col].to_numpy() if source_col in df.columns else None
     labels = df[label_col].to_numpy() if label_col is not None else None
     return _coco_export_rows(cells, len(cells), widths, heights, sources, labels, classes, segmentation, keep_empty_images,
-                             file_names, output_json, skipped_csv, be, stats)
+                             file_names, output_json, skipped_csv, be, stats, None, iscrowd, max_pixels_per_row)
 
 
 def export_coco_csv(input_csv_path, output_json, json_col: str = ANNOTATION_COL, width_col: str = "width",
                     height_col: str = "height", source_col: str = "source", label_col: Optional[str] = None, classes=None,
-                    segmentation: bool = True, keep_empty_images: bool = True, file_names=None, skipped_csv=None, backend=None,
-                    stats: Optional[dict] = None):
+                    segmentation=True, keep_empty_images: bool = True, file_names=None, skipped_csv=None, backend=None,
+                    stats: Optional[dict] = None, iscrowd: int = 0, max_pixels_per_row: int = 1 << 26):
     """CSV -> COCO instances file, export_coco_frame on the native CSV hand-off (the polygon column is never parsed by pandas).
     -> export_coco_frame's dict, or None when the file cannot be read or lacks the column."""
     def native(table):
@@ -3743,11 +3828,13 @@ def export_coco_csv(input_csv_path, output_json, json_col: str = ANNOTATION_COL,
         sources = light[source_col].to_numpy() if source_col in light.columns else None
         labels = light[label_col].to_numpy() if label_col is not None else None
         return _coco_export_rows(None, n, widths, heights, sources, labels, classes, segmentation, keep_empty_images, file_names,
-                                 output_json, skipped_csv, _step_backend(backend, "coco_annotations"), stats, cells_of)
+                                 output_json, skipped_csv, _step_backend(backend, _coco_entry(segmentation)), stats, cells_of, iscrowd,
+                                 max_pixels_per_row)
 
     return _csv_route("coco_export", input_csv_path, json_col, native,
                       lambda df: export_coco_frame(df, output_json, json_col, width_col, height_col, source_col, label_col, classes,
-                                                   segmentation, keep_empty_images, file_names, skipped_csv, backend, stats))
+                                                   segmentation, keep_empty_images, file_names, skipped_csv, backend, stats, iscrowd,
+                                                   max_pixels_per_row))
 
 
 def _coco_image_suffix(images_dir: Path, stem: str, source) -> str:
@@ -3762,16 +3849,16 @@ def _coco_image_suffix(images_dir: Path, stem: str, source) -> str:
 def export_coco_from_excels(category_excels: list, output_dir: str, source_col: str = "source", label_col: str = "分类标签",
                             json_col_primary: str = BBOX_COL, json_col_fallback: str = ANNOTATION_COL, width_col: str = "width",
                             height_col: str = "height", random_seed: int = 42, class_order: Optional[list] = None,
-                            segmentation: bool = True, backend=None) -> dict:
+                            segmentation=True, backend=None, iscrowd: int = 0) -> dict:
     """<output_dir>/<dataset dir>/annotations/instances_<split>.json per category workbook and split sheet, next to the folders
     ``generate_yolo_datasets_from_excels`` writes: the same dataset directory names and classes (category id = YOLO class id
     + 1), the rows in the same shuffled order, each row's polygons that carry its label (the cell is `fallback or primary`
     with segmentation, `primary or fallback` without, as in the two tasks), file_name = the name of the image the YOLO step
     writes for the row (`_safe_image_stem(source, idx)` + the extension of an existing images/<split>/<stem>.*, else the
-    source's own, else .jpg).  Rows without a source or with a label outside the classes are left out and counted.  It
+    source's own, else .jpg).  segmentation="rle" and ``iscrowd`` are export_coco_frame's.  Rows without a source or with a label outside the classes are left out and counted.  It
     downloads nothing and writes no image.  -> dict(outputs=[paths], stats={category: {split: export_coco_frame's dict plus
     rows_without_source and rows_invalid_label}}, dataset_name_map)."""
-    be = _step_backend(backend, "coco_annotations")
+    be = _step_backend(backend, _coco_entry(segmentation))
     output_dir = Path(output_dir)
     splits = ["train", "val", "test"]
     outputs, all_stats, dataset_name_map, used_dir_names = [], {}, {}, set()
@@ -3809,7 +3896,7 @@ def export_coco_from_excels(category_excels: list, output_dir: str, source_col: 
             res = _coco_export_rows(cells_kept, len(keep), [widths[i] for i in keep] if has_size else None,
                                     [heights[i] for i in keep] if has_size else None,
                                     np.asarray([sources[i] for i in keep], object), np.asarray([labels[i] for i in keep], object),
-                                    classes, segmentation, True, names, out_path, None, be, None)
+                                    classes, segmentation, True, names, out_path, None, be, None, None, iscrowd)
             res["rows_without_source"] = len(no_source)
             res["rows_invalid_label"] = len(frame) - len(keep) - len(no_source)
             all_stats[category_name][split] = res
@@ -4420,6 +4507,116 @@ def export_masks_csv(input_csv_path, output_dir, split: str = "train", json_col:
                       lambda df: export_masks_frame(df, output_dir, split, json_col, width_col, height_col, source_col, label_col,
                                                     classes, mode, background, class_offset, order, max_pixels_per_row, batch_pixels,
                                                     png_mode, problems_csv, keep_empty_masks, be, stats))
+
+
+# =============================================================================== f8c2  run-length masks
+# Pixels from the polygons, one mask per polygon: COCO's run-length encoding of every selected polygon's own coverage, which no
+# other polygon can hide and which costs what the polygon's box holds, not what the image holds.  The rule is K23's
+# (include/dyd.h): K21's coverage, the runs in column-major order, COCO's "counts" string.  Native named-polygon
+# scan (_poly_chunk) -> K23 (csrc/k23_rle.hip) -> per polygon the string, its pixel area and pixel box.
+RLE_ACTIONS = {0: "encoded", 2: "bad_coords", 3: "too_few_points", 5: "no_raster"}
+RLE_RESULTS = ("encoded", "empty", "bad_coords", "too_few_points", "no_raster")
+_RLE_POLY_SPEC = (("row", np.int64), ("object", np.int64), ("name", object), ("class_id", np.int64), ("action", object),
+                  (("area", "x", "y", "w", "h", "runs"), np.int64))
+_RLE_ROW_SPEC = (("row", np.int64), (("width", "height"), np.float64), ("status", object), (("polygons", "encoded", "empty"), np.int64))
+
+
+class PolygonRLE:
+    """Result of polygon_rle: rows (row, width, height, status, polygons, encoded, empty), polygons (one row per selected
+    polygon: row, object, name, class_id, action, area, x, y, w, h, runs), counts (per row of `polygons` the COCO "counts" string
+    as bytes, None unless the action is encoded), sizes (per row of `polygons` COCO's [H, W], None for a row that is not
+    rasterised), per_class (class, polygons, encoded, empty, bad_coords, too_few_points, pixels), classes (names, the class id is
+    the position) and totals.  {"size": sizes[k], "counts": counts[k].decode()} is polygon k's COCO segmentation."""
+
+    def __init__(self, rows, polygons, counts, sizes, per_class, classes, totals):
+        self.rows = rows
+        self.polygons = polygons
+        self.counts = counts
+        self.sizes = sizes
+        self.per_class = per_class
+        self.classes = classes
+        self.totals = totals
+
+    def __repr__(self):
+        return f"PolygonRLE({len(self.polygons)} polygons, {self.totals})"
+
+
+def _rle_device(be, xy, pt_off, row_off, sel, W, H, max_pixels: int) -> tuple:
+    """K23 on one chunk, its row status checked against the host's (flatten.mask_rows) -> (host status, action, area, bbox,
+    run_off, text_off, text)"""
+    host_status, _ = _fl.mask_rows(W, H, max_pixels)
+    status, action, area, bbox, run_off, _, text_off, text = be.polygon_rle(xy, pt_off, np.asarray(row_off).astype(np.int32), sel, W, H,
+                                                                            max_pixels)
+    if not np.array_equal(np.asarray(status, np.uint8), host_status):
+        raise RuntimeError("the device's row status differs from the host's")
+    return (host_status, np.asarray(action, np.uint8), np.asarray(area, np.int64), np.asarray(bbox, np.int64).reshape(-1, 4),
+            np.asarray(run_off, np.int64), np.asarray(text_off, np.int64), bytes(text))
+
+
+def _rle_chunk(cells, labels, W, H, be, acc, start: int, max_pixels: int):
+    """one chunk of rows: polygon table and class ids (_tile_class_ids) -> K23 -> the row and polygon tables, strings and sizes"""
+    row_off, xy, pt_off, obj, cls, names, cid = _tile_class_ids(cells, labels, acc)
+    n = len(cells)
+    row_off = np.asarray(row_off, np.int64)
+    host_status, action, area, bbox, run_off, text_off, text = _rle_device(be, xy, pt_off, row_off, cid, W, H, max_pixels)
+    chosen = np.flatnonzero(cid >= 0)
+    prow = np.searchsorted(row_off, chosen, side="right") - 1
+    act_c, area_c = action[chosen], area[chosen]
+    result = np.asarray([RLE_ACTIONS[int(c)] for c in act_c], object) if len(chosen) else np.zeros(0, object)
+    done = act_c == 0
+    result[done & (area_c == 0)] = "empty"
+    count = lambda what: np.bincount(prow[result == what], minlength=n).astype(np.int64)   # noqa: E731
+    acc.rows.append((start + np.arange(n, dtype=np.int64), np.stack([W, H], axis=1), np.asarray(MASK_STATUS, object)[host_status],
+                     np.stack([np.bincount(prow, minlength=n).astype(np.int64), count("encoded"), count("empty")], axis=1)))
+    for p, r, ok in zip(chosen.tolist(), prow.tolist(), done.tolist()):
+        acc.counts.append(text[text_off[p]:text_off[p + 1]] if ok else None)
+        acc.sizes.append([int(H[r]), int(W[r])] if host_status[r] == 0 else None)
+    acc.results.append(result)
+    if len(chosen):
+        acc.polys.append((start + prow, obj[chosen].astype(np.int64), np.asarray(names, object)[cls[chosen]], cid[chosen].astype(np.int64),
+                          np.asarray([RLE_ACTIONS[int(c)] for c in act_c], object),
+                          np.concatenate([area_c[:, None], bbox[chosen], np.diff(run_off)[chosen][:, None]], axis=1)))
+
+
+def polygon_rle(cells, widths, heights, classes=None, labels=None, max_pixels_per_row: int = 1 << 26, backend=None,
+                stats: Optional[dict] = None, sources=None) -> PolygonRLE:
+    """One COCO run-length mask per selected polygon (see the section comment).  Polygons and classes are polygon_masks': every
+    polygon with a str name is selected, with ``labels`` (one per row) only those whose name is str(labels[i]); ``classes`` fixes
+    the ids, without it they are numbered from 0 by first appearance.  A row is encoded only when its size is usable and whole
+    and it has at most max_pixels_per_row pixels (at most 2^30).  -> PolygonRLE."""
+    be = _step_backend(backend, "polygon_rle")
+    max_pixels = _mask_int(max_pixels_per_row, "max_pixels_per_row", 1, _MASK_MAX_PIXELS)
+    cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
+    n = len(cells)
+    if classes is not None:
+        classes = list(classes)
+        if len(set(classes)) != len(classes) or not all(isinstance(c, str) for c in classes):
+            raise ValueError("classes must be distinct strings")
+    if labels is not None and len(labels) != n:
+        raise ValueError("one label per row")
+    _, W, H = _audit_sizes(widths, heights, n)
+    acc = _TileTotals(classes)
+    acc.rows, acc.counts, acc.sizes, acc.results = [], [], [], []
+    for s0, s1, chunk in _chunks(n, cells):
+        _rle_chunk(chunk, None if labels is None else labels[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, max_pixels)
+    rows = _parts_frame(acc.rows, _RLE_ROW_SPEC)
+    polygons = _parts_frame(acc.polys, _RLE_POLY_SPEC, sources)
+    names = list(acc.id_of)
+    k = polygons["class_id"].to_numpy()
+    result = np.concatenate(acc.results) if acc.results else np.zeros(0, object)
+    count = lambda what: np.bincount(k[result == what], minlength=len(names)).astype(np.int64)   # noqa: E731
+    per_class = pd.DataFrame({"class": pd.Series(names, dtype=object), "polygons": np.bincount(k, minlength=len(names)).astype(np.int64),
+                              **{c: count(c) for c in ("encoded", "empty", "bad_coords", "too_few_points")},
+                              "pixels": np.bincount(k, weights=polygons["area"].to_numpy(), minlength=len(names)).astype(np.int64)})
+    status = rows["status"].to_numpy()
+    totals = {"rows": n, **{f"rows_{s}": int((status == s).sum()) for s in MASK_STATUS}, "polygons": acc.polygons,
+              "selected": len(polygons), "unmatchable_name_polygons": acc.unmatchable, "unknown_class": acc.unknown,
+              **{r: int((result == r).sum()) for r in RLE_RESULTS}, "pixels": int(polygons["area"].sum()),
+              "runs": int(polygons["runs"].sum()), "bytes": int(sum(len(c) for c in acc.counts if c is not None)),
+              "python_cells": acc.python_cells}
+    if stats is not None:
+        stats.update(totals)
+    return PolygonRLE(rows, polygons, acc.counts, acc.sizes, per_class, names, totals)
 
 
 # =============================================================================== f8d  polygon comparison

@@ -15,6 +15,7 @@ import json
 import re
 from pathlib import Path
 
+import numpy as np
 import pandas as pd
 
 # any of  ,  ，  ;  ；  |   (reference utils.py:642 and :662 use the same class)
@@ -141,3 +142,66 @@ def _ensure_image_cached(source_url, cache_dir: Path):
     except Exception:  # noqa: BLE001
         pass
     return None
+
+
+# ---- COCO run-length masks (the polygon RLE step, K23; include/dyd.h has the definition) -------------------------------------
+def rle_string_to_runs(counts) -> np.ndarray:
+    """COCO's rleFrString: the "counts" string (str or bytes) -> its run lengths, int64"""
+    data = counts.encode("ascii") if isinstance(counts, str) else bytes(counts)
+    runs, at = [], 0
+    while at < len(data):
+        x, k, more = 0, 0, True
+        while more:
+            if at >= len(data):
+                raise ValueError("the counts string ends inside a code")
+            c = data[at] - 48
+            if not 0 <= c < 64:
+                raise ValueError(f"byte {data[at]!r} is outside the counts alphabet")
+            x |= (c & 0x1f) << (5 * k)
+            more = bool(c & 0x20)
+            at += 1
+            k += 1
+            if not more and (c & 0x10):
+                x |= -1 << (5 * k)
+        if len(runs) > 2:
+            x += runs[-2]
+        runs.append(x)
+    return np.asarray(runs, np.int64)
+
+
+def rle_runs_to_string(runs) -> bytes:
+    """COCO's rleToString: run lengths -> the "counts" string as bytes (every byte lies in 48..111)"""
+    runs = [int(v) for v in np.asarray(runs).reshape(-1).tolist()]
+    out = bytearray()
+    for i, c in enumerate(runs):
+        x = c - runs[i - 2] if i > 2 else c
+        more = True
+        while more:
+            b = x & 0x1f
+            x >>= 5
+            more = x != -1 if b & 0x10 else x != 0
+            out.append((b | 0x20 if more else b) + 48)
+    return bytes(out)
+
+
+def rle_to_mask(counts, size) -> np.ndarray:
+    """A COCO run-length mask as a bool array [H, W].  ``counts`` is the "counts" string (str or bytes) or an array of run
+    lengths (column-major, starting with the zeros); ``size`` is COCO's [H, W]."""
+    h, w = int(size[0]), int(size[1])
+    runs = rle_string_to_runs(counts) if isinstance(counts, (str, bytes, bytearray)) else np.asarray(counts, np.int64).reshape(-1)
+    if (runs < 0).any() or int(runs.sum()) != h * w:
+        raise ValueError(f"the runs sum to {int(runs.sum())}, the mask holds {h * w} pixels")
+    bits = np.repeat(np.arange(len(runs)) & 1, runs).astype(bool)
+    return bits.reshape(w, h).T
+
+
+def mask_to_rle(mask) -> dict:
+    """A 2-D mask (anything but 0 is covered) as COCO's {"size": [H, W], "counts": str}; rle_to_mask's inverse"""
+    mask = np.asarray(mask)
+    if mask.ndim != 2:
+        raise ValueError("mask must be 2-D")
+    h, w = mask.shape
+    flat = (mask != 0).T.reshape(-1)
+    edges = np.flatnonzero(np.diff(np.concatenate([[False], flat]).astype(np.int8)) != 0)
+    runs = np.diff(np.concatenate([[0], edges, [h * w]]))
+    return {"size": [int(h), int(w)], "counts": rle_runs_to_string(runs).decode("ascii")}

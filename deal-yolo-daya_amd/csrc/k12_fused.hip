@@ -235,6 +235,10 @@ void set_k22_strip(int v);
 void set_k22_crossings(int v);
 void set_k22_chunk(int v);
 void set_k22_grid(int v);
+void set_k23_strip(int v);
+void set_k23_band(int v);
+void set_k23_crossings(int v);
+void set_k23_grid(int v);
 void set_k6_variant(int v);
 void set_k4_capacity_shift(int v);
 void set_k8_band(int v);
@@ -486,6 +490,22 @@ int dyd_set_option(const char *key, int64_t value) {
     }
     if (!strcmp(key, "k22_grid")) {
         set_k22_grid((int)value);
+        return DYD_OK;
+    }
+    if (!strcmp(key, "k23_strip")) {   // K23's strip width, band height, list capacity and walk grid (tests reach every limit at small shapes)
+        set_k23_strip((int)value);
+        return DYD_OK;
+    }
+    if (!strcmp(key, "k23_band")) {
+        set_k23_band((int)value);
+        return DYD_OK;
+    }
+    if (!strcmp(key, "k23_crossings")) {
+        set_k23_crossings((int)value);
+        return DYD_OK;
+    }
+    if (!strcmp(key, "k23_grid")) {
+        set_k23_grid((int)value);
         return DYD_OK;
     }
     if (!strcmp(key, "k7_trace_ptr")) {   // device buffer of 8 x n_tiles u64 (0 = off)

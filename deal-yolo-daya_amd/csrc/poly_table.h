@@ -1,11 +1,11 @@
 // poly_table.h — what the host-pointer entries of the polygon steps K13 (k13_seg.hip), K14 (k14_poly_audit.hip), K16
-// (k16_coco.hip), K17 (k17_obb.hip), K20 (k20_tile.hip), K21 (k21_raster.hip) and K22 (k22_poly_compare.hip, two tables) share: the checks of a polygon table in host memory and its staging in device memory.  The polygon twin of
+// (k16_coco.hip), K17 (k17_obb.hip), K20 (k20_tile.hip), K21 (k21_raster.hip), K22 (k22_poly_compare.hip, two tables) and K23 (k23_rle.hip) share: the checks of a polygon table in host memory and its staging in device memory.  The polygon twin of
 // box_table.h; the device code the three kernels share is in k13_poly.h (polygon, clip, walk, row search) and k13_scan.h (scan,
 // print window).
 //
 // A polygon table: xy = P x (x, y) f64, pt_off = B+1 int32, row_off = N+1 int32, width / height = N f64, and per step one or
 // two columns of its own (K13 and K17: sel = B u8, class_id = N int32; K14: cls = B int32, size_status = N u8; K16: cat_id = B int32,
-// size_status = N u8; K20 (k20_tile.hip): cls = B int32; K21 (k21_raster.hip): val = B int32), which each entry checks for NULL and uploads itself.
+// size_status = N u8; K20 (k20_tile.hip): cls = B int32; K21 (k21_raster.hip): val = B int32; K23 (k23_rle.hip): sel = B int32), which each entry checks for NULL and uploads itself.
 // K19 (k19_simplify.hip) has no rows: it passes one row that holds every polygon through the same checks and stages xy and
 // pt_off with poly_column.
 #pragma once

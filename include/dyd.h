@@ -757,6 +757,53 @@ int dyd_compare_polygons_dev(const double *a_xy, const int32_t *a_pt_off, const 
                              int32_t *out_row_counts, uint64_t *out_confusion, uint64_t *out_pixel_confusion, int64_t *out_row_pixels,
                              uint32_t *out_pairs_or_null, int64_t pair_cap, void *stream);
 
+/* ---- K23: COCO RLE — the column-major run lengths of every selected polygon's own mask, as COCO's "counts" string --------
+ * The table is K21's: xy [2*P] f64 (16-B aligned), pt_off [B+1] i32, row_off [n_rows+1] i32, width / height [n_rows] f64, and
+ * sel [B] i32: sel[p] < 0: the polygon is not selected (action 255); any other value selects it.  max_pixels_per_row in 1..2^30,
+ * anything else is DYD_ERR_INVALID.  Offsets are clamped as K13 and K21 clamp them.
+ * Row status: K21's, unchanged (0 encoded, 1 no_size, 2 fractional_size, 3 too_large).
+ * Polygon action: K21's, unchanged (255 not selected, 5 no_raster, 2 bad_coords, 3 too_few_points, 0 encoded).
+ * Coverage.  cover(p, i, j) is K21's, bit for bit, of polygon p alone: no polygon hides another.
+ * Runs.  For a polygon of action 0 in an image of W x H, pixel (i, j) has the column-major index k = i * H + j.  Let
+ * t_0 < t_1 < ... < t_{m-1} be the indices k in [0, W*H) at which cover(k) != cover(k - 1), taking cover(-1) = 0.  The runs are
+ * t_0, t_1 - t_0, ..., W*H - t_{m-1}: m + 1 values, alternating zeros and ones, starting with zeros (the first run is 0 when pixel
+ * (0, 0) is covered; a polygon that covers nothing has the single run W*H; a run continues from the bottom of one column into
+ * the top of the next).  Runs are u32, every value at most 2^30.  A polygon whose action is not 0 has no runs.
+ * String.  COCO's rleToString over the runs c_0 .. c_m: for run i take x = c_i, or x = c_i - c_{i-2} when i > 2 (x is signed);
+ * repeat { b = x & 0x1f; x >>= 5 (arithmetic); more = (b & 0x10) ? x != -1 : x != 0; if (more) b |= 0x20; emit the byte b + 48 }
+ * while more.  At most 7 bytes per run.  {"size": [H, W], "counts": <the string>} is the polygon's COCO "segmentation".
+ * Area and box.  area[p] is the number of covered pixels (K21's covered[p]); bbox[4p ..] = x, y, w, h of the covered pixels (min
+ * column, min line, extent), all 0 when the area is 0.  Both are 0 unless the action is 0.
+ * out_row_status : the codes above                                        u8  [n_rows]
+ * out_action     : the codes above                                        u8  [n_polys]
+ * out_area                                                                i64 [n_polys]
+ * out_bbox                                                                i32 [4*n_polys]
+ * out_run_off    : the runs of polygon p are runs[off[p] .. off[p+1])     i64 [n_polys+1]
+ * runs                                                                    u32 [run_off[n_polys]]
+ * out_text_off   : the string of polygon p is text[off[p] .. off[p+1])    i64 [n_polys+1]
+ * text                                                                    u8  [text_off[n_polys]]
+ * dyd_polygon_rle     : host pointers; *out_runs (*out_runs_len values) and *out_text are allocated by the library (release each
+ *                       with dyd_host_free).
+ * dyd_polygon_rle_dev : device pointers.  It takes NO stream: it hands totals to the host, so it is blocking in any case; it
+ *                       runs on the library's own stream and waits for it before it returns.  A caller whose inputs were produced
+ *                       on another stream synchronises that stream first.
+ *                       out_runs_or_null == NULL only measures the runs: status, action, area, bbox, run_off and *out_run_total
+ *                       (a HOST int64); out_text_off may then be NULL.  With runs but out_text_or_null == NULL it also fills the
+ *                       runs, text_off and *out_text_total (a HOST int64).  With both it produces everything.  When runs_cap
+ *                       (values) or text_cap (bytes) is too small, DYD_ERR_RANGE is returned with the needed size in the total
+ *                       and nothing of that output written.  Output pointers may have any alignment their type allows.
+ *                       n_polys = row_off[n_rows], n_points = pt_off[n_polys].
+ * n_rows, n_polys and n_points stay below 2^31 (DYD_ERR_INVALID otherwise). */
+int dyd_polygon_rle(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *sel, const double *width,
+                    const double *height, int64_t n_rows, int64_t max_pixels_per_row, uint8_t *out_row_status, uint8_t *out_action,
+                    int64_t *out_area, int32_t *out_bbox, int64_t *out_run_off, int64_t *out_text_off, uint32_t **out_runs,
+                    int64_t *out_runs_len, uint8_t **out_text, int64_t *out_text_len);
+int dyd_polygon_rle_dev(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *sel, const double *width,
+                        const double *height, int64_t n_rows, int64_t n_polys, int64_t n_points, int64_t max_pixels_per_row,
+                        uint8_t *out_row_status, uint8_t *out_action, int64_t *out_area, int32_t *out_bbox, int64_t *out_run_off,
+                        uint32_t *out_runs_or_null, int64_t runs_cap, int64_t *out_text_off, uint8_t *out_text_or_null,
+                        int64_t text_cap, int64_t *out_run_total, int64_t *out_text_total);
+
 /* ---- native flatten / emit (HOST code, multithreaded) ------------------------------
  * Schema-specialised JSON scanner + canonical re-emitter that replaces json.loads / json.dumps inside
  * parse_and_replace_ptlist (processor.py:262-281), extract_width_height (:285-292) and extract_boxes
@@ -992,7 +1039,9 @@ void dyd_host_free(void *p);
  * largest one a workgroup stages in LDS (default and at most 1024; beyond it the points stream from HBM); <= 0: the default;
  * "k21_strip" / "k21_crossings" and "k22_strip" / "k22_crossings": the strip width (default and at most 1024) and the capacity of
  * the crossing list (256) of K21 and of K22, "k22_chunk": the B bitmaps K22 holds at a time (32), "k22_grid": a cap on K22's paint
- * workgroups (2^20); <= 0: the default, larger values are capped. */
+ * workgroups (2^20); "k23_strip" / "k23_band" / "k23_crossings" / "k23_grid": K23's strip width (default and at most 1024), the
+ * scanlines per band (default 64), the capacity of its crossing list (256) and a cap on its walk workgroups (2^20); <= 0: the
+ * default, larger values are capped. */
 int dyd_set_option(const char *key, int64_t value);
 /* measurement aid: plain streaming kernel (mode 0 copy, 1 read-only, 2 write-only, 3-5 the same non-temporal, 16 B per
  * lane) used to record the box's HBM ceiling next to the kernels' achieved GB/s; modes 6 / 7 / 8: one 8-byte word per lane

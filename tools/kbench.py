@@ -5,7 +5,8 @@ interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant
     python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k18: box comparison beside K2 and K9; k13: segmentation lines beside K7;
      k14: polygon audit; k14tier: its in-lane / wave threshold; simplify: polygon simplification (K19) beside K14 on rings of 8, 64 and 1024 points; k16: COCO annotation objects beside K13; k17: oriented-box lines beside K13; tile: tiled label lines (K20) beside K13;
      k21: label masks (K21) on many small and few large images, beside Pillow on one core; k22: polygon comparison (K22) on the same
-     two tables, interleaved with K21 over either side)
+     two tables, interleaved with K21 over either side; k23: COCO run-length masks (K23) on the same two tables, measure-only and
+     full, interleaved with K21 over the same table)
 """
 import argparse
 import json
@@ -747,6 +748,73 @@ def main():
 
         for shape in raster_shapes():
             k22_leg(*shape)
+    if "k23" in only:
+        import ctypes as C
+        # K23 (COCO run-length masks) on the k21 leg's two tables: measure-only (status, action, area, bbox, run_off) and full
+        # (runs and strings too), with the runs and the bytes that come out, interleaved with K21 over the same table as a
+        # yardstick: K21's cost follows the image, K23's the polygons' boxes.  The entry takes no stream: it runs on the library's
+        # own stream and is blocking, so it is timed by the host's clock round the call, K21 beside it in the same way.
+        import time
+        n_runs, n_text, total = C.c_int64(), C.c_int64(), C.c_int64()
+
+        def wall(fn, iters=10, warm=2):
+            for _ in range(warm):
+                fn()
+            ts = []
+            for _ in range(iters):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ts.append((time.perf_counter() - t0) * 1e3)
+            return float(np.median(ts)), float(min(ts))
+
+        def k23_leg(name, xy_, pt_, roff, nr, nb, npts, W, H):
+            w = torch.full((nr,), float(W), dtype=torch.float64, device=dev); h = torch.full((nr,), float(H), dtype=torch.float64, device=dev)
+            sel = (torch.arange(nb, device=dev, dtype=torch.int32) % 20).contiguous()
+            e = lambda n_, dt: torch.empty(max(n_, 1), dtype=dt, device=dev)                   # noqa: E731
+            status, act, area, bbox = e(nr, torch.uint8), e(nb, torch.uint8), e(nb, torch.int64), e(4 * nb, torch.int32)
+            roff_, toff_ = e(nb + 1, torch.int64), e(nb + 1, torch.int64)
+            a23 = (xy_.data_ptr(), pt_.data_ptr(), roff.data_ptr(), sel.data_ptr(), w.data_ptr(), h.data_ptr(), nr, nb, npts, 1 << 26,
+                   status.data_ptr(), act.data_ptr(), area.data_ptr(), bbox.data_ptr(), roff_.data_ptr())
+            torch.cuda.synchronize()
+            ck(L.dyd_polygon_rle_dev(*a23, None, 0, None, None, 0, C.byref(n_runs), C.byref(n_text)), "k23 measure")
+            R = n_runs.value
+            runs = e(R, torch.int32)
+            ck(L.dyd_polygon_rle_dev(*a23, runs.data_ptr(), R, toff_.data_ptr(), None, 0, C.byref(n_runs), C.byref(n_text)), "k23 runs")
+            T = n_text.value
+            text = e(T, torch.uint8)
+            val = sel + 1
+            P21 = nr * W * H
+            pix = e(P21, torch.uint8)
+            s21, p21, a21_, c21, o21 = e(nr, torch.uint8), e(nr + 1, torch.int64), e(nb, torch.uint8), e(nb, torch.int64), e(nb, torch.int64)
+            args21 = (xy_.data_ptr(), pt_.data_ptr(), roff.data_ptr(), val.data_ptr(), w.data_ptr(), h.data_ptr(), nr, nb, npts, 0, 1 << 26,
+                      s21.data_ptr(), p21.data_ptr(), a21_.data_ptr(), c21.data_ptr(), o21.data_ptr(), pix.data_ptr(), P21,
+                      C.byref(total), sp)
+            legs = {"k21": lambda: ck(L.dyd_rasterize_polygons_dev(*args21), "k21"),
+                    "k23m": lambda: ck(L.dyd_polygon_rle_dev(*a23, None, 0, None, None, 0, C.byref(n_runs), C.byref(n_text)), "k23 measure"),
+                    "k23": lambda: ck(L.dyd_polygon_rle_dev(*a23, runs.data_ptr(), R, toff_.data_ptr(), text.data_ptr(), T,
+                                                            C.byref(n_runs), C.byref(n_text)), "k23")}
+            res = {}
+            for rnd in range(2):                  # interleaved rounds (guide rule 24)
+                for key, fn in legs.items():
+                    res.setdefault(key, []).append(wall(fn))
+            med = {k: float(np.median([r[0] for r in v])) for k, v in res.items()}
+            mn = {k: min(r[1] for r in v) for k, v in res.items()}
+            assert int(area.sum().item()) == int(c21.sum().item()), "K23's areas are not K21's covered counts"
+            table_bytes = 16 * npts + 4 * (nb + 1) + 4 * nb + 4 * (nr + 1) + 16 * nr
+            small_out = nr + nb + 8 * nb + 16 * nb + 8 * (nb + 1)
+            span = bbox.view(-1, 4)
+            report(f"k23_polygon_rle_{name}_measure_only", table_bytes + small_out, med["k23m"], mn["k23m"], rows=nr, polygons=nb, runs=R,
+                   host_clock=True)
+            report(f"k23_polygon_rle_{name}", table_bytes + small_out + 8 * (nb + 1) + 4 * R + T, med["k23"], mn["k23"], rows=nr, polygons=nb,
+                   points=npts, width=W, height=H, runs=R, text_bytes=T, bytes_out=small_out + 8 * (nb + 1) + 4 * R + T,
+                   covered_pixels=int(area.sum().item()), box_columns=int(span[:, 2].sum().item()), image_pixels=P21,
+                   mask_bytes_k21=P21, k21_ms=round(med["k21"], 4), k21_min_ms=round(mn["k21"], 4),
+                   k23_over_k21=round(med["k23"] / med["k21"], 3), host_clock=True)
+
+        for shape in raster_shapes():
+            k23_leg(*shape)
     if "k14" in only:
         import ctypes as C
         # K14 (polygon audit) on K13's two shapes, and long polygons (convex rings of 256 vertices: no crossing, so the wave

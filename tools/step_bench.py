@@ -4,6 +4,7 @@ out) against the CPU port of the reference, on the same synthetic table.  Region
 SURVEY §8d: includes read_csv / flatten / H2D / kernels / D2H / emit / to_csv, so it is host-bound.
 
     python tools/step_bench.py --rows 20000
+    python tools/step_bench.py --rows 20000 --coco-rle      (only export_coco_csv: polygon lists beside segmentation="rle", one line)
 """
 import argparse
 import json
@@ -19,6 +20,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=20000)
     ap.add_argument("--skip-cpu", action="store_true")
+    ap.add_argument("--coco-rle", action="store_true", help="time export_coco_csv with polygon lists and with run-length masks, nothing else")
     args = ap.parse_args()
 
     import pandas as pd
@@ -35,6 +37,29 @@ def main():
         t0 = time.perf_counter()
         r = fn()
         return time.perf_counter() - t0, r
+
+    if args.coco_rle:
+        # export_coco_csv on the synthetic polygons (3..12 points, 20 class names, 1920 x 1080 images): K16's polygon lists
+        # beside K23's run-length masks, with the share of the run-length route that formats the objects in Python
+        with tempfile.TemporaryDirectory() as d:
+            Q = lambda n: os.path.join(d, n)  # noqa: E731
+            df.assign(width=1920, height=1080).to_csv(Q("in.csv"), index=False, encoding="utf-8-sig")
+            line = {"tool": "step_bench --coco-rle", **out, "input_csv_MB": round(os.path.getsize(Q("in.csv")) / 1e6, 1)}
+            for tag, seg in (("polygons", True), ("rle", "rle")):
+                P.export_coco_csv(Q("in.csv"), Q("warm.json"), json_col=synth.ANN_COL, segmentation=seg)
+                runs = []
+                for _ in range(3):
+                    s, res = clock(lambda: P.export_coco_csv(Q("in.csv"), Q(f"{tag}.json"), json_col=synth.ANN_COL, segmentation=seg))
+                    runs.append((s, res))
+                s, res = sorted(runs, key=lambda r: r[0])[1]
+                line[f"export_coco_csv_{tag}"] = {"s": round(s, 3), "rows_per_s": round(args.rows / s), "polygons": res["polygons"],
+                                                  "annotations": res["annotations"], "file_MB": round(os.path.getsize(Q(f"{tag}.json")) / 1e6, 1)}
+                if seg == "rle":
+                    line[f"export_coco_csv_{tag}"].update(
+                        device_step_s=round(res["rle_device_seconds"], 3), python_format_s=round(res["rle_format_seconds"], 3),
+                        python_format_share=round(res["rle_format_seconds"] / s, 3), empty=res["empty"])
+        print(json.dumps(line, ensure_ascii=False))
+        return
 
     with tempfile.TemporaryDirectory() as d:
         Q = lambda n: os.path.join(d, n)  # noqa: E731
