@@ -3585,6 +3585,104 @@ def simplify_polygons_csv(input_csv_path, output_csv_path="simplified_polygons.c
     return {**totals, "output": output_csv_path, "changes_output": changes_csv, "classes_output": classes_csv}
 
 
+# =============================================================================== f7b2 polygons keyed by class
+# What the COCO, tile, mask and run-length exports (f7c, f8b, f8c, f8c2) have in common.  The rule is in _class_ids alone: a
+# polygon is selected when its name is a str, with `labels` only where that name is str(labels[row]), with `classes` only where
+# it is listed (else it counts as unknown_class); a class id is the name's position in `classes`, without `classes` the order
+# of first appearance among the selected polygons (row order, then object order) over all chunks.  COCO's category id is the
+# class id + 1.
+class _ClassTotals:
+    """what a class-keyed export sums over its chunks: the class numbering and the counts of _class_ids, then each step's own"""
+
+    def __init__(self, classes):
+        self.given = classes is not None
+        self.id_of = {name: k for k, name in enumerate(classes)} if self.given else {}
+        self.polygons = self.unmatchable = self.unknown = self.python_cells = 0
+        self.polys, self.rows = [], []                   # parts of the polygon table (tile, mask, run-length) and the row table
+        self.tiles, self.status = [], []                 # tile
+        self.pixels = 0                                  # mask: pixels of the rasterised rows
+        self.counts, self.sizes, self.results = [], [], []   # run-length: per selected polygon
+        self.actions = np.zeros(len(COCO_ACTIONS), np.int64)  # COCO
+        self.image_parts, self.skipped, self.wrote_text = [], [], False
+        self.rle_seconds = [0.0, 0.0]                    # COCO run-length mode: the device step, the objects formatted in Python
+
+    def write_annotations(self, out, text: bytes):
+        """a COCO chunk's annotation objects to the file, a comma before all but the first"""
+        if text:
+            out.write(b"," + text if self.wrote_text else text)
+            self.wrote_text = True
+
+
+def _class_columns(df, table, json_col: str, width_col: str, height_col: str, source_col: str, label_col) -> tuple:
+    """the columns of a class-keyed export, from a DataFrame (table None) or from a fastcsv table (df None) -> (n, cells,
+    cells_of, widths, heights, sources, labels), cells or cells_of (_table_rows) being None.  A missing label_col is a
+    ValueError for a DataFrame and NotImplemented for a table, whose step then takes the pandas route and raises it there."""
+    frame = df if table is None else table.light
+    if label_col is not None and label_col not in frame.columns:
+        if table is not None:
+            return NotImplemented
+        raise ValueError(f"no column {label_col!r}")
+    if table is None:
+        cells, cells_of = df[json_col].to_numpy(), None
+        n, (widths, heights, _) = len(cells), _size_columns(df, width_col, height_col)
+    else:
+        cells = None
+        n, widths, heights, _, cells_of = _table_rows(table, json_col, width_col, height_col)
+    sources = frame[source_col].to_numpy() if source_col in frame.columns else None
+    labels = frame[label_col].to_numpy() if label_col is not None else None
+    return n, cells, cells_of, widths, heights, sources, labels
+
+
+def _class_prologue(n: int, widths, heights, labels, classes, also=None) -> tuple:
+    """the arguments every class-keyed export checks, in the order their errors win: classes, `also(class list or None)` (a
+    step's own check that belongs between the two), labels, sizes -> (status, W, H of _audit_sizes, a fresh _ClassTotals)"""
+    if classes is not None:
+        classes = list(classes)
+        if len(set(classes)) != len(classes) or not all(isinstance(c, str) for c in classes):
+            raise ValueError("classes must be distinct strings")
+    if also is not None:
+        also(classes)
+    if labels is not None and len(labels) != n:
+        raise ValueError("one label per row")
+    return (*_audit_sizes(widths, heights, n), _ClassTotals(classes))
+
+
+def _class_ids(cells, labels, acc: _ClassTotals) -> tuple:
+    """one chunk of rows: polygon table (_poly_chunk) and the class id of every polygon (0-based; -1: not selected) -> (row_off,
+    xy, pt_off, obj, cls, names, cid).  acc takes the counts, this chunk's polygons among them (a caller that numbers polygons
+    reads acc.polygons first), and, without given classes, numbers the names by first appearance."""
+    row_off, xy, pt_off, obj, cls, names, n_py = _poly_chunk(cells)
+    acc.python_cells += n_py
+    n, nb = len(cells), len(cls)
+    sel = cls >= 0
+    acc.polygons += nb
+    acc.unmatchable += int(nb - sel.sum())
+    if labels is not None and nb:                        # the dataset step's rule: the polygon's name is the row's label
+        ids = {nm: k for k, nm in enumerate(names)}
+        want = np.fromiter((ids.get(str(v), -2) for v in labels), np.int64, count=n)
+        sel &= cls == np.repeat(want, np.diff(row_off))
+    lut = np.full(len(names) + 1, -1, np.int32)          # local name id -> class id (-1: none); the last entry serves cls -1
+    if acc.given:
+        for k, nm in enumerate(names):
+            lut[k] = acc.id_of.get(nm, -1)
+    elif nb:
+        used, first = np.unique(cls[sel], return_index=True)
+        for k in used[np.argsort(first, kind="stable")].tolist():
+            lut[k] = acc.id_of.setdefault(names[k], len(acc.id_of))
+    cid = np.where(sel, lut[cls], -1).astype(np.int32) if nb else np.zeros(0, np.int32)
+    acc.unknown += int((sel & (cid < 0)).sum()) if nb else 0
+    return row_off, xy, pt_off, obj, cls, names, cid
+
+
+def _picked_polygons(table: tuple, pick, start: int) -> tuple:
+    """table: what _class_ids returns; pick: bool per polygon -> (their indices, the chunk's row of each, the first columns of a
+    polygon table: table row (start + chunk row), object, name, class id)"""
+    row_off, _, _, obj, cls, names, cid = table
+    idx = np.flatnonzero(pick)
+    prow = np.searchsorted(row_off, idx, side="right") - 1
+    return idx, prow, (start + prow, obj[idx].astype(np.int64), np.asarray(names, object)[cls[idx]], cid[idx].astype(np.int64))
+
+
 # =============================================================================== f7c  COCO export
 # One COCO instances_*.json from a table's annotation polygons, for the trainers and tools that do not read YOLO folders.  The
 # polygons, sizes and chunks are the polygon audit's (_poly_chunk, _audit_sizes); the host chooses each polygon's category id
@@ -3608,77 +3706,46 @@ def _coco_size(v: float):
     return int(v) if v == int(v) else v
 
 
-class _CocoTotals:
-    def __init__(self, classes):
-        self.given = classes is not None
-        self.cat_of = {name: k + 1 for k, name in enumerate(classes)} if self.given else {}
-        self.actions = np.zeros(len(COCO_ACTIONS), np.int64)
-        self.polygons = self.unmatchable = self.unknown = self.python_cells = self.images = 0
-        self.image_parts, self.skipped = [], []
-        self.wrote_text = False
-
-
-def _coco_category_ids(cells, labels, acc: _CocoTotals) -> tuple:
-    """one chunk of rows: polygon table (_poly_chunk) and the category id of every polygon (0: not selected) -> (row_off, xy,
-    pt_off, obj, cls, names, cat); acc takes the counts and, without given classes, numbers the names by first appearance"""
-    row_off, xy, pt_off, obj, cls, names, n_py = _poly_chunk(cells)
-    acc.python_cells += n_py
-    n, nb = len(cells), len(cls)
-    sel = cls >= 0
-    acc.unmatchable += int(nb - sel.sum())
-    if labels is not None and nb:                        # the dataset step's rule: the polygon's name is the row's label
-        ids = {nm: k for k, nm in enumerate(names)}
-        want = np.fromiter((ids.get(str(v), -2) for v in labels), np.int64, count=n)
-        sel &= cls == np.repeat(want, np.diff(row_off))
-    lut = np.zeros(len(names) + 1, np.int32)             # local name id -> category id (0: none); the last entry serves cls -1
-    if acc.given:
-        for k, nm in enumerate(names):
-            lut[k] = acc.cat_of.get(nm, 0)
-    elif nb:
-        used, first = np.unique(cls[sel], return_index=True)
-        for k in used[np.argsort(first, kind="stable")].tolist():
-            lut[k] = acc.cat_of.setdefault(names[k], len(acc.cat_of) + 1)
-    cat = np.where(sel, lut[cls], 0).astype(np.int32) if nb else np.zeros(0, np.int32)
-    acc.unknown += int((sel & (cat == 0)).sum()) if nb else 0
-    return row_off, xy, pt_off, obj, cls, names, cat
-
-
-def _coco_chunk(cells, labels, status, W, H, names_of_rows, be, acc: _CocoTotals, start: int, flags: int, keep_empty: bool, out):
-    """one chunk of rows: polygon table (_poly_chunk) -> category ids -> K16 -> the annotation text to `out`, image entries"""
-    row_off, xy, pt_off, obj, cls, names, cat = _coco_category_ids(cells, labels, acc)
-    n, nb = len(cells), len(cls)
-    action, _, kept, text = be.coco_annotations(xy, pt_off, row_off.astype(np.int32), cat, W, H, status, start + 1,
-                                                1 + acc.polygons, flags)
-    acc.polygons += nb
-    action, kept = np.asarray(action, np.uint8), np.asarray(kept)
-    chosen = cat > 0
-    acc.actions += np.bincount(action[chosen], minlength=len(COCO_ACTIONS))[:len(COCO_ACTIONS)]
-    if text:
-        out.write(b"," + text if acc.wrote_text else text)
-        acc.wrote_text = True
-    usable = (status == 0) & (W < _SEG_LIMIT) & (H < _SEG_LIMIT)
+def _coco_chunk_end(table: tuple, action, usable, kept, W, H, names_of_rows, acc: _ClassTotals, start: int, keep_empty: bool) -> int:
+    """what the polygon-list and run-length chunks share once the annotations are written: an image entry per usable row that
+    has an annotation (every usable row with keep_empty) and the selected polygons that were not printed (action >= 2)
+    -> the number of rows that are not usable"""
     for k in np.flatnonzero(usable & ((kept > 0) | keep_empty)).tolist():
         acc.image_parts.append(_coco_json({"id": start + k + 1, "width": _coco_size(float(W[k])), "height": _coco_size(float(H[k])),
                                            "file_name": names_of_rows(start + k)}))
-    bad = np.flatnonzero(chosen & (action >= 2))
+    bad, _, head = _picked_polygons(table, (table[-1] >= 0) & (action >= 2), start)
     if len(bad):
-        acc.skipped.append((start + np.searchsorted(row_off, bad, side="right") - 1, obj[bad].astype(np.int64),
-                            np.asarray(names, object)[cls[bad]], np.asarray(COCO_ACTIONS, object)[action[bad]]))
-    return int(n - usable.sum())
+        acc.skipped.append((*head[:3], np.asarray(COCO_ACTIONS, object)[action[bad]]))
+    return int(len(usable) - usable.sum())
+
+
+def _coco_chunk(cells, labels, status, W, H, names_of_rows, be, acc: _ClassTotals, start: int, flags: int, keep_empty: bool, out):
+    """one chunk of rows: polygon table and class ids (_class_ids) -> K16 -> the annotation text to `out`, image entries"""
+    first_id = 1 + acc.polygons                          # read before _class_ids adds this chunk's polygons
+    table = row_off, xy, pt_off, _, _, _, cid = _class_ids(cells, labels, acc)
+    cat = cid + 1                                        # 0: not selected
+    action, _, kept, text = be.coco_annotations(xy, pt_off, row_off.astype(np.int32), cat, W, H, status, start + 1, first_id, flags)
+    action = np.asarray(action, np.uint8)
+    acc.actions += np.bincount(action[cid >= 0], minlength=len(COCO_ACTIONS))[:len(COCO_ACTIONS)]
+    acc.write_annotations(out, text)
+    usable =(status == 0) & (W < _SEG_LIMIT) & (H < _SEG_LIMIT)
+    return _coco_chunk_end(table, action, usable, np.asarray(kept), W, H, names_of_rows, acc, start, keep_empty)
 
 
 _COCO_RLE_ACTION = np.asarray([0, 0, 2, 3, 4, 5], np.uint8)   # K23's action -> its COCO_ACTIONS entry (0 with area 0: empty)
 
 
-def _coco_rle_chunk(cells, labels, W, H, names_of_rows, be, acc: _CocoTotals, start: int, iscrowd: int, max_pixels: int,
+def _coco_rle_chunk(cells, labels, W, H, names_of_rows, be, acc: _ClassTotals, start: int, iscrowd: int, max_pixels: int,
                     keep_empty: bool, out):
-    """_coco_chunk with "segmentation" as a run-length mask: category ids as there -> K23 (polygon_rle's device step) -> one
+    """_coco_chunk with "segmentation" as a run-length mask: class ids as there -> K23 (polygon_rle's device step) -> one
     annotation object per selected polygon of action 0 that covers a pixel, its area and bbox the mask's, formatted here"""
     import time as _time
 
-    row_off, xy, pt_off, obj, cls, names, cat = _coco_category_ids(cells, labels, acc)
-    n, nb = len(cells), len(cls)
-    chosen = cat > 0
+    first_id = 1 + acc.polygons                          # read before _class_ids adds this chunk's polygons
+    table = row_off, xy, pt_off, _, _, _, cid = _class_ids(cells, labels, acc)
+    n = len(cells)
+    chosen = cid >= 0
+    cat = cid + 1
     row_off = np.asarray(row_off, np.int64)
     t0 = _time.perf_counter()
     status, act, area, bbox, _, text_off, text = _rle_device(be, xy, pt_off, row_off, np.where(chosen, cat, -1).astype(np.int32), W, H,
@@ -3695,24 +3762,12 @@ def _coco_rle_chunk(cells, labels, W, H, names_of_rows, be, acc: _CocoTotals, st
         x, y, w, h = bbox[p].tolist()
         parts.append('{"id":%d,"image_id":%d,"category_id":%d,"bbox":[%d.00,%d.00,%d.00,%d.00],"area":%d.00,"iscrowd":%d,'
                      '"segmentation":{"size":[%d,%d],"counts":%s}}'
-                     % (1 + acc.polygons + p, start + r + 1, cat[p], x, y, w, h, area[p], iscrowd, int(H[r]), int(W[r]),
+                     % (first_id + p, start + r + 1, cat[p], x, y, w, h, area[p], iscrowd, int(H[r]), int(W[r]),
                         json.dumps(text[text_off[p]:text_off[p + 1]].decode("ascii"))))
-    if parts:
-        chunk_text = ",".join(parts).encode("ascii")
-        out.write(b"," + chunk_text if acc.wrote_text else chunk_text)
-        acc.wrote_text = True
+    acc.write_annotations(out, ",".join(parts).encode("ascii"))
     acc.rle_seconds[0] += t1 - t0
     acc.rle_seconds[1] += _time.perf_counter() - t1
-    acc.polygons += nb
-    usable = status == 0
-    for k in np.flatnonzero(usable & ((kept > 0) | keep_empty)).tolist():
-        acc.image_parts.append(_coco_json({"id": start + k + 1, "width": _coco_size(float(W[k])), "height": _coco_size(float(H[k])),
-                                           "file_name": names_of_rows(start + k)}))
-    bad = np.flatnonzero(chosen & (action >= 2))
-    if len(bad):
-        acc.skipped.append((start + np.searchsorted(row_off, bad, side="right") - 1, obj[bad].astype(np.int64),
-                            np.asarray(names, object)[cls[bad]], np.asarray(COCO_ACTIONS, object)[action[bad]]))
-    return int(n - usable.sum())
+    return _coco_chunk_end(table, action, status == 0, kept, W, H, names_of_rows, acc, start, keep_empty)
 
 
 def _coco_segmentation(segmentation, iscrowd, max_pixels_per_row) -> tuple:
@@ -3726,26 +3781,23 @@ def _coco_segmentation(segmentation, iscrowd, max_pixels_per_row) -> tuple:
     return True, int(iscrowd), _mask_int(max_pixels_per_row, "max_pixels_per_row", 1, 1 << 30)
 
 
-def _coco_export_rows(cells, n, widths, heights, sources, labels, classes, segmentation, keep_empty_images, file_names,
-                      output_json, skipped_csv, be, stats, cells_of=None, iscrowd: int = 0, max_pixels_per_row: int = 1 << 26) -> dict:
+def _coco_export_rows(cols: tuple, classes, segmentation, keep_empty_images, file_names, output_json, skipped_csv, be, stats,
+                      iscrowd: int = 0, max_pixels_per_row: int = 1 << 26) -> dict:
+    """cols: _class_columns' tuple"""
     rle, iscrowd, max_pixels = _coco_segmentation(segmentation, iscrowd, max_pixels_per_row)
-    if classes is not None:
-        classes = list(classes)
-        if len(set(classes)) != len(classes) or not all(isinstance(c, str) for c in classes):
-            raise ValueError("classes must be distinct strings")
-    if file_names is not None and len(file_names) != n:
-        raise ValueError("file_names must hold one name per row")
-    if labels is not None and len(labels) != n:
-        raise ValueError("one label per row")
-    status, W, H = _audit_sizes(widths, heights, n)
+    n, cells, cells_of, widths, heights, sources, labels = cols
+
+    def check_file_names(_):
+        if file_names is not None and len(file_names) != n:
+            raise ValueError("file_names must hold one name per row")
+
+    status, W, H, acc = _class_prologue(n, widths, heights, labels, classes, check_file_names)
     if file_names is not None:
         name_of = lambda i: str(file_names[i])                            # noqa: E731
     elif sources is not None:
         name_of = lambda i: str(sources[i])                               # noqa: E731
     else:
         name_of = str
-    acc = _CocoTotals(classes)
-    acc.rle_seconds = [0.0, 0.0]                         # run-length mode: the device step, the objects formatted in Python
     flags = 1 if segmentation else 0
     output_json = str(output_json)
     if os.path.dirname(output_json):
@@ -3761,7 +3813,7 @@ def _coco_export_rows(cells, n, widths, heights, sources, labels, classes, segme
                 continue
             no_size += _coco_chunk(chunk, None if labels is None else labels[s0:s1], status[s0:s1], W[s0:s1], H[s0:s1], name_of, be,
                                    acc, s0, flags, bool(keep_empty_images), out)
-        categories = [{"id": k, "name": nm, "supercategory": ""} for nm, k in acc.cat_of.items()]
+        categories = [{"id": k + 1, "name": nm, "supercategory": ""} for nm, k in acc.id_of.items()]
         out.write(b'],"images":[' + b",".join(acc.image_parts) + b'],"categories":[' +
                   b",".join(_coco_json(c) for c in categories) + b"]}")
     os.replace(tmp, output_json)
@@ -3804,14 +3856,9 @@ def export_coco_frame(df: pd.DataFrame, output_json, json_col: str = ANNOTATION_
     COCO_ACTIONS entry over the selected polygons, unmatchable_name_polygons, unknown_class, annotations, categories,
     python_cells, output, skipped_output)."""
     be = _step_backend(backend, _coco_entry(segmentation))
-    if label_col is not None and label_col not in df.columns:
-        raise ValueError(f"no column {label_col!r}")
-    cells = df[json_col].to_numpy()
-    widths, heights, _ = _size_columns(df, width_col, height_col)
-    sources = df[source_col].to_numpy() if source_col in df.columns else None
-    labels = df[label_col].to_numpy() if label_col is not None else None
-    return _coco_export_rows(cells, len(cells), widths, heights, sources, labels, classes, segmentation, keep_empty_images,
-                             file_names, output_json, skipped_csv, be, stats, None, iscrowd, max_pixels_per_row)
+    cols = _class_columns(df, None, json_col, width_col, height_col, source_col, label_col)
+    return _coco_export_rows(cols, classes, segmentation, keep_empty_images, file_names, output_json, skipped_csv, be, stats,
+                             iscrowd, max_pixels_per_row)
 
 
 def export_coco_csv(input_csv_path, output_json, json_col: str = ANNOTATION_COL, width_col: str = "width",
@@ -3821,15 +3868,11 @@ def export_coco_csv(input_csv_path, output_json, json_col: str = ANNOTATION_COL,
     """CSV -> COCO instances file, export_coco_frame on the native CSV hand-off (the polygon column is never parsed by pandas).
     -> export_coco_frame's dict, or None when the file cannot be read or lacks the column."""
     def native(table):
-        light = table.light
-        if label_col is not None and label_col not in light.columns:
-            return NotImplemented                        # the pandas route raises export_coco_frame's error
-        n, widths, heights, _, cells_of = _table_rows(table, json_col, width_col, height_col)
-        sources = light[source_col].to_numpy() if source_col in light.columns else None
-        labels = light[label_col].to_numpy() if label_col is not None else None
-        return _coco_export_rows(None, n, widths, heights, sources, labels, classes, segmentation, keep_empty_images, file_names,
-                                 output_json, skipped_csv, _step_backend(backend, _coco_entry(segmentation)), stats, cells_of, iscrowd,
-                                 max_pixels_per_row)
+        cols = _class_columns(None, table, json_col, width_col, height_col, source_col, label_col)
+        if cols is NotImplemented:
+            return cols                                  # the pandas route raises export_coco_frame's error
+        return _coco_export_rows(cols, classes, segmentation, keep_empty_images, file_names, output_json, skipped_csv,
+                                 _step_backend(backend, _coco_entry(segmentation)), stats, iscrowd, max_pixels_per_row)
 
     return _csv_route("coco_export", input_csv_path, json_col, native,
                       lambda df: export_coco_frame(df, output_json, json_col, width_col, height_col, source_col, label_col, classes,
@@ -3893,10 +3936,10 @@ def export_coco_from_excels(category_excels: list, output_dir: str, source_col: 
             cells_kept[:] = [cells[i] for i in keep]
             has_size = width_col in columns and height_col in columns
             out_path = dataset_dir / "annotations" / f"instances_{split}.json"
-            res = _coco_export_rows(cells_kept, len(keep), [widths[i] for i in keep] if has_size else None,
-                                    [heights[i] for i in keep] if has_size else None,
-                                    np.asarray([sources[i] for i in keep], object), np.asarray([labels[i] for i in keep], object),
-                                    classes, segmentation, True, names, out_path, None, be, None, None, iscrowd)
+            cols = (len(keep), cells_kept, None, [widths[i] for i in keep] if has_size else None,
+                    [heights[i] for i in keep] if has_size else None, np.asarray([sources[i] for i in keep], object),
+                    np.asarray([labels[i] for i in keep], object))
+            res = _coco_export_rows(cols, classes, segmentation, True, names, out_path, None, be, None, iscrowd)
             res["rows_without_source"] = len(no_source)
             res["rows_invalid_label"] = len(frame) - len(keep) - len(no_source)
             all_stats[category_name][split] = res
@@ -3963,44 +4006,9 @@ def _tile_params(tile, overlap, step, min_visibility, task, max_tiles_per_row) -
     return tw, th, sx, sy, float(min_visibility), TILE_TASKS.index(task), int(max_tiles_per_row)
 
 
-class _TileTotals:
-    def __init__(self, classes):
-        self.given = classes is not None
-        self.id_of = {name: k for k, name in enumerate(classes)} if self.given else {}
-        self.polygons = self.unmatchable = self.unknown = self.python_cells = 0
-        self.tiles, self.polys, self.status = [], [], []
-
-
-def _tile_class_ids(cells, labels, acc) -> tuple:
-    """one chunk of rows: polygon table (_poly_chunk) and the class id of every polygon (export_coco_frame's selection, 0-based;
-    -1: not selected) -> (row_off, xy, pt_off, obj, cls, names, cid).  acc (a _TileTotals) takes the counts and, without given
-    classes, numbers the names by first appearance."""
-    row_off, xy, pt_off, obj, cls, names, n_py = _poly_chunk(cells)
-    acc.python_cells += n_py
-    n, nb = len(cells), len(cls)
-    sel = cls >= 0
-    acc.polygons += nb
-    acc.unmatchable += int(nb - sel.sum())
-    if labels is not None and nb:                        # the dataset step's rule: the polygon's name is the row's label
-        ids = {nm: k for k, nm in enumerate(names)}
-        want = np.fromiter((ids.get(str(v), -2) for v in labels), np.int64, count=n)
-        sel &= cls == np.repeat(want, np.diff(row_off))
-    lut = np.full(len(names) + 1, -1, np.int32)          # local name id -> class id (-1: none); the last entry serves cls -1
-    if acc.given:
-        for k, nm in enumerate(names):
-            lut[k] = acc.id_of.get(nm, -1)
-    elif nb:
-        used, first = np.unique(cls[sel], return_index=True)
-        for k in used[np.argsort(first, kind="stable")].tolist():
-            lut[k] = acc.id_of.setdefault(names[k], len(acc.id_of))
-    cid = np.where(sel, lut[cls], -1).astype(np.int32) if nb else np.zeros(0, np.int32)
-    acc.unknown += int((sel & (cid < 0)).sum()) if nb else 0
-    return row_off, xy, pt_off, obj, cls, names, cid
-
-
-def _tile_chunk(cells, labels, W, H, be, acc: _TileTotals, start: int, params: tuple):
-    """one chunk of rows: polygon table and class ids (_tile_class_ids) -> K20 -> tile and polygon tables"""
-    row_off, xy, pt_off, obj, cls, names, cid = _tile_class_ids(cells, labels, acc)
+def _tile_chunk(cells, labels, W, H, be, acc: _ClassTotals, start: int, params: tuple):
+    """one chunk of rows: polygon table and class ids (_class_ids) -> K20 -> tile and polygon tables"""
+    table = row_off, xy, pt_off, _, _, _, cid = _class_ids(cells, labels, acc)
     tw, th, sx, sy, min_vis, mode, max_tiles = params
     status, tile_off, lines, text_off, action, written, cut, dropped, text = be.yolo_tile_lines(
         xy, pt_off, row_off.astype(np.int32), cid, W, H, tw, th, sx, sy, min_vis, mode, max_tiles)
@@ -4015,23 +4023,16 @@ def _tile_chunk(cells, labels, W, H, be, acc: _TileTotals, start: int, params: t
     texts[:] = [raw[a:b] for a, b in zip(text_off[:-1].tolist(), text_off[1:].tolist())]
     acc.status.append(status)
     acc.tiles.append((start + row, np.stack([tile, x0, y0, w, h, np.asarray(lines, np.int64)], axis=1), texts))
-    chosen = np.flatnonzero(cid >= 0)
+    chosen, _, head = _picked_polygons(table, cid >= 0, start)
     if len(chosen):
         counts = np.stack([np.asarray(a, np.int64)[chosen] for a in (written, cut, dropped)], axis=1)
-        acc.polys.append((start + np.searchsorted(row_off, chosen, side="right") - 1, obj[chosen].astype(np.int64),
-                          np.asarray(names, object)[cls[chosen]], cid[chosen].astype(np.int64),
-                          np.asarray(SEG_ACTIONS, object)[np.asarray(action, np.uint8)[chosen]], counts))
+        acc.polys.append((*head, np.asarray(SEG_ACTIONS, object)[np.asarray(action, np.uint8)[chosen]], counts))
 
 
-def _tile_rows(cells, n, widths, heights, sources, labels, classes, params, be, stats, cells_of=None) -> TileLabels:
-    if classes is not None:
-        classes = list(classes)
-        if len(set(classes)) != len(classes) or not all(isinstance(c, str) for c in classes):
-            raise ValueError("classes must be distinct strings")
-    if labels is not None and len(labels) != n:
-        raise ValueError("one label per row")
-    _, W, H = _audit_sizes(widths, heights, n)
-    acc = _TileTotals(classes)
+def _tile_rows(cols: tuple, classes, params, be, stats) -> TileLabels:
+    """cols: _class_columns' tuple"""
+    n, cells, cells_of, widths, heights, sources, labels = cols
+    _, W, H, acc = _class_prologue(n, widths, heights, labels, classes)
     for s0, s1, chunk in _chunks(n, cells, cells_of):
         _tile_chunk(chunk, None if labels is None else labels[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, params)
     tiles = _parts_frame(acc.tiles, _TILE_TABLE_SPEC)
@@ -4070,7 +4071,7 @@ def yolo_tile_label_texts(cells, widths, heights, classes=None, labels=None, til
     be = _step_backend(backend, "yolo_tile_lines")
     params = _tile_params(tile, overlap, step, min_visibility, task, max_tiles_per_row)
     cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
-    return _tile_rows(cells, len(cells), widths, heights, sources, labels, classes, params, be, stats)
+    return _tile_rows((len(cells), cells, None, widths, heights, sources, labels), classes, params, be, stats)
 
 
 def _tile_write(res: TileLabels, sources, output_dir, split: str, keep_empty_tiles: bool, crop_images: bool, lost_csv) -> dict:
@@ -4139,6 +4140,15 @@ def _tile_write(res: TileLabels, sources, output_dir, split: str, keep_empty_til
             "lost_output": str(lost_csv) if lost_csv else None}
 
 
+def _tile_export(cols: tuple, classes, params, be, output_dir, split, keep_empty_tiles, crop_images, lost_csv, stats) -> dict:
+    """tile_yolo_frame and tile_yolo_csv from their columns (_class_columns' tuple) on"""
+    res = _tile_rows(cols, classes, params, be, None)
+    result = _tile_write(res, cols[5], output_dir, split, keep_empty_tiles, crop_images, lost_csv)
+    if stats is not None:
+        stats.update(result)
+    return result
+
+
 def tile_yolo_frame(df: pd.DataFrame, output_dir, split: str = "train", json_col: str = ANNOTATION_COL, width_col: str = "width",
                     height_col: str = "height", source_col: str = "source", label_col: Optional[str] = None, classes=None,
                     tile=640, overlap: float = 0.2, step=None, min_visibility: float = 0.1, task: str = "segment",
@@ -4154,17 +4164,8 @@ def tile_yolo_frame(df: pd.DataFrame, output_dir, split: str = "train", json_col
     -> dict(the totals, classes, label_files, images_written, images_missing, output_dir, manifest, lost_output)."""
     be = _step_backend(backend, "yolo_tile_lines")
     params = _tile_params(tile, overlap, step, min_visibility, task, max_tiles_per_row)
-    if label_col is not None and label_col not in df.columns:
-        raise ValueError(f"no column {label_col!r}")
-    cells = df[json_col].to_numpy()
-    widths, heights, _ = _size_columns(df, width_col, height_col)
-    sources = df[source_col].to_numpy() if source_col in df.columns else None
-    labels = df[label_col].to_numpy() if label_col is not None else None
-    res = _tile_rows(cells, len(cells), widths, heights, sources, labels, classes, params, be, None)
-    result = _tile_write(res, sources, output_dir, split, keep_empty_tiles, crop_images, lost_csv)
-    if stats is not None:
-        stats.update(result)
-    return result
+    cols = _class_columns(df, None, json_col, width_col, height_col, source_col, label_col)
+    return _tile_export(cols, classes, params, be, output_dir, split, keep_empty_tiles, crop_images, lost_csv, stats)
 
 
 def tile_yolo_csv(input_csv_path, output_dir, split: str = "train", json_col: str = ANNOTATION_COL, width_col: str = "width",
@@ -4178,17 +4179,10 @@ def tile_yolo_csv(input_csv_path, output_dir, split: str = "train", json_col: st
     params = _tile_params(tile, overlap, step, min_visibility, task, max_tiles_per_row)
 
     def native(table):
-        light = table.light
-        if label_col is not None and label_col not in light.columns:
-            return NotImplemented                        # the pandas route raises tile_yolo_frame's error
-        n, widths, heights, _, cells_of = _table_rows(table, json_col, width_col, height_col)
-        sources = light[source_col].to_numpy() if source_col in light.columns else None
-        labels = light[label_col].to_numpy() if label_col is not None else None
-        res = _tile_rows(None, n, widths, heights, sources, labels, classes, params, be, None, cells_of)
-        result = _tile_write(res, sources, output_dir, split, keep_empty_tiles, crop_images, lost_csv)
-        if stats is not None:
-            stats.update(result)
-        return result
+        cols = _class_columns(None, table, json_col, width_col, height_col, source_col, label_col)
+        if cols is NotImplemented:
+            return cols                                  # the pandas route raises tile_yolo_frame's error
+        return _tile_export(cols, classes, params, be, output_dir, split, keep_empty_tiles, crop_images, lost_csv, stats)
 
     return _csv_route("tile_yolo", input_csv_path, json_col, native,
                       lambda df: tile_yolo_frame(df, output_dir, split, json_col, width_col, height_col, source_col, label_col,
@@ -4275,11 +4269,11 @@ def _mask_action_names(codes) -> np.ndarray:
     return np.asarray([MASK_ACTIONS[int(c)] for c in codes], object) if len(codes) else np.zeros(0, object)
 
 
-def _mask_chunk(cells, labels, W, H, be, acc, start: int, params: tuple, on_masks):
-    """one chunk of rows: polygon table and class ids (_tile_class_ids) -> values and paint order -> K21 per batch of rows ->
+def _mask_chunk(cells, labels, W, H, be, acc: _ClassTotals, start: int, params: tuple, on_masks):
+    """one chunk of rows: polygon table and class ids (_class_ids) -> values and paint order -> K21 per batch of rows ->
     on_masks(first row, [mask or None per row of the batch]) and the row and polygon tables"""
     mode, background, class_offset, order, max_pixels, batch_pixels = params
-    row_off, xy, pt_off, obj, cls, names, cid = _tile_class_ids(cells, labels, acc)
+    table = row_off, xy, pt_off, _, _, _, cid = _class_ids(cells, labels, acc)
     n, nb = len(cells), len(cid)
     row_off = np.asarray(row_off, np.int64)
     too_many = np.zeros(n, bool)
@@ -4316,8 +4310,7 @@ def _mask_chunk(cells, labels, W, H, be, acc, start: int, params: tuple, on_mask
         back = np.empty(nb, np.int64)
         back[perm] = np.arange(nb)
         action, covered, owned = action[back], covered[back], owned[back]
-    chosen = np.flatnonzero(cid >= 0)
-    prow = np.searchsorted(row_off, chosen, side="right") - 1
+    chosen, prow, head = _picked_polygons(table, cid >= 0, start)
     act_c, cov_c, own_c = action[chosen], covered[chosen], owned[chosen]
     result = _mask_action_names(act_c)
     done = act_c == 0
@@ -4331,24 +4324,20 @@ def _mask_chunk(cells, labels, W, H, be, acc, start: int, params: tuple, on_mask
                      np.stack([np.bincount(prow, minlength=n).astype(np.int64), count("painted"), count("hidden"), count("empty")], axis=1)))
     acc.pixels += int(host_pixels[~too_many].sum())
     if len(chosen):
-        acc.polys.append((start + prow, obj[chosen].astype(np.int64), np.asarray(names, object)[cls[chosen]], cid[chosen].astype(np.int64),
-                          val[chosen].astype(np.int64), _mask_action_names(act_c), np.stack([cov_c, own_c], axis=1), result))
+        acc.polys.append((*head, val[chosen].astype(np.int64), _mask_action_names(act_c), np.stack([cov_c, own_c], axis=1), result))
 
 
-def _mask_rows(cells, n, widths, heights, sources, labels, classes, params, be, stats, on_masks, cells_of=None) -> PolygonMasks:
-    """the chunks of n rows through _mask_chunk -> PolygonMasks without masks (on_masks receives them as they arrive)"""
+def _mask_rows(cols: tuple, classes, params, be, stats, on_masks) -> PolygonMasks:
+    """the chunks of the rows of cols (_class_columns' tuple) through _mask_chunk -> PolygonMasks without masks (on_masks
+    receives them as they arrive)"""
     mode, background, class_offset = params[:3]
-    if classes is not None:
-        classes = list(classes)
-        if len(set(classes)) != len(classes) or not all(isinstance(c, str) for c in classes):
-            raise ValueError("classes must be distinct strings")
-        if mode == "semantic" and classes:
-            _mask_values(np.arange(len(classes)), background, class_offset)
-    if labels is not None and len(labels) != n:
-        raise ValueError("one label per row")
-    _, W, H = _audit_sizes(widths, heights, n)
-    acc = _TileTotals(classes)
-    acc.rows, acc.pixels = [], 0
+    n, cells, cells_of, widths, heights, sources, labels = cols
+
+    def check_values(given):                             # with classes every value is known up front
+        if mode == "semantic" and given:
+            _mask_values(np.arange(len(given)), background, class_offset)
+
+    _, W, H, acc = _class_prologue(n, widths, heights, labels, classes, check_values)
     for s0, s1, chunk in _chunks(n, cells, cells_of):
         _mask_chunk(chunk, None if labels is None else labels[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, params, on_masks)
     rows = _parts_frame(acc.rows, _MASK_ROW_SPEC)
@@ -4394,7 +4383,7 @@ def polygon_masks(cells, widths, heights, classes=None, labels=None, mode: str =
         if keep_masks:
             kept[first:first + len(masks)] = [None if m is None else m.copy() for m in masks]
 
-    res = _mask_rows(cells, len(cells), widths, heights, sources, labels, classes, params, be, stats, on_masks)
+    res = _mask_rows((len(cells), cells, None, widths, heights, sources, labels), classes, params, be, stats, on_masks)
     res.masks = kept
     return res
 
@@ -4409,11 +4398,12 @@ def mask_palette() -> np.ndarray:
     return pal
 
 
-def _mask_export(run, n: int, sources, output_dir, split: str, png_mode: str, problems_csv, keep_empty_masks: bool, background: int) -> dict:
-    """run(on_masks) -> PolygonMasks; the masks are written as they arrive: masks/<split>/<stem>.png, then masks_<split>.csv,
-    mask_classes.csv and the problems"""
+def _mask_export(cols: tuple, classes, params, be, output_dir, split: str, png_mode: str, problems_csv, keep_empty_masks: bool, stats) -> dict:
+    """export_masks_frame and export_masks_csv from their columns (_class_columns' tuple) on: _mask_rows, the masks written as
+    they arrive: masks/<split>/<stem>.png, then masks_<split>.csv, mask_classes.csv and the problems"""
     from PIL import Image
 
+    n, sources, background = cols[0], cols[5], params[1]
     out = Path(output_dir)
     masks_dir = out / "masks" / split
     masks_dir.mkdir(parents=True, exist_ok=True)
@@ -4432,7 +4422,7 @@ def _mask_export(run, n: int, sources, output_dir, split: str, png_mode: str, pr
             im.save(masks_dir / name)
             files[i] = f"masks/{split}/{name}"
 
-    res = run(on_masks)
+    res = _mask_rows(cols, classes, params, be, None, on_masks)
     manifest = res.rows.assign(mask_file=files)
     if sources is not None:
         manifest.insert(0, "source", np.asarray(sources, object) if n else np.zeros(0, object))
@@ -4442,9 +4432,12 @@ def _mask_export(run, n: int, sources, output_dir, split: str, png_mode: str, pr
     if problems_csv:
         poly = res.polygons
         poly[poly["result"].isin(("hidden", "empty", "bad_coords", "too_few_points"))].to_csv(problems_csv, index=False, encoding="utf-8-sig")
-    return {**res.totals, "classes": list(res.classes), "mask_files": int((files != "").sum()), "output_dir": str(out),
-            "paths": {"masks": str(masks_dir), "manifest": str(manifest_path), "classes": str(classes_path),
-                      "problems": str(problems_csv) if problems_csv else None}}
+    result = {**res.totals, "classes": list(res.classes), "mask_files": int((files != "").sum()), "output_dir": str(out),
+              "paths": {"masks": str(masks_dir), "manifest": str(manifest_path), "classes": str(classes_path),
+                        "problems": str(problems_csv) if problems_csv else None}}
+    if stats is not None:
+        stats.update(result)
+    return result
 
 
 def _mask_export_params(png_mode, mode, background, class_offset, order, max_pixels_per_row, batch_pixels) -> tuple:
@@ -4467,17 +4460,8 @@ def export_masks_frame(df: pd.DataFrame, output_dir, split: str = "train", json_
     -> dict(the totals, classes, mask_files, output_dir, paths)."""
     be = _step_backend(backend, "rasterize_polygons")
     params = _mask_export_params(png_mode, mode, background, class_offset, order, max_pixels_per_row, batch_pixels)
-    if label_col is not None and label_col not in df.columns:
-        raise ValueError(f"no column {label_col!r}")
-    cells = df[json_col].to_numpy()
-    widths, heights, _ = _size_columns(df, width_col, height_col)
-    sources = df[source_col].to_numpy() if source_col in df.columns else None
-    labels = df[label_col].to_numpy() if label_col is not None else None
-    run = lambda on_masks: _mask_rows(cells, len(cells), widths, heights, sources, labels, classes, params, be, None, on_masks)   # noqa: E731
-    result = _mask_export(run, len(cells), sources, output_dir, split, png_mode, problems_csv, keep_empty_masks, params[1])
-    if stats is not None:
-        stats.update(result)
-    return result
+    cols = _class_columns(df, None, json_col, width_col, height_col, source_col, label_col)
+    return _mask_export(cols, classes, params, be, output_dir, split, png_mode, problems_csv, keep_empty_masks, stats)
 
 
 def export_masks_csv(input_csv_path, output_dir, split: str = "train", json_col: str = ANNOTATION_COL, width_col: str = "width",
@@ -4491,17 +4475,10 @@ def export_masks_csv(input_csv_path, output_dir, split: str = "train", json_col:
     params = _mask_export_params(png_mode, mode, background, class_offset, order, max_pixels_per_row, batch_pixels)
 
     def native(table):
-        light = table.light
-        if label_col is not None and label_col not in light.columns:
-            return NotImplemented                        # the pandas route raises export_masks_frame's error
-        n, widths, heights, _, cells_of = _table_rows(table, json_col, width_col, height_col)
-        sources = light[source_col].to_numpy() if source_col in light.columns else None
-        labels = light[label_col].to_numpy() if label_col is not None else None
-        run = lambda on_masks: _mask_rows(None, n, widths, heights, sources, labels, classes, params, be, None, on_masks, cells_of)   # noqa: E731
-        result = _mask_export(run, n, sources, output_dir, split, png_mode, problems_csv, keep_empty_masks, params[1])
-        if stats is not None:
-            stats.update(result)
-        return result
+        cols = _class_columns(None, table, json_col, width_col, height_col, source_col, label_col)
+        if cols is NotImplemented:
+            return cols                                  # the pandas route raises export_masks_frame's error
+        return _mask_export(cols, classes, params, be, output_dir, split, png_mode, problems_csv, keep_empty_masks, stats)
 
     return _csv_route("export_masks", input_csv_path, json_col, native,
                       lambda df: export_masks_frame(df, output_dir, split, json_col, width_col, height_col, source_col, label_col,
@@ -4553,14 +4530,13 @@ def _rle_device(be, xy, pt_off, row_off, sel, W, H, max_pixels: int) -> tuple:
             np.asarray(run_off, np.int64), np.asarray(text_off, np.int64), bytes(text))
 
 
-def _rle_chunk(cells, labels, W, H, be, acc, start: int, max_pixels: int):
-    """one chunk of rows: polygon table and class ids (_tile_class_ids) -> K23 -> the row and polygon tables, strings and sizes"""
-    row_off, xy, pt_off, obj, cls, names, cid = _tile_class_ids(cells, labels, acc)
+def _rle_chunk(cells, labels, W, H, be, acc: _ClassTotals, start: int, max_pixels: int):
+    """one chunk of rows: polygon table and class ids (_class_ids) -> K23 -> the row and polygon tables, strings and sizes"""
+    table = row_off, xy, pt_off, _, _, _, cid = _class_ids(cells, labels, acc)
     n = len(cells)
     row_off = np.asarray(row_off, np.int64)
     host_status, action, area, bbox, run_off, text_off, text = _rle_device(be, xy, pt_off, row_off, cid, W, H, max_pixels)
-    chosen = np.flatnonzero(cid >= 0)
-    prow = np.searchsorted(row_off, chosen, side="right") - 1
+    chosen, prow, head = _picked_polygons(table, cid >= 0, start)
     act_c, area_c = action[chosen], area[chosen]
     result = np.asarray([RLE_ACTIONS[int(c)] for c in act_c], object) if len(chosen) else np.zeros(0, object)
     done = act_c == 0
@@ -4573,8 +4549,7 @@ def _rle_chunk(cells, labels, W, H, be, acc, start: int, max_pixels: int):
         acc.sizes.append([int(H[r]), int(W[r])] if host_status[r] == 0 else None)
     acc.results.append(result)
     if len(chosen):
-        acc.polys.append((start + prow, obj[chosen].astype(np.int64), np.asarray(names, object)[cls[chosen]], cid[chosen].astype(np.int64),
-                          np.asarray([RLE_ACTIONS[int(c)] for c in act_c], object),
+        acc.polys.append((*head, np.asarray([RLE_ACTIONS[int(c)] for c in act_c], object),
                           np.concatenate([area_c[:, None], bbox[chosen], np.diff(run_off)[chosen][:, None]], axis=1)))
 
 
@@ -4588,15 +4563,7 @@ def polygon_rle(cells, widths, heights, classes=None, labels=None, max_pixels_pe
     max_pixels = _mask_int(max_pixels_per_row, "max_pixels_per_row", 1, _MASK_MAX_PIXELS)
     cells = cells.to_numpy() if hasattr(cells, "to_numpy") else cells
     n = len(cells)
-    if classes is not None:
-        classes = list(classes)
-        if len(set(classes)) != len(classes) or not all(isinstance(c, str) for c in classes):
-            raise ValueError("classes must be distinct strings")
-    if labels is not None and len(labels) != n:
-        raise ValueError("one label per row")
-    _, W, H = _audit_sizes(widths, heights, n)
-    acc = _TileTotals(classes)
-    acc.rows, acc.counts, acc.sizes, acc.results = [], [], [], []
+    _, W, H, acc = _class_prologue(n, widths, heights, labels, classes)
     for s0, s1, chunk in _chunks(n, cells):
         _rle_chunk(chunk, None if labels is None else labels[s0:s1], W[s0:s1], H[s0:s1], be, acc, s0, max_pixels)
     rows = _parts_frame(acc.rows, _RLE_ROW_SPEC)

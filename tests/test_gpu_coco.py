@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import coco_ref as C
+import test_class_selection_cpu as S
 from test_coco_cpu import BE, _wound
 from test_gpu_polygon_audit import random_table as k14_table
 from test_gpu_yolo_seg import random_table as k13_table
@@ -232,3 +233,10 @@ def test_export_coco_csv_end_to_end(native, tmp_path):
     assert open(got["skipped_output"], "rb").read() == open(want["skipped_output"], "rb").read()
     drop = ("output", "skipped_output")
     assert {k: v for k, v in got.items() if k not in drop} == {k: v for k, v in want.items() if k not in drop}
+
+
+def test_four_exports_select_and_number_alike(native, tmp_path, monkeypatch):
+    """tests/test_class_selection_cpu.py's table (6 rows in 3 chunks, images of at most 64 x 64) through K16, K23, K20 and K21"""
+    monkeypatch.setattr(P, "_NATIVE_CHUNK_CELLS", 2)
+    for classes, with_labels in S.CASES:
+        S.check_steps(S.run_steps(S.table(), tmp_path, classes, with_labels, None), classes, with_labels)
