@@ -104,18 +104,21 @@ inline hipStream_t pick_stream(void *s) { return reinterpret_cast<hipStream_t>(s
         if (rc__ != DYD_OK) return rc__;                             \
     } while (0)
 
-// RAII device buffer for the host-pointer entry points: stream-ordered allocation from the device's default memory pool, whose
-// release threshold the context raises at start (dyd_context.hip), so a buffer freed on return is handed to the next call instead
-// of going back to the driver — hipFree waits for the whole device, hipFreeAsync only takes its place in the stream.
+// RAII device buffer: stream-ordered allocation from the device's default memory pool, whose release threshold the context raises
+// at start (dyd_context.hip), so freed memory stays in the pool instead of going back to the driver — hipFree waits for the whole
+// device, hipFreeAsync only takes its place in the stream.  The buffer is allocated and freed in one stream, the one its kernels
+// run on: the free is then ordered after them, and the pool hands the block to a later allocation only behind that free.
+// alloc(bytes) takes the library's stream (the host-pointer entries); alloc(bytes, st) takes exactly st, HIP's null stream included.
 struct DevBuf {
     void *p = nullptr;
     hipStream_t st = nullptr;
     ~DevBuf() {
         if (p) (void)hipFreeAsync(p, st);
     }
-    int alloc(size_t bytes, hipStream_t stream = nullptr) {
+    int alloc(size_t bytes) { return alloc(bytes, ctx().stream); }
+    int alloc(size_t bytes, hipStream_t stream) {
         if (bytes == 0) bytes = 16;
-        st = stream ? stream : ctx().stream;
+        st = stream;
         hipError_t e = hipMallocAsync(&p, bytes, st);
         if (e != hipSuccess) {
             p = nullptr;

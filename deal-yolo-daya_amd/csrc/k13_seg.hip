@@ -26,6 +26,8 @@
 #include "k13_scan.h"
 #include "poly_table.h"
 #include "round6.h"
+#include "sized_out.h"
+#include "text_window.h"
 
 namespace dyd {
 
@@ -255,48 +257,38 @@ __global__ __launch_bounds__(K13_BLOCK) void k13_print_kernel(const double *__re
     }
 }
 
+constexpr SizedName K13_TEXT{"K13", "text", "bytes", 1};
+
+// Measure, scan and print on device pointers.  `text` is asked for the buffer once the size is known (none: measure only);
+// *total_out is a host value.
 static int seg_launch(const double *xy, const int32_t *pt_off, const int32_t *row_off, const uint8_t *sel, const double *width,
                       const double *height, const int32_t *class_id, int64_t n_rows, int64_t n_polys, int64_t n_points,
-                      int64_t *text_off, uint8_t *flag, uint8_t *action, uint8_t *text, int64_t text_cap, int64_t *total_out,
-                      hipStream_t st) {
+                      int64_t *text_off, uint8_t *flag, uint8_t *action, SizedOut &text, int64_t *total_out, hipStream_t st) {
     const int64_t n_parts = k13_scan_parts(n_rows);
     const size_t rel_bytes = 8 * (size_t)max(n_polys, (int64_t)1), m_bytes = 4 * (size_t)max(n_polys, (int64_t)1);
     const size_t part_bytes = 8 * (size_t)n_parts;
+    ScratchLease lease(st);
     void *scr = nullptr;
-    int rc = get_scratch(rel_bytes + part_bytes + m_bytes, &scr, st);
+    int rc = lease.get(rel_bytes + part_bytes + m_bytes, &scr);
     if (rc) return rc;
     int64_t *rel = static_cast<int64_t *>(scr), *part = rel + rel_bytes / 8;
     int32_t *mcount = reinterpret_cast<int32_t *>(part + n_parts);
     hipLaunchKernelGGL(k13_measure_kernel, dim3((unsigned)ceil_div(n_rows, (int64_t)K13_BLOCK)), dim3(K13_BLOCK), 0, st, xy, pt_off,
                        row_off, sel, width, height, class_id, n_rows, n_polys, n_points, text_off, flag, action, rel, mcount);
     k13_scan_inclusive(text_off + 1, n_rows, part, st);
-    DYD_HIP(hipGetLastError());
     int64_t total = 0;
-    DYD_HIP(hipMemcpyAsync(&total, text_off + n_rows, 8, hipMemcpyDeviceToHost, st));
-    DYD_HIP(hipStreamSynchronize(st));
+    if ((rc = read_totals("K13", "the measure step", {{&total, text_off + n_rows}}, st))) return rc;
     if (total_out) *total_out = total;
-    if (!text || total == 0) {
-        release_scratch(st);
-        return DYD_OK;
-    }
-    if (total > text_cap) {
-        release_scratch(st);
-        set_error("K13: text buffer too small (%lld bytes needed, %lld given)", (long long)total, (long long)text_cap);
-        return DYD_ERR_RANGE;
-    }
-    const int64_t phase = (int64_t)(reinterpret_cast<uintptr_t>(text) & 15u);
-    const int64_t n_tiles = ceil_div(total + phase, (int64_t)K13_WINDOW);
+    if (total == 0 || (rc = text.get(total)) || !text.p) return rc;
+    const TextWindows tw = text_windows(text.p, total, K13_WINDOW);
     DevBuf d_tiles;
-    if ((rc = d_tiles.alloc(16 * (size_t)n_tiles, st))) {
-        release_scratch(st);
-        return rc;
-    }
-    hipLaunchKernelGGL(k13_tile_rows_kernel, dim3((unsigned)ceil_div(n_tiles, (int64_t)K13_BLOCK)), dim3(K13_BLOCK), 0, st, text_off,
-                       n_rows, total, phase, n_tiles, d_tiles.as<int64_t>());
-    hipLaunchKernelGGL(k13_print_kernel, dim3((unsigned)n_tiles), dim3(K13_BLOCK), 0, st, xy, pt_off, row_off, width, height,
-                       class_id, n_polys, n_points, text_off, flag, action, rel, mcount, d_tiles.as<int64_t>(), total, phase, text);
+    if ((rc = d_tiles.alloc(16 * (size_t)tw.count, st))) return rc;
+    hipLaunchKernelGGL(k13_tile_rows_kernel, dim3((unsigned)ceil_div(tw.count, (int64_t)K13_BLOCK)), dim3(K13_BLOCK), 0, st, text_off,
+                       n_rows, total, tw.phase, tw.count, d_tiles.as<int64_t>());
+    hipLaunchKernelGGL(k13_print_kernel, dim3((unsigned)tw.count), dim3(K13_BLOCK), 0, st, xy, pt_off, row_off, width, height,
+                       class_id, n_polys, n_points, text_off, flag, action, rel, mcount, d_tiles.as<int64_t>(), total, tw.phase,
+                       text.as<uint8_t>());
     DYD_HIP(hipGetLastError());
-    release_scratch(st);
     return DYD_OK;
 }
 
@@ -323,8 +315,9 @@ int dyd_yolo_seg_lines_dev(const double *xy, const int32_t *pt_off, const int32_
     DYD_REQUIRE(row_off && width && height && class_id && out_flag, "null pointer");
     DYD_REQUIRE(n_polys == 0 || (pt_off && out_action), "null pointer");
     DYD_REQUIRE(n_points == 0 || xy, "null pointer");
+    SizedOut text(K13_TEXT, out_text_or_null, text_cap);
     return seg_launch(xy, pt_off, row_off, sel_or_null, width, height, class_id, n_rows, n_polys, n_points, out_text_off, out_flag,
-                      out_action, out_text_or_null, text_cap, out_total, st);
+                      out_action, text, out_total, st);
 }
 
 int dyd_yolo_seg_lines(const double *xy, const int32_t *pt_off, const int32_t *row_off, const uint8_t *sel_or_null,
@@ -343,27 +336,21 @@ int dyd_yolo_seg_lines(const double *xy, const int32_t *pt_off, const int32_t *r
     if (rc) return rc;
     hipStream_t st = ctx().stream;
     PolyTableDev t;
-    DevBuf d_sel, d_cid, d_toff, d_flag, d_act, d_text;
+    DevBuf d_sel, d_cid, d_toff, d_flag, d_act;
     if ((rc = t.upload(xy, pt_off, row_off, width, height, n_rows, n_polys, n_points)) ||
         (rc = poly_column(d_sel, sel_or_null, (size_t)n_polys)) || (rc = poly_column(d_cid, class_id, 4 * (size_t)n_rows)) ||
         (rc = d_toff.alloc(8 * (size_t)(n_rows + 1))) || (rc = d_flag.alloc((size_t)n_rows)) || (rc = d_act.alloc((size_t)n_polys)))
         return rc;
     const uint8_t *sel = sel_or_null ? d_sel.as<uint8_t>() : nullptr;
-    // first launch measures (no text buffer), second prints into a buffer of exactly that size
+    SizedOut text(K13_TEXT, st);
     int64_t total = 0;
-    auto launch = [&](uint8_t *text, int64_t cap) {
-        return seg_launch(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), sel, t.w.as<double>(), t.h.as<double>(),
-                          d_cid.as<int32_t>(), n_rows, n_polys, n_points, d_toff.as<int64_t>(), d_flag.as<uint8_t>(),
-                          d_act.as<uint8_t>(), text, cap, &total, st);
-    };
-    if ((rc = launch(nullptr, 0))) return rc;
-    if (total > 0) {
-        if ((rc = d_text.alloc((size_t)total))) return rc;
-        KernelTimer timer(st);
-        if ((rc = launch(d_text.as<uint8_t>(), total))) return rc;
-        timer.finish();
-    }
-    return hand_back_text(d_text.p, total,
+    KernelTimer timer(st);
+    rc = seg_launch(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), sel, t.w.as<double>(), t.h.as<double>(),
+                    d_cid.as<int32_t>(), n_rows, n_polys, n_points, d_toff.as<int64_t>(), d_flag.as<uint8_t>(), d_act.as<uint8_t>(),
+                    text, &total, st);
+    if (rc) return rc;
+    timer.finish();
+    return hand_back_text(text.p, total,
                           {{out_text_off, d_toff.p, 8 * (size_t)(n_rows + 1)}, {out_flag, d_flag.p, (size_t)n_rows},
                            {out_action, d_act.p, (size_t)n_polys}},
                           st, out_text, out_text_len);

@@ -33,6 +33,8 @@
 #include "k13_scan.h"
 #include "poly_table.h"
 #include "round6.h"
+#include "sized_out.h"
+#include "text_window.h"
 
 namespace dyd {
 
@@ -145,13 +147,9 @@ __global__ __launch_bounds__(K16_BLOCK) void k16_row_kept_kernel(const int32_t *
 
 // ---- 3. print ------------------------------------------------------------------------------------------------
 // what a print lane writes through: text position `at`, bytes outside the window [wlo, whi) dropped
-struct K16Out {
-    uint8_t *img;
-    int64_t base, wlo, whi, at;
+struct K16Out : TextWindow {
+    int64_t at;
 
-    __device__ __forceinline__ void put(int64_t a, uint8_t c) const {
-        if (a >= wlo && a < whi) img[a - base] = c;
-    }
     __device__ __forceinline__ bool meets(int64_t len) const { return at + len > wlo && at < whi; }
     __device__ __forceinline__ void ch(uint8_t c) {
         put(at, c);
@@ -210,9 +208,8 @@ __global__ __launch_bounds__(K16_BLOCK) void k16_print_kernel(const double *__re
                                                               int64_t total, int64_t phase, uint8_t *__restrict__ text) {
     __shared__ __attribute__((aligned(16))) uint8_t img[K16_WINDOW];
     __shared__ int64_t ends[4];                // first and last polygon of the window, and their rows
-    const int64_t t = blockIdx.x;
-    const int64_t base = t * K16_WINDOW - phase;   // text byte at img[0]
-    const int64_t wlo = max(base, (int64_t)0), whi = min(base + K16_WINDOW, total);
+    const TextWindow win = text_window(img, blockIdx.x, K16_WINDOW, phase, total);
+    const int64_t wlo = win.wlo, whi = win.whi;
     if (threadIdx.x < 2) {
         // poff[n_polys] = total + 1 > whi - 1, so both answers are polygons
         const int64_t q = last_le(poff, 0, n_polys, threadIdx.x == 0 ? wlo : whi - 1);
@@ -225,7 +222,7 @@ __global__ __launch_bounds__(K16_BLOCK) void k16_print_kernel(const double *__re
         const int64_t start = poff[p], end = poff[p + 1];
         if (end == start || end <= wlo || start >= whi) continue;
         const int64_t r = last_le(row_off, ra, rb, p);
-        K16Out o{img, base, wlo, whi, start};
+        K16Out o{win, start};
         o.lit("{\"id\":");
         o.integer((uint64_t)(ann_id_base + p));
         o.lit(",\"image_id\":");
@@ -268,64 +265,45 @@ __global__ __launch_bounds__(K16_BLOCK) void k16_print_kernel(const double *__re
         o.put(end - 1, ',');
     }
     __syncthreads();
-    // stream the window out: text + base is 16-byte aligned; chunks cut by the text's ends go byte by byte
-    for (int64_t c = threadIdx.x; c < K16_WINDOW / 16; c += K16_BLOCK) {
-        const int64_t a = base + 16 * c;
-        if (a + 16 <= wlo || a >= whi) continue;
-        if (a >= wlo && a + 16 <= whi) {
-            *reinterpret_cast<uint4 *>(text + a) = *reinterpret_cast<const uint4 *>(img + 16 * c);
-        } else {
-            for (int k = 0; k < 16; ++k)
-                if (a + k >= wlo && a + k < whi) text[a + k] = img[16 * c + k];
-        }
-    }
+    win.flush<K16_WINDOW, K16_BLOCK>(text);
 }
 
-// device buffers that live from the measure step to the print step
-struct CocoWork {
-    DevBuf poff, box, part;
-};
 
-// actions, areas, row counts and the text's length (a host value: the stream is synchronised)
-static int coco_measure(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *cat_id, const double *width,
-                        const double *height, const uint8_t *size_status, int64_t n_rows, int64_t n_polys, int64_t n_points,
-                        int64_t image_id_base, int64_t ann_id_base, uint32_t flags, uint8_t *out_action, double *out_area,
-                        int32_t *out_row_kept, CocoWork &w, int64_t *total, hipStream_t st) {
-    *total = 0;
+constexpr SizedName K16_TEXT{"K16", "text", "bytes", 1};
+
+// Measure, scan and print on device pointers.  `text` is asked for the buffer once the size is known (none: measure only);
+// *total_out is a host value.
+static int coco_launch(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *cat_id, const double *width,
+                       const double *height, const uint8_t *size_status, int64_t n_rows, int64_t n_polys, int64_t n_points,
+                       int64_t image_id_base, int64_t ann_id_base, uint32_t flags, uint8_t *out_action, double *out_area,
+                       int32_t *out_row_kept, SizedOut &text, int64_t *total_out, hipStream_t st) {
+    *total_out = 0;
     if (n_rows == 0) return DYD_OK;
     if (n_polys == 0) {
         DYD_HIP(hipMemsetAsync(out_row_kept, 0, 4 * (size_t)n_rows, st));
         return DYD_OK;
     }
+    DevBuf d_poff, d_box, d_part;
     int rc;
-    if ((rc = w.poff.alloc(8 * (size_t)(n_polys + 1), st)) || (rc = w.box.alloc(32 * (size_t)n_polys, st)) ||
-        (rc = w.part.alloc(8 * (size_t)k13_scan_parts(n_polys), st)))
+    if ((rc = d_poff.alloc(8 * (size_t)(n_polys + 1), st)) || (rc = d_box.alloc(32 * (size_t)n_polys, st)) ||
+        (rc = d_part.alloc(8 * (size_t)k13_scan_parts(n_polys), st)))
         return rc;
-    int64_t *poff = w.poff.as<int64_t>();
+    int64_t *poff = d_poff.as<int64_t>();
     hipLaunchKernelGGL(k16_measure_kernel, dim3((unsigned)ceil_div(n_polys, (int64_t)K16_BLOCK)), dim3(K16_BLOCK), 0, st, xy, pt_off,
                        row_off, cat_id, width, height, size_status, n_rows, n_polys, n_points, image_id_base, ann_id_base, flags,
-                       out_action, out_area, poff, w.box.as<double>());
-    k13_scan_inclusive(poff + 1, n_polys, w.part.as<int64_t>(), st);
+                       out_action, out_area, poff, d_box.as<double>());
+    k13_scan_inclusive(poff + 1, n_polys, d_part.as<int64_t>(), st);
     hipLaunchKernelGGL(k16_row_kept_kernel, dim3((unsigned)ceil_div(n_rows, (int64_t)K16_BLOCK)), dim3(K16_BLOCK), 0, st, row_off,
                        out_action, n_rows, n_polys, out_row_kept);
-    DYD_HIP(hipGetLastError());
     int64_t sum = 0;
-    DYD_HIP(hipMemcpyAsync(&sum, poff + n_polys, 8, hipMemcpyDeviceToHost, st));
-    DYD_HIP(hipStreamSynchronize(st));
-    *total = sum > 0 ? sum - 1 : 0;           // the last object's comma is not part of the text
-    return DYD_OK;
-}
-
-static int coco_print(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *cat_id, const double *width,
-                      const double *height, int64_t n_rows, int64_t n_polys, int64_t n_points, int64_t image_id_base,
-                      int64_t ann_id_base, uint32_t flags, const double *area, CocoWork &w, int64_t total, uint8_t *text,
-                      hipStream_t st) {
-    if (total == 0) return DYD_OK;
-    const int64_t phase = (int64_t)(reinterpret_cast<uintptr_t>(text) & 15u);
-    const int64_t n_tiles = ceil_div(total + phase, (int64_t)K16_WINDOW);
-    hipLaunchKernelGGL(k16_print_kernel, dim3((unsigned)n_tiles), dim3(K16_BLOCK), 0, st, xy, pt_off, row_off, cat_id, width, height,
-                       n_rows, n_polys, n_points, image_id_base, ann_id_base, flags, area, w.poff.as<int64_t>(), w.box.as<double>(),
-                       total, phase, text);
+    if ((rc = read_totals("K16", "the measure step", {{&sum, poff + n_polys}}, st))) return rc;
+    const int64_t total = sum > 0 ? sum - 1 : 0;   // the last object's comma is not part of the text
+    *total_out = total;
+    if (total == 0 || (rc = text.get(total)) || !text.p) return rc;
+    const TextWindows tw = text_windows(text.p, total, K16_WINDOW);
+    hipLaunchKernelGGL(k16_print_kernel, dim3((unsigned)tw.count), dim3(K16_BLOCK), 0, st, xy, pt_off, row_off, cat_id, width, height,
+                       n_rows, n_polys, n_points, image_id_base, ann_id_base, flags, out_area, poff, d_box.as<double>(), total,
+                       tw.phase, text.as<uint8_t>());
     DYD_HIP(hipGetLastError());
     return DYD_OK;
 }
@@ -350,20 +328,12 @@ int dyd_coco_annotations_dev(const double *xy, const int32_t *pt_off, const int3
     DYD_REQUIRE(n_polys == 0 || (n_rows > 0 && pt_off && cat_id && out_action && out_area), "null pointer");
     DYD_REQUIRE(n_points == 0 || xy, "null pointer");
     DYD_REQUIRE((reinterpret_cast<uintptr_t>(xy) & 15) == 0, "xy must be 16-byte aligned");
-    hipStream_t st = pick_stream(stream);
-    CocoWork w;
+    SizedOut text(K16_TEXT, out_text_or_null, text_cap);
     int64_t total = 0;
-    int rc = coco_measure(xy, pt_off, row_off, cat_id, width, height, size_status, n_rows, n_polys, n_points, image_id_base,
-                          ann_id_base, flags, out_action, out_area, out_row_kept, w, &total, st);
-    if (rc) return rc;
-    if (out_total) *out_total = total;
-    if (!out_text_or_null || total == 0) return DYD_OK;
-    if (total > text_cap) {
-        set_error("K16: text buffer too small (%lld bytes needed, %lld given)", (long long)total, (long long)text_cap);
-        return DYD_ERR_RANGE;
-    }
-    return coco_print(xy, pt_off, row_off, cat_id, width, height, n_rows, n_polys, n_points, image_id_base, ann_id_base, flags,
-                      out_area, w, total, out_text_or_null, st);
+    const int rc = coco_launch(xy, pt_off, row_off, cat_id, width, height, size_status, n_rows, n_polys, n_points, image_id_base,
+                               ann_id_base, flags, out_action, out_area, out_row_kept, text, &total, pick_stream(stream));
+    if (out_total && (rc == DYD_OK || rc == DYD_ERR_RANGE)) *out_total = total;
+    return rc;
 }
 
 int dyd_coco_annotations(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *cat_id, const double *width,
@@ -385,27 +355,20 @@ int dyd_coco_annotations(const double *xy, const int32_t *pt_off, const int32_t 
     if (n_rows == 0) return DYD_OK;
     hipStream_t st = ctx().stream;
     PolyTableDev t;
-    DevBuf d_cat, d_st, d_act, d_area, d_kept, d_text;
+    DevBuf d_cat, d_st, d_act, d_area, d_kept;
     if ((rc = t.upload(xy, pt_off, row_off, width, height, n_rows, nb, np)) || (rc = poly_column(d_cat, cat_id, 4 * (size_t)nb)) ||
         (rc = poly_column(d_st, size_status, (size_t)n_rows)) || (rc = d_act.alloc((size_t)nb)) ||
         (rc = d_area.alloc(8 * (size_t)nb)) || (rc = d_kept.alloc(4 * (size_t)n_rows)))
         return rc;
-    CocoWork w;
+    SizedOut text(K16_TEXT, st);
     int64_t total = 0;
     KernelTimer timer(st);
-    rc = coco_measure(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), d_cat.as<int32_t>(), t.w.as<double>(),
-                      t.h.as<double>(), d_st.as<uint8_t>(), n_rows, nb, np, image_id_base, ann_id_base, flags, d_act.as<uint8_t>(),
-                      d_area.as<double>(), d_kept.as<int32_t>(), w, &total, st);
+    rc = coco_launch(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), d_cat.as<int32_t>(), t.w.as<double>(),
+                     t.h.as<double>(), d_st.as<uint8_t>(), n_rows, nb, np, image_id_base, ann_id_base, flags, d_act.as<uint8_t>(),
+                     d_area.as<double>(), d_kept.as<int32_t>(), text, &total, st);
     if (rc) return rc;
-    if (total > 0) {
-        if ((rc = d_text.alloc((size_t)total))) return rc;
-        rc = coco_print(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), d_cat.as<int32_t>(), t.w.as<double>(),
-                        t.h.as<double>(), n_rows, nb, np, image_id_base, ann_id_base, flags, d_area.as<double>(), w, total,
-                        d_text.as<uint8_t>(), st);
-        if (rc) return rc;
-    }
     timer.finish();
-    return hand_back_text(d_text.p, total,
+    return hand_back_text(text.p, total,
                           {{out_action, d_act.p, (size_t)nb}, {out_area, d_area.p, 8 * (size_t)nb},
                            {out_row_kept, d_kept.p, 4 * (size_t)n_rows}},
                           st, out_text, out_text_len);

@@ -34,6 +34,7 @@
 #include "k17_walk.h"
 #include "poly_table.h"
 #include "round6.h"
+#include "sized_out.h"
 
 namespace dyd {
 
@@ -174,42 +175,34 @@ __global__ __launch_bounds__(K17_BLOCK) void k17_print_kernel(const int32_t *__r
     }
 }
 
-// device buffers that live from the walk to the print step
-struct ObbWork {
-    DevBuf rel, part, corners;
-    double *cor = nullptr;                     // the caller's corners, or `corners`
-};
+constexpr SizedName K17_TEXT{"K17", "text", "bytes", 1};
 
-// actions, flags, offsets and the text's length (a host value: the stream is synchronised)
-static int obb_measure(const double *xy, const int32_t *pt_off, const int32_t *row_off, const uint8_t *sel, const double *width,
-                       const double *height, const int32_t *class_id, int64_t n_rows, int64_t n_polys, int64_t n_points,
-                       int64_t *text_off, uint8_t *flag, uint8_t *action, uint8_t *clamped, double *out_corners, ObbWork &w,
-                       int64_t *total, hipStream_t st) {
+// Walk, rows, scan and print on device pointers, n_rows > 0.  `text` is asked for the buffer once the size is known (none:
+// measure only); *total_out is a host value.
+static int obb_launch(const double *xy, const int32_t *pt_off, const int32_t *row_off, const uint8_t *sel, const double *width,
+                      const double *height, const int32_t *class_id, int64_t n_rows, int64_t n_polys, int64_t n_points,
+                      int64_t *text_off, uint8_t *flag, uint8_t *action, uint8_t *clamped, double *corners_or_null, SizedOut &text,
+                      int64_t *total_out, hipStream_t st) {
+    DevBuf d_rel, d_part, d_corners;
     int rc;
-    if ((rc = w.rel.alloc(4 * (size_t)n_polys, st)) || (rc = w.part.alloc(8 * (size_t)k13_scan_parts(n_rows), st))) return rc;
-    w.cor = out_corners;
-    if (!out_corners) {
-        if ((rc = w.corners.alloc(64 * (size_t)n_polys, st))) return rc;
-        w.cor = w.corners.as<double>();
+    if ((rc = d_rel.alloc(4 * (size_t)n_polys, st)) || (rc = d_part.alloc(8 * (size_t)k13_scan_parts(n_rows), st))) return rc;
+    double *cor = corners_or_null;             // the caller's corners, or d_corners
+    if (!cor) {
+        if ((rc = d_corners.alloc(64 * (size_t)n_polys, st))) return rc;
+        cor = d_corners.as<double>();
     }
     if (n_polys > 0)
         hipLaunchKernelGGL(k17_walk_kernel, dim3((unsigned)ceil_div(n_polys, (int64_t)K17_BLOCK)), dim3(K17_BLOCK), 0, st, xy, pt_off,
-                           row_off, sel, width, height, n_rows, n_polys, n_points, action, clamped, w.cor);
+                           row_off, sel, width, height, n_rows, n_polys, n_points, action, clamped, cor);
     hipLaunchKernelGGL(k17_rows_kernel, dim3((unsigned)ceil_div(n_rows, (int64_t)K17_BLOCK)), dim3(K17_BLOCK), 0, st, row_off, width,
-                       height, class_id, action, n_rows, n_polys, text_off, flag, w.rel.as<int32_t>());
-    k13_scan_inclusive(text_off + 1, n_rows, w.part.as<int64_t>(), st);
-    DYD_HIP(hipGetLastError());
-    DYD_HIP(hipMemcpyAsync(total, text_off + n_rows, 8, hipMemcpyDeviceToHost, st));
-    DYD_HIP(hipStreamSynchronize(st));
-    return DYD_OK;
-}
-
-static int obb_print(const int32_t *row_off, const double *width, const double *height, const int32_t *class_id, int64_t n_rows,
-                     int64_t n_polys, const int64_t *text_off, const uint8_t *flag, const uint8_t *action, ObbWork &w, int64_t total,
-                     uint8_t *text, hipStream_t st) {
-    if (total == 0) return DYD_OK;
+                       height, class_id, action, n_rows, n_polys, text_off, flag, d_rel.as<int32_t>());
+    k13_scan_inclusive(text_off + 1, n_rows, d_part.as<int64_t>(), st);
+    int64_t total = 0;
+    if ((rc = read_totals("K17", "the measure step", {{&total, text_off + n_rows}}, st))) return rc;
+    *total_out = total;
+    if (total == 0 || (rc = text.get(total)) || !text.p) return rc;
     hipLaunchKernelGGL(k17_print_kernel, dim3((unsigned)ceil_div(n_polys, (int64_t)K17_BLOCK)), dim3(K17_BLOCK), 0, st, row_off, width,
-                       height, class_id, n_rows, n_polys, text_off, flag, action, w.rel.as<int32_t>(), w.cor, total, text);
+                       height, class_id, n_rows, n_polys, text_off, flag, action, d_rel.as<int32_t>(), cor, total, text.as<uint8_t>());
     DYD_HIP(hipGetLastError());
     return DYD_OK;
 }
@@ -240,19 +233,12 @@ int dyd_yolo_obb_lines_dev(const double *xy, const int32_t *pt_off, const int32_
     DYD_REQUIRE(n_points == 0 || xy, "null pointer");
     DYD_REQUIRE((reinterpret_cast<uintptr_t>(xy) & 15) == 0, "xy must be 16-byte aligned");
     DYD_REQUIRE((reinterpret_cast<uintptr_t>(out_corners_or_null) & 15) == 0, "out_corners must be 16-byte aligned");
-    ObbWork w;
+    SizedOut text(K17_TEXT, out_text_or_null, text_cap);
     int64_t total = 0;
-    int rc = obb_measure(xy, pt_off, row_off, sel_or_null, width, height, class_id, n_rows, n_polys, n_points, out_text_off, out_flag,
-                         out_action, out_clamped, out_corners_or_null, w, &total, st);
-    if (rc) return rc;
-    if (out_total) *out_total = total;
-    if (!out_text_or_null || total == 0) return DYD_OK;
-    if (total > text_cap) {
-        set_error("K17: text buffer too small (%lld bytes needed, %lld given)", (long long)total, (long long)text_cap);
-        return DYD_ERR_RANGE;
-    }
-    return obb_print(row_off, width, height, class_id, n_rows, n_polys, out_text_off, out_flag, out_action, w, total, out_text_or_null,
-                     st);
+    const int rc = obb_launch(xy, pt_off, row_off, sel_or_null, width, height, class_id, n_rows, n_polys, n_points, out_text_off,
+                              out_flag, out_action, out_clamped, out_corners_or_null, text, &total, st);
+    if (out_total && (rc == DYD_OK || rc == DYD_ERR_RANGE)) *out_total = total;
+    return rc;
 }
 
 int dyd_yolo_obb_lines(const double *xy, const int32_t *pt_off, const int32_t *row_off, const uint8_t *sel_or_null,
@@ -273,7 +259,7 @@ int dyd_yolo_obb_lines(const double *xy, const int32_t *pt_off, const int32_t *r
     if (rc) return rc;
     hipStream_t st = ctx().stream;
     PolyTableDev t;
-    DevBuf d_sel, d_cid, d_toff, d_flag, d_act, d_cl, d_cor, d_text;
+    DevBuf d_sel, d_cid, d_toff, d_flag, d_act, d_cl, d_cor;
     if ((rc = t.upload(xy, pt_off, row_off, width, height, n_rows, n_polys, n_points)) ||
         (rc = poly_column(d_sel, sel_or_null, (size_t)n_polys)) || (rc = poly_column(d_cid, class_id, 4 * (size_t)n_rows)) ||
         (rc = d_toff.alloc(8 * (size_t)(n_rows + 1))) || (rc = d_flag.alloc((size_t)n_rows)) || (rc = d_act.alloc((size_t)n_polys)) ||
@@ -282,21 +268,15 @@ int dyd_yolo_obb_lines(const double *xy, const int32_t *pt_off, const int32_t *r
     // the caller's corners go up first, so that a polygon without a line keeps what the caller had there
     if (out_corners_or_null && (rc = poly_column(d_cor, out_corners_or_null, 64 * (size_t)n_polys))) return rc;
     const uint8_t *sel = sel_or_null ? d_sel.as<uint8_t>() : nullptr;
-    ObbWork w;
+    SizedOut text(K17_TEXT, st);
     int64_t total = 0;
     KernelTimer timer(st);
-    rc = obb_measure(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), sel, t.w.as<double>(), t.h.as<double>(),
-                     d_cid.as<int32_t>(), n_rows, n_polys, n_points, d_toff.as<int64_t>(), d_flag.as<uint8_t>(), d_act.as<uint8_t>(),
-                     d_cl.as<uint8_t>(), out_corners_or_null ? d_cor.as<double>() : nullptr, w, &total, st);
+    rc = obb_launch(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), sel, t.w.as<double>(), t.h.as<double>(),
+                    d_cid.as<int32_t>(), n_rows, n_polys, n_points, d_toff.as<int64_t>(), d_flag.as<uint8_t>(), d_act.as<uint8_t>(),
+                    d_cl.as<uint8_t>(), out_corners_or_null ? d_cor.as<double>() : nullptr, text, &total, st);
     if (rc) return rc;
-    if (total > 0) {
-        if ((rc = d_text.alloc((size_t)total))) return rc;
-        rc = obb_print(t.row.as<int32_t>(), t.w.as<double>(), t.h.as<double>(), d_cid.as<int32_t>(), n_rows, n_polys,
-                       d_toff.as<int64_t>(), d_flag.as<uint8_t>(), d_act.as<uint8_t>(), w, total, d_text.as<uint8_t>(), st);
-        if (rc) return rc;
-    }
     timer.finish();
-    return hand_back_text(d_text.p, total,
+    return hand_back_text(text.p, total,
                           {{out_text_off, d_toff.p, 8 * (size_t)(n_rows + 1)}, {out_flag, d_flag.p, (size_t)n_rows},
                            {out_action, d_act.p, (size_t)n_polys}, {out_clamped, d_cl.p, (size_t)n_polys},
                            {out_corners_or_null, d_cor.p, out_corners_or_null ? 64 * (size_t)n_polys : 0}},

@@ -23,6 +23,8 @@
 #include "k13_scan.h"
 #include "poly_table.h"
 #include "round6.h"
+#include "sized_out.h"
+#include "text_window.h"
 
 namespace dyd {
 
@@ -248,13 +250,10 @@ __global__ __launch_bounds__(K20_PRINT_BLOCK) void k20_print_kernel(const double
                                                                     uint8_t *__restrict__ text) {
     __shared__ __attribute__((aligned(16))) uint8_t img[K20_WINDOW];
     __shared__ int64_t range[2];
-    const int64_t base = (int64_t)blockIdx.x * K20_WINDOW - phase;   // text byte at img[0]
-    const int64_t wlo = max(base, (int64_t)0), whi = min(base + K20_WINDOW, total);
+    const TextWindow win = text_window(img, blockIdx.x, K20_WINDOW, phase, total);
+    const int64_t wlo = win.wlo, whi = win.whi;
     if (threadIdx.x < 2) range[threadIdx.x] = min(last_le(text_off, 0, n_tiles, threadIdx.x == 0 ? wlo : whi - 1), n_tiles - 1);
     __syncthreads();
-    auto put = [&](int64_t a, uint8_t c) {
-        if (a >= wlo && a < whi) img[a - base] = c;
-    };
     for (int64_t g = range[0] + threadIdx.x; g <= range[1]; g += K20_PRINT_BLOCK) {
         const int64_t end = text_off[g + 1];
         int64_t at = text_off[g];                  // the next line's first byte (its "\n" when it is not the tile's first)
@@ -262,37 +261,26 @@ __global__ __launch_bounds__(K20_PRINT_BLOCK) void k20_print_kernel(const double
         Tile t;
         if (!k20_tile(g, tile_off, row_off, width, height, n_rows, n_polys, tp, t)) continue;
         bool first = true;
-        auto num = [&](int64_t a, double v) {      // " %.6f" at a
-            const uint64_t d = k13_num8(v);
-            put(a, ' ');
-#pragma unroll
-            for (int k = 0; k < 8; ++k) put(a + 1 + k, (uint8_t)(d >> (8 * k)));
-        };
         auto line = [&](int64_t, int32_t cid, const TilePoly &pg, bool is_cut, const ClipWalk &w) {
             if (at >= whi) return false;
             const int cd = k13_digits(cid);
             const int64_t len = (first ? 0 : 1) + cd + (tp.mode ? 36 : 18 * (int64_t)w.m);
             if (at + len > wlo) {
                 int64_t a = at;
-                if (!first) put(a++, '\n');
-                uint32_t v = (uint32_t)cid;
-                for (int k = cd - 1; k >= 0; --k) {
-                    const uint32_t d = v / 10u;
-                    put(a + k, (uint8_t)('0' + (v - d * 10u)));
-                    v = d;
-                }
+                if (!first) win.put(a++, '\n');
+                win.class_id(a, cid, cd);
                 a += cd;
                 if (tp.mode) {
-                    num(a, (w.lx + w.hx) / 2.0 / t.tw);
-                    num(a + 9, (w.ly + w.hy) / 2.0 / t.th);
-                    num(a + 18, (w.hx - w.lx) / t.tw);
-                    num(a + 27, (w.hy - w.ly) / t.th);
+                    win.field(a, (w.lx + w.hx) / 2.0 / t.tw);
+                    win.field(a + 9, (w.ly + w.hy) / 2.0 / t.th);
+                    win.field(a + 18, (w.hx - w.lx) / t.tw);
+                    win.field(a + 27, (w.hy - w.ly) / t.th);
                 } else {
                     auto print = [&](double x, double y) {
                         if (a >= whi) return false;
                         if (a + 18 > wlo) {
-                            num(a, x / t.tw);
-                            num(a + 9, y / t.th);
+                            win.field(a, x / t.tw);
+                            win.field(a + 9, y / t.th);
                         }
                         a += 18;
                         return true;
@@ -308,17 +296,7 @@ __global__ __launch_bounds__(K20_PRINT_BLOCK) void k20_print_kernel(const double
         k20_walk_tile(t, xy, pt_off, cls, action, info, n_points, tp.min_vis, on_pair, line);
     }
     __syncthreads();
-    // stream the window out: text + base is 16-byte aligned; chunks cut by the text's ends go byte by byte
-    for (int64_t c = threadIdx.x; c < K20_WINDOW / 16; c += K20_PRINT_BLOCK) {
-        const int64_t a = base + 16 * c;
-        if (a + 16 <= wlo || a >= whi) continue;
-        if (a >= wlo && a + 16 <= whi) {
-            *reinterpret_cast<uint4 *>(text + a) = *reinterpret_cast<const uint4 *>(img + 16 * c);
-        } else {
-            for (int k = 0; k < 16; ++k)
-                if (a + k >= wlo && a + k < whi) text[a + k] = img[16 * c + k];
-        }
-    }
+    win.flush<K20_WINDOW, K20_PRINT_BLOCK>(text);
 }
 
 struct TileOut {
@@ -341,18 +319,19 @@ static int tile_params(int64_t tile_w, int64_t tile_h, int64_t step_x, int64_t s
     return DYD_OK;
 }
 
-// Steps 1 to 5 on device pointers.  get_text(total, &text, &cap) is asked for the text buffer once its size is known (text
-// NULL: measure only).  *n_tiles_out and *total_out are host values.
-template <class GetText>
+constexpr SizedName K20_TEXT{"K20", "text", "bytes", 1};
+
+// Steps 1 to 5 on device pointers.  `text` is asked for the buffer once the size is known (none: measure only).
+// *n_tiles_out and *total_out are host values.
 static int tile_launch(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *cls, const double *width,
                        const double *height, int64_t n_rows, int64_t n_polys, int64_t n_points, const TileParams &tp,
-                       int64_t tiles_cap, const TileOut &o, int64_t *n_tiles_out, int64_t *total_out, GetText get_text,
-                       hipStream_t st) {
+                       int64_t tiles_cap, const TileOut &o, int64_t *n_tiles_out, int64_t *total_out, SizedOut &text, hipStream_t st) {
     // 1. the grid
     const size_t info_bytes = 40 * (size_t)max(n_polys, (int64_t)1);
     const int64_t row_parts = k13_scan_parts(n_rows);
+    ScratchLease lease(st);
     void *scr = nullptr;
-    int rc = get_scratch(info_bytes + 8 * (size_t)row_parts, &scr, st);
+    int rc = lease.get(info_bytes + 8 * (size_t)row_parts, &scr);
     if (rc) return rc;
     double *info = static_cast<double *>(scr);
     hipLaunchKernelGGL(k20_grid_kernel, dim3((unsigned)ceil_div(n_rows, (int64_t)K20_BLOCK)), dim3(K20_BLOCK), 0, st, width, height,
@@ -363,64 +342,36 @@ static int tile_launch(const double *xy, const int32_t *pt_off, const int32_t *r
         hipLaunchKernelGGL(k20_poly_kernel, dim3((unsigned)ceil_div(n_polys, (int64_t)K20_BLOCK)), dim3(K20_BLOCK), 0, st, xy, pt_off,
                            row_off, cls, width, height, n_rows, n_polys, n_points, o.action, info, o.written, o.cut, o.dropped);
     int64_t n_tiles = 0, total = 0;
-    auto fail = [&](int code) {
-        release_scratch(st);
-        return code;
-    };
-    // the launches' status, then the copy of one int64 to the host and the wait for it: the first error of the three
-    auto read_back = [&](int64_t *dst, const int64_t *src) {
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(dst, src, 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        return e;
-    };
-    hipError_t err = read_back(&n_tiles, o.tile_off + n_rows);
-    if (err != hipSuccess) {
-        set_error("K20: the grid step failed: %s", hipGetErrorString(err));
-        return fail(err == hipErrorOutOfMemory ? DYD_ERR_OOM : DYD_ERR_HIP);
-    }
+    if ((rc = read_totals("K20", "the grid step", {{&n_tiles, o.tile_off + n_rows}}, st))) return rc;
     *n_tiles_out = n_tiles;
     *total_out = 0;
     if (n_tiles > INT32_MAX) {
         set_error("K20: %lld tiles, more than 2^31 - 1", (long long)n_tiles);
-        return fail(DYD_ERR_RANGE);
+        return DYD_ERR_RANGE;
     }
     if (n_tiles > tiles_cap) {
         set_error("K20: tile arrays too small (%lld tiles, room for %lld)", (long long)n_tiles, (long long)tiles_cap);
-        return fail(DYD_ERR_RANGE);
+        return DYD_ERR_RANGE;
     }
     if (n_tiles == 0) {
-        release_scratch(st);
         DYD_HIP(hipMemsetAsync(o.text_off, 0, 8, st));
         return DYD_OK;
     }
     // 3. and 4. measure, offsets
     DevBuf d_part;
-    if ((rc = d_part.alloc(8 * (size_t)k13_scan_parts(n_tiles), st))) return fail(rc);
+    if ((rc = d_part.alloc(8 * (size_t)k13_scan_parts(n_tiles), st))) return rc;
     hipLaunchKernelGGL(k20_measure_kernel, dim3((unsigned)ceil_div(n_tiles, (int64_t)K20_BLOCK)), dim3(K20_BLOCK), 0, st, xy, pt_off,
                        row_off, cls, width, height, n_rows, n_polys, n_points, tp, o.tile_off, n_tiles, o.action, info, o.line_count,
                        o.text_off, o.written, o.cut, o.dropped);
     k13_scan_inclusive(o.text_off + 1, n_tiles, d_part.as<int64_t>(), st);
-    err = read_back(&total, o.text_off + n_tiles);
-    if (err != hipSuccess) {
-        set_error("K20: the measure step failed: %s", hipGetErrorString(err));
-        return fail(err == hipErrorOutOfMemory ? DYD_ERR_OOM : DYD_ERR_HIP);
-    }
+    if ((rc = read_totals("K20", "the measure step", {{&total, o.text_off + n_tiles}}, st))) return rc;
     *total_out = total;
-    uint8_t *text = nullptr;
-    int64_t cap = 0;
-    if (total > 0 && (rc = get_text(total, &text, &cap))) return fail(rc);
-    if (!text || total == 0) return fail(DYD_OK);
-    if (total > cap) {
-        set_error("K20: text buffer too small (%lld bytes needed, %lld given)", (long long)total, (long long)cap);
-        return fail(DYD_ERR_RANGE);
-    }
+    if (total == 0 || (rc = text.get(total)) || !text.p) return rc;
     // 5. print
-    const int64_t phase = (int64_t)(reinterpret_cast<uintptr_t>(text) & 15u);
-    const int64_t n_windows = ceil_div(total + phase, (int64_t)K20_WINDOW);
-    hipLaunchKernelGGL(k20_print_kernel, dim3((unsigned)n_windows), dim3(K20_PRINT_BLOCK), 0, st, xy, pt_off, row_off, cls, width,
-                       height, n_rows, n_polys, n_points, tp, o.tile_off, n_tiles, o.action, info, o.text_off, total, phase, text);
-    release_scratch(st);
+    const TextWindows tw = text_windows(text.p, total, K20_WINDOW);
+    hipLaunchKernelGGL(k20_print_kernel, dim3((unsigned)tw.count), dim3(K20_PRINT_BLOCK), 0, st, xy, pt_off, row_off, cls, width,
+                       height, n_rows, n_polys, n_points, tp, o.tile_off, n_tiles, o.action, info, o.text_off, total, tw.phase,
+                       text.as<uint8_t>());
     DYD_HIP(hipGetLastError());
     return DYD_OK;
 }
@@ -460,13 +411,9 @@ int dyd_yolo_tile_lines_dev(const double *xy, const int32_t *pt_off, const int32
     DYD_REQUIRE(n_points == 0 || xy, "null pointer");
     const TileOut o{out_row_status, out_tile_off, out_tile_line_count, out_text_off, out_action, out_tiles_written, out_tiles_cut,
                     out_tiles_dropped};
-    auto get_text = [&](int64_t, uint8_t **text, int64_t *cap) {
-        *text = out_text_or_null;
-        *cap = text_cap;
-        return DYD_OK;
-    };
+    SizedOut text(K20_TEXT, out_text_or_null, text_cap);
     return tile_launch(xy, pt_off, row_off, cls, width, height, n_rows, n_polys, n_points, tp, tiles_cap, o, out_n_tiles, out_total,
-                       get_text, st);
+                       text, st);
 }
 
 int dyd_yolo_tile_lines(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *cls, const double *width,
@@ -495,7 +442,7 @@ int dyd_yolo_tile_lines(const double *xy, const int32_t *pt_off, const int32_t *
     if (rc) return rc;
     hipStream_t st = ctx().stream;
     PolyTableDev t;
-    DevBuf d_cls, d_status, d_toff, d_lines, d_xoff, d_act, d_wr, d_cut, d_drop, d_text;
+    DevBuf d_cls, d_status, d_toff, d_lines, d_xoff, d_act, d_wr, d_cut, d_drop;
     const size_t nb4 = 4 * (size_t)n_polys;
     if ((rc = t.upload(xy, pt_off, row_off, width, height, n_rows, n_polys, n_points)) || (rc = poly_column(d_cls, cls, nb4)) ||
         (rc = d_status.alloc((size_t)n_rows)) || (rc = d_toff.alloc(8 * (size_t)(n_rows + 1))) ||
@@ -504,16 +451,11 @@ int dyd_yolo_tile_lines(const double *xy, const int32_t *pt_off, const int32_t *
         return rc;
     const TileOut o{d_status.as<uint8_t>(), d_toff.as<int64_t>(), d_lines.as<int32_t>(), d_xoff.as<int64_t>(), d_act.as<uint8_t>(),
                     d_wr.as<int32_t>(), d_cut.as<int32_t>(), d_drop.as<int32_t>()};
-    auto get_text = [&](int64_t total, uint8_t **text, int64_t *cap) {
-        const int r = d_text.alloc((size_t)total);
-        *text = d_text.as<uint8_t>();
-        *cap = total;
-        return r;
-    };
+    SizedOut text(K20_TEXT, st);
     int64_t n_tiles = 0, total = 0;
     KernelTimer timer(st);
     rc = tile_launch(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), d_cls.as<int32_t>(), t.w.as<double>(),
-                     t.h.as<double>(), n_rows, n_polys, n_points, tp, tiles_cap, o, &n_tiles, &total, get_text, st);
+                     t.h.as<double>(), n_rows, n_polys, n_points, tp, tiles_cap, o, &n_tiles, &total, text, st);
     *out_n_tiles = n_tiles;
     if (rc == DYD_ERR_RANGE && n_tiles > tiles_cap && n_tiles <= INT32_MAX) {   // the caller sizes its arrays from these and calls again
         DYD_HIP(hipMemcpyAsync(out_row_status, d_status.p, (size_t)n_rows, hipMemcpyDeviceToHost, st));
@@ -522,7 +464,7 @@ int dyd_yolo_tile_lines(const double *xy, const int32_t *pt_off, const int32_t *
     }
     if (rc) return rc;
     timer.finish();
-    return hand_back_text(d_text.p, total,
+    return hand_back_text(text.p, total,
                           {{out_row_status, d_status.p, (size_t)n_rows}, {out_tile_off, d_toff.p, 8 * (size_t)(n_rows + 1)},
                            {out_tile_line_count, d_lines.p, 4 * (size_t)n_tiles}, {out_text_off, d_xoff.p, 8 * (size_t)(n_tiles + 1)},
                            {out_action, d_act.p, (size_t)n_polys}, {out_tiles_written, d_wr.p, nb4}, {out_tiles_cut, d_cut.p, nb4},

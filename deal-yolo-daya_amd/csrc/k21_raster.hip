@@ -26,6 +26,7 @@
 #include "k13_scan.h"
 #include "k21_cover.h"
 #include "poly_table.h"
+#include "sized_out.h"
 
 namespace dyd {
 
@@ -203,60 +204,44 @@ static int raster_params(int32_t background, int64_t max_pixels) {
     return DYD_OK;
 }
 
-// Steps 1 to 3 on device pointers.  get_pixels(total, &pixels, &cap) is asked for the pixel buffer once its size is known
-// (pixels NULL: measure only).  *total_out is a host value.
-template <class GetPixels>
+constexpr SizedName K21_PIXELS{"K21", "pixel", "bytes", 1};
+
+// Steps 1 to 3 on device pointers.  `pixels` is asked for the buffer once the size is known (none: measure only).
+// *total_out is a host value.
 static int raster_launch(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *val, const double *width,
                          const double *height, int64_t n_rows, int64_t n_polys, int64_t n_points, int32_t background,
-                         int64_t max_pixels, const RasterOut &o, int64_t *total_out, GetPixels get_pixels, hipStream_t st) {
+                         int64_t max_pixels, const RasterOut &o, int64_t *total_out, SizedOut &pixels, hipStream_t st) {
     const int strip = g_k21_strip, cap = g_k21_crossings;
     const size_t info_bytes = 32 * (size_t)max(n_polys, (int64_t)1), item_bytes = 8 * (size_t)(n_rows + 1);
+    ScratchLease lease(st);
     void *scr = nullptr;
-    int rc = get_scratch(info_bytes + item_bytes + 8 * (size_t)k13_scan_parts(n_rows), &scr, st);
+    int rc = lease.get(info_bytes + item_bytes + 8 * (size_t)k13_scan_parts(n_rows), &scr);
     if (rc) return rc;
     double *info = static_cast<double *>(scr);
     int64_t *item_off = reinterpret_cast<int64_t *>(info + info_bytes / 8), *part = item_off + n_rows + 1;
-    auto fail = [&](int code) {
-        release_scratch(st);
-        return code;
-    };
     hipLaunchKernelGGL(k21_rows_kernel, dim3((unsigned)ceil_div(n_rows, (int64_t)K21_BLOCK)), dim3(K21_BLOCK), 0, st, width, height,
                        n_rows, max_pixels, strip, o.row_status, o.pix_off, item_off);
     k13_scan_inclusive(o.pix_off + 1, n_rows, part, st);
     k13_scan_inclusive(item_off + 1, n_rows, part, st);   // after the first scan in the stream, so the partial sums are free again
     k21_polys(xy, pt_off, row_off, val, o.row_status, n_rows, n_polys, n_points, o.action, info, st);
     int64_t total = 0, n_items = 0;
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipMemcpyAsync(&total, o.pix_off + n_rows, 8, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipMemcpyAsync(&n_items, item_off + n_rows, 8, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    if (err != hipSuccess) {
-        set_error("K21: the row and polygon steps failed: %s", hipGetErrorString(err));
-        return fail(err == hipErrorOutOfMemory ? DYD_ERR_OOM : DYD_ERR_HIP);
-    }
+    if ((rc = read_totals("K21", "the row and polygon steps", {{&total, o.pix_off + n_rows}, {&n_items, item_off + n_rows}}, st)))
+        return rc;
     *total_out = total;
-    uint8_t *pixels = nullptr;
-    int64_t pix_cap = 0;
-    if ((rc = get_pixels(total, &pixels, &pix_cap))) return fail(rc);
-    if (!pixels) return fail(DYD_OK);
-    if (total > pix_cap) {
-        set_error("K21: pixel buffer too small (%lld bytes needed, %lld given)", (long long)total, (long long)pix_cap);
-        return fail(DYD_ERR_RANGE);
-    }
+    if ((rc = pixels.get(total)) || !pixels.p) return rc;
     if (n_polys > 0) {
         hipError_t e = hipMemsetAsync(o.covered, 0, 8 * (size_t)n_polys, st);
         if (e == hipSuccess) e = hipMemsetAsync(o.owned, 0, 8 * (size_t)n_polys, st);
         if (e != hipSuccess) {
             set_error("K21: clearing the counters failed: %s", hipGetErrorString(e));
-            return fail(DYD_ERR_HIP);
+            return DYD_ERR_HIP;
         }
     }
     if (n_items > 0)
         hipLaunchKernelGGL(k21_paint_kernel, dim3((unsigned)(n_items < K21_MAX_GRID ? n_items : K21_MAX_GRID)), dim3(kWave), 0, st, xy, pt_off, row_off, val,
                            width, height, n_rows, n_polys, n_points, (int)background, strip, cap, o.row_status, o.pix_off, item_off,
                            n_items, o.action, info, reinterpret_cast<unsigned long long *>(o.covered),
-                           reinterpret_cast<unsigned long long *>(o.owned), pixels);
-    release_scratch(st);
+                           reinterpret_cast<unsigned long long *>(o.owned), pixels.as<uint8_t>());
     DYD_HIP(hipGetLastError());
     return DYD_OK;
 }
@@ -289,13 +274,9 @@ int dyd_rasterize_polygons_dev(const double *xy, const int32_t *pt_off, const in
     DYD_REQUIRE(n_polys == 0 || !out_pixels_or_null || (out_covered && out_owned), "null pointer");
     DYD_REQUIRE(n_points == 0 || xy, "null pointer");
     const RasterOut o{out_row_status, out_pix_off, out_action, out_covered, out_owned};
-    auto get_pixels = [&](int64_t, uint8_t **pixels, int64_t *cap) {
-        *pixels = out_pixels_or_null;
-        *cap = pix_cap;
-        return DYD_OK;
-    };
+    SizedOut pixels(K21_PIXELS, out_pixels_or_null, pix_cap);
     return raster_launch(xy, pt_off, row_off, val, width, height, n_rows, n_polys, n_points, background, max_pixels_per_row, o,
-                         out_total, get_pixels, st);
+                         out_total, pixels, st);
 }
 
 int dyd_rasterize_polygons(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *val, const double *width,
@@ -319,7 +300,7 @@ int dyd_rasterize_polygons(const double *xy, const int32_t *pt_off, const int32_
     for (int64_t p = 0; p < n_polys; ++p) DYD_REQUIRE(val[p] <= 255, "val above 255");
     hipStream_t st = ctx().stream;
     PolyTableDev t;
-    DevBuf d_val, d_status, d_poff, d_act, d_cov, d_own, d_pix;
+    DevBuf d_val, d_status, d_poff, d_act, d_cov, d_own;
     const size_t nb8 = 8 * (size_t)n_polys;
     if ((rc = t.upload(xy, pt_off, row_off, width, height, n_rows, n_polys, n_points)) ||
         (rc = poly_column(d_val, val, 4 * (size_t)n_polys)) || (rc = d_status.alloc((size_t)n_rows)) ||
@@ -327,19 +308,14 @@ int dyd_rasterize_polygons(const double *xy, const int32_t *pt_off, const int32_
         (rc = d_own.alloc(nb8)))
         return rc;
     const RasterOut o{d_status.as<uint8_t>(), d_poff.as<int64_t>(), d_act.as<uint8_t>(), d_cov.as<int64_t>(), d_own.as<int64_t>()};
-    auto get_pixels = [&](int64_t total, uint8_t **pixels, int64_t *cap) {
-        const int r = d_pix.alloc((size_t)total);
-        *pixels = d_pix.as<uint8_t>();
-        *cap = total;
-        return r;
-    };
+    SizedOut pixels(K21_PIXELS, st);
     int64_t total = 0;
     KernelTimer timer(st);
     rc = raster_launch(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), d_val.as<int32_t>(), t.w.as<double>(),
-                       t.h.as<double>(), n_rows, n_polys, n_points, background, max_pixels_per_row, o, &total, get_pixels, st);
+                       t.h.as<double>(), n_rows, n_polys, n_points, background, max_pixels_per_row, o, &total, pixels, st);
     if (rc) return rc;
     timer.finish();
-    return hand_back_text(d_pix.p, total,
+    return hand_back_text(pixels.p, total,
                           {{out_row_status, d_status.p, (size_t)n_rows}, {out_pix_off, d_poff.p, 8 * (size_t)(n_rows + 1)},
                            {out_action, d_act.p, (size_t)n_polys}, {out_covered, d_cov.p, nb8}, {out_owned, d_own.p, nb8}},
                           st, out_pixels, out_pixels_len);

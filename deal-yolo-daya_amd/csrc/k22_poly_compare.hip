@@ -28,6 +28,7 @@
 #include "k18_pick.h"
 #include "k21_cover.h"
 #include "poly_table.h"
+#include "sized_out.h"
 
 namespace dyd {
 
@@ -344,39 +345,31 @@ static int compare_params(int32_t n_classes, int64_t max_pixels, int64_t max_pai
     return DYD_OK;
 }
 
-// Steps 1 to 4 on device pointers.  get_pairs(total, &pairs) is asked for the pair buffer once its size is known; it fails
-// before anything but row_status and pair_off is written.
-template <class GetPairs>
+constexpr SizedName K22_PAIRS{"K22", "pair", "elements", 4};
+
+// Steps 1 to 4 on device pointers.  `pairs` is asked for the pair buffer once its size is known; it fails before anything but
+// row_status and pair_off is written.
 static int compare_launch(const K22Table &a, const K22Table &b, const double *width, const double *height, int64_t n_rows,
                           int32_t C, double thr, int by_label, int64_t max_pixels, int64_t max_pairs, const K22Out &o,
-                          GetPairs get_pairs, hipStream_t st) {
+                          SizedOut &pairs_out, hipStream_t st) {
     const int strip = g_k22_strip, cap = g_k22_crossings, chunk = g_k22_chunk;
     const size_t info_a = 32 * (size_t)max(a.n_polys, (int64_t)1), info_b = 32 * (size_t)max(b.n_polys, (int64_t)1);
+    ScratchLease lease(st);
     void *scr = nullptr;
-    int rc = get_scratch(info_a + info_b + 8 * (size_t)(n_rows + 1) + 8 * (size_t)k13_scan_parts(n_rows), &scr, st);
+    int rc = lease.get(info_a + info_b + 8 * (size_t)(n_rows + 1) + 8 * (size_t)k13_scan_parts(n_rows), &scr);
     if (rc) return rc;
     double *inf_a = static_cast<double *>(scr), *inf_b = inf_a + info_a / 8;
     int64_t *item_off = reinterpret_cast<int64_t *>(inf_b + info_b / 8), *part = item_off + n_rows + 1;
-    auto fail = [&](int code) {
-        release_scratch(st);
-        return code;
-    };
     const dim3 row_grid((unsigned)ceil_div(n_rows, (int64_t)K22_BLOCK));
     hipLaunchKernelGGL(k22_rows_kernel, row_grid, dim3(K22_BLOCK), 0, st, width, height, a.row_off, b.row_off, n_rows, a.n_polys,
                        b.n_polys, max_pixels, max_pairs, strip, o.row_status, o.pair_off, item_off);
     k13_scan_inclusive(o.pair_off + 1, n_rows, part, st);
     k13_scan_inclusive(item_off + 1, n_rows, part, st);   // after the first scan in the stream, so the partial sums are free again
     int64_t pair_total = 0, n_items = 0;
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipMemcpyAsync(&pair_total, o.pair_off + n_rows, 8, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipMemcpyAsync(&n_items, item_off + n_rows, 8, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    if (err != hipSuccess) {
-        set_error("K22: the row step failed: %s", hipGetErrorString(err));
-        return fail(err == hipErrorOutOfMemory ? DYD_ERR_OOM : DYD_ERR_HIP);
-    }
-    uint32_t *pairs = nullptr;
-    if ((rc = get_pairs(pair_total, &pairs))) return fail(rc);
+    if ((rc = read_totals("K22", "the row step", {{&pair_total, o.pair_off + n_rows}, {&n_items, item_off + n_rows}}, st)) ||
+        (rc = pairs_out.get(pair_total)))
+        return rc;
+    uint32_t *pairs = pairs_out.as<uint32_t>();
     const size_t cells = 8 * (size_t)(C + 1) * (size_t)(C + 1);
     hipError_t e = hipMemsetAsync(o.confusion, 0, cells, st);
     if (e == hipSuccess) e = hipMemsetAsync(o.pixel_confusion, 0, cells, st);
@@ -386,7 +379,7 @@ static int compare_launch(const K22Table &a, const K22Table &b, const double *wi
     if (e == hipSuccess && b.n_polys > 0) e = hipMemsetAsync(b.pixels, 0, 8 * (size_t)b.n_polys, st);
     if (e != hipSuccess) {
         set_error("K22: clearing the counters failed: %s", hipGetErrorString(e));
-        return fail(DYD_ERR_HIP);
+        return DYD_ERR_HIP;
     }
     k21_polys(a.xy, a.pt_off, a.row_off, a.cls, o.row_status, n_rows, a.n_polys, a.n_points, a.action, inf_a, st);
     k21_polys(b.xy, b.pt_off, b.row_off, b.cls, o.row_status, n_rows, b.n_polys, b.n_points, b.action, inf_b, st);
@@ -405,7 +398,6 @@ static int compare_launch(const K22Table &a, const K22Table &b, const double *wi
     hipLaunchKernelGGL(k22_match_kernel, dim3((unsigned)(n_rows < want ? n_rows : want)), dim3(kWave), 0, st, a.row_off, a.cls,
                        a.action, a_pix, b.row_off, b.cls, b.action, b_pix, n_rows, a.n_polys, b.n_polys, C, thr, by_label,
                        o.row_status, o.pair_off, pairs, a.match, b.match, o.b_iou, a.best, b.best, o.row_counts, conf);
-    release_scratch(st);
     DYD_HIP(hipGetLastError());
     return DYD_OK;
 }
@@ -442,37 +434,10 @@ int dyd_compare_polygons_dev(const double *a_xy, const int32_t *a_pt_off, const 
     const K22Table a{a_xy, a_pt_off, a_row_off, a_cls, n_a, n_a_points, out_a_action, out_a_pixels, out_a_match, out_a_best};
     const K22Table b{b_xy, b_pt_off, b_row_off, b_cls, n_b, n_b_points, out_b_action, out_b_pixels, out_b_match, out_b_best};
     const K22Out o{out_row_status, out_pair_off, out_b_iou, out_row_counts, out_confusion, out_pixel_confusion, out_row_pixels};
-    // the pair counts when the caller keeps none: allocated and freed in the caller's stream itself, the null stream included
-    // (DevBuf would take the library's stream for it)
-    struct OwnPairs {
-        void *p = nullptr;
-        hipStream_t st = nullptr;
-        ~OwnPairs() {
-            if (p) (void)hipFreeAsync(p, st);
-        }
-    } own;
-    own.st = st;
-    auto get_pairs = [&](int64_t total, uint32_t **pairs) {
-        if (out_pairs_or_null) {
-            if (total > pair_cap) {
-                set_error("K22: pair buffer too small (%lld elements needed, %lld given)", (long long)total, (long long)pair_cap);
-                return (int)DYD_ERR_RANGE;
-            }
-            *pairs = out_pairs_or_null;
-            return (int)DYD_OK;
-        }
-        const hipError_t e = hipMallocAsync(&own.p, total > 0 ? 4 * (size_t)total : 16, st);
-        if (e != hipSuccess) {
-            own.p = nullptr;
-            (void)hipGetLastError();
-            set_error("K22: no buffer for %lld pair counts: %s", (long long)total, hipGetErrorString(e));
-            return (int)DYD_ERR_OOM;
-        }
-        *pairs = static_cast<uint32_t *>(own.p);
-        return (int)DYD_OK;
-    };
+    // no buffer from the caller is not "measure only" here: the pair counts then live in one the library allocates in st
+    SizedOut given(K22_PAIRS, out_pairs_or_null, pair_cap), own(K22_PAIRS, st);
     return compare_launch(a, b, width, height, n_rows, n_classes, thr, by_label != 0, max_pixels_per_row, max_pairs_per_row, o,
-                          get_pairs, st);
+                          out_pairs_or_null ? given : own, st);
 }
 
 int dyd_compare_polygons(const double *a_xy, const int32_t *a_pt_off, const int32_t *a_row_off, const int32_t *a_cls,
@@ -500,7 +465,7 @@ int dyd_compare_polygons(const double *a_xy, const int32_t *a_pt_off, const int3
     hipStream_t st = ctx().stream;
     PolyTableDev ta;
     DevBuf b_xyd, b_pt, b_row, d_ca, d_cb, d_status, d_poff, d_aact, d_bact, d_apix, d_bpix, d_am, d_bm, d_bi, d_ab, d_bb, d_rows,
-        d_conf, d_pconf, d_rpix, d_pairs;
+        d_conf, d_pconf, d_rpix;
     const size_t cells = 8 * (size_t)(n_classes + 1) * (size_t)(n_classes + 1);
     if ((rc = ta.upload(a_xy, a_pt_off, a_row_off, width, height, n_rows, na, npa)) ||
         (rc = poly_column(b_xyd, npb ? b_xy : nullptr, 16 * (size_t)npb)) ||
@@ -519,14 +484,10 @@ int dyd_compare_polygons(const double *a_xy, const int32_t *a_pt_off, const int3
                      d_bact.as<uint8_t>(), d_bpix.as<int64_t>(), d_bm.as<int32_t>(), d_bb.as<double>()};
     const K22Out o{d_status.as<uint8_t>(), d_poff.as<int64_t>(), d_bi.as<double>(), d_rows.as<int32_t>(), d_conf.as<uint64_t>(),
                    d_pconf.as<uint64_t>(), d_rpix.as<int64_t>()};
-    auto get_pairs = [&](int64_t total, uint32_t **pairs) {
-        const int r = d_pairs.alloc(4 * (size_t)total);
-        *pairs = d_pairs.as<uint32_t>();
-        return r;
-    };
+    SizedOut pairs(K22_PAIRS, st);
     KernelTimer timer(st);
     rc = compare_launch(a, b, ta.w.as<double>(), ta.h.as<double>(), n_rows, n_classes, thr, by_label != 0, max_pixels_per_row,
-                        max_pairs_per_row, o, get_pairs, st);
+                        max_pairs_per_row, o, pairs, st);
     if (rc) return rc;
     timer.finish();
     const CopyBack back[] = {{out_row_status, d_status.p, (size_t)n_rows}, {out_pair_off, d_poff.p, 8 * (size_t)(n_rows + 1)},

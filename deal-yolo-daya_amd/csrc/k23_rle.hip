@@ -39,9 +39,9 @@
 #include "k13_scan.h"
 #include "k21_cover.h"
 #include "poly_table.h"
+#include "sized_out.h"
 
 #include <climits>
-#include <utility>
 
 namespace dyd {
 
@@ -440,28 +440,15 @@ static int rle_scan(int64_t *v, int64_t n, hipStream_t st) {
     return DYD_OK;
 }
 
-// host values from the device, st synchronised
-static int rle_read(std::initializer_list<std::pair<const int64_t *, int64_t *>> what, hipStream_t st, const char *step) {
-    hipError_t err = hipGetLastError();
-    for (const auto &w : what)
-        if (err == hipSuccess) err = hipMemcpyAsync(w.second, w.first, 8, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    if (err != hipSuccess) {
-        set_error("K23: %s failed: %s", step, hipGetErrorString(err));
-        return err == hipErrorOutOfMemory ? DYD_ERR_OOM : DYD_ERR_HIP;
-    }
-    return DYD_OK;
-}
-
 static inline dim3 rle_grid(int64_t n) { return dim3((unsigned)ceil_div(n, (int64_t)K23_BLOCK)); }
 
-// Steps 1 to 6 on device pointers, n_rows > 0.  get_runs(total, &runs, &cap) and get_text(total, &text, &cap) are asked for
-// the buffers once their sizes are known (NULL: stop there).  *run_total and *text_total are host values; st is synchronised
-// on return.
-template <class GetRuns, class GetText>
+constexpr SizedName K23_RUNS{"K23", "run", "runs", 4}, K23_TEXT{"K23", "text", "bytes", 1};
+
+// Steps 1 to 6 on device pointers, n_rows > 0.  `runs_out` and `text_out` are asked for the buffers once their sizes are known
+// (none: stop there).  *run_total and *text_total are host values; st is synchronised on return.
 static int rle_launch(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *sel, const double *width,
                       const double *height, int64_t n_rows, int64_t n_polys, int64_t n_points, int64_t max_pixels, const RleOut &o,
-                      int64_t *run_total, int64_t *text_total, GetRuns get_runs, GetText get_text, hipStream_t st) {
+                      int64_t *run_total, int64_t *text_total, SizedOut &runs_out, SizedOut &text_out, hipStream_t st) {
     const int strip = g_k23_strip, cap = g_k23_crossings;
     *run_total = *text_total = 0;
     hipLaunchKernelGGL(k23_rows_kernel, rle_grid(n_rows), dim3(K23_BLOCK), 0, st, width, height, n_rows, max_pixels, o.row_status);
@@ -469,14 +456,11 @@ static int rle_launch(const double *xy, const int32_t *pt_off, const int32_t *ro
     if (n_polys == 0) {
         DYD_HIP(hipGetLastError());
         DYD_HIP(hipStreamSynchronize(st));
-        uint32_t *runs = nullptr;
-        int64_t c = 0;
-        int rc = get_runs(0, &runs, &c);
-        if (rc || !runs) return rc;
+        const int rc = runs_out.get(0);
+        if (rc || !runs_out.p) return rc;
         DYD_HIP(hipMemsetAsync(o.text_off, 0, 8, st));
         DYD_HIP(hipStreamSynchronize(st));
-        uint8_t *text = nullptr;
-        return get_text(0, &text, &c);
+        return text_out.get(0);
     }
     DevBuf d_info, d_geo, d_ext, d_off, d_cells, d_bits, d_col_tr, d_trans, d_code_off;
     int rc;
@@ -498,8 +482,8 @@ static int rle_launch(const double *xy, const int32_t *pt_off, const int32_t *ro
         if ((rc = rle_scan(item_off + 1, n_polys, st)) || (rc = rle_scan(col_off + 1, n_polys, st)) ||
             (rc = rle_scan(cell_off + 1, n_polys, st)))
             return rc;
-        if ((rc = rle_read({{item_off + n_polys, &n_items}, {col_off + n_polys, &n_cols}, {cell_off + n_polys, &n_cells}}, st,
-                           "the row and polygon steps")))
+        if ((rc = read_totals("K23", "the row and polygon steps",
+                              {{&n_items, item_off + n_polys}, {&n_cols, col_off + n_polys}, {&n_cells, cell_off + n_polys}}, st)))
             return rc;
         if (n_cells <= K23_MAX_CELLS || n_cells == n_cols || band >= (1 << 30)) break;
         band *= 2;
@@ -524,15 +508,10 @@ static int rle_launch(const double *xy, const int32_t *pt_off, const int32_t *ro
                        o.area, o.bbox);
     if ((rc = rle_scan(o.run_off + 1, n_polys, st))) return rc;
     int64_t n_runs = 0, n_trans = 0;
-    if ((rc = rle_read({{o.run_off + n_polys, &n_runs}, {col_tr + n_cols, &n_trans}}, st, "the count step"))) return rc;
+    if ((rc = read_totals("K23", "the count step", {{&n_runs, o.run_off + n_polys}, {&n_trans, col_tr + n_cols}}, st))) return rc;
     *run_total = n_runs;
-    uint32_t *runs = nullptr;
-    int64_t runs_cap = 0;
-    if ((rc = get_runs(n_runs, &runs, &runs_cap)) || !runs) return rc;
-    if (n_runs > runs_cap) {
-        set_error("K23: run buffer too small (%lld runs needed, %lld given)", (long long)n_runs, (long long)runs_cap);
-        return DYD_ERR_RANGE;
-    }
+    if ((rc = runs_out.get(n_runs)) || !runs_out.p) return rc;
+    uint32_t *runs = runs_out.as<uint32_t>();
     // the transitions, the runs and the offsets of their codes
     if ((rc = d_trans.alloc(4 * (size_t)n_trans, st)) || (rc = d_code_off.alloc(8 * (size_t)(n_runs + 1), st))) return rc;
     int64_t *code_off = d_code_off.as<int64_t>();
@@ -546,18 +525,12 @@ static int rle_launch(const double *xy, const int32_t *pt_off, const int32_t *ro
     if ((rc = rle_scan(code_off + 1, n_runs, st))) return rc;
     hipLaunchKernelGGL(k23_text_off_kernel, rle_grid(n_polys + 1), dim3(K23_BLOCK), 0, st, n_polys, o.run_off, code_off, o.text_off);
     int64_t total = 0;
-    if ((rc = rle_read({{code_off + n_runs, &total}}, st, "the run step"))) return rc;
+    if ((rc = read_totals("K23", "the run step", {{&total, code_off + n_runs}}, st))) return rc;
     *text_total = total;
-    uint8_t *text = nullptr;
-    int64_t text_cap = 0;
-    if ((rc = get_text(total, &text, &text_cap)) || !text) return rc;
-    if (total > text_cap) {
-        set_error("K23: text buffer too small (%lld bytes needed, %lld given)", (long long)total, (long long)text_cap);
-        return DYD_ERR_RANGE;
-    }
+    if ((rc = text_out.get(total)) || !text_out.p) return rc;
     if (n_runs > 0)
         hipLaunchKernelGGL(k23_print_kernel, rle_grid(n_runs), dim3(K23_BLOCK), 0, st, n_polys, o.run_off, n_runs, runs, code_off, total,
-                           text);
+                           text_out.as<uint8_t>());
     DYD_HIP(hipGetLastError());
     DYD_HIP(hipStreamSynchronize(st));
     return DYD_OK;
@@ -600,18 +573,9 @@ int dyd_polygon_rle_dev(const double *xy, const int32_t *pt_off, const int32_t *
     DYD_REQUIRE(n_polys == 0 || (pt_off && sel && out_action && out_area && out_bbox), "null pointer");
     DYD_REQUIRE(n_points == 0 || xy, "null pointer");
     const RleOut o{out_row_status, out_action, out_area, out_bbox, out_run_off, out_text_off};
-    auto get_runs = [&](int64_t, uint32_t **runs, int64_t *cap) {
-        *runs = out_runs_or_null;
-        *cap = runs_cap;
-        return (int)DYD_OK;
-    };
-    auto get_text = [&](int64_t, uint8_t **text, int64_t *cap) {
-        *text = out_text_or_null;
-        *cap = text_cap;
-        return (int)DYD_OK;
-    };
+    SizedOut runs(K23_RUNS, out_runs_or_null, runs_cap), text(K23_TEXT, out_text_or_null, text_cap);
     return rle_launch(xy, pt_off, row_off, sel, width, height, n_rows, n_polys, n_points, max_pixels_per_row, o, out_run_total,
-                      out_text_total, get_runs, get_text, st);
+                      out_text_total, runs, text, st);
 }
 
 int dyd_polygon_rle(const double *xy, const int32_t *pt_off, const int32_t *row_off, const int32_t *sel, const double *width,
@@ -635,7 +599,7 @@ int dyd_polygon_rle(const double *xy, const int32_t *pt_off, const int32_t *row_
     if (rc) return rc;
     hipStream_t st = ctx().stream;
     PolyTableDev t;
-    DevBuf d_sel, d_status, d_act, d_area, d_bbox, d_roff, d_toff, d_runs, d_text;
+    DevBuf d_sel, d_status, d_act, d_area, d_bbox, d_roff, d_toff;
     const size_t off_bytes = 8 * (size_t)(n_polys + 1);
     if ((rc = t.upload(xy, pt_off, row_off, width, height, n_rows, n_polys, n_points)) ||
         (rc = poly_column(d_sel, sel, 4 * (size_t)n_polys)) || (rc = d_status.alloc((size_t)n_rows)) ||
@@ -644,28 +608,17 @@ int dyd_polygon_rle(const double *xy, const int32_t *pt_off, const int32_t *row_
         return rc;
     const RleOut o{d_status.as<uint8_t>(), d_act.as<uint8_t>(), d_area.as<int64_t>(), d_bbox.as<int32_t>(), d_roff.as<int64_t>(),
                    d_toff.as<int64_t>()};
-    auto get_runs = [&](int64_t total, uint32_t **runs, int64_t *cap) {
-        const int r = d_runs.alloc(4 * (size_t)total);
-        *runs = d_runs.as<uint32_t>();
-        *cap = total;
-        return r;
-    };
-    auto get_text = [&](int64_t total, uint8_t **text, int64_t *cap) {
-        const int r = d_text.alloc((size_t)total);
-        *text = d_text.as<uint8_t>();
-        *cap = total;
-        return r;
-    };
+    SizedOut runs(K23_RUNS, st), text(K23_TEXT, st);
     int64_t n_runs = 0, total = 0;
     KernelTimer timer(st);
     rc = rle_launch(t.xy.as<double>(), t.pt.as<int32_t>(), t.row.as<int32_t>(), d_sel.as<int32_t>(), t.w.as<double>(),
-                    t.h.as<double>(), n_rows, n_polys, n_points, max_pixels_per_row, o, &n_runs, &total, get_runs, get_text, st);
+                    t.h.as<double>(), n_rows, n_polys, n_points, max_pixels_per_row, o, &n_runs, &total, runs, text, st);
     if (rc) return rc;
     timer.finish();
     uint8_t *host_runs = nullptr;
     int64_t run_bytes = 0;
-    if ((rc = hand_back_text(d_runs.p, 4 * n_runs, {}, st, &host_runs, &run_bytes))) return rc;
-    rc = hand_back_text(d_text.p, total,
+    if ((rc = hand_back_text(runs.p, 4 * n_runs, {}, st, &host_runs, &run_bytes))) return rc;
+    rc = hand_back_text(text.p, total,
                         {{out_row_status, d_status.p, (size_t)n_rows}, {out_action, d_act.p, (size_t)n_polys},
                          {out_area, d_area.p, 8 * (size_t)n_polys}, {out_bbox, d_bbox.p, 16 * (size_t)n_polys},
                          {out_run_off, d_roff.p, off_bytes}, {out_text_off, d_toff.p, off_bytes}},
