@@ -2668,36 +2668,30 @@ class BoxComparison:
         self.totals = totals
 
     def __repr__(self):
-        return f"BoxComparison({len(self.classes)} classes, {self.totals})"
+        return f"{type(self).__name__}({len(self.classes)} classes, {self.totals})"
 
 
 class _CompareTotals:
-    """class-keyed sums over the chunks (classes in first-seen order, None = the names that are no str), per-row counts and
-    differences per chunk"""
+    """sums over the chunks of a comparison, keyed by class (classes in first-seen order, None = the names that are no str): the
+    IoU histogram and the step's own per-class quantities (`shapes`) in a _ClassSums, the confusion counts as a bordered matrix
+    (`matrix`); and per chunk the per-row counts and the differences"""
 
-    def __init__(self):
-        self.index = {}
-        self.pairs = np.zeros((0, 0), np.int64)          # [A class, B class] matched pairs
-        self.missing = np.zeros(0, np.int64)
-        self.extra = np.zeros(0, np.int64)
-        self.hist = np.zeros((0, COMPARE_HIST_BINS), np.int64)
+    def __init__(self, *shapes):
+        self.sums = _ClassSums((COMPARE_HIST_BINS,), *shapes)
+        self.index = self.sums.index
+        self.conf = np.zeros((1, 1), np.int64)           # [A class, B class] matched pairs; the last row and column: no partner
         self.rows, self.n_a, self.n_b, self.diffs = [], [], [], []
         self.python_cells = 0
 
-    def add(self, names, conf, hist):
-        """adds a chunk's (C+1) x (C+1) confusion counts and [C, 20] histogram, C = len(names)"""
-        g = np.asarray([self.index.setdefault(nm, len(self.index)) for nm in names], np.int64)
-        grow = len(self.index) - len(self.missing)
-        if grow:
-            self.pairs = np.pad(self.pairs, ((0, grow), (0, grow)))
-            self.missing, self.extra = np.pad(self.missing, (0, grow)), np.pad(self.extra, (0, grow))
-            self.hist = np.pad(self.hist, ((0, grow), (0, 0)))
-        c = len(names)
-        if c:
-            self.pairs[np.ix_(g, g)] += conf[:c, :c]
-            self.missing[g] += conf[:c, c]
-            self.extra[g] += conf[c, :c]
-            self.hist[g] += hist
+    def matrix(self, total, names, part):
+        """-> total + a chunk's (C+1) x (C+1) counts on its C = len(names) classes, which the index holds already (sums.add):
+        both keep their border in the last row and column"""
+        g = np.asarray([self.index[nm] for nm in names] + [-1], np.int64)
+        new = [len(total) - 1] * (len(self.index) + 1 - len(total))       # the new classes go in front of the border
+        if new:
+            total = np.insert(np.insert(total, new, 0, axis=0), new, 0, axis=1)
+        total[np.ix_(g, g)] += part
+        return total
 
 
 def _compare_threshold(iou_threshold) -> float:
@@ -2706,14 +2700,69 @@ def _compare_threshold(iou_threshold) -> float:
     return float(iou_threshold)
 
 
-def _box_names(names: list, cls, odd_names: dict, sel) -> np.ndarray:
-    """the names of the boxes `sel` of one side: names[class id], None for class id -1, then the names that are no str"""
+def _compare_names(names: list, cls, odd_names: dict, sel) -> np.ndarray:
+    """the names of the items `sel` of one side: names[class id], None for class id -1, then the names that are no str"""
     out = np.asarray(names + [None], object)[np.asarray(cls, np.int64)[sel]]
     for b, nm in odd_names.items():
         p = int(np.searchsorted(sel, b))
         if p < len(sel) and sel[p] == b:
             out[p] = nm
     return out
+
+
+def _compare_classes(names_a, cls_a, names_b, cls_b) -> tuple:
+    """one class list for both sides, the names that are no str (class id -1) last as None -> (names, [A's class column on it,
+    B's], int32)"""
+    ids, cls = {}, []
+    for names, c in ((names_a, cls_a), (names_b, cls_b)):
+        to = np.asarray([ids.setdefault(nm, len(ids)) for nm in names] + [-1], np.int32)
+        cls.append(to[np.asarray(c, np.int64)])
+    names = list(ids)
+    if any((c < 0).any() for c in cls):
+        names.append(None)
+        cls = [np.where(c < 0, len(names) - 1, c).astype(np.int32) for c in cls]
+    return names, cls
+
+
+def _compare_pairs(names, start: int, n: int, off, cls, match, b_iou, best, compared, obj, odd_names, tail, filler) -> tuple:
+    """The matched pairs of one chunk of n rows -> (hist [C, 20]: the IoU of the agreeing pairs per class, the differences'
+    columns sorted by (row, kind, position), None without a difference).  Each of off (row offsets), cls, match, best, obj is a
+    pair (A's, B's); so are `compared` (bool per item, or True: only a compared item is missing / extra), `odd_names` ({item: a
+    name that is no str}: listed as it is, else such a name is None) and `tail`, the step's own last column(s) per item, which
+    hold `filler` where a line has no item of that side."""
+    (off_a, off_b), (a_match, b_match), (a_best, b_best) = off, match, best
+    row_a = np.repeat(np.arange(n, dtype=np.int64), np.diff(off_a))
+    row_b = np.repeat(np.arange(n, dtype=np.int64), np.diff(off_b))
+    hit = np.flatnonzero(b_match >= 0)                   # matched B items and their A items
+    hit_a = off_a[row_b[hit]] + b_match[hit]
+    same = cls[0][hit_a] == cls[1][hit]
+    hist = np.zeros((len(names), COMPARE_HIST_BINS), np.int64)
+    np.add.at(hist, (cls[1][hit[same]], np.minimum((b_iou[hit[same]] * COMPARE_HIST_BINS).astype(np.int64),
+                                                   COMPARE_HIST_BINS - 1)), 1)
+    miss, extra = np.flatnonzero(compared[0] & (a_match < 0)), np.flatnonzero(compared[1] & (b_match < 0))
+    rel_a, rel_b = hit_a[~same], hit[~same]
+    k = (len(miss), len(extra), len(rel_b))
+    if not sum(k):
+        return hist, None
+
+    def side(s, take, fill):
+        """a column of side s over the lines: take(items) on its own lines, `fill` on the lines of the other side alone"""
+        own, rel = ((miss, rel_a), (extra, rel_b))[s]
+        last = take(rel)
+        gap = np.full((k[1 - s], *last.shape[1:]), fill, last.dtype)
+        return np.concatenate([take(own), gap, last] if s == 0 else [gap, take(own), last])
+
+    row = np.concatenate([row_a[miss], row_b[extra], row_b[rel_b]])
+    kind = np.repeat(np.arange(3), k)
+    at = np.concatenate([miss - off_a[row_a[miss]], extra - off_b[row_b[extra]], rel_a - off_a[row_b[rel_b]]])
+    order = np.lexsort((at, kind, row))
+    cols = (start + row, np.asarray(COMPARE_KINDS, object)[kind],
+            *(side(s, obj[s].__getitem__, -1) for s in (0, 1)),
+            *(side(s, lambda sel, s=s: _compare_names(names, cls[s], odd_names[s], sel), None) for s in (0, 1)),
+            np.concatenate([np.zeros(k[0] + k[1]), b_iou[rel_b]]),
+            np.concatenate([a_best[miss], b_best[extra], b_iou[rel_b]]),
+            *(side(s, tail[s].__getitem__, filler) for s in (0, 1)))
+    return hist, tuple(c[order] for c in cols)
 
 
 def _compare_chunk(cells_a, cells_b, thr: float, by_label: bool, be, acc: _CompareTotals, start: int):
@@ -2727,91 +2776,59 @@ def _compare_chunk(cells_a, cells_b, thr: float, by_label: bool, be, acc: _Compa
     ta, tb = sides
     n = len(cells_a)
     acc.python_cells += len(ta.irregular) + len(tb.irregular)
-    ids, cls = {}, []
-    for t in sides:                                      # one class list for both sides, the names that are no str last
-        to = np.asarray([ids.setdefault(nm, len(ids)) for nm in t.names] + [-1], np.int32)
-        cls.append(to[np.asarray(t.cls, np.int64)])
-    names = list(ids)
-    if any((c < 0).any() for c in cls):
-        names.append(None)
-        cls = [np.where(c < 0, len(names) - 1, c).astype(np.int32) for c in cls]
+    names, cls = _compare_classes(ta.names, ta.cls, tb.names, tb.cls)
     C = len(names)
-    off_a, off_b = ta.row_off, tb.row_off
-    box_a, box_b = (np.asarray(t.box4, np.float64).reshape(-1, 4) for t in sides)
+    off = ta.row_off, tb.row_off
+    box = [np.asarray(t.box4, np.float64).reshape(-1, 4) for t in sides]
     a_match, b_match, b_iou, a_best, b_best, rows, conf = be.compare_boxes(
-        box_a, off_a.astype(np.int32), cls[0], box_b, off_b.astype(np.int32), cls[1], C, thr, by_label)
-    a_match, b_match = np.asarray(a_match, np.int64), np.asarray(b_match, np.int64)
+        box[0], off[0].astype(np.int32), cls[0], box[1], off[1].astype(np.int32), cls[1], C, thr, by_label)
     b_iou, a_best, b_best = (np.asarray(v, np.float64) for v in (b_iou, a_best, b_best))
-    row_a = np.repeat(np.arange(n, dtype=np.int64), np.diff(off_a))
-    row_b = np.repeat(np.arange(n, dtype=np.int64), np.diff(off_b))
-    hit = np.flatnonzero(b_match >= 0)                   # matched B boxes and their A boxes
-    hit_a = off_a[row_b[hit]] + b_match[hit]
-    same = cls[0][hit_a] == cls[1][hit]
-    hist = np.zeros((C, COMPARE_HIST_BINS), np.int64)
-    np.add.at(hist, (cls[1][hit[same]], np.minimum((b_iou[hit[same]] * COMPARE_HIST_BINS).astype(np.int64),
-                                                   COMPARE_HIST_BINS - 1)), 1)
-    acc.add(names, np.asarray(conf).astype(np.int64).reshape(C + 1, C + 1), hist)
+    hist, diffs = _compare_pairs(names, start, n, off, cls, (np.asarray(a_match, np.int64), np.asarray(b_match, np.int64)), b_iou,
+                                 (a_best, b_best), (True, True), [np.asarray(t.obj, np.int64) for t in sides],
+                                 (ta.odd_names, tb.odd_names), box, np.nan)
+    acc.sums.add(names, hist)
+    acc.conf = acc.matrix(acc.conf, names, np.asarray(conf).astype(np.int64).reshape(C + 1, C + 1))
     acc.rows.append(np.asarray(rows, np.int64).reshape(n, 4))
-    acc.n_a.append(np.diff(off_a))
-    acc.n_b.append(np.diff(off_b))
-    miss, extra, rel_b = np.flatnonzero(a_match < 0), np.flatnonzero(b_match < 0), hit[~same]
-    rel_a = hit_a[~same]
-    k = (len(miss), len(extra), len(rel_b))
-    if sum(k):
-        nan4 = lambda m: np.full((m, 4), np.nan)         # noqa: E731
-        absent = lambda m: np.full(m, -1, np.int64)      # noqa: E731
-        none = lambda m: np.full(m, None, object)        # noqa: E731
-        row = np.concatenate([row_a[miss], row_b[extra], row_b[rel_b]])
-        kind = np.repeat(np.arange(3), k)
-        at = np.concatenate([miss - off_a[row_a[miss]], extra - off_b[row_b[extra]], rel_a - off_a[row_b[rel_b]]])
-        order = np.lexsort((at, kind, row))
-        obj_a, obj_b = np.asarray(ta.obj, np.int64), np.asarray(tb.obj, np.int64)
-        cols = (start + row, np.asarray(COMPARE_KINDS, object)[kind],
-                np.concatenate([obj_a[miss], absent(k[1]), obj_a[rel_a]]),
-                np.concatenate([absent(k[0]), obj_b[extra], obj_b[rel_b]]),
-                np.concatenate([_box_names(ta.names, ta.cls, ta.odd_names, miss), none(k[1]),
-                                _box_names(ta.names, ta.cls, ta.odd_names, rel_a)]),
-                np.concatenate([none(k[0]), _box_names(tb.names, tb.cls, tb.odd_names, extra),
-                                _box_names(tb.names, tb.cls, tb.odd_names, rel_b)]),
-                np.concatenate([np.zeros(k[0] + k[1]), b_iou[rel_b]]),
-                np.concatenate([a_best[miss], b_best[extra], b_iou[rel_b]]),
-                np.concatenate([box_a[miss], nan4(k[1]), box_a[rel_a]]),
-                np.concatenate([nan4(k[0]), box_b[extra], box_b[rel_b]]))
-        acc.diffs.append(tuple(c[order] for c in cols))
+    acc.n_a.append(np.diff(off[0]))
+    acc.n_b.append(np.diff(off[1]))
+    if diffs is not None:
+        acc.diffs.append(diffs)
 
 
-def _compare_result(acc: _CompareTotals, n: int, sources, thr: float, by_label: bool, stats) -> BoxComparison:
+def _compare_result(acc: _CompareTotals, n: int, sources, noun: str, diff_spec: tuple, lead: dict) -> tuple:
+    """What the results of both steps share -> (BoxComparison's arguments by name, perm).  Classes sorted as str with None
+    last; perm takes a class-keyed sum into that order and, through np.ix_(perm, perm), a bordered matrix, whose border stays
+    last.  per_class and per_row are still dicts of columns, to which the step adds its own before it makes the frames:
+    per_class counts the `noun` (boxes / polygons) in its first eight columns; per_row is row, source, `lead`'s columns, the
+    two sides' counts and the four kinds.  differences has source second; totals holds its first eight keys."""
     classes = sorted(acc.index, key=lambda c: (c is None, str(c)))
-    perm = np.asarray([acc.index[c] for c in classes], np.int64)
-    pairs, missing, extra, hist = acc.pairs[np.ix_(perm, perm)], acc.missing[perm], acc.extra[perm], acc.hist[perm]
     C = len(classes)
-    full = np.zeros((C + 1, C + 1), np.int64)
-    full[:C, :C], full[:C, C], full[C, :C] = pairs, missing, extra
+    perm = np.asarray([acc.index[c] for c in classes] + [-1], np.int64)
+    full = acc.conf[np.ix_(perm, perm)]
+    pairs, missing, extra = full[:C, :C], full[:C, C], full[C, :C]
     labels = pd.Index(classes + [COMPARE_NONE], dtype=object)
     confusion = pd.DataFrame(full, index=labels, columns=labels)
     agree = np.diagonal(pairs).copy() if C else np.zeros(0, np.int64)
-    per_class = pd.DataFrame({"class": pd.Series(classes, dtype=object), "a_boxes": full[:C].sum(axis=1),
-                              "b_boxes": full[:, :C].sum(axis=0), "agree": agree,
-                              "relabelled_to_other": pairs.sum(axis=1) - agree, "relabelled_from_other": pairs.sum(axis=0) - agree,
-                              "missing": missing, "extra": extra})
+    per_class = {"class": pd.Series(classes, dtype=object), f"a_{noun}": full[:C].sum(axis=1), f"b_{noun}": full[:, :C].sum(axis=0),
+                 "agree": agree, "relabelled_to_other": pairs.sum(axis=1) - agree, "relabelled_from_other": pairs.sum(axis=0) - agree,
+                 "missing": missing, "extra": extra}
     rows = np.concatenate(acc.rows) if acc.rows else np.zeros((0, 4), np.int64)
     pr = {"row": np.arange(n, dtype=np.int64)}
     if sources is not None:
         pr["source"] = np.asarray(sources, object)
-    pr["a_boxes"] = np.concatenate(acc.n_a) if acc.n_a else np.zeros(0, np.int64)
-    pr["b_boxes"] = np.concatenate(acc.n_b) if acc.n_b else np.zeros(0, np.int64)
+    pr.update(lead)
+    pr[f"a_{noun}"] = np.concatenate(acc.n_a) if acc.n_a else np.zeros(0, np.int64)
+    pr[f"b_{noun}"] = np.concatenate(acc.n_b) if acc.n_b else np.zeros(0, np.int64)
     pr.update({k: rows[:, j] for j, k in enumerate(_COMPARE_ROW_COLS)})
-    differences = _parts_frame(acc.diffs, _COMPARE_DIFF_SPEC, sources)
+    differences = _parts_frame(acc.diffs, diff_spec, sources)
     if sources is not None:                              # row first, as in per_row
         differences = differences[["row", "source", *differences.columns[2:]]]
-    totals = {"rows": n, "a_boxes": int(pr["a_boxes"].sum()), "b_boxes": int(pr["b_boxes"].sum()),
+    totals = {"rows": n, f"a_{noun}": int(pr[f"a_{noun}"].sum()), f"b_{noun}": int(pr[f"b_{noun}"].sum()),
               "matched": int(rows[:, :2].sum()), "agree": int(rows[:, 0].sum()), "relabelled": int(rows[:, 1].sum()),
-              "missing": int(rows[:, 2].sum()), "extra": int(rows[:, 3].sum()), "python_cells": acc.python_cells,
-              "iou_threshold": thr, "by_label": by_label}
-    if stats is not None:
-        stats.update(totals)
+              "missing": int(rows[:, 2].sum()), "extra": int(rows[:, 3].sum())}
     unpaired = pd.DataFrame({"key": np.zeros(0, object), "side": np.zeros(0, object)})
-    return BoxComparison(classes, confusion, per_class, hist, pd.DataFrame(pr), differences, unpaired, totals)
+    return dict(classes=classes, confusion=confusion, per_class=per_class, hist_iou=acc.sums.sums[0][perm[:C]], per_row=pr,
+                differences=differences, unpaired=unpaired, totals=totals), perm
 
 
 def compare_boxes_cells(cells_a, cells_b, iou_threshold: float = 0.5, by_label: bool = False, backend=None,
@@ -2829,7 +2846,11 @@ def compare_boxes_cells(cells_a, cells_b, iou_threshold: float = 0.5, by_label: 
     acc = _CompareTotals()
     for s0, s1, chunk in _chunks(n, cells_a):
         _compare_chunk(chunk, cells_b[s0:s1], thr, by_label, be, acc, s0)
-    return _compare_result(acc, n, sources, thr, by_label, stats)
+    res, _ = _compare_result(acc, n, sources, "boxes", _COMPARE_DIFF_SPEC, {})
+    res["totals"].update(python_cells=acc.python_cells, iou_threshold=thr, by_label=by_label)
+    if stats is not None:
+        stats.update(res["totals"])
+    return BoxComparison(**{**res, "per_class": pd.DataFrame(res["per_class"]), "per_row": pd.DataFrame(res["per_row"])})
 
 
 def _compare_align(keys_a, keys_b, key) -> tuple:
@@ -2849,8 +2870,18 @@ def _compare_align(keys_a, keys_b, key) -> tuple:
     return rows_a, rows_b, only_a, np.flatnonzero(~seen)
 
 
-def _compare_aligned(res, rows_a, keys_a, only_a, keys_b, only_b, stats):
-    """a comparison of the aligned rows, reported in positions of A, with the rows found on one side only"""
+def _compare_tables(compare, cells_a, keys_a, sources, cells_b, keys_b, key, stats):
+    """two tables (cells, keys or None) -> compare(A's cells, B's cells, A's sources, rows_a, rows_b) over their aligned rows,
+    reported in positions of A, with the rows found on one side only: by position without keys, else on the keys
+    (_compare_align)"""
+    cells_a, cells_b = np.asarray(cells_a, object), np.asarray(cells_b, object)
+    if keys_a is None:
+        rows_a = rows_b = np.arange(len(cells_a), dtype=np.int64)
+        only_a = only_b = np.zeros(0, np.int64)
+        keys_a = keys_b = np.zeros(0, object)
+    else:
+        rows_a, rows_b, only_a, only_b = _compare_align(keys_a, keys_b, key)
+    res = compare(cells_a[rows_a], cells_b[rows_b], None if sources is None else np.asarray(sources, object)[rows_a], rows_a, rows_b)
     res.per_row["row"] = rows_a[res.per_row["row"].to_numpy()]
     res.differences["row"] = rows_a[res.differences["row"].to_numpy()]
     res.unpaired = pd.DataFrame({"key": np.concatenate([np.asarray(keys_a, object)[only_a], np.asarray(keys_b, object)[only_b]]),
@@ -2861,13 +2892,60 @@ def _compare_aligned(res, rows_a, keys_a, only_a, keys_b, only_b, stats):
     return res
 
 
-def _compare_keyed(cells_a, keys_a, sources_a, cells_b, keys_b, key, thr, by_label, backend, stats) -> BoxComparison:
-    """the comparison of the rows of A whose key is also in B (each key at most once per side); rows are positions in A"""
-    rows_a, rows_b, only_a, only_b = _compare_align(keys_a, keys_b, key)
-    cells_a, cells_b = np.asarray(cells_a, object), np.asarray(cells_b, object)
-    res = compare_boxes_cells(cells_a[rows_a], cells_b[rows_b], thr, by_label, backend, None,
-                              None if sources_a is None else np.asarray(sources_a, object)[rows_a])
-    return _compare_aligned(res, rows_a, keys_a, only_a, keys_b, only_b, stats)
+def _compare_frames(df_a, df_b, json_col, other_col, key) -> tuple:
+    """the frame entries' choice of what to compare -> (cells_a, keys_a, cells_b, keys_b): json_col against other_col of df_a
+    without df_b, else the two frames by position (key=None, equal lengths; no keys) or on the column `key`"""
+    if df_b is None:
+        if other_col is None:
+            raise ValueError("with one frame, other_col names the column to compare json_col against")
+        return df_a[json_col].to_numpy(), None, df_a[other_col].to_numpy(), None
+    col_b = other_col if other_col is not None else json_col
+    if key is None:
+        if len(df_b) != len(df_a):
+            raise ValueError(f"without a key the frames are compared by position: {len(df_a)} against {len(df_b)} rows")
+        return df_a[json_col].to_numpy(), None, df_b[col_b].to_numpy(), None
+    return df_a[json_col].to_numpy(), df_a[key].to_numpy(), df_b[col_b].to_numpy(), df_b[key].to_numpy()
+
+
+def _compare_read(io_key: str, a_csv, b_csv, json_col: str, key):
+    """the CSV entries' two sides through _csv_route -> (light_a, cells_a, keys_a, light_b, cells_b, keys_b), keys None for
+    key=None (equal lengths then); None after 读取失败：... or 错误：缺少必要列 ... (json_col, key).  LAST_IO_PATH[io_key] is "native"
+    only when both sides took the native route."""
+    sides, routes = [], []
+    for path in (a_csv, b_csv):
+        side = _csv_route(
+            io_key, path, json_col,
+            lambda table: (table.light, _fc_cells(table.heavy[json_col], 0, table.n_rows)),
+            lambda df: (df, df[json_col].to_numpy()))
+        if side is None:
+            return None
+        routes.append(LAST_IO_PATH[io_key])
+        if key is not None and key not in side[0].columns:
+            print(f"错误：缺少必要列 {key}")
+            return None
+        sides += [*side, None if key is None else side[0][key].to_numpy()]
+    LAST_IO_PATH[io_key] = "native" if routes == ["native", "native"] else "pandas"
+    if key is None and len(sides[1]) != len(sides[4]):
+        raise ValueError(f"without a key the files are compared by position: {len(sides[1])} against {len(sides[4])} rows")
+    return sides
+
+
+def _write_comparison(res: BoxComparison, output_dir, prefix: str) -> dict:
+    """-> the paths of {prefix}_confusion.csv, (a PolygonComparison's) {prefix}_pixels.csv, {prefix}_classes.csv,
+    {prefix}_differences.csv, {prefix}_rows.csv and {prefix}_hist.npz under output_dir, written"""
+    out = Path(output_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    matrices = {"confusion": res.confusion, **({"pixels": res.pixel_confusion} if hasattr(res, "pixel_confusion") else {})}
+    tables = {"classes": res.per_class, "differences": res.differences, "rows": res.per_row}
+    paths = {k: str(out / f"{prefix}_{k}.csv") for k in (*matrices, *tables)}
+    paths["hist"] = str(out / f"{prefix}_hist.npz")
+    for k, frame in matrices.items():
+        frame.to_csv(paths[k], index_label="a_class", encoding="utf-8-sig")
+    for k, frame in tables.items():
+        frame.to_csv(paths[k], index=False, encoding="utf-8-sig")
+    np.savez(paths["hist"], classes=np.asarray([COMPARE_NONE if c is None else c for c in res.classes], dtype=str),
+             hist_iou=res.hist_iou)
+    return paths
 
 
 def compare_boxes_frame(df_a: pd.DataFrame, df_b: Optional[pd.DataFrame] = None, json_col: str = BBOX_COL, other_col=None,
@@ -2879,37 +2957,9 @@ def compare_boxes_frame(df_a: pd.DataFrame, df_b: Optional[pd.DataFrame] = None,
     ``unpaired`` lists their keys.  per_row["row"] / differences["row"] are positions in df_a."""
     thr = _compare_threshold(iou_threshold)
     sources = df_a["source"].to_numpy() if "source" in df_a.columns else None
-    if df_b is None or key is None:
-        if df_b is None:
-            if other_col is None:
-                raise ValueError("with one frame, other_col names the column to compare json_col against")
-            cells_b = df_a[other_col].to_numpy()
-        else:
-            if len(df_b) != len(df_a):
-                raise ValueError(f"without a key the frames are compared by position: {len(df_a)} against {len(df_b)} rows")
-            cells_b = df_b[other_col if other_col is not None else json_col].to_numpy()
-        res = compare_boxes_cells(df_a[json_col].to_numpy(), cells_b, thr, by_label, backend, None, sources)
-        res.totals.update(rows_only_a=0, rows_only_b=0)
-        if stats is not None:
-            stats.update(res.totals)
-        return res
-    return _compare_keyed(df_a[json_col].to_numpy(), df_a[key].to_numpy(), sources,
-                          df_b[other_col if other_col is not None else json_col].to_numpy(), df_b[key].to_numpy(), key, thr,
-                          by_label, backend, stats)
-
-
-def _write_comparison(res: BoxComparison, output_dir) -> dict:
-    out = Path(output_dir)
-    out.mkdir(parents=True, exist_ok=True)
-    paths = {k: str(out / f"box_compare_{k}.csv") for k in ("confusion", "classes", "differences", "rows")}
-    paths["hist"] = str(out / "box_compare_hist.npz")
-    res.confusion.to_csv(paths["confusion"], index_label="a_class", encoding="utf-8-sig")
-    res.per_class.to_csv(paths["classes"], index=False, encoding="utf-8-sig")
-    res.differences.to_csv(paths["differences"], index=False, encoding="utf-8-sig")
-    res.per_row.to_csv(paths["rows"], index=False, encoding="utf-8-sig")
-    np.savez(paths["hist"], classes=np.asarray([COMPARE_NONE if c is None else c for c in res.classes], dtype=str),
-             hist_iou=res.hist_iou)
-    return paths
+    cells_a, keys_a, cells_b, keys_b = _compare_frames(df_a, df_b, json_col, other_col, key)
+    return _compare_tables(lambda a, b, src, *_: compare_boxes_cells(a, b, thr, by_label, backend, None, src),
+                           cells_a, keys_a, sources, cells_b, keys_b, key, stats)
 
 
 def compare_boxes_csv(a_csv, b_csv, output_dir, json_col: str = BBOX_COL, key="source", iou_threshold: float = 0.5,
@@ -2919,31 +2969,14 @@ def compare_boxes_csv(a_csv, b_csv, output_dir, json_col: str = BBOX_COL, key="s
     prints 读取失败：... and a missing column 错误：缺少必要列 ..., both returning None.  key=None compares by position.
     -> dict(totals, paths=...)"""
     thr = _compare_threshold(iou_threshold)
-    sides, routes = [], []
-    for path in (a_csv, b_csv):
-        side = _csv_route(
-            "compare", path, json_col,
-            lambda table: (table.light, _fc_cells(table.heavy[json_col], 0, table.n_rows)),
-            lambda df: (df, df[json_col].to_numpy()))
-        if side is None:
-            return None
-        routes.append(LAST_IO_PATH["compare"])
-        if key is not None and key not in side[0].columns:
-            print(f"错误：缺少必要列 {key}")
-            return None
-        sides.append(side)
-    LAST_IO_PATH["compare"] = "native" if routes == ["native", "native"] else "pandas"
-    (light_a, cells_a), (light_b, cells_b) = sides
+    read = _compare_read("compare", a_csv, b_csv, json_col, key)
+    if read is None:
+        return None
+    light_a, cells_a, keys_a, _, cells_b, keys_b = read
     sources = light_a["source"].to_numpy() if "source" in light_a.columns else None
-    if key is None:
-        if len(cells_a) != len(cells_b):
-            raise ValueError(f"without a key the files are compared by position: {len(cells_a)} against {len(cells_b)} rows")
-        res = compare_boxes_cells(cells_a, cells_b, thr, by_label, backend, None, sources)
-        res.totals.update(rows_only_a=0, rows_only_b=0)
-    else:
-        res = _compare_keyed(cells_a, light_a[key].to_numpy(), sources, cells_b, light_b[key].to_numpy(), key, thr, by_label,
-                             backend, None)
-    return {**res.totals, "paths": _write_comparison(res, output_dir)}
+    res = _compare_tables(lambda a, b, src, *_: compare_boxes_cells(a, b, thr, by_label, backend, None, src),
+                          cells_a, keys_a, sources, cells_b, keys_b, key, None)
+    return {**res.totals, "paths": _write_comparison(res, output_dir, "box_compare")}
 
 
 # =============================================================================== f7  YOLO segmentation label lines
@@ -4604,55 +4637,25 @@ _POLY_COMPARE_DIFF_SPEC = (("row", np.int64), ("kind", object), ("a_object", np.
                            ("b_pixels", np.int64))
 
 
-class PolygonComparison:
+class PolygonComparison(BoxComparison):
     """Result of compare_polygons_*: classes (sorted as str, None last), confusion (frame of polygon counts, index = A class,
     columns = B class, plus a last "(none)" row and column), pixel_confusion (the same shape in pixels, the last row and column
     "(background)"), per_class, hist_iou (int64 [C, 20], the mask IoU of the agreeing pairs), per_row, differences (one line per
     missing / extra / relabelled polygon), unpaired (key, side: rows found in one frame only) and totals."""
 
     def __init__(self, classes, confusion, pixel_confusion, per_class, hist_iou, per_row, differences, unpaired, totals):
-        self.classes = classes
-        self.confusion = confusion
+        super().__init__(classes, confusion, per_class, hist_iou, per_row, differences, unpaired, totals)
         self.pixel_confusion = pixel_confusion
-        self.per_class = per_class
-        self.hist_iou = hist_iou
-        self.per_row = per_row
-        self.differences = differences
-        self.unpaired = unpaired
-        self.totals = totals
-
-    def __repr__(self):
-        return f"PolygonComparison({len(self.classes)} classes, {self.totals})"
 
 
 class _PolyCompareTotals(_CompareTotals):
-    """_CompareTotals plus the class-keyed pixel counts ([A class, B class], class against background either way), the skipped
-    polygons per class and side, and the rows' status and pixel counts per chunk"""
+    """_CompareTotals with the skipped polygons per class and side among its class-keyed sums, plus the pixel counts as a second
+    bordered matrix (its border: the background, the corner both sides') and the rows' status and pixel counts per chunk"""
 
     def __init__(self):
-        super().__init__()
-        self.pix = np.zeros((0, 0), np.int64)
-        self.pix_a = np.zeros(0, np.int64)               # A's class where B is background
-        self.pix_b = np.zeros(0, np.int64)
-        self.pix_none = 0                                # background on both sides
-        self.skipped = np.zeros((0, 2), np.int64)
+        super().__init__((2,))
+        self.pix = np.zeros((1, 1), np.int64)
         self.status, self.row_pixels = [], []
-
-    def add_pixels(self, names, pconf, skipped):
-        """after add(names, ...): a chunk's (C+1) x (C+1) pixel counts and [C, 2] skipped polygons"""
-        g = np.asarray([self.index[nm] for nm in names], np.int64)
-        grow = len(self.index) - len(self.pix_a)
-        if grow:
-            self.pix = np.pad(self.pix, ((0, grow), (0, grow)))
-            self.pix_a, self.pix_b = np.pad(self.pix_a, (0, grow)), np.pad(self.pix_b, (0, grow))
-            self.skipped = np.pad(self.skipped, ((0, grow), (0, 0)))
-        c = len(names)
-        self.pix_none += int(pconf[c, c])
-        if c:
-            self.pix[np.ix_(g, g)] += pconf[:c, :c]
-            self.pix_a[g] += pconf[:c, c]
-            self.pix_b[g] += pconf[c, :c]
-            self.skipped[g] += skipped
 
 
 def _poly_compare_params(iou_threshold, by_label, max_pixels_per_row, max_pairs_per_row, batch_pixels, batch_pairs) -> tuple:
@@ -4668,14 +4671,7 @@ def _poly_compare_chunk(cells_a, cells_b, W, H, be, acc: _PolyCompareTotals, sta
     n = len(cells_a)
     sides = [_poly_chunk(cells) for cells in (cells_a, cells_b)]
     acc.python_cells += sides[0][6] + sides[1][6]
-    ids, cls = {}, []
-    for t in sides:                                      # one class list for both sides, the names that are no str last
-        to = np.asarray([ids.setdefault(nm, len(ids)) for nm in t[5]] + [-1], np.int32)
-        cls.append(to[np.asarray(t[4], np.int64)])
-    names = list(ids)
-    if any((c < 0).any() for c in cls):
-        names.append(None)
-        cls = [np.where(c < 0, len(names) - 1, c).astype(np.int32) for c in cls]
+    names, cls = _compare_classes(sides[0][5], sides[0][4], sides[1][5], sides[1][4])
     C = max(len(names), 1)                               # K22 takes at least one class; a chunk without polygons uses none
     if C > _POLY_COMPARE_MAX_CLASSES:
         raise ValueError(f"a chunk holds {C} classes; the polygon comparison takes at most {_POLY_COMPARE_MAX_CLASSES}")
@@ -4711,107 +4707,57 @@ def _poly_compare_chunk(cells_a, cells_b, W, H, be, acc: _PolyCompareTotals, sta
         rows[a:b], row_pixels[a:b] = np.asarray(out[11], np.int64).reshape(b - a, 4), np.asarray(out[14], np.int64).reshape(b - a, 2)
         conf += np.asarray(out[12]).astype(np.int64).reshape(C + 1, C + 1)
         pconf += np.asarray(out[13]).astype(np.int64).reshape(C + 1, C + 1)
-    (off_a, off_b), (a_match, b_match), (a_best, b_best) = off, match, best
-    row_a = np.repeat(np.arange(n, dtype=np.int64), count[0])
-    row_b = np.repeat(np.arange(n, dtype=np.int64), count[1])
-    hit = np.flatnonzero(b_match >= 0)                   # matched B polygons and their A polygons
-    hit_a = off_a[row_b[hit]] + b_match[hit]
-    same = cls[0][hit_a] == cls[1][hit]
+    hist, diffs = _compare_pairs(names, start, n, off, cls, match, b_iou, best, [x == 0 for x in act], obj, ({}, {}), pix, -1)
     Cn = len(names)
-    hist = np.zeros((Cn, COMPARE_HIST_BINS), np.int64)
-    np.add.at(hist, (cls[1][hit[same]], np.minimum((b_iou[hit[same]] * COMPARE_HIST_BINS).astype(np.int64),
-                                                   COMPARE_HIST_BINS - 1)), 1)
     skipped = np.stack([np.bincount(c[(x == 2) | (x == 3)], minlength=Cn)[:Cn] for c, x in zip(cls, act)], axis=1) if Cn \
         else np.zeros((0, 2), np.int64)
     keep = np.r_[np.arange(Cn), C].astype(np.int64)       # without the stand-in class of a chunk that has none
-    acc.add(names, conf[np.ix_(keep, keep)], hist)
-    acc.add_pixels(names, pconf[np.ix_(keep, keep)], skipped)
+    acc.sums.add(names, hist, skipped)
+    acc.conf = acc.matrix(acc.conf, names, conf[np.ix_(keep, keep)])
+    acc.pix = acc.matrix(acc.pix, names, pconf[np.ix_(keep, keep)])
     acc.rows.append(rows)
     acc.n_a.append(count[0])
     acc.n_b.append(count[1])
     acc.status.append(host_status)
     acc.row_pixels.append(np.concatenate([row_pixels, host_pixels[:, None]], axis=1))
-    miss, extra, rel_b = np.flatnonzero((act[0] == 0) & (a_match < 0)), np.flatnonzero((act[1] == 0) & (b_match < 0)), hit[~same]
-    rel_a = hit_a[~same]
-    k = (len(miss), len(extra), len(rel_b))
-    if sum(k):
-        absent = lambda m: np.full(m, -1, np.int64)      # noqa: E731
-        none = lambda m: np.full(m, None, object)        # noqa: E731
-        name_of = np.asarray(names + [None], object)
-        row = np.concatenate([row_a[miss], row_b[extra], row_b[rel_b]])
-        kind = np.repeat(np.arange(3), k)
-        at = np.concatenate([miss - off_a[row_a[miss]], extra - off_b[row_b[extra]], rel_a - off_a[row_b[rel_b]]])
-        order = np.lexsort((at, kind, row))
-        cols = (start + row, np.asarray(COMPARE_KINDS, object)[kind],
-                np.concatenate([obj[0][miss], absent(k[1]), obj[0][rel_a]]),
-                np.concatenate([absent(k[0]), obj[1][extra], obj[1][rel_b]]),
-                np.concatenate([name_of[cls[0][miss]], none(k[1]), name_of[cls[0][rel_a]]]),
-                np.concatenate([none(k[0]), name_of[cls[1][extra]], name_of[cls[1][rel_b]]]),
-                np.concatenate([np.zeros(k[0] + k[1]), b_iou[rel_b]]),
-                np.concatenate([a_best[miss], b_best[extra], b_iou[rel_b]]),
-                np.concatenate([pix[0][miss], absent(k[1]), pix[0][rel_a]]),
-                np.concatenate([absent(k[0]), pix[1][extra], pix[1][rel_b]]))
-        acc.diffs.append(tuple(c[order] for c in cols))
+    if diffs is not None:
+        acc.diffs.append(diffs)
 
 
 def _poly_compare_result(acc: _PolyCompareTotals, n: int, sources, params: tuple, mismatch, stats) -> PolygonComparison:
+    """_compare_result plus the polygon step's own: the pixel matrix, the skipped and pixel columns, the rows' status"""
     thr, by_label, max_pixels, max_pairs = params[:4]
-    classes = sorted(acc.index, key=lambda c: (c is None, str(c)))
-    perm = np.asarray([acc.index[c] for c in classes], np.int64)
-    pairs, missing, extra, hist = acc.pairs[np.ix_(perm, perm)], acc.missing[perm], acc.extra[perm], acc.hist[perm]
-    C = len(classes)
-    full, pfull = np.zeros((C + 1, C + 1), np.int64), np.zeros((C + 1, C + 1), np.int64)
-    full[:C, :C], full[:C, C], full[C, :C] = pairs, missing, extra
-    pfull[:C, :C], pfull[:C, C], pfull[C, :C], pfull[C, C] = acc.pix[np.ix_(perm, perm)], acc.pix_a[perm], acc.pix_b[perm], acc.pix_none
-    labels = pd.Index(classes + [COMPARE_NONE], dtype=object)
-    confusion = pd.DataFrame(full, index=labels, columns=labels)
-    plabels = pd.Index(classes + [COMPARE_BACKGROUND], dtype=object)
-    pixel_confusion = pd.DataFrame(pfull, index=plabels, columns=plabels)
-    agree = np.diagonal(pairs).copy() if C else np.zeros(0, np.int64)
+    status = np.asarray(POLY_COMPARE_STATUS, object)[np.concatenate(acc.status) if acc.status else np.zeros(0, np.uint8)]
+    if mismatch is not None:
+        status[mismatch] = "size_mismatch"
+    res, perm = _compare_result(acc, n, sources, "polygons", _POLY_COMPARE_DIFF_SPEC, {"status": status})
+    C = len(res["classes"])
+    pfull = acc.pix[np.ix_(perm, perm)]
+    plabels = pd.Index(res["classes"] + [COMPARE_BACKGROUND], dtype=object)
     both = np.diagonal(pfull)[:C].copy()
     a_px, b_px = pfull[:C].sum(axis=1), pfull[:, :C].sum(axis=0)
     union = a_px + b_px - both
     with np.errstate(invalid="ignore", divide="ignore"):
         pixel_iou = np.where(union > 0, both / np.where(union > 0, union, 1), np.nan)
-    skipped = acc.skipped[perm] if C else np.zeros((0, 2), np.int64)
-    per_class = pd.DataFrame({"class": pd.Series(classes, dtype=object), "a_polygons": full[:C].sum(axis=1),
-                              "b_polygons": full[:, :C].sum(axis=0), "agree": agree,
-                              "relabelled_to_other": pairs.sum(axis=1) - agree, "relabelled_from_other": pairs.sum(axis=0) - agree,
-                              "missing": missing, "extra": extra, "a_skipped": skipped[:, 0], "b_skipped": skipped[:, 1],
-                              "a_pixels": a_px, "b_pixels": b_px, "pixels_both": both, "pixel_iou": pixel_iou})
-    rows = np.concatenate(acc.rows) if acc.rows else np.zeros((0, 4), np.int64)
+    skipped = acc.sums.sums[1][perm[:C]]
+    res["per_class"].update(a_skipped=skipped[:, 0], b_skipped=skipped[:, 1], a_pixels=a_px, b_pixels=b_px, pixels_both=both,
+                            pixel_iou=pixel_iou)
     rpix = np.concatenate(acc.row_pixels) if acc.row_pixels else np.zeros((0, 3), np.int64)
-    status = np.asarray(POLY_COMPARE_STATUS, object)[np.concatenate(acc.status) if acc.status else np.zeros(0, np.uint8)]
-    if mismatch is not None:
-        status[mismatch] = "size_mismatch"
-    pr = {"row": np.arange(n, dtype=np.int64)}
-    if sources is not None:
-        pr["source"] = np.asarray(sources, object)
-    pr["status"] = status
-    pr["a_polygons"] = np.concatenate(acc.n_a) if acc.n_a else np.zeros(0, np.int64)
-    pr["b_polygons"] = np.concatenate(acc.n_b) if acc.n_b else np.zeros(0, np.int64)
-    pr.update({k: rows[:, j] for j, k in enumerate(_COMPARE_ROW_COLS)})
-    pr["pixels_agree_fg"], pr["pixels_fg"] = rpix[:, 0], rpix[:, 1]
     with np.errstate(invalid="ignore", divide="ignore"):
-        pr["fg_iou"] = np.where(rpix[:, 1] > 0, rpix[:, 0] / np.where(rpix[:, 1] > 0, rpix[:, 1], 1), np.nan)
-    differences = _parts_frame(acc.diffs, _POLY_COMPARE_DIFF_SPEC, sources)
-    if sources is not None:                              # row first, as in per_row
-        differences = differences[["row", "source", *differences.columns[2:]]]
+        fg_iou = np.where(rpix[:, 1] > 0, rpix[:, 0] / np.where(rpix[:, 1] > 0, rpix[:, 1], 1), np.nan)
+    res["per_row"].update(pixels_agree_fg=rpix[:, 0], pixels_fg=rpix[:, 1], fg_iou=fg_iou)
     n_pixels = int(rpix[:, 2].sum())
     seen = union > 0
-    totals = {"rows": n, "a_polygons": int(pr["a_polygons"].sum()), "b_polygons": int(pr["b_polygons"].sum()),
-              "matched": int(rows[:, :2].sum()), "agree": int(rows[:, 0].sum()), "relabelled": int(rows[:, 1].sum()),
-              "missing": int(rows[:, 2].sum()), "extra": int(rows[:, 3].sum()), "a_skipped": int(skipped[:, 0].sum()),
-              "b_skipped": int(skipped[:, 1].sum()),
-              **{f"rows_{s}": int((status == s).sum()) for s in (*POLY_COMPARE_STATUS, "size_mismatch")}, "pixels": n_pixels,
-              "pixel_accuracy": float(np.trace(pfull)) / n_pixels if n_pixels else float("nan"),
-              "mean_pixel_iou": float(pixel_iou[seen].mean()) if seen.any() else float("nan"),
-              "python_cells": acc.python_cells, "iou_threshold": thr, "by_label": by_label, "max_pixels_per_row": max_pixels,
-              "max_pairs_per_row": max_pairs}
+    res["totals"].update(
+        a_skipped=int(skipped[:, 0].sum()), b_skipped=int(skipped[:, 1].sum()),
+        **{f"rows_{s}": int((status == s).sum()) for s in (*POLY_COMPARE_STATUS, "size_mismatch")}, pixels=n_pixels,
+        pixel_accuracy=float(np.trace(pfull)) / n_pixels if n_pixels else float("nan"),
+        mean_pixel_iou=float(pixel_iou[seen].mean()) if seen.any() else float("nan"),
+        python_cells=acc.python_cells, iou_threshold=thr, by_label=by_label, max_pixels_per_row=max_pixels, max_pairs_per_row=max_pairs)
     if stats is not None:
-        stats.update(totals)
-    unpaired = pd.DataFrame({"key": np.zeros(0, object), "side": np.zeros(0, object)})
-    return PolygonComparison(classes, confusion, pixel_confusion, per_class, hist, pd.DataFrame(pr), differences, unpaired, totals)
+        stats.update(res["totals"])
+    return PolygonComparison(**{**res, "per_class": pd.DataFrame(res["per_class"]), "per_row": pd.DataFrame(res["per_row"])},
+                             pixel_confusion=pd.DataFrame(pfull, index=plabels, columns=plabels))
 
 
 def _poly_compare_rows(cells_a, cells_b, n, widths, heights, mismatch, params, be, stats, sources) -> PolygonComparison:
@@ -4855,20 +4801,14 @@ def _poly_compare_mismatch(sizes_a, sizes_b, rows_a, rows_b):
 
 
 def _poly_compare_tables(cells_a, sizes_a, keys_a, sources, cells_b, sizes_b, keys_b, key, params, be, stats) -> PolygonComparison:
-    """two tables (cells, (widths, heights), keys or None) -> the comparison of their aligned rows: by position without keys,
-    else on the keys (_compare_align, the box comparison's); sizes from A, a row whose two usable sizes differ is size_mismatch"""
-    cells_a, cells_b = np.asarray(cells_a, object), np.asarray(cells_b, object)
-    if keys_a is None:
-        rows_a = rows_b = np.arange(len(cells_a), dtype=np.int64)
-        only_a = only_b = np.zeros(0, np.int64)
-        keys_a = keys_b = np.zeros(0, object)
-    else:
-        rows_a, rows_b, only_a, only_b = _compare_align(keys_a, keys_b, key)
-    mismatch = _poly_compare_mismatch(sizes_a, sizes_b, rows_a, rows_b)
-    widths, heights = (None if v is None else np.asarray(v)[rows_a] for v in sizes_a)
-    res = _poly_compare_rows(cells_a[rows_a], cells_b[rows_b], len(rows_a), widths, heights, mismatch, params, be, None,
-                             None if sources is None else np.asarray(sources, object)[rows_a])
-    return _compare_aligned(res, rows_a, keys_a, only_a, keys_b, only_b, stats)
+    """the box comparison's _compare_tables over two tables that also carry (widths, heights): the sizes come from A, and a row
+    whose two usable sizes differ is size_mismatch"""
+    def compare(a, b, src, rows_a, rows_b):
+        mismatch = _poly_compare_mismatch(sizes_a, sizes_b, rows_a, rows_b)
+        widths, heights = (None if v is None else np.asarray(v)[rows_a] for v in sizes_a)
+        return _poly_compare_rows(a, b, len(rows_a), widths, heights, mismatch, params, be, None, src)
+
+    return _compare_tables(compare, cells_a, keys_a, sources, cells_b, keys_b, key, stats)
 
 
 def compare_polygons_frame(df_a: pd.DataFrame, df_b: Optional[pd.DataFrame] = None, json_col: str = ANNOTATION_COL, other_col=None,
@@ -4884,35 +4824,9 @@ def compare_polygons_frame(df_a: pd.DataFrame, df_b: Optional[pd.DataFrame] = No
     params = _poly_compare_params(iou_threshold, by_label, max_pixels_per_row, max_pairs_per_row, batch_pixels, batch_pairs)
     be = _step_backend(backend, "compare_polygons")
     wa, ha, sources = _size_columns(df_a, width_col, height_col)
-    if df_b is None:
-        if other_col is None:
-            raise ValueError("with one frame, other_col names the column to compare json_col against")
-        return _poly_compare_tables(df_a[json_col].to_numpy(), (wa, ha), None, sources, df_a[other_col].to_numpy(), (None, None),
-                                    None, None, params, be, stats)
-    col_b = other_col if other_col is not None else json_col
-    wb, hb, _ = _size_columns(df_b, width_col, height_col)
-    if key is None:
-        if len(df_b) != len(df_a):
-            raise ValueError(f"without a key the frames are compared by position: {len(df_a)} against {len(df_b)} rows")
-        return _poly_compare_tables(df_a[json_col].to_numpy(), (wa, ha), None, sources, df_b[col_b].to_numpy(), (wb, hb), None, None,
-                                    params, be, stats)
-    return _poly_compare_tables(df_a[json_col].to_numpy(), (wa, ha), df_a[key].to_numpy(), sources, df_b[col_b].to_numpy(), (wb, hb),
-                                df_b[key].to_numpy(), key, params, be, stats)
-
-
-def _write_polygon_comparison(res: PolygonComparison, output_dir) -> dict:
-    out = Path(output_dir)
-    out.mkdir(parents=True, exist_ok=True)
-    paths = {k: str(out / f"polygon_compare_{k}.csv") for k in ("confusion", "pixels", "classes", "differences", "rows")}
-    paths["hist"] = str(out / "polygon_compare_hist.npz")
-    res.confusion.to_csv(paths["confusion"], index_label="a_class", encoding="utf-8-sig")
-    res.pixel_confusion.to_csv(paths["pixels"], index_label="a_class", encoding="utf-8-sig")
-    res.per_class.to_csv(paths["classes"], index=False, encoding="utf-8-sig")
-    res.differences.to_csv(paths["differences"], index=False, encoding="utf-8-sig")
-    res.per_row.to_csv(paths["rows"], index=False, encoding="utf-8-sig")
-    np.savez(paths["hist"], classes=np.asarray([COMPARE_NONE if c is None else c for c in res.classes], dtype=str),
-             hist_iou=res.hist_iou)
-    return paths
+    cells_a, keys_a, cells_b, keys_b = _compare_frames(df_a, df_b, json_col, other_col, key)
+    sizes_b = (None, None) if df_b is None else _size_columns(df_b, width_col, height_col)[:2]
+    return _poly_compare_tables(cells_a, (wa, ha), keys_a, sources, cells_b, sizes_b, keys_b, key, params, be, stats)
 
 
 def compare_polygons_csv(a_csv, b_csv, output_dir, json_col: str = ANNOTATION_COL, key="source", width_col: str = "width",
@@ -4925,28 +4839,14 @@ def compare_polygons_csv(a_csv, b_csv, output_dir, json_col: str = ANNOTATION_CO
     ..., both returning None.  key=None compares by position.  -> dict(totals, paths=...)"""
     params = _poly_compare_params(iou_threshold, by_label, max_pixels_per_row, max_pairs_per_row, batch_pixels, batch_pairs)
     be = _step_backend(backend, "compare_polygons")
-    sides, routes = [], []
-    for path in (a_csv, b_csv):
-        side = _csv_route(
-            "compare_polygons", path, json_col,
-            lambda table: (table.light, _fc_cells(table.heavy[json_col], 0, table.n_rows)),
-            lambda df: (df, df[json_col].to_numpy()))
-        if side is None:
-            return None
-        routes.append(LAST_IO_PATH["compare_polygons"])
-        if key is not None and key not in side[0].columns:
-            print(f"错误：缺少必要列 {key}")
-            return None
-        sides.append(side)
-    LAST_IO_PATH["compare_polygons"] = "native" if routes == ["native", "native"] else "pandas"
-    (light_a, cells_a), (light_b, cells_b) = sides
+    read = _compare_read("compare_polygons", a_csv, b_csv, json_col, key)
+    if read is None:
+        return None
+    light_a, cells_a, keys_a, light_b, cells_b, keys_b = read
     wa, ha, sources = _size_columns(light_a, width_col, height_col)
-    wb, hb, _ = _size_columns(light_b, width_col, height_col)
-    if key is None and len(cells_a) != len(cells_b):
-        raise ValueError(f"without a key the files are compared by position: {len(cells_a)} against {len(cells_b)} rows")
-    res = _poly_compare_tables(cells_a, (wa, ha), None if key is None else light_a[key].to_numpy(), sources, cells_b, (wb, hb),
-                               None if key is None else light_b[key].to_numpy(), key, params, be, None)
-    return {**res.totals, "paths": _write_polygon_comparison(res, output_dir)}
+    res = _poly_compare_tables(cells_a, (wa, ha), keys_a, sources, cells_b, _size_columns(light_b, width_col, height_col)[:2], keys_b,
+                               key, params, be, None)
+    return {**res.totals, "paths": _write_comparison(res, output_dir, "polygon_compare")}
 
 
 def _dataset_dir_name(excel_path: Path, idx_excel: int, used_dir_names: set) -> tuple:

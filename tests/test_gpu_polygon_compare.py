@@ -13,6 +13,7 @@ import polygon_compare_ref as R
 import test_gpu_polygon_raster as k21
 from polygon_compare_tables import (RANDOM, assert_same_cover, blob, box, comb, random_rows, random_table, random_want, raster_side,
                                     shared_table, shared_want, strip_rows, table)
+from test_compare_path_cpu import TWIN_CONFIGS, assert_one_story, twin_results
 from deal_yolo_daya_amd.core import processor as P
 
 pytestmark = pytest.mark.gpu
@@ -335,6 +336,13 @@ def test_long_sparse_table(native):
 
 
 # ----------------------------------------------------------------------------------------------- through the product
+@pytest.mark.parametrize("thr,by_label", TWIN_CONFIGS)
+def test_k18_and_k22_tell_one_story(native, thr, by_label):
+    """the twin table of tests/test_compare_path_cpu.py (24 rows of integer rectangles, as boxes and as four-corner polygons)
+    through K18 and K22: the same assertions as between the restatements, the IoU columns bit for bit"""
+    assert_one_story(*twin_results(thr, by_label, None), by_label)
+
+
 def test_compare_polygons_csv_end_to_end(native, tmp_path):
     from helpers import OracleBackend
 

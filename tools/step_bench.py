@@ -5,6 +5,7 @@ SURVEY §8d: includes read_csv / flatten / H2D / kernels / D2H / emit / to_csv, 
 
     python tools/step_bench.py --rows 20000
     python tools/step_bench.py --rows 20000 --coco-rle      (only export_coco_csv: polygon lists beside segmentation="rle", one line)
+    python tools/step_bench.py --rows 20000 --compare       (only compare_boxes_frame and compare_polygons_cells, one line)
 """
 import argparse
 import json
@@ -15,12 +16,40 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+COMPARE_POLYGON_ROWS = 25000         # --compare: at most so many rows go to the polygon comparison, about a second on one MI355X
+
+
+def _other_cells(cells, rng, names=("猫", "new")):
+    """the other annotation set of --compare: about 10 % of the objects dropped, 10 % moved (half a little, half far away: a
+    two-point box by its second corner, a polygon as a whole), 5 % renamed, one row in ten with its objects reversed"""
+    out = []
+    for c in cells:
+        doc = json.loads(c)
+        objs = []
+        for o in doc.get("objects", []):
+            u = rng.random()
+            if u < 0.10:
+                continue
+            pts = o["polygon"]["ptList"]
+            if u < 0.20:
+                for pt in pts[1:] if len(pts) == 2 else pts:
+                    pt["y"] += 2.5 if u < 0.15 else 400
+            elif u < 0.25:
+                o["name"] = names[int(rng.integers(0, len(names)))]
+            objs.append(o)
+        if rng.random() < 0.1:
+            objs.reverse()
+        doc["objects"] = objs
+        out.append(json.dumps(doc, ensure_ascii=False))
+    return out
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=20000)
     ap.add_argument("--skip-cpu", action="store_true")
     ap.add_argument("--coco-rle", action="store_true", help="time export_coco_csv with polygon lists and with run-length masks, nothing else")
+    ap.add_argument("--compare", action="store_true", help="time compare_boxes_frame and compare_polygons_cells against a perturbed twin, nothing else")
     args = ap.parse_args()
 
     import pandas as pd
@@ -58,6 +87,28 @@ def main():
                     line[f"export_coco_csv_{tag}"].update(
                         device_step_s=round(res["rle_device_seconds"], 3), python_format_s=round(res["rle_format_seconds"], 3),
                         python_format_share=round(res["rle_format_seconds"] / s, 3), empty=res["empty"])
+        print(json.dumps(line, ensure_ascii=False))
+        return
+
+    if args.compare:
+        # the two comparison steps end to end, B made from A by _other_cells: compare_boxes_frame on the replace step's boxes,
+        # aligned on `source`; compare_polygons_cells on the first COMPARE_POLYGON_ROWS rows' polygons (1920 x 1080 images)
+        import numpy as np
+
+        line = {"tool": "step_bench --compare", **out}
+        kept = P.replace_ptlist_frame(df)[0].reset_index(drop=True)
+        kept["source"] = kept["source"] + "#" + kept.index.astype(str)      # synth repeats sources for the dedup step: one key per row
+        other = kept.assign(**{P.BBOX_COL: pd.Series(_other_cells(kept[P.BBOX_COL].tolist(), np.random.default_rng(52)), dtype=object)})
+        n_poly = min(args.rows, COMPARE_POLYGON_ROWS)
+        poly_a = df[synth.ANN_COL].tolist()[:n_poly]
+        poly_b = _other_cells(poly_a, np.random.default_rng(53))
+        size = ([t.width] * n_poly, [t.height] * n_poly)
+        for tag, rows, fn in (("compare_boxes_frame", len(kept), lambda: P.compare_boxes_frame(kept, other)),
+                              ("compare_polygons_cells", n_poly, lambda: P.compare_polygons_cells(poly_a, poly_b, *size))):
+            fn()
+            s, res = sorted((clock(fn) for _ in range(3)), key=lambda r: r[0])[1]
+            line[tag] = {"s": round(s, 3), "rows": rows, "rows_per_s": round(rows / s),
+                         **{k: res.totals[k] for k in ("agree", "relabelled", "missing", "extra")}}
         print(json.dumps(line, ensure_ascii=False))
         return
 
