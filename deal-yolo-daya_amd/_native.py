@@ -83,6 +83,9 @@ SIGNATURES = {
     "dyd_compare_boxes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                         C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dyd_eval_match_boxes": (C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
+    "dyd_eval_accumulate": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+                            + [C.c_void_p] * 8),
     "dyd_json_emit_repaired": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_void_p)]),
     "dyd_json_emit_simplified": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
@@ -658,6 +661,55 @@ def compare_boxes(a_box4, a_row_off, a_cls, b_box4, b_row_off, b_cls, n_classes:
                                   n_classes, float(thr), int(bool(by_label)), _ptr(a_match), _ptr(b_match), _ptr(b_iou),
                                   _ptr(a_best), _ptr(b_best), _ptr(rows), _ptr(conf)), "dyd_compare_boxes")
     return a_match, b_match, b_iou, a_best, b_best, rows, conf
+
+
+def eval_match_boxes(gt_box4, gt_row_off, gt_cls, dt_box4, dt_row_off, dt_cls, dt_score, n_classes: int, iou_thr,
+                     max_dets: int = 100):
+    """K24's matching over host arrays: a ground-truth table and a detection table with scores over the same rows ->
+    (dt_state [D] i32, dt_tp [D] u32, dt_gt [D] i32, dt_iou [D] f64, dt_best [D] f64, gt_hit [G] u32, gt_best [G] f64).  See
+    include/dyd.h for the rule."""
+    gt_box4, gt_row_off, gt_cls, ng = _compare_side(gt_box4, gt_row_off, gt_cls, "GT")
+    dt_box4, dt_row_off, dt_cls, nd = _compare_side(dt_box4, dt_row_off, dt_cls, "detections")
+    n = len(gt_row_off) - 1
+    if len(dt_row_off) - 1 != n:
+        raise ValueError("the two tables must cover the same rows")
+    dt_score = np.ascontiguousarray(dt_score, dtype=np.float64).reshape(-1)
+    if dt_score.size != nd:
+        raise ValueError("dt_score must hold one score per detection")
+    iou_thr = np.ascontiguousarray(iou_thr, dtype=np.float64).reshape(-1)
+    state, tp, gt = np.zeros(nd, np.int32), np.zeros(nd, np.uint32), np.full(nd, -1, np.int32)
+    iou, best = np.zeros(nd, np.float64), np.zeros(nd, np.float64)
+    hit, gbest = np.zeros(ng, np.uint32), np.zeros(ng, np.float64)
+    check(lib().dyd_eval_match_boxes(_ptr(gt_box4), _ptr(gt_row_off), _ptr(gt_cls), _ptr(dt_box4), _ptr(dt_row_off), _ptr(dt_cls),
+                                     _ptr(dt_score), n, int(n_classes), _ptr(iou_thr), int(iou_thr.size), int(max_dets),
+                                     _ptr(state), _ptr(tp), _ptr(gt), _ptr(iou), _ptr(best), _ptr(hit), _ptr(gbest)),
+          "dyd_eval_match_boxes")
+    return state, tp, gt, iou, best, hit, gbest
+
+
+def eval_accumulate(cls, score, tp, n_classes: int, n_thresholds: int, npig, rec):
+    """K24's accumulation over host arrays: the evaluated detections of a whole table in table order (class, score, matched-at
+    mask), npig [C] GT boxes per class, rec [R] recall points -> (precision [C,T,R], score_at [C,T,R], recall [C,T], ap [C,T],
+    best_f1 [C,T], best_score [C,T] f64, best_tp [C,T], best_dets [C,T] i64).  See include/dyd.h for the rule."""
+    cls = np.ascontiguousarray(cls, dtype=np.int32).reshape(-1)
+    score = np.ascontiguousarray(score, dtype=np.float64).reshape(-1)
+    tp = np.ascontiguousarray(tp, dtype=np.uint32).reshape(-1)
+    if not cls.size == score.size == tp.size:
+        raise ValueError("cls, score and tp must hold one entry per detection")
+    C_, T = int(n_classes), int(n_thresholds)
+    npig = np.ascontiguousarray(npig, dtype=np.int64).reshape(-1)
+    if npig.size != C_:
+        raise ValueError("npig must hold one count per class")
+    rec = np.ascontiguousarray(rec, dtype=np.float64).reshape(-1)
+    R = rec.size
+    shape = (C_, max(T, 0))
+    precision, score_at = np.zeros((*shape, R), np.float64), np.zeros((*shape, R), np.float64)
+    recall, ap, f1, bs = (np.zeros(shape, np.float64) for _ in range(4))
+    btp, bd = np.zeros(shape, np.int64), np.zeros(shape, np.int64)
+    check(lib().dyd_eval_accumulate(_ptr(cls), _ptr(score), _ptr(tp), cls.size, C_, T, _ptr(npig), _ptr(rec), R, _ptr(precision),
+                                    _ptr(score_at), _ptr(recall), _ptr(ap), _ptr(f1), _ptr(bs), _ptr(btp), _ptr(bd)),
+          "dyd_eval_accumulate")
+    return precision, score_at, recall, ap, f1, bs, btp, bd
 
 
 def bbox_iou_fused(xy: np.ndarray, pt_off: np.ndarray, box_off: np.ndarray, min_boxes: int, thr: float,

@@ -2979,6 +2979,354 @@ def compare_boxes_csv(a_csv, b_csv, output_dir, json_col: str = BBOX_COL, key="s
     return {**res.totals, "paths": _write_comparison(res, output_dir, "box_compare")}
 
 
+# =============================================================================== f6b  scored box evaluation
+# What a model's predictions, or model-assisted pre-labels, are worth against the corrected table: average precision per class and
+# the confidence at which to accept them.  Boxes are the comparison's (_box_chunk, one class list for both sides); every
+# predicted box carries a score.  K24 (csrc/k24_eval.hip, rule in include/dyd.h and DESIGN §5v, after COCOeval's evaluateImg /
+# accumulate for boxes, area range "all", no crowd regions) matches per image row the detections of each class in score order to
+# the free ground-truth box of that class with the largest reference IoU, at every threshold on its own, and then builds per
+# class and threshold the precision / recall curve over the whole table.  Native scan of both sides -> one matching launch per
+# chunk -> one accumulation after the last chunk -> frames.
+EVAL_STATES = ("evaluated", "cut", "bad_score")      # K24 codes 0..2
+EVAL_RECALL_POINTS = np.linspace(0, 1, 101)          # computed once and handed down, as the thresholds are
+EVAL_IOU_THRESHOLDS = np.linspace(0.5, 0.95, 10)
+_EVAL_DET_SPEC = (("row", np.int64), ("object", np.int64), ("name", object), ("score", np.float64), ("state", object),
+                  ("tp_thresholds", np.int64), ("gt_object", np.int64), ("iou", np.float64), ("best_iou", np.float64))
+_EVAL_MISSED_SPEC = (("row", np.int64), ("object", np.int64), ("name", object), ("best_iou", np.float64),
+                     (("x1", "y1", "x2", "y2"), np.float64))
+
+
+class BoxEvaluation:
+    """Result of evaluate_boxes_*: classes (sorted as str, None last), iou_thresholds, per_class, precision and score_at
+    ([C, T, 101] over the recall points 0, 0.01 .. 1), recall and ap ([C, T]), per_row, detections (one line per predicted box),
+    missed (ground-truth boxes unmatched at the first threshold), unpaired (keys of rows found in the predictions only), totals.
+    A class without ground truth has NaN curves and is left out of every mean."""
+
+    def __init__(self, classes, iou_thresholds, per_class, precision, score_at, recall, ap, per_row, detections, missed, unpaired,
+                 totals):
+        self.classes = classes
+        self.iou_thresholds = iou_thresholds
+        self.per_class = per_class
+        self.precision = precision
+        self.score_at = score_at
+        self.recall = recall
+        self.ap = ap
+        self.per_row = per_row
+        self.detections = detections
+        self.missed = missed
+        self.unpaired = unpaired
+        self.totals = totals
+
+    def __repr__(self):
+        return f"{type(self).__name__}({len(self.classes)} classes, {self.totals})"
+
+
+def _eval_thresholds(iou_thresholds) -> np.ndarray:
+    if iou_thresholds is None:
+        return EVAL_IOU_THRESHOLDS
+    values = [iou_thresholds] if isinstance(iou_thresholds, _NUMBER_TYPES) else list(iou_thresholds)
+    if not 1 <= len(values) <= 32:
+        raise ValueError(f"iou_thresholds must hold 1 to 32 values, got {len(values)}")
+    for v in values:
+        if isinstance(v, bool) or not isinstance(v, _NUMBER_TYPES) or not 0.0 < float(v) <= 1.0:
+            raise ValueError(f"iou_thresholds must be numbers in (0, 1], got {v!r}")
+    return np.asarray(values, np.float64)
+
+
+def _eval_max_dets(max_dets) -> int:
+    if isinstance(max_dets, bool) or not isinstance(max_dets, (int, np.integer)) or max_dets < 1:
+        raise ValueError(f"max_dets must be an int >= 1, got {max_dets!r}")
+    return min(int(max_dets), (1 << 31) - 1)
+
+
+def _eval_number(v) -> float:
+    """a score as f64; what is no number (a bool included) is NaN, which K24 reports as bad_score"""
+    if isinstance(v, bool) or not isinstance(v, _NUMBER_TYPES):
+        return float("nan")
+    try:
+        return float(v)
+    except OverflowError:
+        return float("nan")
+
+
+def _eval_mean(values) -> float:
+    """the mean of the values that are not NaN, added in order; NaN without one"""
+    vals = [float(v) for v in values if v == v]
+    return sum(vals) / len(vals) if vals else float("nan")
+
+
+def _eval_scores(cells, off, obj, scores, score_key, start: int, acc) -> np.ndarray:
+    """the score of every predicted box of a chunk: scores[row][object] or, with score_key, that member of the box's object read
+    by CPython's json"""
+    out = np.full(int(off[-1]), np.nan)
+    for i in np.flatnonzero(np.diff(off)).tolist():
+        p, q = int(off[i]), int(off[i + 1])
+        if score_key is not None:
+            acc.python_score_cells += 1
+            objs = json.loads(cells[i]).get("objects", [])
+            for b in range(p, q):
+                o = objs[obj[b]]
+                out[b] = _eval_number(o.get(score_key)) if isinstance(o, dict) else np.nan
+            continue
+        seq = scores[start + i]
+        if seq is None or len(seq) <= int(obj[p:q].max()):
+            raise ValueError(f"scores of row {start + i} must hold one number per entry of the cell's objects list: a box sits in "
+                             f"object {int(obj[p:q].max())}, got {'None' if seq is None else f'{len(seq)} scores'}")
+        for b in range(p, q):
+            out[b] = _eval_number(seq[obj[b]])
+    return out
+
+
+class _EvalTotals:
+    """what the chunks of an evaluation leave: the classes in first-seen order (None = the names that are no str), per chunk the
+    detections' and the ground-truth boxes' columns"""
+
+    def __init__(self):
+        self.index = {}
+        self.dets, self.gts, self.det_lines, self.missed = [], [], [], []
+        self.n_gt, self.n_dt = [], []
+        self.python_cells = self.python_score_cells = 0
+
+
+def _eval_chunk(cells_gt, cells_pred, scores, score_key, thr, max_dets: int, be, acc: _EvalTotals, start: int):
+    """one chunk of rows: both box tables (_box_chunk) on one class list -> K24's matching -> the chunk's columns"""
+    sides = []
+    for cells in (cells_gt, cells_pred):
+        t = _box_chunk(cells)
+        if t.scan is not None:
+            t.scan.close()
+        sides.append(t)
+    tg, td = sides
+    n = len(cells_gt)
+    acc.python_cells += len(tg.irregular) + len(td.irregular)
+    names, cls = _compare_classes(tg.names, tg.cls, td.names, td.cls)
+    off = tg.row_off, td.row_off
+    box = [np.asarray(t.box4, np.float64).reshape(-1, 4) for t in sides]
+    obj = [np.asarray(t.obj, np.int64) for t in sides]
+    score = _eval_scores(cells_pred, off[1], obj[1], scores, score_key, start, acc)
+    state, tp, gt, iou, best, hit, g_best = be.eval_match_boxes(box[0], off[0].astype(np.int32), cls[0], box[1],
+                                                                off[1].astype(np.int32), cls[1], score, len(names), thr, max_dets)
+    state, tp, gt, hit = (np.asarray(v, np.int64) for v in (state, tp, gt, hit))
+    iou, best, g_best = (np.asarray(v, np.float64) for v in (iou, best, g_best))
+    to = np.asarray([acc.index.setdefault(nm, len(acc.index)) for nm in names], np.int64)
+    row_g = np.repeat(np.arange(n, dtype=np.int64), np.diff(off[0]))
+    row_d = np.repeat(np.arange(n, dtype=np.int64), np.diff(off[1]))
+    cls_g, cls_d = to[cls[0]] if len(to) else np.zeros(0, np.int64), to[cls[1]] if len(to) else np.zeros(0, np.int64)
+    acc.gts.append((start + row_g, cls_g, hit))
+    acc.dets.append((start + row_d, cls_d, score, state, tp))
+    acc.n_gt.append(np.diff(off[0]))
+    acc.n_dt.append(np.diff(off[1]))
+    every = np.arange(len(row_d), dtype=np.int64)
+    gt_at = np.where(gt >= 0, off[0][row_d] + gt, 0)
+    acc.det_lines.append((start + row_d, obj[1], _compare_names(names, cls[1], td.odd_names, every), score,
+                          np.asarray(EVAL_STATES, object)[state], np.asarray([bin(int(v)).count("1") for v in tp], np.int64),
+                          np.where(gt >= 0, obj[0][gt_at] if len(obj[0]) else -1, -1), iou, best))
+    miss = np.flatnonzero((hit & 1) == 0)
+    if len(miss):
+        acc.missed.append((start + row_g[miss], obj[0][miss], _compare_names(names, cls[0], tg.odd_names, miss), g_best[miss],
+                           box[0][miss]))
+
+
+def _eval_result(acc: _EvalTotals, n: int, thr, max_dets: int, be, sources) -> BoxEvaluation:
+    classes = sorted(acc.index, key=lambda c: (c is None, str(c)))
+    C, T = len(classes), len(thr)
+    rank = np.zeros(len(acc.index), np.int64)
+    rank[[acc.index[c] for c in classes]] = np.arange(C)
+
+    def column(parts, k, dtype):
+        return np.concatenate([p[k] for p in parts]).astype(dtype) if parts else np.zeros(0, dtype)
+
+    row_g, cls_g, hit = (column(acc.gts, k, np.int64) for k in range(3))
+    row_d, cls_d = column(acc.dets, 0, np.int64), column(acc.dets, 1, np.int64)
+    score, state, tp = column(acc.dets, 2, np.float64), column(acc.dets, 3, np.int64), column(acc.dets, 4, np.int64)
+    cls_g, cls_d = rank[cls_g], rank[cls_d]
+    npig = np.bincount(cls_g, minlength=C).astype(np.int64)
+    ev = state == 0
+    if int(ev.sum()) >= (1 << 31):
+        raise ValueError("the table holds 2^31 evaluated detections or more")
+    precision, score_at, recall, ap, f1, best_score, best_tp, best_dets = (
+        np.asarray(v) for v in be.eval_accumulate(cls_d[ev].astype(np.int32), score[ev], tp[ev].astype(np.uint32), C, T, npig,
+                                                  EVAL_RECALL_POINTS))
+    tp0 = (tp & 1) == 1
+
+    def count(mask):
+        return np.bincount(cls_d[mask], minlength=C).astype(np.int64)
+
+    def at(value):
+        k = np.flatnonzero(thr == value)
+        return int(k[0]) if len(k) else None
+
+    k50, k75 = at(0.5), at(0.75)
+    nan_c = np.full(C, np.nan)
+    evaluated, matched = count(ev), count(tp0)
+    bd = best_dets[:, 0] if C else np.zeros(0, np.int64)
+    bt = best_tp[:, 0] if C else np.zeros(0, np.int64)
+    with np.errstate(all="ignore"):
+        per_class = pd.DataFrame({
+            "class": pd.Series(classes, dtype=object), "gt_boxes": npig, "detections": count(np.ones(len(cls_d), bool)),
+            "evaluated": evaluated, "cut": count(state == 1), "bad_score": count(state == 2),
+            "ap": np.asarray([_eval_mean(ap[c]) for c in range(C)], np.float64),
+            "ap50": ap[:, k50] if k50 is not None else nan_c, "ap75": ap[:, k75] if k75 is not None else nan_c,
+            "recall": np.asarray([_eval_mean(recall[c]) for c in range(C)], np.float64),
+            "tp": matched, "fp": evaluated - matched, "fn": npig - matched,
+            "best_f1": f1[:, 0] if C else nan_c, "best_score": best_score[:, 0] if C else nan_c,
+            "precision_at_best": np.where(bd > 0, bt / np.where(bd > 0, bd, 1), np.nan),
+            "recall_at_best": np.where(bd > 0, bt / np.where(npig > 0, npig, 1), np.nan)})
+    pr = {"row": np.arange(n, dtype=np.int64)}
+    if sources is not None:
+        pr["source"] = np.asarray(sources, object)
+    tp_r = np.bincount(row_d[tp0], minlength=n).astype(np.int64)
+    n_gt = np.concatenate(acc.n_gt) if acc.n_gt else np.zeros(0, np.int64)
+    pr.update({"gt_boxes": n_gt, "detections": np.concatenate(acc.n_dt) if acc.n_dt else np.zeros(0, np.int64), "tp": tp_r,
+               "fp": np.bincount(row_d[ev], minlength=n).astype(np.int64) - tp_r, "fn": n_gt - tp_r})
+    frames = []
+    for parts, spec in ((acc.det_lines, _EVAL_DET_SPEC), (acc.missed, _EVAL_MISSED_SPEC)):
+        frame = _parts_frame(parts, spec, sources)
+        frames.append(frame[["row", "source", *frame.columns[2:]]] if sources is not None else frame)
+    has = npig > 0
+    totals = {"rows": n, "gt_boxes": int(npig.sum()), "detections": len(cls_d), "evaluated": int(ev.sum()),
+              "cut": int((state == 1).sum()), "bad_score": int((state == 2).sum()),
+              "map": _eval_mean(per_class["ap"].to_numpy()[has]),
+              "map50": _eval_mean(ap[has, k50]) if k50 is not None else float("nan"),
+              "map75": _eval_mean(ap[has, k75]) if k75 is not None else float("nan"),
+              "mar": _eval_mean(per_class["recall"].to_numpy()[has]), "python_cells": acc.python_cells,
+              "python_score_cells": acc.python_score_cells, "max_dets": max_dets}
+    unpaired = pd.DataFrame({"key": np.zeros(0, object)})
+    return BoxEvaluation(classes, thr, per_class, precision, score_at, recall, ap, pd.DataFrame(pr), frames[0], frames[1], unpaired,
+                         totals)
+
+
+def evaluate_boxes_cells(cells_gt, cells_pred, scores=None, score_key=None, iou_thresholds=None, max_dets: int = 100,
+                         backend=None, stats: Optional[dict] = None, sources=None) -> BoxEvaluation:
+    """Scored evaluation of predicted annotation cells against the ground-truth cells of the same images, row by row (see the
+    section comment) -> BoxEvaluation.  Exactly one of ``scores`` (per row a sequence with one number per entry of the predicted
+    cell's "objects" list, None for a row without predictions) and ``score_key`` (the number is that member of each predicted
+    object) gives the scores; a score that is missing or no finite number makes the box `bad_score`, which takes no part.
+    score_key reads every predicted cell that holds a box with CPython's json, at Python speed:
+    totals["python_score_cells"] counts them.  iou_thresholds: numbers in (0, 1], at most 32, default 0.5, 0.55 .. 0.95;
+    per (row, class) the max_dets best-scored detections are evaluated.  ``sources`` (optional) adds a source column."""
+    thr, max_dets = _eval_thresholds(iou_thresholds), _eval_max_dets(max_dets)
+    if (scores is None) == (score_key is None):
+        raise ValueError("exactly one of scores and score_key must be given")
+    be = _step_backend(_step_backend(backend, "eval_match_boxes"), "eval_accumulate")
+    cells_gt = cells_gt.to_numpy() if hasattr(cells_gt, "to_numpy") else cells_gt
+    cells_pred = cells_pred.to_numpy() if hasattr(cells_pred, "to_numpy") else cells_pred
+    n = len(cells_gt)
+    if len(cells_pred) != n:
+        raise ValueError(f"the two lists must hold one cell per image each: {n} against {len(cells_pred)} cells")
+    if scores is not None and len(scores) != n:
+        raise ValueError(f"scores must hold one entry per row: {len(scores)} against {n} rows")
+    acc = _EvalTotals()
+    for s0, s1, chunk in _chunks(n, cells_gt):
+        _eval_chunk(chunk, cells_pred[s0:s1], scores, score_key, thr, max_dets, be, acc, s0)
+    res = _eval_result(acc, n, thr, max_dets, be, sources)
+    if stats is not None:
+        stats.update(res.totals)
+    return res
+
+
+def _eval_score_cells(col) -> list:
+    """a score column -> per row a sequence of numbers or None: its cells are JSON lists or Python sequences"""
+    out = []
+    for v in col:
+        if isinstance(v, str):
+            try:
+                v = json.loads(v)
+            except ValueError:
+                v = None
+        out.append(v if isinstance(v, (list, tuple, np.ndarray)) else None)
+    return out
+
+
+def _eval_tables(cells_gt, keys_gt, sources, cells_pred, keys_pred, key, score_cells, score_key, thr, max_dets, backend,
+                 stats) -> BoxEvaluation:
+    """two tables (cells, keys or None) -> the evaluation over ALL rows of the ground truth, in its positions: a row that the
+    predictions lack is evaluated without detections (its boxes are missed, as COCO counts them), a row found in the predictions
+    only is not evaluated and listed in `unpaired`"""
+    cells_gt, cells_pred = np.asarray(cells_gt, object), np.asarray(cells_pred, object)
+    only_gt = only_pred = np.zeros(0, np.int64)
+    if keys_gt is not None:
+        rows_gt, rows_pred, only_gt, only_pred = _compare_align(keys_gt, keys_pred, key)
+        aligned = np.full(len(cells_gt), "{}", object)
+        aligned[rows_gt] = cells_pred[rows_pred]
+        cells_pred = aligned
+        if score_cells is not None:
+            picked = [None] * len(cells_gt)
+            for a, b in zip(rows_gt.tolist(), rows_pred.tolist()):
+                picked[a] = score_cells[b]
+            score_cells = picked
+    res = evaluate_boxes_cells(cells_gt, cells_pred, score_cells, score_key, thr, max_dets, backend, None, sources)
+    res.unpaired = pd.DataFrame({"key": np.asarray(keys_pred, object)[only_pred] if len(only_pred) else np.zeros(0, object)})
+    res.totals.update(rows_only_gt=len(only_gt), rows_only_pred=len(only_pred))
+    if stats is not None:
+        stats.update(res.totals)
+    return res
+
+
+def _eval_score_source(score_col, score_key):
+    if (score_col is None) == (score_key is None):
+        raise ValueError("exactly one of score_col and score_key must be given")
+
+
+def evaluate_boxes_frame(df_gt: pd.DataFrame, df_pred: Optional[pd.DataFrame] = None, json_col: str = BBOX_COL, other_col=None,
+                         key="source", score_col=None, score_key=None, iou_thresholds=None, max_dets: int = 100, backend=None,
+                         stats: Optional[dict] = None) -> BoxEvaluation:
+    """Scored evaluation of two annotation columns, the frames chosen as compare_boxes_frame chooses them: json_col against
+    other_col of df_gt, two frames by position (key=None), or two frames on the column `key`.  The scores come from
+    ``score_col``, a column of the predictions' frame whose cells are JSON lists (or Python sequences) with one number per
+    entry of the cell's "objects" list, or from ``score_key`` (see evaluate_boxes_cells).  Unlike the comparison, a row found in
+    df_gt only is evaluated, without detections; a row found in the predictions only is not: ``unpaired`` lists its key and
+    totals["rows_only_pred"] counts it.  Rows are positions in df_gt."""
+    thr, max_dets = _eval_thresholds(iou_thresholds), _eval_max_dets(max_dets)
+    _eval_score_source(score_col, score_key)
+    sources = df_gt["source"].to_numpy() if "source" in df_gt.columns else None
+    cells_gt, keys_gt, cells_pred, keys_pred = _compare_frames(df_gt, df_pred, json_col, other_col, key)
+    pred = df_gt if df_pred is None else df_pred
+    score_cells = _eval_score_cells(pred[score_col].tolist()) if score_col is not None else None
+    return _eval_tables(cells_gt, keys_gt, sources, cells_pred, keys_pred, key, score_cells, score_key, thr, max_dets, backend, stats)
+
+
+def _write_evaluation(res: BoxEvaluation, output_dir, detections_csv) -> dict:
+    """-> the paths of box_eval_classes.csv, box_eval_rows.csv, box_eval_missed.csv and box_eval_curves.npz under output_dir and
+    of the detections table (when asked for), written"""
+    out = Path(output_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    tables = {"classes": res.per_class, "rows": res.per_row, "missed": res.missed}
+    paths = {k: str(out / f"box_eval_{k}.csv") for k in tables}
+    paths["curves"] = str(out / "box_eval_curves.npz")
+    for k, frame in tables.items():
+        frame.to_csv(paths[k], index=False, encoding="utf-8-sig")
+    np.savez(paths["curves"], classes=np.asarray([COMPARE_NONE if c is None else c for c in res.classes], dtype=str),
+             iou_thresholds=res.iou_thresholds, recall_points=EVAL_RECALL_POINTS, precision=res.precision, score_at=res.score_at,
+             recall=res.recall, ap=res.ap)
+    if detections_csv is not None:
+        Path(detections_csv).parent.mkdir(parents=True, exist_ok=True)
+        res.detections.to_csv(detections_csv, index=False, encoding="utf-8-sig")
+        paths["detections"] = str(detections_csv)
+    return paths
+
+
+def evaluate_boxes_csv(gt_csv, pred_csv, output_dir, json_col: str = BBOX_COL, key="source", score_col=None, score_key=None,
+                       iou_thresholds=None, max_dets: int = 100, backend=None, detections_csv=None):
+    """Two CSVs -> box_eval_classes.csv, box_eval_rows.csv, box_eval_missed.csv and box_eval_curves.npz (classes, iou_thresholds,
+    recall_points, precision, score_at, recall, ap) under output_dir, and the detections table when detections_csv names a file;
+    read in compare_boxes_csv's conventions (utf-8-sig; 读取失败：... / 错误：缺少必要列 ... and None).  key=None evaluates by position.
+    -> dict(totals, paths=...)"""
+    thr, max_dets = _eval_thresholds(iou_thresholds), _eval_max_dets(max_dets)
+    _eval_score_source(score_col, score_key)
+    read = _compare_read("evaluate", gt_csv, pred_csv, json_col, key)
+    if read is None:
+        return None
+    light_gt, cells_gt, keys_gt, light_pred, cells_pred, keys_pred = read
+    if score_col is not None and score_col not in light_pred.columns:
+        print(f"错误：缺少必要列 {score_col}")
+        return None
+    sources = light_gt["source"].to_numpy() if "source" in light_gt.columns else None
+    score_cells = _eval_score_cells(light_pred[score_col].to_numpy().tolist()) if score_col is not None else None
+    res = _eval_tables(cells_gt, keys_gt, sources, cells_pred, keys_pred, key, score_cells, score_key, thr, max_dets, backend, None)
+    return {**res.totals, "paths": _write_evaluation(res, output_dir, detections_csv)}
+
+
 # =============================================================================== f7  YOLO segmentation label lines
 # One line per matched polygon, "cls x1 y1 ... xn yn" normalised to [0, 1] (YOLO segment models), each polygon clipped to the image
 # (include/dyd.h, K13, has the definition).  Native labelled-polygon scan (csrc/host_json.cpp; flatten.seg_cell_polygons for

@@ -25,7 +25,6 @@
 //   global u64 atomics otherwise and in the big-row kernel.  The counts do not depend on the order.
 //   The exact IoU of every candidate is needed, so K2's rejecting bound (thr_lo) is not used here.
 #include "k18_pick.h"
-#include "k2_wave.h"
 
 namespace dyd {
 
@@ -40,38 +39,6 @@ struct K18Lds {
     double iou[K18_BCAP], best[K18_BCAP];
     int32_t cls[K18_BCAP], match[K18_BCAP];
 };
-
-__device__ __forceinline__ Corners k18_load(const double *box4, int64_t b) {
-    const double2 *g = reinterpret_cast<const double2 *>(box4 + 4 * b);
-    return normalise(g[0], g[1]);
-}
-
-// calculate_iou(a, b) :328-339, a_ar = area of a.  NO_NAN as in pair_hits (k2_wave.h): the same value from v_max_f64 / v_min_f64.
-template <bool NO_NAN>
-__device__ __forceinline__ double k18_iou(const Corners &a, const Corners &b, double a_ar) {
-    double ix1, iy1, ix2, iy2, w, h;
-    if (NO_NAN) {
-        ix1 = vmax(a.x1, b.x1);
-        iy1 = vmax(a.y1, b.y1);
-        ix2 = vmin(a.x2, b.x2);
-        iy2 = vmin(a.y2, b.y2);
-        w = vmax0(ix2 - ix1);
-        h = vmax0(iy2 - iy1);
-    } else {
-        ix1 = (b.x1 > a.x1) ? b.x1 : a.x1;
-        iy1 = (b.y1 > a.y1) ? b.y1 : a.y1;
-        ix2 = (b.x2 < a.x2) ? b.x2 : a.x2;
-        iy2 = (b.y2 < a.y2) ? b.y2 : a.y2;
-        w = ix2 - ix1;
-        h = iy2 - iy1;
-        w = (w > 0.0) ? w : 0.0;
-        h = (h > 0.0) ? h : 0.0;
-    }
-    const double inter = w * h;
-    if (inter == 0.0) return 0.0;
-    const double uni = a_ar + area_of(b) - inter;
-    return (uni != 0.0) ? inter / uni : 0.0;
-}
 
 // k18_count in the workgroup's LDS copy of the matrix when there is one
 __device__ __forceinline__ void k18_count(unsigned int *lds_conf, unsigned long long *conf, int32_t C, int32_t a, int32_t b) {
@@ -419,37 +386,6 @@ int launch_k18(const double *a_box4, const int32_t *a_off, const int32_t *a_cls,
     release_scratch(st);
     return DYD_OK;
 }
-
-// one side of a comparison in host memory: offsets monotone from 0, class ids inside the list -> *n_boxes
-static int k18_check_side(const double *box4, const int32_t *row_off, const int32_t *cls, int64_t n_rows, int32_t n_classes,
-                          int64_t *n_boxes) {
-    DYD_REQUIRE(row_off, "null pointer");
-    DYD_REQUIRE(row_off[0] == 0, "row_off[0] != 0");
-    for (int64_t i = 0; i < n_rows; ++i) DYD_REQUIRE(row_off[i + 1] >= row_off[i], "row_off not monotone");
-    const int64_t nb = row_off[n_rows];
-    if (nb > 0) {
-        DYD_REQUIRE(box4 && cls, "null pointer");
-        for (int64_t b = 0; b < nb; ++b) DYD_REQUIRE(cls[b] >= 0 && cls[b] < n_classes, "class id outside 0..n_classes-1");
-    }
-    *n_boxes = nb;
-    return DYD_OK;
-}
-
-struct K18Side {
-    DevBuf box, off, cls;
-    int upload(const double *box4, const int32_t *row_off, const int32_t *cls_, int64_t n_rows, int64_t nb) {
-        int rc;
-        if ((rc = box.alloc(32 * (size_t)nb)) || (rc = off.alloc(4 * (size_t)(n_rows + 1))) || (rc = cls.alloc(4 * (size_t)nb)))
-            return rc;
-        hipStream_t s = ctx().stream;
-        if (nb) {
-            DYD_HIP(hipMemcpyAsync(box.p, box4, 32 * (size_t)nb, hipMemcpyHostToDevice, s));
-            DYD_HIP(hipMemcpyAsync(cls.p, cls_, 4 * (size_t)nb, hipMemcpyHostToDevice, s));
-        }
-        DYD_HIP(hipMemcpyAsync(off.p, row_off, 4 * (size_t)(n_rows + 1), hipMemcpyHostToDevice, s));
-        return DYD_OK;
-    }
-};
 
 }  // namespace dyd
 

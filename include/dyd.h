@@ -241,6 +241,60 @@ int dyd_compare_boxes_dev(const double *a_box4, const int32_t *a_row_off, const 
                           double *out_b_iou, double *out_a_best, double *out_b_best,
                           int32_t *out_row_counts, uint64_t *out_confusion, void *stream);
 
+/* ---- K24: scored box evaluation — COCO-style AP per class ----------------------------
+ * After COCOeval's evaluateImg / accumulate for iouType "bbox", area range "all", no crowd
+ * or ignore regions.  Table A holds the ground truth (GT), table B the detections, one
+ * score each, over the same n_rows rows and one class list.  iou(g, d) is K18's (above),
+ * the GT box first.  Host pointers only.
+ * Selection, per row: a detection whose score is not finite is bad_score (state 2): it takes
+ *   no part and is no false positive.  Scores compare as numbers, -0.0 equal to 0.0 (they
+ *   are taken as score + 0.0 everywhere, also where an output reports one).  The others are
+ *   ranked within (row, class) by score descending, ties to the earlier position in the row;
+ *   rank >= max_dets is cut (state 1) and takes no part; the rest is evaluated (state 0).
+ * Matching, per threshold index t on its own, lim = min(iou_thr[t], 1 - 1e-10): the row's
+ *   evaluated detections in rank order (any interleaving of the classes: only equal classes
+ *   match); detection d takes the GT box g of its row and class, still free at t, with the
+ *   largest iou(g, d) >= lim, ties to the HIGHEST g (K18: the lowest).  A NaN IoU never
+ *   matches; a GT box with a NaN corner still counts as ground truth.
+ * gt_box4, dt_box4, *_row_off, *_cls: as K18's a_ / b_ tables        dt_score [n_dt] f64
+ * iou_thr [T] f64, 1 <= T <= 32; max_dets >= 1
+ * out_dt_state [n_dt] i32: 0 evaluated, 1 cut, 2 bad_score
+ * out_dt_tp [n_dt] u32: bit t = matched at threshold t
+ * out_dt_gt [n_dt] i32: in-row index of the GT box matched at t = 0, else -1
+ * out_dt_iou [n_dt] f64: that pair's IoU, else 0.0
+ * out_dt_best [n_dt] f64: largest IoU with any GT box of its row and class, free or not
+ *             (from 0.0 by `iou > best`); 0.0 for a detection that is not evaluated
+ * out_gt_hit [n_gt] u32: bit t = matched at threshold t
+ * out_gt_best [n_gt] f64: largest IoU with any evaluated detection of its row and class
+ * Every output element is written.  n_rows == 0 returns at once. */
+int dyd_eval_match_boxes(const double *gt_box4, const int32_t *gt_row_off, const int32_t *gt_cls,
+                         const double *dt_box4, const int32_t *dt_row_off, const int32_t *dt_cls,
+                         const double *dt_score, int64_t n_rows, int32_t n_classes,
+                         const double *iou_thr, int32_t T, int32_t max_dets,
+                         int32_t *out_dt_state, uint32_t *out_dt_tp, int32_t *out_dt_gt,
+                         double *out_dt_iou, double *out_dt_best, uint32_t *out_gt_hit,
+                         double *out_gt_best);
+/* Accumulation over the evaluated detections of a whole table in table order (n < 2^31,
+ * finite scores): cls [n] i32, score [n] f64, tp [n] u32 (out_dt_tp), npig [C] i64 = GT boxes
+ * per class, rec [R] f64 ascending recall points (R >= 1).  Per class c and threshold t:
+ *   the detections of c by score descending, ties in table order; tp_k, fp_k = running counts
+ *   after k+1 of them; rc_k = tp_k / npig; pr_k = tp_k / ((tp_k + fp_k) + 2^-52); pr replaced
+ *   by its running maximum from the right; for each r the first k with rc_k >= rec[r]:
+ *   precision[c,t,r] = pr_k, score_at[c,t,r] = score of k, both 0.0 without such a k;
+ *   recall[c,t] = rc_last (0.0 without detections); ap[c,t] = (sum of precision[c,t,r] in
+ *   ascending r) / R.  npig == 0: all of these are NaN.
+ *   Operating point: over the k that end a run of equal scores, the largest
+ *   f1_k = 2 tp_k / ((k+1) + npig), ties to the smallest k -> best_f1, best_score, best_tp,
+ *   best_dets = k+1; NaN, NaN, 0, 0 when npig == 0 or c has no detection.
+ * Integers and single correctly rounded f64 divisions in a fixed order: defined bit for bit.
+ * out_precision, out_score_at [C*T*R] f64; out_recall, out_ap, out_best_f1, out_best_score
+ * [C*T] f64; out_best_tp, out_best_dets [C*T] i64.  n_classes == 0 returns at once. */
+int dyd_eval_accumulate(const int32_t *cls, const double *score, const uint32_t *tp, int64_t n,
+                        int32_t n_classes, int32_t T, const int64_t *npig, const double *rec,
+                        int32_t R, double *out_precision, double *out_score_at,
+                        double *out_recall, double *out_ap, double *out_best_f1,
+                        double *out_best_score, int64_t *out_best_tp, int64_t *out_best_dets);
+
 /* ---- K1+K2 fused: poly -> bbox -> IoU flag in one pass ---------------------------
  * One launch that produces K1's outputs and K2's flag for rows whose boxes all come
  * from K1 (processing.py:580-598 runs the two steps back to back on the same rows).

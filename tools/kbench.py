@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmarks on one MI355X (device-resident inputs, HIP-event timing,
 interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant.
 
-    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k18: box comparison beside K2 and K9; k13: segmentation lines beside K7;
+    python tools/kbench.py [--rows 1000000] [--iters 20] [--only k1,k2,...]   (k9: suppression, k10: box audit, k11: box repair, each against K2 alone; k18: box comparison beside K2 and K9; k24: scored evaluation beside K18; k13: segmentation lines beside K7;
      k14: polygon audit; k14tier: its in-lane / wave threshold; simplify: polygon simplification (K19) beside K14 on rings of 8, 64 and 1024 points; k16: COCO annotation objects beside K13; k17: oriented-box lines beside K13; tile: tiled label lines (K20) beside K13;
      k21: label masks (K21) on many small and few large images, beside Pillow on one core; k22: polygon comparison (K22) on the same
      two tables, interleaved with K21 over either side; k23: COCO run-length masks (K23) on the same two tables, measure-only and
@@ -259,9 +259,9 @@ def main():
                               ("keep", "clip", "no_size", "bad_coords", "degenerate", "outside", "low_visibility", "small"))}}),
               flush=True)
 
-    if "k18" in only:
-        # K18 (box comparison) beside K2 alone and K9 on the same device buffers, interleaved rounds.  A = the K1 boxes with 20
-        # classes; B = a copy with 10 % of the boxes dropped, 10 % jittered and 5 % put into another class.
+    def compare_table():
+        """A = the K1 boxes with 20 classes; B = a copy with 10 % of the boxes dropped, 10 % jittered and 5 % put into another
+        class -> (cls20, b_box, b_off, b_cls, Bb, u of the kept boxes): the table of the k18 and k24 legs"""
         ck(L.dyd_bbox_minmax_dev(xy.data_ptr(), pt_off.data_ptr(), B, P, out_box.data_ptr(), out_arg.data_ptr(), sp), "k1")
         g = torch.Generator(device=dev).manual_seed(18)
         cls20 = (labels.to(torch.int64) % 20).to(torch.int32).contiguous()
@@ -274,8 +274,11 @@ def main():
         row = torch.repeat_interleave(torch.arange(N, device=dev), nbox.to(torch.int64))
         b_off = torch.zeros(N + 1, dtype=torch.int32, device=dev)
         b_off[1:] = torch.cumsum(torch.bincount(row[kept], minlength=N), 0).to(torch.int32)
-        Bb = b_box.shape[0]
-        del u, ub, row
+        return cls20, b_box, b_off, b_cls, b_box.shape[0], ub
+
+    if "k18" in only:
+        # K18 (box comparison) beside K2 alone and K9 on the same device buffers, interleaved rounds, on compare_table()
+        cls20, b_box, b_off, b_cls, Bb, _ = compare_table()
         keep = torch.empty(B, dtype=torch.uint8, device=dev)
         partner = torch.empty(B, dtype=torch.int32, device=dev)
         a_match = torch.empty(B, dtype=torch.int32, device=dev)
@@ -312,6 +315,47 @@ def main():
         print(json.dumps({"kernel": "k18_compare", "a_boxes": B, "b_boxes": Bb, "matched": int((b_match >= 0).sum().item()),
                           "agree": int(conf[:20, :20].diagonal().sum().item()), "missing": int(conf[:20, 20].sum().item()),
                           "extra": int(conf[20, :20].sum().item())}), flush=True)
+
+    if "k24" in only:
+        # K24 (scored evaluation) through its host entries on compare_table() with a score per B box, kernel time from
+        # dyd_last_kernel_ms; K18 by_label through its host entry on the same table, timed the same way, is the yardstick: K24
+        # at T = 1 does K18's pair work within the classes plus the ranking.  Then the accumulation alone on the T = 10 result.
+        cls20, b_box, b_off, b_cls, Bb, ub = compare_table()
+        host = [t.cpu().numpy() for t in (out_box, box_off, cls20, b_box, b_off, b_cls)]
+        score = np.round(ub.cpu().numpy() * 0.37 % 1.0, 3)               # three decimals: ties within and across rows
+        thr10 = np.linspace(0.5, 0.95, 10)
+
+        def kernel_ms(fn, iters=max(3, args.iters // 4)):
+            fn()
+            ts = []
+            for _ in range(iters):
+                fn()
+                ts.append(_native.last_kernel_ms())
+            return float(np.median(ts)), float(np.min(ts))
+
+        k24_bytes = 36 * B + 44 * Bb + 8 * (N + 1) + 12 * B + 32 * Bb
+        k18_bytes = 36 * (B + Bb) + 12 * B + 20 * Bb + 8 * (N + 1) + 16 * N
+        legs = {"k18_compare by_label (host entry)": (k18_bytes, lambda: _native.compare_boxes(*host, 20, 0.5, True)),
+                "k24_match T=1": (k24_bytes, lambda: _native.eval_match_boxes(*host, score, 20, [0.5], 100)),
+                "k24_match T=10": (k24_bytes, lambda: _native.eval_match_boxes(*host, score, 20, thr10, 100))}
+        res = {}
+        for rnd in range(2):
+            for nm, (_, fn) in legs.items():
+                res.setdefault(nm, []).append(kernel_ms(fn))
+        for nm, (nbytes, _) in legs.items():
+            med = float(np.median([r[0] for r in res[nm]])); mn = min(r[1] for r in res[nm])
+            report(nm, nbytes, med, mn, rows_per_s=round(N / med * 1e3))
+        state, tp, *_ = _native.eval_match_boxes(*host, score, 20, thr10, 100)
+        ev = state == 0
+        npig = np.bincount(host[2], minlength=20).astype(np.int64)
+        acc = lambda: _native.eval_accumulate(host[5][ev], score[ev], tp[ev], 20, 10, npig, np.linspace(0, 1, 101))   # noqa: E731
+        med, mn = kernel_ms(acc)
+        n_ev = int(ev.sum())
+        report("k24_accumulate C=20 T=10", 16 * n_ev + 2 * 8 * 20 * 10 * 101, med, mn, detections_per_s=round(n_ev / med * 1e3))
+        ap = acc()[3]
+        print(json.dumps({"kernel": "k24_eval", "gt_boxes": B, "detections": Bb, "evaluated": n_ev,
+                          "tp_at_0.5": int((tp[ev] & 1).sum()), "map": round(float(np.nanmean(ap)), 6),
+                          "map50": round(float(np.nanmean(ap[:, 0])), 6)}), flush=True)
 
     if "k12" in only:
         k12_bytes = 16 * P + 4 * (B + 1) + 48 * B + 4 * (N + 1) + N
