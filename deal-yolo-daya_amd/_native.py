@@ -86,6 +86,8 @@ SIGNATURES = {
     "dyd_eval_match_boxes": (C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
     "dyd_eval_accumulate": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
                             + [C.c_void_p] * 8),
+    "dyd_eval_match_polygons": (C.c_int, [C.c_void_p] * 11 + [C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                                              C.c_int64] + [C.c_void_p] * 13),
     "dyd_json_emit_repaired": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_void_p)]),
     "dyd_json_emit_simplified": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p),
@@ -710,6 +712,37 @@ def eval_accumulate(cls, score, tp, n_classes: int, n_thresholds: int, npig, rec
                                     _ptr(score_at), _ptr(recall), _ptr(ap), _ptr(f1), _ptr(bs), _ptr(btp), _ptr(bd)),
           "dyd_eval_accumulate")
     return precision, score_at, recall, ap, f1, bs, btp, bd
+
+
+def eval_match_polygons(gt_xy, gt_pt_off, gt_row_off, gt_cls, dt_xy, dt_pt_off, dt_row_off, dt_cls, dt_score, width, height,
+                        n_classes: int, iou_thr, max_dets: int = 100, max_pixels_per_row: int = 1 << 26,
+                        max_pairs_per_row: int = 1 << 20):
+    """K25's matching over host arrays: a ground-truth polygon table and a detection table with scores over the same rows ->
+    (row_status u8 [n], pair_off i64 [n+1], gt_action u8 [G], dt_action u8 [D], gt_pixels i64 [G], dt_pixels i64 [D], dt_state
+    i32 [D], dt_tp u32 [D], dt_gt i32 [D], dt_iou f64 [D], dt_best f64 [D], gt_hit u32 [G], gt_best f64 [G]).  Rule and codes:
+    include/dyd.h."""
+    gt_xy, gt_pt_off, gt_row_off, width, height, _, gt_cls, n, ng = _poly_table(gt_xy, gt_pt_off, gt_row_off, width, height,
+                                                                                ("width", width, np.float64), ("gt_cls", gt_cls, np.int32))
+    dt_xy, dt_pt_off, dt_row_off, _, _, _, dt_cls, _, nd = _poly_table(dt_xy, dt_pt_off, dt_row_off, width, height,
+                                                                       ("width", width, np.float64), ("dt_cls", dt_cls, np.int32))
+    dt_score = np.ascontiguousarray(dt_score, dtype=np.float64).reshape(-1)
+    if dt_score.size != nd:
+        raise ValueError("dt_score must hold one score per detection")
+    iou_thr = np.ascontiguousarray(iou_thr, dtype=np.float64).reshape(-1)
+    status, pair_off = np.zeros(n, np.uint8), np.zeros(n + 1, np.int64)
+    g_act, d_act = np.zeros(ng, np.uint8), np.zeros(nd, np.uint8)
+    g_pix, d_pix = np.zeros(ng, np.int64), np.zeros(nd, np.int64)
+    state, tp, gt = np.zeros(nd, np.int32), np.zeros(nd, np.uint32), np.full(nd, -1, np.int32)
+    iou, best = np.zeros(nd, np.float64), np.zeros(nd, np.float64)
+    hit, gbest = np.zeros(ng, np.uint32), np.zeros(ng, np.float64)
+    opt = lambda a: _ptr(a) if a.size else None          # noqa: E731
+    check(lib().dyd_eval_match_polygons(opt(gt_xy), _ptr(gt_pt_off), _ptr(gt_row_off), opt(gt_cls), opt(dt_xy), _ptr(dt_pt_off),
+                                        _ptr(dt_row_off), opt(dt_cls), opt(dt_score), _ptr(width), _ptr(height), n, int(n_classes),
+                                        _ptr(iou_thr), int(iou_thr.size), int(max_dets), int(max_pixels_per_row),
+                                        int(max_pairs_per_row), _ptr(status), _ptr(pair_off), opt(g_act), opt(d_act), opt(g_pix),
+                                        opt(d_pix), opt(state), opt(tp), opt(gt), opt(iou), opt(best), opt(hit), opt(gbest)),
+          "dyd_eval_match_polygons")
+    return status, pair_off, g_act, d_act, g_pix, d_pix, state, tp, gt, iou, best, hit, gbest
 
 
 def bbox_iou_fused(xy: np.ndarray, pt_off: np.ndarray, box_off: np.ndarray, min_boxes: int, thr: float,

@@ -9,7 +9,7 @@ injects its own checker there; no such object exists inside this package.
 from __future__ import annotations
 
 # The later steps ask for their own entry on top of these (core/processor.py: _step_backend), e.g. compare_boxes (K18),
-# rasterize_polygons (K21), polygon_rle (K23), compare_polygons (K22), eval_match_boxes and eval_accumulate (K24): a backend without it raises TypeError there, never a CPU fallback.
+# rasterize_polygons (K21), polygon_rle (K23), compare_polygons (K22), eval_match_boxes and eval_accumulate (K24), eval_match_polygons (K25): a backend without it raises TypeError there, never a CPU fallback.
 REQUIRED = ("bbox_minmax", "iou_any_ge", "bbox_iou_fused", "hash128", "dedup", "isin", "mt19937_permutation", "split_ids", "yolo_lines")
 
 

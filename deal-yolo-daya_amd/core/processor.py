@@ -3127,7 +3127,11 @@ def _eval_chunk(cells_gt, cells_pred, scores, score_key, thr, max_dets: int, be,
                            box[0][miss]))
 
 
-def _eval_result(acc: _EvalTotals, n: int, thr, max_dets: int, be, sources) -> BoxEvaluation:
+def _eval_fields(acc: _EvalTotals, n: int, thr, max_dets: int, be, sources, noun: str, det_spec: tuple, missed_spec: tuple) -> tuple:
+    """What evaluate_boxes_* and evaluate_polygons_* share once the chunks are matched: the one accumulation over the table and
+    the per-class, per-row and total counts -> (the fields of a BoxEvaluation, rank: chunk class id -> position in classes).
+    acc.gts holds the ground truth that counts (npig), acc.dets every detection with its state; noun names the objects in the
+    columns (gt_boxes / gt_polygons)."""
     classes = sorted(acc.index, key=lambda c: (c is None, str(c)))
     C, T = len(classes), len(thr)
     rank = np.zeros(len(acc.index), np.int64)
@@ -3163,7 +3167,7 @@ def _eval_result(acc: _EvalTotals, n: int, thr, max_dets: int, be, sources) -> B
     bt = best_tp[:, 0] if C else np.zeros(0, np.int64)
     with np.errstate(all="ignore"):
         per_class = pd.DataFrame({
-            "class": pd.Series(classes, dtype=object), "gt_boxes": npig, "detections": count(np.ones(len(cls_d), bool)),
+            "class": pd.Series(classes, dtype=object), f"gt_{noun}": npig, "detections": count(np.ones(len(cls_d), bool)),
             "evaluated": evaluated, "cut": count(state == 1), "bad_score": count(state == 2),
             "ap": np.asarray([_eval_mean(ap[c]) for c in range(C)], np.float64),
             "ap50": ap[:, k50] if k50 is not None else nan_c, "ap75": ap[:, k75] if k75 is not None else nan_c,
@@ -3177,14 +3181,14 @@ def _eval_result(acc: _EvalTotals, n: int, thr, max_dets: int, be, sources) -> B
         pr["source"] = np.asarray(sources, object)
     tp_r = np.bincount(row_d[tp0], minlength=n).astype(np.int64)
     n_gt = np.concatenate(acc.n_gt) if acc.n_gt else np.zeros(0, np.int64)
-    pr.update({"gt_boxes": n_gt, "detections": np.concatenate(acc.n_dt) if acc.n_dt else np.zeros(0, np.int64), "tp": tp_r,
+    pr.update({f"gt_{noun}": n_gt, "detections": np.concatenate(acc.n_dt) if acc.n_dt else np.zeros(0, np.int64), "tp": tp_r,
                "fp": np.bincount(row_d[ev], minlength=n).astype(np.int64) - tp_r, "fn": n_gt - tp_r})
     frames = []
-    for parts, spec in ((acc.det_lines, _EVAL_DET_SPEC), (acc.missed, _EVAL_MISSED_SPEC)):
+    for parts, spec in ((acc.det_lines, det_spec), (acc.missed, missed_spec)):
         frame = _parts_frame(parts, spec, sources)
         frames.append(frame[["row", "source", *frame.columns[2:]]] if sources is not None else frame)
     has = npig > 0
-    totals = {"rows": n, "gt_boxes": int(npig.sum()), "detections": len(cls_d), "evaluated": int(ev.sum()),
+    totals = {"rows": n, f"gt_{noun}": int(npig.sum()), "detections": len(cls_d), "evaluated": int(ev.sum()),
               "cut": int((state == 1).sum()), "bad_score": int((state == 2).sum()),
               "map": _eval_mean(per_class["ap"].to_numpy()[has]),
               "map50": _eval_mean(ap[has, k50]) if k50 is not None else float("nan"),
@@ -3192,8 +3196,12 @@ def _eval_result(acc: _EvalTotals, n: int, thr, max_dets: int, be, sources) -> B
               "mar": _eval_mean(per_class["recall"].to_numpy()[has]), "python_cells": acc.python_cells,
               "python_score_cells": acc.python_score_cells, "max_dets": max_dets}
     unpaired = pd.DataFrame({"key": np.zeros(0, object)})
-    return BoxEvaluation(classes, thr, per_class, precision, score_at, recall, ap, pd.DataFrame(pr), frames[0], frames[1], unpaired,
-                         totals)
+    return dict(classes=classes, iou_thresholds=thr, per_class=per_class, precision=precision, score_at=score_at, recall=recall,
+                ap=ap, per_row=pd.DataFrame(pr), detections=frames[0], missed=frames[1], unpaired=unpaired, totals=totals), rank
+
+
+def _eval_result(acc: _EvalTotals, n: int, thr, max_dets: int, be, sources) -> BoxEvaluation:
+    return BoxEvaluation(**_eval_fields(acc, n, thr, max_dets, be, sources, "boxes", _EVAL_DET_SPEC, _EVAL_MISSED_SPEC)[0])
 
 
 def evaluate_boxes_cells(cells_gt, cells_pred, scores=None, score_key=None, iou_thresholds=None, max_dets: int = 100,
@@ -3243,10 +3251,21 @@ def _eval_tables(cells_gt, keys_gt, sources, cells_pred, keys_pred, key, score_c
     """two tables (cells, keys or None) -> the evaluation over ALL rows of the ground truth, in its positions: a row that the
     predictions lack is evaluated without detections (its boxes are missed, as COCO counts them), a row found in the predictions
     only is not evaluated and listed in `unpaired`"""
+    cells_gt, cells_pred, score_cells, rows, only = _eval_align(cells_gt, keys_gt, cells_pred, keys_pred, key, score_cells)
+    res = evaluate_boxes_cells(cells_gt, cells_pred, score_cells, score_key, thr, max_dets, backend, None, sources)
+    return _eval_unpaired(res, keys_pred, only, stats)
+
+
+def _eval_align(cells_gt, keys_gt, cells_pred, keys_pred, key, score_cells) -> tuple:
+    """the predictions' cells and score cells in the ground truth's positions ("{}" and None where the predictions lack the
+    row) -> (cells_gt, cells_pred, score_cells, (rows_gt, rows_pred): the positions of the rows found in both or None without
+    keys, (only_gt, only_pred))"""
     cells_gt, cells_pred = np.asarray(cells_gt, object), np.asarray(cells_pred, object)
     only_gt = only_pred = np.zeros(0, np.int64)
+    rows = None
     if keys_gt is not None:
         rows_gt, rows_pred, only_gt, only_pred = _compare_align(keys_gt, keys_pred, key)
+        rows = rows_gt, rows_pred
         aligned = np.full(len(cells_gt), "{}", object)
         aligned[rows_gt] = cells_pred[rows_pred]
         cells_pred = aligned
@@ -3255,7 +3274,12 @@ def _eval_tables(cells_gt, keys_gt, sources, cells_pred, keys_pred, key, score_c
             for a, b in zip(rows_gt.tolist(), rows_pred.tolist()):
                 picked[a] = score_cells[b]
             score_cells = picked
-    res = evaluate_boxes_cells(cells_gt, cells_pred, score_cells, score_key, thr, max_dets, backend, None, sources)
+    return cells_gt, cells_pred, score_cells, rows, (only_gt, only_pred)
+
+
+def _eval_unpaired(res, keys_pred, only: tuple, stats):
+    """an evaluation over aligned tables with the rows found in the predictions only listed and both sides' lone rows counted"""
+    only_gt, only_pred = only
     res.unpaired = pd.DataFrame({"key": np.asarray(keys_pred, object)[only_pred] if len(only_pred) else np.zeros(0, object)})
     res.totals.update(rows_only_gt=len(only_gt), rows_only_pred=len(only_pred))
     if stats is not None:
@@ -3286,14 +3310,14 @@ def evaluate_boxes_frame(df_gt: pd.DataFrame, df_pred: Optional[pd.DataFrame] = 
     return _eval_tables(cells_gt, keys_gt, sources, cells_pred, keys_pred, key, score_cells, score_key, thr, max_dets, backend, stats)
 
 
-def _write_evaluation(res: BoxEvaluation, output_dir, detections_csv) -> dict:
-    """-> the paths of box_eval_classes.csv, box_eval_rows.csv, box_eval_missed.csv and box_eval_curves.npz under output_dir and
+def _write_evaluation(res: BoxEvaluation, output_dir, detections_csv, prefix: str = "box_eval") -> dict:
+    """-> the paths of {prefix}_classes.csv, {prefix}_rows.csv, {prefix}_missed.csv and {prefix}_curves.npz under output_dir and
     of the detections table (when asked for), written"""
     out = Path(output_dir)
     out.mkdir(parents=True, exist_ok=True)
     tables = {"classes": res.per_class, "rows": res.per_row, "missed": res.missed}
-    paths = {k: str(out / f"box_eval_{k}.csv") for k in tables}
-    paths["curves"] = str(out / "box_eval_curves.npz")
+    paths = {k: str(out / f"{prefix}_{k}.csv") for k in tables}
+    paths["curves"] = str(out / f"{prefix}_curves.npz")
     for k, frame in tables.items():
         frame.to_csv(paths[k], index=False, encoding="utf-8-sig")
     np.savez(paths["curves"], classes=np.asarray([COMPARE_NONE if c is None else c for c in res.classes], dtype=str),
@@ -5012,22 +5036,42 @@ def _poly_compare_params(iou_threshold, by_label, max_pixels_per_row, max_pairs_
             _mask_int(batch_pixels, "batch_pixels", 1, 1 << 40), _mask_int(batch_pairs, "batch_pairs", 1, 1 << 40))
 
 
+def _poly_pair_tables(cells_a, cells_b, acc, step: str) -> tuple:
+    """both polygon tables of one chunk of rows (_poly_chunk) on one class list, for the two-table polygon steps -> (names, cls,
+    C: the class count the device gets, at least one, off, xy, pt, obj, count: per side the row offsets, points, point offsets,
+    object indices and polygons per row)"""
+    sides = [_poly_chunk(cells) for cells in (cells_a, cells_b)]
+    acc.python_cells += sides[0][6] + sides[1][6]
+    names, cls = _compare_classes(sides[0][5], sides[0][4], sides[1][5], sides[1][4])
+    C = max(len(names), 1)                               # K22 and K25 take at least one class; a chunk without polygons uses none
+    if C > _POLY_COMPARE_MAX_CLASSES:
+        raise ValueError(f"a chunk holds {C} classes; the polygon {step} takes at most {_POLY_COMPARE_MAX_CLASSES}")
+    off = [np.asarray(t[0], np.int64) for t in sides]
+    xy = [np.asarray(t[1], np.float64).reshape(-1) for t in sides]
+    pt = [np.asarray(t[2], np.int64) for t in sides]
+    obj = [np.asarray(t[3], np.int64) for t in sides]
+    return names, cls, C, off, xy, pt, obj, [np.diff(o) for o in off]
+
+
+def _poly_pair_batch(off, xy, pt, cls, a: int, b: int) -> tuple:
+    """the rows [a, b) of both tables as the device takes them -> ([xy, pt_off, row_off, cls] of A then of B, rebased to the
+    batch, [(first, last polygon) of A, of B])"""
+    tabs, span = [], []
+    for k in (0, 1):
+        p0, p1 = int(off[k][a]), int(off[k][b])
+        q0, q1 = int(pt[k][p0]), int(pt[k][p1])
+        span.append((p0, p1))
+        tabs += [xy[k][2 * q0:2 * q1], (pt[k][p0:p1 + 1] - q0).astype(np.int32), (off[k][a:b + 1] - p0).astype(np.int32),
+                 cls[k][p0:p1]]
+    return tabs, span
+
+
 def _poly_compare_chunk(cells_a, cells_b, W, H, be, acc: _PolyCompareTotals, start: int, params: tuple):
     """one chunk of rows: both polygon tables (_poly_chunk) on one class list -> K22 per batch of rows -> class-keyed sums,
     per-row counts, differences"""
     thr, by_label, max_pixels, max_pairs, batch_pixels, batch_pairs = params
     n = len(cells_a)
-    sides = [_poly_chunk(cells) for cells in (cells_a, cells_b)]
-    acc.python_cells += sides[0][6] + sides[1][6]
-    names, cls = _compare_classes(sides[0][5], sides[0][4], sides[1][5], sides[1][4])
-    C = max(len(names), 1)                               # K22 takes at least one class; a chunk without polygons uses none
-    if C > _POLY_COMPARE_MAX_CLASSES:
-        raise ValueError(f"a chunk holds {C} classes; the polygon comparison takes at most {_POLY_COMPARE_MAX_CLASSES}")
-    off = [np.asarray(t[0], np.int64) for t in sides]
-    xy = [np.asarray(t[1], np.float64).reshape(-1) for t in sides]
-    pt = [np.asarray(t[2], np.int64) for t in sides]
-    obj = [np.asarray(t[3], np.int64) for t in sides]
-    count = [np.diff(o) for o in off]
+    names, cls, C, off, xy, pt, obj, count = _poly_pair_tables(cells_a, cells_b, acc, "comparison")
     host_status, host_pixels, host_pairs = _fl.compare_rows(W, H, count[0], count[1], max_pixels, max_pairs)
     act = [np.zeros(len(c), np.uint8) for c in cls]
     pix = [np.zeros(len(c), np.int64) for c in cls]
@@ -5037,13 +5081,7 @@ def _poly_compare_chunk(cells_a, cells_b, W, H, be, acc: _PolyCompareTotals, sta
     rows, row_pixels = np.zeros((n, 4), np.int64), np.zeros((n, 2), np.int64)
     conf, pconf = np.zeros((C + 1, C + 1), np.int64), np.zeros((C + 1, C + 1), np.int64)
     for a, b in _fl.compare_batches(host_pixels, host_pairs, batch_pixels, batch_pairs):
-        tabs, span = [], []
-        for k in (0, 1):
-            p0, p1 = int(off[k][a]), int(off[k][b])
-            q0, q1 = int(pt[k][p0]), int(pt[k][p1])
-            span.append((p0, p1))
-            tabs += [xy[k][2 * q0:2 * q1], (pt[k][p0:p1 + 1] - q0).astype(np.int32), (off[k][a:b + 1] - p0).astype(np.int32),
-                     cls[k][p0:p1]]
+        tabs, span = _poly_pair_batch(off, xy, pt, cls, a, b)
         out = be.compare_polygons(*tabs, W[a:b], H[a:b], C, thr, by_label, max_pixels, max_pairs)
         status, pair_off = np.asarray(out[0], np.uint8), np.asarray(out[1], np.int64)
         if not np.array_equal(status, host_status[a:b]) or not np.array_equal(np.diff(pair_off), host_pairs[a:b]):
@@ -5195,6 +5233,210 @@ def compare_polygons_csv(a_csv, b_csv, output_dir, json_col: str = ANNOTATION_CO
     res = _poly_compare_tables(cells_a, (wa, ha), keys_a, sources, cells_b, _size_columns(light_b, width_col, height_col)[:2], keys_b,
                                key, params, be, None)
     return {**res.totals, "paths": _write_comparison(res, output_dir, "polygon_compare")}
+
+
+# ------------------------------------------------------------------------------- scored polygon evaluation (mask AP per class)
+# evaluate_boxes_* on the annotation polygons: the ground truth's and the predictions' polygons of the same images, the
+# predictions with one score each, matched by mask IoU (K22's cover, pixel counts and intersections) under K24's selection and
+# matching rule (include/dyd.h, K25), then K24's accumulation over the whole table.  Both polygon tables come from _poly_chunk
+# on one class list; rows reach the device (csrc/k25_poly_eval.hip) in the polygon comparison's batches.  No CPU fallback.
+# Equality with pycocotools' "segm" numbers is not verified and not claimed.
+POLY_EVAL_STATES = (*EVAL_STATES, "skipped")                # K25 codes 0..3
+POLY_EVAL_STATUS = ("evaluated", *POLY_COMPARE_STATUS[1:])  # K22 row status codes 0..4
+_POLY_EVAL_DET_SPEC = (*_EVAL_DET_SPEC, ("pixels", np.int64))
+_POLY_EVAL_MISSED_SPEC = (("row", np.int64), ("object", np.int64), ("name", object), ("best_iou", np.float64), ("pixels", np.int64))
+
+
+class PolygonEvaluation(BoxEvaluation):
+    """Result of evaluate_polygons_*: a BoxEvaluation over polygons (gt_polygons where that one says gt_boxes) whose IoU is the
+    mask IoU.  Added: per_row["status"] and ["pixels"]; per_class["gt_skipped"] / ["dt_skipped"] (polygons that are not
+    evaluated: bad coordinates, too few points, or a row that is not evaluated); the state `skipped` and a pixels column in
+    detections; pixels in missed; totals rows_evaluated, rows_no_size, rows_fractional_size, rows_too_large,
+    rows_too_many_pairs, rows_size_mismatch, pixels, gt_skipped and skipped.  A skipped ground-truth polygon is no ground truth."""
+
+
+class _PolyEvalTotals(_EvalTotals):
+    """_EvalTotals plus, per chunk, the rows' status and pixel counts and the classes of the skipped polygons of either side"""
+
+    def __init__(self):
+        super().__init__()
+        self.status, self.row_pixels, self.skipped = [], [], []
+
+
+def _poly_eval_params(max_pixels_per_row, max_pairs_per_row, batch_pixels, batch_pairs) -> tuple:
+    return _poly_compare_params(0.5, False, max_pixels_per_row, max_pairs_per_row, batch_pixels, batch_pairs)[2:]
+
+
+def _poly_eval_chunk(cells_gt, cells_pred, scores, score_key, W, H, thr, max_dets: int, be, acc: _PolyEvalTotals, start: int,
+                     params: tuple):
+    """one chunk of rows: both polygon tables (_poly_chunk) on one class list -> K25 per batch of rows -> the chunk's columns"""
+    max_pixels, max_pairs, batch_pixels, batch_pairs = params
+    n = len(cells_gt)
+    names, cls, C, off, xy, pt, obj, count = _poly_pair_tables(cells_gt, cells_pred, acc, "evaluation")
+    score = _eval_scores(cells_pred, off[1], obj[1], scores, score_key, start, acc)
+    host_status, host_pixels, host_pairs = _fl.compare_rows(W, H, count[0], count[1], max_pixels, max_pairs)
+    act = [np.zeros(len(c), np.uint8) for c in cls]
+    pix = [np.zeros(len(c), np.int64) for c in cls]
+    state, tp, gt = np.zeros(len(cls[1]), np.int64), np.zeros(len(cls[1]), np.int64), np.full(len(cls[1]), -1, np.int64)
+    iou, best = np.zeros(len(cls[1])), np.zeros(len(cls[1]))
+    hit, g_best = np.zeros(len(cls[0]), np.int64), np.zeros(len(cls[0]))
+    for a, b in _fl.compare_batches(host_pixels, host_pairs, batch_pixels, batch_pairs):
+        tabs, span = _poly_pair_batch(off, xy, pt, cls, a, b)
+        (g0, g1), (d0, d1) = span
+        out = be.eval_match_polygons(*tabs, score[d0:d1], W[a:b], H[a:b], C, thr, max_dets, max_pixels, max_pairs)
+        status, pair_off = np.asarray(out[0], np.uint8), np.asarray(out[1], np.int64)
+        if not np.array_equal(status, host_status[a:b]) or not np.array_equal(np.diff(pair_off), host_pairs[a:b]):
+            raise RuntimeError("the device's row status or pair counts differ from the host's")
+        act[0][g0:g1], act[1][d0:d1], pix[0][g0:g1], pix[1][d0:d1] = out[2], out[3], out[4], out[5]
+        state[d0:d1], tp[d0:d1], gt[d0:d1], iou[d0:d1], best[d0:d1] = out[6], out[7], out[8], out[9], out[10]
+        hit[g0:g1], g_best[g0:g1] = out[11], out[12]
+    to = np.asarray([acc.index.setdefault(nm, len(acc.index)) for nm in names], np.int64)
+    row_g = np.repeat(np.arange(n, dtype=np.int64), count[0])
+    row_d = np.repeat(np.arange(n, dtype=np.int64), count[1])
+    cls_g, cls_d = to[cls[0]] if len(to) else np.zeros(0, np.int64), to[cls[1]] if len(to) else np.zeros(0, np.int64)
+    live = act[0] == 0                                   # the ground truth that counts
+    acc.gts.append((start + row_g[live], cls_g[live], hit[live]))
+    acc.dets.append((start + row_d, cls_d, score, state, tp))
+    acc.n_gt.append(np.bincount(row_g[live], minlength=n).astype(np.int64))
+    acc.n_dt.append(count[1])
+    acc.skipped.append((cls_g[~live], cls_d[state == 3]))
+    acc.status.append(host_status)
+    acc.row_pixels.append(host_pixels)
+    every = np.arange(len(row_d), dtype=np.int64)
+    gt_at = np.where(gt >= 0, off[0][row_d] + gt, 0)
+    acc.det_lines.append((start + row_d, obj[1], _compare_names(names, cls[1], {}, every), score,
+                          np.asarray(POLY_EVAL_STATES, object)[state], np.asarray([bin(int(v)).count("1") for v in tp], np.int64),
+                          np.where(gt >= 0, obj[0][gt_at] if len(obj[0]) else -1, -1), iou, best, pix[1]))
+    miss = np.flatnonzero(live & ((hit & 1) == 0))
+    if len(miss):
+        acc.missed.append((start + row_g[miss], obj[0][miss], _compare_names(names, cls[0], {}, miss), g_best[miss], pix[0][miss]))
+
+
+def _poly_eval_result(acc: _PolyEvalTotals, n: int, thr, max_dets: int, be, sources, params: tuple, mismatch, stats) -> PolygonEvaluation:
+    """_eval_fields plus the polygon step's own: the rows' status and pixels, the skipped polygons"""
+    fields, rank = _eval_fields(acc, n, thr, max_dets, be, sources, "polygons", _POLY_EVAL_DET_SPEC, _POLY_EVAL_MISSED_SPEC)
+    C = len(fields["classes"])
+    status = np.asarray(POLY_EVAL_STATUS, object)[np.concatenate(acc.status) if acc.status else np.zeros(0, np.uint8)]
+    if mismatch is not None:
+        status[mismatch] = "size_mismatch"
+    pixels = np.concatenate(acc.row_pixels) if acc.row_pixels else np.zeros(0, np.int64)
+    fields["per_row"]["status"], fields["per_row"]["pixels"] = status, pixels
+    skipped = [np.bincount(rank[np.concatenate([s[k] for s in acc.skipped])] if acc.skipped else np.zeros(0, np.int64),
+                           minlength=C).astype(np.int64) for k in (0, 1)]
+    fields["per_class"]["gt_skipped"], fields["per_class"]["dt_skipped"] = skipped
+    fields["totals"].update(
+        gt_skipped=int(skipped[0].sum()), skipped=int(skipped[1].sum()),
+        **{f"rows_{s}": int((status == s).sum()) for s in (*POLY_EVAL_STATUS, "size_mismatch")}, pixels=int(pixels.sum()),
+        max_pixels_per_row=params[0], max_pairs_per_row=params[1])
+    if stats is not None:
+        stats.update(fields["totals"])
+    return PolygonEvaluation(**fields)
+
+
+def _poly_eval_rows(cells_gt, cells_pred, scores, score_key, n, widths, heights, mismatch, thr, max_dets, params, be, stats,
+                    sources) -> PolygonEvaluation:
+    """the chunks of n aligned rows through _poly_eval_chunk, then the one accumulation; mismatch as in _poly_compare_rows"""
+    _, W, H = _audit_sizes(widths, heights, n)
+    if mismatch is not None:
+        W, H = np.where(mismatch, np.nan, W), np.where(mismatch, np.nan, H)
+    acc = _PolyEvalTotals()
+    for s0, s1, chunk in _chunks(n, cells_gt):
+        _poly_eval_chunk(chunk, cells_pred[s0:s1], scores, score_key, W[s0:s1], H[s0:s1], thr, max_dets, be, acc, s0, params)
+    return _poly_eval_result(acc, n, thr, max_dets, be, sources, params, mismatch, stats)
+
+
+def _poly_eval_backend(backend):
+    return _step_backend(_step_backend(backend, "eval_match_polygons"), "eval_accumulate")
+
+
+def evaluate_polygons_cells(cells_gt, cells_pred, widths, heights, scores=None, score_key=None, iou_thresholds=None,
+                            max_dets: int = 100, max_pixels_per_row: int = 1 << 26, max_pairs_per_row: int = 1 << 20,
+                            batch_pixels: int = 1 << 28, batch_pairs: int = 1 << 26, backend=None, stats: Optional[dict] = None,
+                            sources=None) -> PolygonEvaluation:
+    """Scored evaluation of predicted annotation polygons against the ground-truth polygons of the same images by mask IoU, row
+    by row (see the section comment) -> PolygonEvaluation.  widths / heights are the images' sizes; a row is evaluated only when
+    its size is usable and whole, it has at most max_pixels_per_row pixels and at most max_pairs_per_row pairs of polygons
+    (per_row["status"] says which); the polygons of any other row are skipped: its ground truth does not count and its
+    detections take no part.  scores / score_key, iou_thresholds and max_dets as in evaluate_boxes_cells; batches as in
+    compare_polygons_cells."""
+    thr, max_dets = _eval_thresholds(iou_thresholds), _eval_max_dets(max_dets)
+    params = _poly_eval_params(max_pixels_per_row, max_pairs_per_row, batch_pixels, batch_pairs)
+    if (scores is None) == (score_key is None):
+        raise ValueError("exactly one of scores and score_key must be given")
+    be = _poly_eval_backend(backend)
+    cells_gt = cells_gt.to_numpy() if hasattr(cells_gt, "to_numpy") else cells_gt
+    cells_pred = cells_pred.to_numpy() if hasattr(cells_pred, "to_numpy") else cells_pred
+    n = len(cells_gt)
+    if len(cells_pred) != n:
+        raise ValueError(f"the two lists must hold one cell per image each: {n} against {len(cells_pred)} cells")
+    if scores is not None and len(scores) != n:
+        raise ValueError(f"scores must hold one entry per row: {len(scores)} against {n} rows")
+    return _poly_eval_rows(cells_gt, cells_pred, scores, score_key, n, widths, heights, None, thr, max_dets, params, be, stats, sources)
+
+
+def _poly_eval_tables(cells_gt, sizes_gt, keys_gt, sources, cells_pred, sizes_pred, keys_pred, key, score_cells, score_key, thr,
+                      max_dets, params, be, stats) -> PolygonEvaluation:
+    """_eval_tables over two tables that also carry (widths, heights): the sizes come from the ground truth, and a row found in
+    both whose two usable sizes differ is size_mismatch"""
+    n = len(cells_gt)
+    cells_gt, cells_pred, score_cells, rows, only = _eval_align(cells_gt, keys_gt, cells_pred, keys_pred, key, score_cells)
+    rows_gt, rows_pred = rows if rows is not None else (np.arange(n, dtype=np.int64),) * 2
+    mismatch = None
+    found = _poly_compare_mismatch(sizes_gt, sizes_pred, rows_gt, rows_pred)
+    if found is not None:
+        mismatch = np.zeros(n, bool)
+        mismatch[rows_gt] = found
+    res = _poly_eval_rows(cells_gt, cells_pred, score_cells, score_key, n, sizes_gt[0], sizes_gt[1], mismatch, thr, max_dets, params,
+                          be, None, sources)
+    return _eval_unpaired(res, keys_pred, only, stats)
+
+
+def evaluate_polygons_frame(df_gt: pd.DataFrame, df_pred: Optional[pd.DataFrame] = None, json_col: str = ANNOTATION_COL,
+                            other_col=None, key="source", width_col: str = "width", height_col: str = "height", score_col=None,
+                            score_key=None, iou_thresholds=None, max_dets: int = 100, max_pixels_per_row: int = 1 << 26,
+                            max_pairs_per_row: int = 1 << 20, batch_pixels: int = 1 << 28, batch_pairs: int = 1 << 26, backend=None,
+                            stats: Optional[dict] = None) -> PolygonEvaluation:
+    """Scored polygon evaluation of two annotation columns, the frames chosen and the scores read as evaluate_boxes_frame does.
+    The sizes come from df_gt's width_col / height_col; when df_pred carries them too, a row found in both whose two usable
+    sizes differ is reported as size_mismatch and not evaluated.  A row found in df_gt only is evaluated without detections; a
+    row found in the predictions only is listed in ``unpaired``.  Rows are positions in df_gt."""
+    thr, max_dets = _eval_thresholds(iou_thresholds), _eval_max_dets(max_dets)
+    params = _poly_eval_params(max_pixels_per_row, max_pairs_per_row, batch_pixels, batch_pairs)
+    _eval_score_source(score_col, score_key)
+    be = _poly_eval_backend(backend)
+    wg, hg, sources = _size_columns(df_gt, width_col, height_col)
+    cells_gt, keys_gt, cells_pred, keys_pred = _compare_frames(df_gt, df_pred, json_col, other_col, key)
+    pred = df_gt if df_pred is None else df_pred
+    sizes_pred = (None, None) if df_pred is None else _size_columns(df_pred, width_col, height_col)[:2]
+    score_cells = _eval_score_cells(pred[score_col].tolist()) if score_col is not None else None
+    return _poly_eval_tables(cells_gt, (wg, hg), keys_gt, sources, cells_pred, sizes_pred, keys_pred, key, score_cells, score_key,
+                             thr, max_dets, params, be, stats)
+
+
+def evaluate_polygons_csv(gt_csv, pred_csv, output_dir, json_col: str = ANNOTATION_COL, key="source", width_col: str = "width",
+                          height_col: str = "height", score_col=None, score_key=None, iou_thresholds=None, max_dets: int = 100,
+                          max_pixels_per_row: int = 1 << 26, max_pairs_per_row: int = 1 << 20, batch_pixels: int = 1 << 28,
+                          batch_pairs: int = 1 << 26, backend=None, detections_csv=None):
+    """Two CSVs -> polygon_eval_classes.csv, polygon_eval_rows.csv, polygon_eval_missed.csv and polygon_eval_curves.npz (classes,
+    iou_thresholds, recall_points, precision, score_at, recall, ap) under output_dir, and the detections table when
+    detections_csv names a file; read in evaluate_boxes_csv's conventions (utf-8-sig; 读取失败：... / 错误：缺少必要列 ... and None).
+    key=None evaluates by position.  -> dict(totals, paths=...)"""
+    thr, max_dets = _eval_thresholds(iou_thresholds), _eval_max_dets(max_dets)
+    params = _poly_eval_params(max_pixels_per_row, max_pairs_per_row, batch_pixels, batch_pairs)
+    _eval_score_source(score_col, score_key)
+    be = _poly_eval_backend(backend)
+    read = _compare_read("evaluate_polygons", gt_csv, pred_csv, json_col, key)
+    if read is None:
+        return None
+    light_gt, cells_gt, keys_gt, light_pred, cells_pred, keys_pred = read
+    if score_col is not None and score_col not in light_pred.columns:
+        print(f"错误：缺少必要列 {score_col}")
+        return None
+    wg, hg, sources = _size_columns(light_gt, width_col, height_col)
+    score_cells = _eval_score_cells(light_pred[score_col].to_numpy().tolist()) if score_col is not None else None
+    res = _poly_eval_tables(cells_gt, (wg, hg), keys_gt, sources, cells_pred, _size_columns(light_pred, width_col, height_col)[:2],
+                            keys_pred, key, score_cells, score_key, thr, max_dets, params, be, None)
+    return {**res.totals, "paths": _write_evaluation(res, output_dir, detections_csv, "polygon_eval")}
 
 
 def _dataset_dir_name(excel_path: Path, idx_excel: int, used_dir_names: set) -> tuple:

@@ -3,7 +3,8 @@
 // matrix in device memory.  The wave's arg-max over the candidates of one B object (largest key, then the lowest index among
 // its holders, the largest best key carried along) stays written out in both kernels: as a function, in four spellings, it
 // moved the register count of k18_big_rows_kernel.  K24 (k24_eval.hip, scored evaluation) takes from here the box
-// load, the pair IoU (K2's arithmetic, the first box's area handed in), the keys, and the host side's check and upload of a table.
+// load, the pair IoU (K2's arithmetic, the first box's area handed in), the keys, and the host side's check and upload of a table;
+// K25 (k25_poly_eval.hip, scored polygon evaluation) the keys alone.
 #pragma once
 
 #include "k2_wave.h"

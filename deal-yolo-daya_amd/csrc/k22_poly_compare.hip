@@ -24,11 +24,13 @@
 //      the strip once and adds it with one u64 atomic.  Integer atomics only: no result depends on the schedule;
 //   4. match, a wave per row: K18's big-row scheme.  Lanes stride over the A polygons, the B polygons are taken in order, the
 //      arg-max (largest IoU, then lowest index) by shuffles; the matched state is out_a_match, which only the owning lane touches.
+// Steps 1 to 3 are also K25's pair step (k25_poly_eval.hip, through compare_pairs_launch of k22_pairs.h), with the paint kernel
+// in its evaluation flavour (the template argument), which keeps no owners and counts no pixel classes.
 #include "k13_scan.h"
 #include "k18_pick.h"
 #include "k21_cover.h"
+#include "k22_pairs.h"
 #include "poly_table.h"
-#include "sized_out.h"
 
 namespace dyd {
 
@@ -41,7 +43,6 @@ constexpr int K22_PITCH = K22_WORDS + 1;     // words per stored B bitmap: lanes
 constexpr int64_t K22_MAX_PIXELS = 1LL << 30;
 constexpr int64_t K22_MAX_PAIRS = 1LL << 24;
 constexpr int64_t K22_MAX_GRID = 1 << 20;    // paint workgroups; the items beyond are taken grid-stride
-constexpr uint8_t CMP_ROW_PAIRS = 4;         // row status: more pairs than max_pairs_per_row
 
 // ---- 1. rows: a lane per row -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(K22_BLOCK) void k22_rows_kernel(const double *__restrict__ width, const double *__restrict__ height,
@@ -108,6 +109,9 @@ __device__ __forceinline__ int k22_bitmap(const K22Side &t, int64_t p, const K21
     return n_covered;
 }
 
+// EVAL: the flavour of K25 (scored evaluation), which needs the pair cells of equal classes and the pixel counts only: no
+// owners, no class-pair pass, no row_pixels; a pair of different classes is neither intersected nor added.
+template <bool EVAL>
 __global__ __launch_bounds__(kWave) void k22_paint_kernel(K22Side A, K22Side B, const double *__restrict__ width,
                                                           const double *__restrict__ height, int64_t n_rows, int32_t C, int strip,
                                                           int cap, int chunk, const uint8_t *__restrict__ row_status,
@@ -115,12 +119,13 @@ __global__ __launch_bounds__(kWave) void k22_paint_kernel(K22Side A, K22Side B, 
                                                           int64_t n_items, int64_t pair_total, uint32_t *__restrict__ pairs,
                                                           unsigned long long *__restrict__ pixel_conf,
                                                           unsigned long long *__restrict__ row_pixels) {
-    __shared__ int32_t owner_a[K22_STRIP];   // polygon index, then the pixel's class pair
-    __shared__ int32_t owner_b[K22_STRIP];
+    __shared__ int32_t owner_a[EVAL ? 1 : K22_STRIP];   // polygon index, then the pixel's class pair
+    __shared__ int32_t owner_b[EVAL ? 1 : K22_STRIP];
     __shared__ double list[K22_CROSSINGS];
     __shared__ unsigned long long bits_b[K22_CHUNK * K22_PITCH];
     __shared__ unsigned long long bits_a[K22_WORDS];
     __shared__ int32_t idx_b[K22_CHUNK];
+    __shared__ int32_t cls_b[EVAL ? K22_CHUNK : 1];
     const int lane = threadIdx.x;
     for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
         const int64_t r = last_le(item_off, 0, n_rows - 1, item);
@@ -131,7 +136,8 @@ __global__ __launch_bounds__(kWave) void k22_paint_kernel(K22Side A, K22Side B, 
         const int64_t j = local / n_strips, x0 = (local - j * n_strips) * strip;
         const int npx = (int)min((int64_t)strip, W - x0);   // at most K22_WORDS words: strip <= K22_STRIP
         const K21Strip s{(double)j + 0.5, (double)x0 + 0.5, (double)(x0 + npx - 1) + 0.5, x0, npx, (npx + kWave - 1) / kWave};
-        for (int px = lane; px < s.npx; px += kWave) owner_a[px] = owner_b[px] = -1;
+        if constexpr (!EVAL)
+            for (int px = lane; px < s.npx; px += kWave) owner_a[px] = owner_b[px] = -1;
         int64_t a0, a1, b0, b1;
         k21_row_polys(A.row_off, r, A.n_polys, &a0, &a1);
         k21_row_polys(B.row_off, r, B.n_polys, &b0, &b1);
@@ -144,10 +150,12 @@ __global__ __launch_bounds__(kWave) void k22_paint_kernel(K22Side A, K22Side B, 
                 if (!k21_reaches(B.action, B.info, q, s)) continue;
                 uint32_t par;
                 const int n_cov = k22_bitmap(B, q, s, cap, list, bits_b + n_chunk * K22_PITCH, &par);
-                for (int c = 0; c < s.n_words; ++c)
-                    if ((par >> c) & 1u) owner_b[c * kWave + lane] = (int32_t)q;
+                if constexpr (!EVAL)
+                    for (int c = 0; c < s.n_words; ++c)
+                        if ((par >> c) & 1u) owner_b[c * kWave + lane] = (int32_t)q;
                 if (lane == 0) {
                     idx_b[n_chunk] = (int32_t)(q - b0);
+                    if constexpr (EVAL) cls_b[n_chunk] = B.cls[q];
                     if (n_cov > 0) atomicAdd(B.pixels + q, (unsigned long long)n_cov);
                 }
                 ++n_chunk;
@@ -159,11 +167,14 @@ __global__ __launch_bounds__(kWave) void k22_paint_kernel(K22Side A, K22Side B, 
                 uint32_t par;
                 const int n_cov = k22_bitmap(A, p, s, cap, list, bits_a, &par);
                 if (first) {
-                    for (int c = 0; c < s.n_words; ++c)
-                        if ((par >> c) & 1u) owner_a[c * kWave + lane] = (int32_t)p;
+                    if constexpr (!EVAL)
+                        for (int c = 0; c < s.n_words; ++c)
+                            if ((par >> c) & 1u) owner_a[c * kWave + lane] = (int32_t)p;
                     if (lane == 0 && n_cov > 0) atomicAdd(A.pixels + p, (unsigned long long)n_cov);
                 }
-                if (lane < n_chunk && n_cov > 0) {
+                bool mine = lane < n_chunk && n_cov > 0;
+                if constexpr (EVAL) mine = mine && cls_b[lane] == A.cls[p];
+                if (mine) {
                     const unsigned long long *wb = bits_b + lane * K22_PITCH;
                     unsigned int sum = 0;
                     for (int c = 0; c < s.n_words; ++c) sum += (unsigned int)__popcll(bits_a[c] & wb[c]);
@@ -174,6 +185,7 @@ __global__ __launch_bounds__(kWave) void k22_paint_kernel(K22Side A, K22Side B, 
             }
             if (q >= b1) break;
         }
+        if constexpr (EVAL) continue;   // the chunk loop ends behind a barrier or without a bitmap since the last one
         // owners -> class pairs, kept in owner_a; the row's two pixel counts
         const int32_t stride = C + 1;
         uint32_t rem = 0;
@@ -318,27 +330,7 @@ void set_k22_crossings(int v) { g_k22_crossings = k21_capped(v, K22_CROSSINGS); 
 void set_k22_chunk(int v) { g_k22_chunk = k21_capped(v, K22_CHUNK); }
 void set_k22_grid(int v) { g_k22_grid = k21_capped(v, (int)K22_MAX_GRID); }
 
-// one table of a comparison in device memory with its outputs
-struct K22Table {
-    const double *xy;
-    const int32_t *pt_off, *row_off, *cls;
-    int64_t n_polys, n_points;
-    uint8_t *action;
-    int64_t *pixels;
-    int32_t *match;
-    double *best;
-};
-
-struct K22Out {
-    uint8_t *row_status;
-    int64_t *pair_off;
-    double *b_iou;
-    int32_t *row_counts;
-    uint64_t *confusion, *pixel_confusion;
-    int64_t *row_pixels;
-};
-
-static int compare_params(int32_t n_classes, int64_t max_pixels, int64_t max_pairs) {
+int compare_params(int32_t n_classes, int64_t max_pixels, int64_t max_pairs) {
     DYD_REQUIRE(n_classes >= 1 && n_classes <= 1023, "n_classes must lie in 1..1023");
     DYD_REQUIRE(max_pixels >= 1 && max_pixels <= K22_MAX_PIXELS, "max_pixels_per_row must lie in 1..2^30");
     DYD_REQUIRE(max_pairs >= 1 && max_pairs <= K22_MAX_PAIRS, "max_pairs_per_row must lie in 1..2^24");
@@ -347,11 +339,9 @@ static int compare_params(int32_t n_classes, int64_t max_pixels, int64_t max_pai
 
 constexpr SizedName K22_PAIRS{"K22", "pair", "elements", 4};
 
-// Steps 1 to 4 on device pointers.  `pairs` is asked for the pair buffer once its size is known; it fails before anything but
-// row_status and pair_off is written.
-static int compare_launch(const K22Table &a, const K22Table &b, const double *width, const double *height, int64_t n_rows,
-                          int32_t C, double thr, int by_label, int64_t max_pixels, int64_t max_pairs, const K22Out &o,
-                          SizedOut &pairs_out, hipStream_t st) {
+// Steps 1 to 3 on device pointers (k22_pairs.h).
+int compare_pairs_launch(const K22Table &a, const K22Table &b, const double *width, const double *height, int64_t n_rows, int32_t C,
+                         int64_t max_pixels, int64_t max_pairs, const K22Out &o, bool for_eval, SizedOut &pairs_out, hipStream_t st) {
     const int strip = g_k22_strip, cap = g_k22_crossings, chunk = g_k22_chunk;
     const size_t info_a = 32 * (size_t)max(a.n_polys, (int64_t)1), info_b = 32 * (size_t)max(b.n_polys, (int64_t)1);
     ScratchLease lease(st);
@@ -371,9 +361,12 @@ static int compare_launch(const K22Table &a, const K22Table &b, const double *wi
         return rc;
     uint32_t *pairs = pairs_out.as<uint32_t>();
     const size_t cells = 8 * (size_t)(C + 1) * (size_t)(C + 1);
-    hipError_t e = hipMemsetAsync(o.confusion, 0, cells, st);
-    if (e == hipSuccess) e = hipMemsetAsync(o.pixel_confusion, 0, cells, st);
-    if (e == hipSuccess) e = hipMemsetAsync(o.row_pixels, 0, 16 * (size_t)n_rows, st);
+    hipError_t e = hipSuccess;
+    if (!for_eval) {
+        e = hipMemsetAsync(o.confusion, 0, cells, st);
+        if (e == hipSuccess) e = hipMemsetAsync(o.pixel_confusion, 0, cells, st);
+        if (e == hipSuccess) e = hipMemsetAsync(o.row_pixels, 0, 16 * (size_t)n_rows, st);
+    }
     if (e == hipSuccess && pair_total > 0) e = hipMemsetAsync(pairs, 0, 4 * (size_t)pair_total, st);
     if (e == hipSuccess && a.n_polys > 0) e = hipMemsetAsync(a.pixels, 0, 8 * (size_t)a.n_polys, st);
     if (e == hipSuccess && b.n_polys > 0) e = hipMemsetAsync(b.pixels, 0, 8 * (size_t)b.n_polys, st);
@@ -385,15 +378,35 @@ static int compare_launch(const K22Table &a, const K22Table &b, const double *wi
     k21_polys(b.xy, b.pt_off, b.row_off, b.cls, o.row_status, n_rows, b.n_polys, b.n_points, b.action, inf_b, st);
     unsigned long long *a_pix = reinterpret_cast<unsigned long long *>(a.pixels);
     unsigned long long *b_pix = reinterpret_cast<unsigned long long *>(b.pixels);
-    unsigned long long *conf = reinterpret_cast<unsigned long long *>(o.confusion);
     if (n_items > 0) {
         const K22Side A{a.xy, a.pt_off, a.row_off, a.cls, a.action, inf_a, a_pix, a.n_polys, a.n_points};
         const K22Side B{b.xy, b.pt_off, b.row_off, b.cls, b.action, inf_b, b_pix, b.n_polys, b.n_points};
-        hipLaunchKernelGGL(k22_paint_kernel, dim3((unsigned)(n_items < g_k22_grid ? n_items : g_k22_grid)), dim3(kWave), 0, st, A, B,
-                           width, height, n_rows, C, strip, cap, chunk, o.row_status, o.pair_off, item_off, n_items, pair_total,
-                           pairs, reinterpret_cast<unsigned long long *>(o.pixel_confusion),
-                           reinterpret_cast<unsigned long long *>(o.row_pixels));
+        const dim3 grid((unsigned)(n_items < g_k22_grid ? n_items : g_k22_grid));
+        if (for_eval)
+            hipLaunchKernelGGL(k22_paint_kernel<true>, grid, dim3(kWave), 0, st, A, B, width, height, n_rows, C, strip, cap, chunk,
+                               o.row_status, o.pair_off, item_off, n_items, pair_total, pairs, (unsigned long long *)nullptr,
+                               (unsigned long long *)nullptr);
+        else
+            hipLaunchKernelGGL(k22_paint_kernel<false>, grid, dim3(kWave), 0, st, A, B, width, height, n_rows, C, strip, cap, chunk,
+                               o.row_status, o.pair_off, item_off, n_items, pair_total, pairs,
+                               reinterpret_cast<unsigned long long *>(o.pixel_confusion),
+                               reinterpret_cast<unsigned long long *>(o.row_pixels));
     }
+    DYD_HIP(hipGetLastError());
+    return DYD_OK;
+}
+
+// Steps 1 to 4 on device pointers.  `pairs` is asked for the pair buffer once its size is known; it fails before anything but
+// row_status and pair_off is written.
+static int compare_launch(const K22Table &a, const K22Table &b, const double *width, const double *height, int64_t n_rows,
+                          int32_t C, double thr, int by_label, int64_t max_pixels, int64_t max_pairs, const K22Out &o,
+                          SizedOut &pairs_out, hipStream_t st) {
+    const int rc = compare_pairs_launch(a, b, width, height, n_rows, C, max_pixels, max_pairs, o, false, pairs_out, st);
+    if (rc) return rc;
+    const uint32_t *pairs = pairs_out.as<uint32_t>();
+    const unsigned long long *a_pix = reinterpret_cast<const unsigned long long *>(a.pixels);
+    const unsigned long long *b_pix = reinterpret_cast<const unsigned long long *>(b.pixels);
+    unsigned long long *conf = reinterpret_cast<unsigned long long *>(o.confusion);
     const int64_t want = (int64_t)ctx().num_cu * 32;
     hipLaunchKernelGGL(k22_match_kernel, dim3((unsigned)(n_rows < want ? n_rows : want)), dim3(kWave), 0, st, a.row_off, a.cls,
                        a.action, a_pix, b.row_off, b.cls, b.action, b_pix, n_rows, a.n_polys, b.n_polys, C, thr, by_label,

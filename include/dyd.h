@@ -811,6 +811,47 @@ int dyd_compare_polygons_dev(const double *a_xy, const int32_t *a_pt_off, const 
                              int32_t *out_row_counts, uint64_t *out_confusion, uint64_t *out_pixel_confusion, int64_t *out_row_pixels,
                              uint32_t *out_pairs_or_null, int64_t pair_cap, void *stream);
 
+/* ---- K25: scored polygon evaluation — COCO-style mask AP per class: K24's selection and matching on K22's mask IoU ---------
+ * After COCOeval's evaluateImg for iouType "segm", area range "all", no crowd or ignore regions.  Table A holds the ground truth
+ * (GT), table B the detections, both polygon tables in K22's layout (xy, pt_off, row_off, cls with cls < 0 = not selected) over
+ * the same n_rows rows, width / height [n_rows] f64 and one class list; dt_score [n_dt] f64 holds one score per detection.
+ * Host pointers only; the pair table stays inside the library.  The accumulation is dyd_eval_accumulate (K24), unchanged.
+ * Parameters: 1 <= T <= 32; max_dets >= 1; n_classes in 1..1023; max_pixels_per_row in 1..2^30; max_pairs_per_row in 1..2^24; a
+ * class id >= n_classes: anything else is DYD_ERR_INVALID.
+ * Rows and polygons.  Row status (status 4 too_many_pairs included), the action per polygon, cover(p), pixels[p] and
+ *   inter(g, d) are exactly K22's.  iou(g, d) = (double)inter / (double)(pixels[g] + pixels[d] - inter) when inter > 0, else
+ *   exactly 0.0: one correctly rounded division, no NaN IoU.  Only polygons of action 0 (in rows of status 0) take part.
+ * Detection state: 3 skipped: the action is not 0 (not selected, row not evaluated, bad_coords, too_few_points).  2 bad_score:
+ *   the score is not finite.  The others are ranked within (row, class) by score descending, ties to the earlier position in the
+ *   row, -0.0 equal to 0.0 (score + 0.0 everywhere, also where an output reports a score): 1 cut: rank >= max_dets;
+ *   0 evaluated: the rest.
+ * Matching, per threshold index t on its own, lim = min(iou_thr[t], 1 - 1e-10): the row's evaluated detections in score order
+ *   (any interleaving of the classes); detection d takes the GT polygon g of its row and class (action 0) that is still free
+ *   at t, has inter(g, d) > 0 and the largest iou(g, d) >= lim, ties to the HIGHEST g (K24's rule; K22 takes the lowest).  A
+ *   NaN threshold matches nothing.
+ * Ground truth.  A GT polygon of action 0 counts as ground truth also when it covers no pixel centre; it can never be matched.
+ *   A GT polygon of any other action is no ground truth (the caller reports it as skipped).  A detection that covers no pixel
+ *   is evaluated and is a false positive at every threshold.
+ * out_row_status u8 [n_rows], out_pair_off i64 [n_rows+1], out_gt_action / out_dt_action u8, out_gt_pixels / out_dt_pixels i64:
+ *   K22's out_row_status, out_pair_off, out_a_action / out_b_action and out_a_pixels / out_b_pixels
+ * out_dt_state [n_dt] i32: the codes above
+ * out_dt_tp [n_dt] u32: bit t = matched at threshold t
+ * out_dt_gt [n_dt] i32: in-row index of the GT polygon matched at t = 0, else -1
+ * out_dt_iou [n_dt] f64: that pair's IoU, else 0.0
+ * out_dt_best [n_dt] f64: largest IoU with any GT polygon of its row and class of action 0, free or not; 0.0 for a detection
+ *             that is not evaluated
+ * out_gt_hit [n_gt] u32: bit t = matched at threshold t
+ * out_gt_best [n_gt] f64: largest IoU over the evaluated detections of its row and class
+ * Every output element is written, also in rows that are not evaluated (0, -1 and 0.0).  n_rows == 0 returns at once. */
+int dyd_eval_match_polygons(const double *gt_xy, const int32_t *gt_pt_off, const int32_t *gt_row_off, const int32_t *gt_cls,
+                            const double *dt_xy, const int32_t *dt_pt_off, const int32_t *dt_row_off, const int32_t *dt_cls,
+                            const double *dt_score, const double *width, const double *height, int64_t n_rows, int32_t n_classes,
+                            const double *iou_thr, int32_t T, int32_t max_dets, int64_t max_pixels_per_row,
+                            int64_t max_pairs_per_row, uint8_t *out_row_status, int64_t *out_pair_off, uint8_t *out_gt_action,
+                            uint8_t *out_dt_action, int64_t *out_gt_pixels, int64_t *out_dt_pixels, int32_t *out_dt_state,
+                            uint32_t *out_dt_tp, int32_t *out_dt_gt, double *out_dt_iou, double *out_dt_best, uint32_t *out_gt_hit,
+                            double *out_gt_best);
+
 /* ---- K23: COCO RLE — the column-major run lengths of every selected polygon's own mask, as COCO's "counts" string --------
  * The table is K21's: xy [2*P] f64 (16-B aligned), pt_off [B+1] i32, row_off [n_rows+1] i32, width / height [n_rows] f64, and
  * sel [B] i32: sel[p] < 0: the polygon is not selected (action 255); any other value selects it.  max_pixels_per_row in 1..2^30,

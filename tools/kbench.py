@@ -6,7 +6,8 @@ interleaved A/B rounds in one process).  Prints one JSON line per kernel/variant
      k14: polygon audit; k14tier: its in-lane / wave threshold; simplify: polygon simplification (K19) beside K14 on rings of 8, 64 and 1024 points; k16: COCO annotation objects beside K13; k17: oriented-box lines beside K13; tile: tiled label lines (K20) beside K13;
      k21: label masks (K21) on many small and few large images, beside Pillow on one core; k22: polygon comparison (K22) on the same
      two tables, interleaved with K21 over either side; k23: COCO run-length masks (K23) on the same two tables, measure-only and
-     full, interleaved with K21 over the same table)
+     full, interleaved with K21 over the same table; k25: scored polygon evaluation (K25) at T = 1 and T = 10 beside K22 on the same
+     two tables, through the host entries)
 """
 import argparse
 import json
@@ -667,6 +668,24 @@ def main():
         rol = torch.arange(0, 33, 4, dtype=torch.int32, device=dev)
         yield "large_images", xl, ptl, rol, 8, 32, 32 * m, 4096, 4096
 
+    def compare_polygon_tables(xy_, pt_, roff, nr, nb, nc):
+        """table B of the k22 and k25 legs from table A: 10 % of the polygons dropped, 10 % with jittered vertices, 5 % put into
+        another class -> (A's row_off, A's cls, B's xy [P, 2], pt_off, row_off, cls, the draw u of the kept polygons), numpy"""
+        rng = np.random.default_rng(22)
+        hx, hp, hr = xy_.cpu().numpy().reshape(-1, 2), pt_.cpu().numpy().astype(np.int64), roff.cpu().numpy().astype(np.int64)
+        u = rng.random(nb)
+        keep = np.flatnonzero(u >= 0.10)
+        cls_a = (np.arange(nb) % nc).astype(np.int32)
+        cls_b = np.where(u[keep] >= 0.95, (cls_a[keep] + 1) % nc, cls_a[keep]).astype(np.int32)
+        cnt = np.diff(hp)[keep]
+        pb = np.concatenate([[0], np.cumsum(cnt)])
+        src = np.repeat(hp[:-1][keep] - pb[:-1], cnt) + np.arange(int(pb[-1]))
+        xb = hx[src].copy()
+        jit = np.repeat((u[keep] >= 0.10) & (u[keep] < 0.20), cnt)
+        xb[jit] += rng.uniform(-2.0, 2.0, (int(jit.sum()), 2))
+        rb = np.concatenate([[0], np.cumsum(np.bincount(np.searchsorted(hr, keep, side="right") - 1, minlength=nr))])
+        return hr, cls_a, xb, pb, rb, cls_b, u[keep]
+
     if "k21" in only:
         import ctypes as C
         import time
@@ -725,20 +744,8 @@ def main():
         nc = 20
 
         def k22_leg(name, xy_, pt_, roff, nr, nb, npts, W, H):
-            rng = np.random.default_rng(22)
-            hx, hp, hr = xy_.cpu().numpy().reshape(-1, 2), pt_.cpu().numpy().astype(np.int64), roff.cpu().numpy().astype(np.int64)
-            u = rng.random(nb)
-            keep = np.flatnonzero(u >= 0.10)
-            cls_a = (np.arange(nb) % nc).astype(np.int32)
-            cls_b = np.where(u[keep] >= 0.95, (cls_a[keep] + 1) % nc, cls_a[keep]).astype(np.int32)
-            cnt = np.diff(hp)[keep]
-            pb = np.concatenate([[0], np.cumsum(cnt)])
-            src = np.repeat(hp[:-1][keep] - pb[:-1], cnt) + np.arange(int(pb[-1]))
-            xb = hx[src].copy()
-            jit = np.repeat((u[keep] >= 0.10) & (u[keep] < 0.20), cnt)
-            xb[jit] += rng.uniform(-2.0, 2.0, (int(jit.sum()), 2))
-            rb = np.concatenate([[0], np.cumsum(np.bincount(np.searchsorted(hr, keep, side="right") - 1, minlength=nr))])
-            nbb, npb = len(keep), int(pb[-1])
+            hr, cls_a, xb, pb, rb, cls_b, _ = compare_polygon_tables(xy_, pt_, roff, nr, nb, nc)
+            nbb, npb = len(cls_b), int(pb[-1])
             up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)   # noqa: E731
             b_xy, b_pt, b_row, d_ca, d_cb = up(xb.reshape(-1), np.float64), up(pb, np.int32), up(rb, np.int32), up(cls_a, np.int32), up(cls_b, np.int32)
             w = torch.full((nr,), float(W), dtype=torch.float64, device=dev); h = torch.full((nr,), float(H), dtype=torch.float64, device=dev)
@@ -792,6 +799,51 @@ def main():
 
         for shape in raster_shapes():
             k22_leg(*shape)
+    if "k25" in only:
+        # K25 (scored polygon evaluation) through its host entry on the k22 leg's two tables, B with a score of three decimals per
+        # polygon, at T = 1 and T = 10; K22 through its host entry on the same tables in the same interleaved rounds is the
+        # yardstick: K25 does K22's paint without the owners, the class-pair pass and the pairs of different classes, plus the
+        # ranking.  Kernel time from dyd_last_kernel_ms, as in the k24 leg.
+        nc = 20
+        thr10 = np.linspace(0.5, 0.95, 10)
+
+        def k25_leg(name, xy_, pt_, roff, nr, nb, npts, W, H):
+            hr, cls_a, xb, pb, rb, cls_b, ub = compare_polygon_tables(xy_, pt_, roff, nr, nb, nc)
+            nbb, npb = len(cls_b), int(pb[-1])
+            score = np.round(ub * 0.37 % 1.0, 3)                         # three decimals: ties within and across rows
+            tabs = (xy_.cpu().numpy().reshape(-1), pt_.cpu().numpy(), roff.cpu().numpy(), cls_a, xb.reshape(-1), pb.astype(np.int32),
+                    rb.astype(np.int32), cls_b)
+            w, h = np.full(nr, float(W)), np.full(nr, float(H))
+
+            def kernel_ms(fn, iters=max(3, args.iters // 4)):
+                fn()
+                ts = []
+                for _ in range(iters):
+                    fn()
+                    ts.append(_native.last_kernel_ms())
+                return float(np.median(ts)), float(np.min(ts))
+
+            legs = {"k22": lambda: _native.compare_polygons(*tabs, w, h, nc, 0.5, False),
+                    "k25 T=1": lambda: _native.eval_match_polygons(*tabs, score, w, h, nc, [0.5], 100),
+                    "k25 T=10": lambda: _native.eval_match_polygons(*tabs, score, w, h, nc, thr10, 100)}
+            res = {}
+            for rnd in range(2):                  # interleaved rounds (guide rule 24)
+                for key, fn in legs.items():
+                    res.setdefault(key, []).append(kernel_ms(fn))
+            med = {k: float(np.median([r[0] for r in v])) for k, v in res.items()}
+            mn = {k: min(r[1] for r in v) for k, v in res.items()}
+            out = legs["k25 T=10"]()
+            n_pairs = int(out[1][-1])
+            table_bytes = 16 * (npts + npb) + 4 * (nb + nbb + 2) + 4 * (nb + nbb) + 8 * (nr + 1) + 16 * nr + 8 * nbb
+            for key, T_ in (("k25 T=1", 1), ("k25 T=10", 10)):
+                report(f"k25_eval_match_polygons_{name} T={T_}", table_bytes + 4 * n_pairs + 21 * nb + 37 * nbb + 9 * nr, med[key], mn[key],
+                       rows=nr, gt_polygons=nb, detections=nbb, width=W, height=H, pixels=nr * W * H, pairs=n_pairs,
+                       evaluated=int((out[6] == 0).sum()), tp_at_first=int((out[7] & 1).sum()),
+                       k22_host_entry_ms=round(med["k22"], 4), k22_host_entry_min_ms=round(mn["k22"], 4),
+                       k25_over_k22=round(med[key] / med["k22"], 3))
+
+        for shape in raster_shapes():
+            k25_leg(*shape)
     if "k23" in only:
         import ctypes as C
         # K23 (COCO run-length masks) on the k21 leg's two tables: measure-only (status, action, area, bbox, run_off) and full
