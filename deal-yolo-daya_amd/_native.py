@@ -665,6 +665,18 @@ def compare_boxes(a_box4, a_row_off, a_cls, b_box4, b_row_off, b_cls, n_classes:
     return a_match, b_match, b_iou, a_best, b_best, rows, conf
 
 
+def _eval_match_arrays(dt_score, iou_thr, ng: int, nd: int):
+    """what both matchers take and give back: the scores and thresholds as flat f64, and the seven result arrays
+    (dt_state, dt_tp, dt_gt, dt_iou, dt_best per detection; gt_hit, gt_best per ground-truth object)"""
+    dt_score = np.ascontiguousarray(dt_score, dtype=np.float64).reshape(-1)
+    if dt_score.size != nd:
+        raise ValueError("dt_score must hold one score per detection")
+    iou_thr = np.ascontiguousarray(iou_thr, dtype=np.float64).reshape(-1)
+    out = (np.zeros(nd, np.int32), np.zeros(nd, np.uint32), np.full(nd, -1, np.int32), np.zeros(nd, np.float64),
+           np.zeros(nd, np.float64), np.zeros(ng, np.uint32), np.zeros(ng, np.float64))
+    return dt_score, iou_thr, out
+
+
 def eval_match_boxes(gt_box4, gt_row_off, gt_cls, dt_box4, dt_row_off, dt_cls, dt_score, n_classes: int, iou_thr,
                      max_dets: int = 100):
     """K24's matching over host arrays: a ground-truth table and a detection table with scores over the same rows ->
@@ -675,18 +687,11 @@ def eval_match_boxes(gt_box4, gt_row_off, gt_cls, dt_box4, dt_row_off, dt_cls, d
     n = len(gt_row_off) - 1
     if len(dt_row_off) - 1 != n:
         raise ValueError("the two tables must cover the same rows")
-    dt_score = np.ascontiguousarray(dt_score, dtype=np.float64).reshape(-1)
-    if dt_score.size != nd:
-        raise ValueError("dt_score must hold one score per detection")
-    iou_thr = np.ascontiguousarray(iou_thr, dtype=np.float64).reshape(-1)
-    state, tp, gt = np.zeros(nd, np.int32), np.zeros(nd, np.uint32), np.full(nd, -1, np.int32)
-    iou, best = np.zeros(nd, np.float64), np.zeros(nd, np.float64)
-    hit, gbest = np.zeros(ng, np.uint32), np.zeros(ng, np.float64)
+    dt_score, iou_thr, out = _eval_match_arrays(dt_score, iou_thr, ng, nd)
     check(lib().dyd_eval_match_boxes(_ptr(gt_box4), _ptr(gt_row_off), _ptr(gt_cls), _ptr(dt_box4), _ptr(dt_row_off), _ptr(dt_cls),
                                      _ptr(dt_score), n, int(n_classes), _ptr(iou_thr), int(iou_thr.size), int(max_dets),
-                                     _ptr(state), _ptr(tp), _ptr(gt), _ptr(iou), _ptr(best), _ptr(hit), _ptr(gbest)),
-          "dyd_eval_match_boxes")
-    return state, tp, gt, iou, best, hit, gbest
+                                     *map(_ptr, out)), "dyd_eval_match_boxes")
+    return out
 
 
 def eval_accumulate(cls, score, tp, n_classes: int, n_thresholds: int, npig, rec):
@@ -725,24 +730,17 @@ def eval_match_polygons(gt_xy, gt_pt_off, gt_row_off, gt_cls, dt_xy, dt_pt_off, 
                                                                                 ("width", width, np.float64), ("gt_cls", gt_cls, np.int32))
     dt_xy, dt_pt_off, dt_row_off, _, _, _, dt_cls, _, nd = _poly_table(dt_xy, dt_pt_off, dt_row_off, width, height,
                                                                        ("width", width, np.float64), ("dt_cls", dt_cls, np.int32))
-    dt_score = np.ascontiguousarray(dt_score, dtype=np.float64).reshape(-1)
-    if dt_score.size != nd:
-        raise ValueError("dt_score must hold one score per detection")
-    iou_thr = np.ascontiguousarray(iou_thr, dtype=np.float64).reshape(-1)
+    dt_score, iou_thr, out = _eval_match_arrays(dt_score, iou_thr, ng, nd)
     status, pair_off = np.zeros(n, np.uint8), np.zeros(n + 1, np.int64)
     g_act, d_act = np.zeros(ng, np.uint8), np.zeros(nd, np.uint8)
     g_pix, d_pix = np.zeros(ng, np.int64), np.zeros(nd, np.int64)
-    state, tp, gt = np.zeros(nd, np.int32), np.zeros(nd, np.uint32), np.full(nd, -1, np.int32)
-    iou, best = np.zeros(nd, np.float64), np.zeros(nd, np.float64)
-    hit, gbest = np.zeros(ng, np.uint32), np.zeros(ng, np.float64)
     opt = lambda a: _ptr(a) if a.size else None          # noqa: E731
     check(lib().dyd_eval_match_polygons(opt(gt_xy), _ptr(gt_pt_off), _ptr(gt_row_off), opt(gt_cls), opt(dt_xy), _ptr(dt_pt_off),
                                         _ptr(dt_row_off), opt(dt_cls), opt(dt_score), _ptr(width), _ptr(height), n, int(n_classes),
                                         _ptr(iou_thr), int(iou_thr.size), int(max_dets), int(max_pixels_per_row),
                                         int(max_pairs_per_row), _ptr(status), _ptr(pair_off), opt(g_act), opt(d_act), opt(g_pix),
-                                        opt(d_pix), opt(state), opt(tp), opt(gt), opt(iou), opt(best), opt(hit), opt(gbest)),
-          "dyd_eval_match_polygons")
-    return status, pair_off, g_act, d_act, g_pix, d_pix, state, tp, gt, iou, best, hit, gbest
+                                        opt(d_pix), *map(opt, out)), "dyd_eval_match_polygons")
+    return (status, pair_off, g_act, d_act, g_pix, d_pix, *out)
 
 
 def bbox_iou_fused(xy: np.ndarray, pt_off: np.ndarray, box_off: np.ndarray, min_boxes: int, thr: float,

@@ -3108,23 +3108,37 @@ def _eval_chunk(cells_gt, cells_pred, scores, score_key, thr, max_dets: int, be,
                                                                 off[1].astype(np.int32), cls[1], score, len(names), thr, max_dets)
     state, tp, gt, hit = (np.asarray(v, np.int64) for v in (state, tp, gt, hit))
     iou, best, g_best = (np.asarray(v, np.float64) for v in (iou, best, g_best))
+    _eval_chunk_columns(acc, start, n, names, cls, off, (np.diff(off[0]), np.diff(off[1])), obj, score,
+                        (state, tp, gt, iou, best, hit, g_best), (tg.odd_names, td.odd_names), EVAL_STATES, None, (box[0], None))
+
+
+def _eval_chunk_columns(acc: _EvalTotals, start: int, n: int, names, cls, off, count, obj, score, matched: tuple, odd_names: tuple,
+                        states: tuple, live, tail: tuple) -> tuple:
+    """The columns one matched chunk of n rows leaves in acc (gts, dets, n_gt, n_dt, det_lines, missed), for boxes and polygons:
+    names / cls the chunk's class list and ids, off / count / obj the offsets, counts and object indices of (GT, detections),
+    matched the matcher's seven outputs, states the names of dt_state, live the mask of the ground truth that counts (None:
+    all of it), tail the last column of (missed, detections), None for none -> the table-wide class ids (cls_g, cls_d)"""
+    state, tp, gt, iou, best, hit, g_best = matched
     to = np.asarray([acc.index.setdefault(nm, len(acc.index)) for nm in names], np.int64)
-    row_g = np.repeat(np.arange(n, dtype=np.int64), np.diff(off[0]))
-    row_d = np.repeat(np.arange(n, dtype=np.int64), np.diff(off[1]))
+    row_g = np.repeat(np.arange(n, dtype=np.int64), count[0])
+    row_d = np.repeat(np.arange(n, dtype=np.int64), count[1])
     cls_g, cls_d = to[cls[0]] if len(to) else np.zeros(0, np.int64), to[cls[1]] if len(to) else np.zeros(0, np.int64)
-    acc.gts.append((start + row_g, cls_g, hit))
+    keep = np.ones(len(hit), bool) if live is None else live
+    acc.gts.append((start + row_g[keep], cls_g[keep], hit[keep]))
+    acc.n_gt.append(count[0] if live is None else np.bincount(row_g[keep], minlength=n).astype(np.int64))
     acc.dets.append((start + row_d, cls_d, score, state, tp))
-    acc.n_gt.append(np.diff(off[0]))
-    acc.n_dt.append(np.diff(off[1]))
+    acc.n_dt.append(count[1])
     every = np.arange(len(row_d), dtype=np.int64)
     gt_at = np.where(gt >= 0, off[0][row_d] + gt, 0)
-    acc.det_lines.append((start + row_d, obj[1], _compare_names(names, cls[1], td.odd_names, every), score,
-                          np.asarray(EVAL_STATES, object)[state], np.asarray([bin(int(v)).count("1") for v in tp], np.int64),
-                          np.where(gt >= 0, obj[0][gt_at] if len(obj[0]) else -1, -1), iou, best))
-    miss = np.flatnonzero((hit & 1) == 0)
+    acc.det_lines.append((start + row_d, obj[1], _compare_names(names, cls[1], odd_names[1], every), score,
+                          np.asarray(states, object)[state], np.asarray([bin(int(v)).count("1") for v in tp], np.int64),
+                          np.where(gt >= 0, obj[0][gt_at] if len(obj[0]) else -1, -1), iou, best,
+                          *(() if tail[1] is None else (tail[1],))))
+    miss = np.flatnonzero(keep & ((hit & 1) == 0))
     if len(miss):
-        acc.missed.append((start + row_g[miss], obj[0][miss], _compare_names(names, cls[0], tg.odd_names, miss), g_best[miss],
-                           box[0][miss]))
+        acc.missed.append((start + row_g[miss], obj[0][miss], _compare_names(names, cls[0], odd_names[0], miss), g_best[miss],
+                           tail[0][miss]))
+    return cls_g, cls_d
 
 
 def _eval_fields(acc: _EvalTotals, n: int, thr, max_dets: int, be, sources, noun: str, det_spec: tuple, missed_spec: tuple) -> tuple:
@@ -3214,16 +3228,7 @@ def evaluate_boxes_cells(cells_gt, cells_pred, scores=None, score_key=None, iou_
     totals["python_score_cells"] counts them.  iou_thresholds: numbers in (0, 1], at most 32, default 0.5, 0.55 .. 0.95;
     per (row, class) the max_dets best-scored detections are evaluated.  ``sources`` (optional) adds a source column."""
     thr, max_dets = _eval_thresholds(iou_thresholds), _eval_max_dets(max_dets)
-    if (scores is None) == (score_key is None):
-        raise ValueError("exactly one of scores and score_key must be given")
-    be = _step_backend(_step_backend(backend, "eval_match_boxes"), "eval_accumulate")
-    cells_gt = cells_gt.to_numpy() if hasattr(cells_gt, "to_numpy") else cells_gt
-    cells_pred = cells_pred.to_numpy() if hasattr(cells_pred, "to_numpy") else cells_pred
-    n = len(cells_gt)
-    if len(cells_pred) != n:
-        raise ValueError(f"the two lists must hold one cell per image each: {n} against {len(cells_pred)} cells")
-    if scores is not None and len(scores) != n:
-        raise ValueError(f"scores must hold one entry per row: {len(scores)} against {n} rows")
+    be, cells_gt, cells_pred, n = _eval_cells_args(cells_gt, cells_pred, scores, score_key, backend, "eval_match_boxes")
     acc = _EvalTotals()
     for s0, s1, chunk in _chunks(n, cells_gt):
         _eval_chunk(chunk, cells_pred[s0:s1], scores, score_key, thr, max_dets, be, acc, s0)
@@ -3231,6 +3236,22 @@ def evaluate_boxes_cells(cells_gt, cells_pred, scores=None, score_key=None, iou_
     if stats is not None:
         stats.update(res.totals)
     return res
+
+
+def _eval_cells_args(cells_gt, cells_pred, scores, score_key, backend, matcher: str) -> tuple:
+    """the head of evaluate_boxes_cells and evaluate_polygons_cells behind their own parameters: one source of scores, a
+    backend with `matcher` and the accumulation, both cell lists as arrays of one length -> (be, cells_gt, cells_pred, n)"""
+    if (scores is None) == (score_key is None):
+        raise ValueError("exactly one of scores and score_key must be given")
+    be = _step_backend(_step_backend(backend, matcher), "eval_accumulate")
+    cells_gt = cells_gt.to_numpy() if hasattr(cells_gt, "to_numpy") else cells_gt
+    cells_pred = cells_pred.to_numpy() if hasattr(cells_pred, "to_numpy") else cells_pred
+    n = len(cells_gt)
+    if len(cells_pred) != n:
+        raise ValueError(f"the two lists must hold one cell per image each: {n} against {len(cells_pred)} cells")
+    if scores is not None and len(scores) != n:
+        raise ValueError(f"scores must hold one entry per row: {len(scores)} against {n} rows")
+    return be, cells_gt, cells_pred, n
 
 
 def _eval_score_cells(col) -> list:
@@ -5290,26 +5311,12 @@ def _poly_eval_chunk(cells_gt, cells_pred, scores, score_key, W, H, thr, max_det
         act[0][g0:g1], act[1][d0:d1], pix[0][g0:g1], pix[1][d0:d1] = out[2], out[3], out[4], out[5]
         state[d0:d1], tp[d0:d1], gt[d0:d1], iou[d0:d1], best[d0:d1] = out[6], out[7], out[8], out[9], out[10]
         hit[g0:g1], g_best[g0:g1] = out[11], out[12]
-    to = np.asarray([acc.index.setdefault(nm, len(acc.index)) for nm in names], np.int64)
-    row_g = np.repeat(np.arange(n, dtype=np.int64), count[0])
-    row_d = np.repeat(np.arange(n, dtype=np.int64), count[1])
-    cls_g, cls_d = to[cls[0]] if len(to) else np.zeros(0, np.int64), to[cls[1]] if len(to) else np.zeros(0, np.int64)
     live = act[0] == 0                                   # the ground truth that counts
-    acc.gts.append((start + row_g[live], cls_g[live], hit[live]))
-    acc.dets.append((start + row_d, cls_d, score, state, tp))
-    acc.n_gt.append(np.bincount(row_g[live], minlength=n).astype(np.int64))
-    acc.n_dt.append(count[1])
+    cls_g, cls_d = _eval_chunk_columns(acc, start, n, names, cls, off, count, obj, score, (state, tp, gt, iou, best, hit, g_best),
+                                       ({}, {}), POLY_EVAL_STATES, live, pix)
     acc.skipped.append((cls_g[~live], cls_d[state == 3]))
     acc.status.append(host_status)
     acc.row_pixels.append(host_pixels)
-    every = np.arange(len(row_d), dtype=np.int64)
-    gt_at = np.where(gt >= 0, off[0][row_d] + gt, 0)
-    acc.det_lines.append((start + row_d, obj[1], _compare_names(names, cls[1], {}, every), score,
-                          np.asarray(POLY_EVAL_STATES, object)[state], np.asarray([bin(int(v)).count("1") for v in tp], np.int64),
-                          np.where(gt >= 0, obj[0][gt_at] if len(obj[0]) else -1, -1), iou, best, pix[1]))
-    miss = np.flatnonzero(live & ((hit & 1) == 0))
-    if len(miss):
-        acc.missed.append((start + row_g[miss], obj[0][miss], _compare_names(names, cls[0], {}, miss), g_best[miss], pix[0][miss]))
 
 
 def _poly_eval_result(acc: _PolyEvalTotals, n: int, thr, max_dets: int, be, sources, params: tuple, mismatch, stats) -> PolygonEvaluation:
@@ -5361,16 +5368,7 @@ def evaluate_polygons_cells(cells_gt, cells_pred, widths, heights, scores=None, 
     compare_polygons_cells."""
     thr, max_dets = _eval_thresholds(iou_thresholds), _eval_max_dets(max_dets)
     params = _poly_eval_params(max_pixels_per_row, max_pairs_per_row, batch_pixels, batch_pairs)
-    if (scores is None) == (score_key is None):
-        raise ValueError("exactly one of scores and score_key must be given")
-    be = _poly_eval_backend(backend)
-    cells_gt = cells_gt.to_numpy() if hasattr(cells_gt, "to_numpy") else cells_gt
-    cells_pred = cells_pred.to_numpy() if hasattr(cells_pred, "to_numpy") else cells_pred
-    n = len(cells_gt)
-    if len(cells_pred) != n:
-        raise ValueError(f"the two lists must hold one cell per image each: {n} against {len(cells_pred)} cells")
-    if scores is not None and len(scores) != n:
-        raise ValueError(f"scores must hold one entry per row: {len(scores)} against {n} rows")
+    be, cells_gt, cells_pred, n = _eval_cells_args(cells_gt, cells_pred, scores, score_key, backend, "eval_match_polygons")
     return _poly_eval_rows(cells_gt, cells_pred, scores, score_key, n, widths, heights, None, thr, max_dets, params, be, stats, sources)
 
 

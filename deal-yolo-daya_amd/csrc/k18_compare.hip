@@ -25,6 +25,7 @@
 //   global u64 atomics otherwise and in the big-row kernel.  The counts do not depend on the order.
 //   The exact IoU of every candidate is needed, so K2's rejecting bound (thr_lo) is not used here.
 #include "k18_pick.h"
+#include "sized_out.h"
 
 namespace dyd {
 
@@ -365,8 +366,9 @@ int launch_k18(const double *a_box4, const int32_t *a_off, const int32_t *a_cls,
     // rows that fit no tile: more than 64 A boxes or more than K18_BCAP B boxes
     int64_t cap = n_a / (kWave + 1) + n_b / (K18_BCAP + 1);
     cap = (cap < n_rows) ? cap : n_rows;
+    ScratchLease lease(st);   // the list of big rows
     void *scratch = nullptr;
-    int rc = get_scratch(4 * (size_t)(cap + 1), &scratch, st);
+    int rc = lease.get(4 * (size_t)(cap + 1), &scratch);
     if (rc) return rc;
     int32_t *bigl = static_cast<int32_t *>(scratch);
     DYD_HIP(hipMemsetAsync(bigl, 0, 4, st));
@@ -383,7 +385,6 @@ int launch_k18(const double *a_box4, const int32_t *a_off, const int32_t *a_cls,
                            out_b_best, out_rows, conf, bigl, (int32_t)cap);
         DYD_HIP(hipGetLastError());
     }
-    release_scratch(st);
     return DYD_OK;
 }
 

@@ -4,7 +4,7 @@
 // its holders, the largest best key carried along) stays written out in both kernels: as a function, in four spellings, it
 // moved the register count of k18_big_rows_kernel.  K24 (k24_eval.hip, scored evaluation) takes from here the box
 // load, the pair IoU (K2's arithmetic, the first box's area handed in), the keys, and the host side's check and upload of a table;
-// K25 (k25_poly_eval.hip, scored polygon evaluation) the keys alone.
+// K25 (k25_poly_eval.hip, scored polygon evaluation) the keys alone, both through eval_match.h, which holds what those two share.
 #pragma once
 
 #include "k2_wave.h"

@@ -21,8 +21,8 @@
 //   First launch GW = 16 over all rows (16 rows per workgroup); a row of more than 16 GT boxes or 32 detections goes onto a list
 //   for the GW = 64 launch (a wave per row, 64 GT boxes, 128 detections); what fits neither goes to k24_big_rows_kernel: a
 //   workgroup per row, the GT boxes strided over the 256 lanes, the state in out_gt_hit / out_gt_best (read and written by the
-//   owning lane only), the detections' score order in a scratch column, two or three barriers per evaluated detection whatever T
-//   is.  Exact for any row length, O(n_gt * n_dt) IoUs per row (times T in the big-row kernel, which recomputes instead of
+//   owning lane only), the detections' score order in a scratch column (eval_match.h's eval_rank_row, which k25_match_kernel
+//   runs too), two or three barriers per evaluated detection whatever T is.  Exact for any row length, O(n_gt * n_dt) IoUs per row (times T in the big-row kernel, which recomputes instead of
 //   keeping a row of IoUs), never an n_gt x n_dt matrix.
 //
 // Entry 2, dyd_eval_accumulate.  The evaluated detections of the whole table are ordered by (class, score descending, index)
@@ -30,19 +30,18 @@
 // counts the segment's TPs, then walks it BACKWARDS in tiles of 256 with the carried TP count and the carried maximum from the
 // right, so that the precision envelope is known at every position without a stored precision column; a detection that raises
 // the recall writes the recall points it is the first to reach.  The best-F1 point is folded on the way.
-#include <cmath>
 #include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
-#include "k18_pick.h"
+#include "eval_match.h"
+#include "sized_out.h"
 
 namespace dyd {
 
 constexpr int K24_BLOCK = 256;
 constexpr int K24_WAVES = K24_BLOCK / kWave;
-constexpr int K24_MAX_T = 32;
 
 template <int DCAP>
 struct K24Lds {
@@ -53,41 +52,18 @@ struct K24Lds {
     unsigned short perm[DCAP];   // score order -> detection, 0xFFFF: none
 };
 
-struct K24Out {
-    int32_t *dt_state;
-    uint32_t *dt_tp;
-    int32_t *dt_gt;
-    double *dt_iou, *dt_best;
-    uint32_t *gt_hit;
-    double *gt_best;
-};
-
-__device__ __forceinline__ bool k24_finite(double s) { return (s - s) == 0.0; }
-// detection j goes before detection k (both finite scores)
-__device__ __forceinline__ bool k24_before(double sj, int j, double sk, int k) { return sj > sk || (sj == sk && j < k); }
-
-template <int GW>
-__device__ __forceinline__ unsigned long long k24_group_max(unsigned long long v) {
-#pragma unroll
-    for (int d = GW / 2; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d);
-        v = (o > v) ? o : v;
-    }
-    return v;
-}
-
 // One group of GW lanes per item; item = row, or list[1 + item] with list[0] entries.  A row that fits no tile is pushed onto next.
 template <int GW>
 __global__ __launch_bounds__(K24_BLOCK) void k24_rows_kernel(
     const double *__restrict__ a_box4, const int32_t *__restrict__ a_off, const int32_t *__restrict__ a_cls,
     const double *__restrict__ b_box4, const int32_t *__restrict__ b_off, const int32_t *__restrict__ b_cls,
     const double *__restrict__ b_score, int64_t n_rows, const int32_t *__restrict__ list, int32_t list_cap,
-    const double *__restrict__ lim, int T, double minlim, int32_t max_dets, K24Out out, int32_t *__restrict__ next,
+    const double *__restrict__ lim, int T, double minlim, int32_t max_dets, EvalOut out, int32_t *__restrict__ next,
     int32_t next_cap) {
     constexpr int DCAP = 2 * GW;
     constexpr int GROUPS = K24_BLOCK / GW;
     __shared__ K24Lds<DCAP> s_all[GROUPS];
-    __shared__ double s_lim[K24_MAX_T];
+    __shared__ double s_lim[EVAL_MAX_T];
     if ((int)threadIdx.x < T) s_lim[threadIdx.x] = lim[threadIdx.x];
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -131,7 +107,7 @@ __global__ __launch_bounds__(K24_BLOCK) void k24_rows_kernel(
             S.x1[k] = v.x1; S.y1[k] = v.y1; S.x2[k] = v.x2; S.y2[k] = v.y2;
             S.score[k] = sc;
             S.cls[k] = b_cls[b_base + k];
-            S.state[k] = k24_finite(sc) ? 0 : 2;
+            S.state[k] = eval_finite(sc) ? EVAL_EVALUATED : EVAL_BAD_SCORE;
             S.gt[k] = -1;
             S.tp[k] = 0u;
             S.iou[k] = 0.0;
@@ -143,17 +119,17 @@ __global__ __launch_bounds__(K24_BLOCK) void k24_rows_kernel(
         wave_sync();
         for (int k = gl; k < nd; k += GW) {   // rank within the class, place in the row's score order
             const double sk = S.score[k];
-            if (!k24_finite(sk)) continue;
+            if (!eval_finite(sk)) continue;
             const int32_t ck = S.cls[k];
             int rank = 0, ord = 0;
             for (int j = 0; j < nd; ++j) {
                 const double sj = S.score[j];
-                if (k24_finite(sj) && k24_before(sj, j, sk, k)) {
+                if (eval_finite(sj) && eval_before(sj, j, sk, k)) {
                     ++ord;
                     rank += (S.cls[j] == ck) ? 1 : 0;
                 }
             }
-            if (rank >= max_dets) S.state[k] = 1;
+            if (rank >= max_dets) S.state[k] = EVAL_CUT;
             S.perm[ord] = (unsigned short)k;
         }
         int maxnd = nd;
@@ -168,7 +144,7 @@ __global__ __launch_bounds__(K24_BLOCK) void k24_rows_kernel(
         double gbest = 0.0;
         for (int s = 0; s < maxnd; ++s) {
             const int k = (s < nd) ? (int)S.perm[s] : 0xFFFF;   // the same in every lane of a group
-            const bool act = k != 0xFFFF && S.state[k] == 0;
+            const bool act = k != 0xFFFF && S.state[k] == EVAL_EVALUATED;
             if (__ballot(act) == 0ull) continue;                // wave-uniform
             const int kk = act ? k : 0;
             const Corners o = {S.x1[kk], S.y1[kk], S.x2[kk], S.y2[kk]};
@@ -176,7 +152,7 @@ __global__ __launch_bounds__(K24_BLOCK) void k24_rows_kernel(
             double iou = 0.0;
             if (same) iou = no_nan ? k18_iou<true>(me, o, me_ar) : k18_iou<false>(me, o, me_ar);
             if (iou > gbest) gbest = iou;
-            const unsigned long long bk = k24_group_max<GW>(same ? k18_best_key(iou) : 0ull);
+            const unsigned long long bk = eval_group_max<GW>(same ? k18_best_key(iou) : 0ull);
             const bool near = same && iou >= minlim;
             uint32_t tp = 0u;
             int w0 = -1;
@@ -187,7 +163,7 @@ __global__ __launch_bounds__(K24_BLOCK) void k24_rows_kernel(
                     unsigned long long m = __ballot(cand) & gmask;
                     if (__ballot(__popcll(m) > 1) != 0ull) {    // some group must compare IoUs
                         const unsigned long long key = cand ? k18_cand_key(iou) : 0ull;
-                        const unsigned long long top = k24_group_max<GW>(key);
+                        const unsigned long long top = eval_group_max<GW>(key);
                         m = __ballot(cand && key == top) & gmask;
                     }
                     const int w = m ? 63 - __clzll((long long)m) : -1;   // the highest lane among the group's maxima
@@ -234,10 +210,10 @@ __global__ __launch_bounds__(K24_BLOCK) void k24_big_rows_kernel(
     const double *__restrict__ a_box4, const int32_t *__restrict__ a_off, const int32_t *__restrict__ a_cls,
     const double *__restrict__ b_box4, const int32_t *__restrict__ b_off, const int32_t *__restrict__ b_cls,
     const double *__restrict__ b_score, const int32_t *__restrict__ list, int32_t list_cap, const double *__restrict__ lim, int T,
-    double minlim, int32_t max_dets, K24Out out, int32_t *ord) {
-    __shared__ double s_lim[K24_MAX_T];
+    double minlim, int32_t max_dets, EvalOut out, int32_t *ord) {
+    __shared__ double s_lim[EVAL_MAX_T];
     __shared__ K24Sum sum[2][K24_WAVES];          // per evaluated detection, taking turns
-    __shared__ K24Pick pick[K24_WAVES][K24_MAX_T];
+    __shared__ K24Pick pick[K24_WAVES][EVAL_MAX_T];
     if ((int)threadIdx.x < T) s_lim[threadIdx.x] = lim[threadIdx.x];
     const int wave = threadIdx.x >> 6;
     const int lane = threadIdx.x & 63;
@@ -247,41 +223,14 @@ __global__ __launch_bounds__(K24_BLOCK) void k24_big_rows_kernel(
         const int64_t a_base = a_off[r], b_base = b_off[r];
         const int32_t na = a_off[r + 1] - (int32_t)a_base;
         const int32_t nb = b_off[r + 1] - (int32_t)b_base;
-        for (int32_t i = threadIdx.x; i < na; i += K24_BLOCK) {
-            out.gt_hit[a_base + i] = 0u;
-            out.gt_best[a_base + i] = 0.0;
-        }
-        for (int32_t k = threadIdx.x; k < nb; k += K24_BLOCK) ord[b_base + k] = -1;
-        __syncthreads();
-        for (int32_t k = threadIdx.x; k < nb; k += K24_BLOCK) {
-            const double sk = b_score[b_base + k] + 0.0;
-            int32_t state = 2;
-            if (k24_finite(sk)) {
-                const int32_t ck = b_cls[b_base + k];
-                int32_t rank = 0, o = 0;
-                for (int32_t j = 0; j < nb; ++j) {
-                    const double sj = b_score[b_base + j] + 0.0;
-                    if (k24_finite(sj) && k24_before(sj, j, sk, k)) {
-                        ++o;
-                        rank += (b_cls[b_base + j] == ck) ? 1 : 0;
-                    }
-                }
-                state = (rank >= max_dets) ? 1 : 0;
-                ord[b_base + o] = k;
-            }
-            out.dt_state[b_base + k] = state;
-            out.dt_tp[b_base + k] = 0u;
-            out.dt_gt[b_base + k] = -1;
-            out.dt_iou[b_base + k] = 0.0;
-            out.dt_best[b_base + k] = 0.0;
-        }
-        __syncthreads();
+        eval_rank_row<K24_BLOCK>((int)threadIdx.x, a_base, na, b_base, nb, b_score, b_cls, max_dets, [](int64_t) { return true; }, out,
+                                 ord);
 
         int turn = 0;
         for (int32_t s = 0; s < nb; ++s) {
             const int32_t k = ord[b_base + s];
             if (k < 0) break;                                   // the finite-scored ones come first
-            if (out.dt_state[b_base + k] != 0) continue;        // block-uniform
+            if (out.dt_state[b_base + k] != EVAL_EVALUATED) continue;   // block-uniform
             const Corners o = k18_load(b_box4, b_base + k);
             const int32_t o_cls = b_cls[b_base + k];
             // the detection's best IoU, the GT boxes' best IoU, and whether any pair comes near the lowest threshold
@@ -296,7 +245,7 @@ __global__ __launch_bounds__(K24_BLOCK) void k24_big_rows_kernel(
                 bk = (b1 > bk) ? b1 : bk;
                 near |= iou >= minlim;
             }
-            bk = k24_group_max<64>(bk);
+            bk = eval_group_max<64>(bk);
             const bool wnear = __ballot(near) != 0ull;
             K24Sum *slot = sum[turn & 1];
             ++turn;
@@ -331,7 +280,7 @@ __global__ __launch_bounds__(K24_BLOCK) void k24_big_rows_kernel(
                         }
                     }
                 }
-                const unsigned long long wk = k24_group_max<64>(key);
+                const unsigned long long wk = eval_group_max<64>(key);
                 int32_t wi = (key == wk && key != 0ull) ? idx : -1;
                 for (int d = 32; d >= 1; d >>= 1) {
                     const int32_t oi = __shfl_xor(wi, d);
@@ -377,14 +326,15 @@ __global__ __launch_bounds__(K24_BLOCK) void k24_big_rows_kernel(
 
 static int launch_k24_match(const double *a_box4, const int32_t *a_off, const int32_t *a_cls, const double *b_box4,
                             const int32_t *b_off, const int32_t *b_cls, const double *b_score, int64_t n_rows, int64_t n_a,
-                            int64_t n_b, const double *lim, int T, double minlim, int32_t max_dets, K24Out out, hipStream_t st) {
+                            int64_t n_b, const double *lim, int T, double minlim, int32_t max_dets, EvalOut out, hipStream_t st) {
     // rows that leave the 16-lane launch, and those that also leave the 64-lane one
     int64_t cap_mid = n_a / 17 + n_b / 33, cap_big = n_a / 65 + n_b / 129;
     cap_mid = (cap_mid < n_rows) ? cap_mid : n_rows;
     cap_big = (cap_big < n_rows) ? cap_big : n_rows;
     const size_t words = (size_t)(cap_mid + 1) + (size_t)(cap_big + 1) + (size_t)(cap_big > 0 ? n_b : 0);
+    ScratchLease lease(st);   // the two row lists and the big rows' score order
     void *scratch = nullptr;
-    int rc = get_scratch(4 * words, &scratch, st);
+    int rc = lease.get(4 * words, &scratch);
     if (rc) return rc;
     int32_t *mid = static_cast<int32_t *>(scratch);
     int32_t *big = mid + cap_mid + 1;
@@ -410,7 +360,6 @@ static int launch_k24_match(const double *a_box4, const int32_t *a_off, const in
                            max_dets, out, ord);
         DYD_HIP(hipGetLastError());
     }
-    release_scratch(st);
     return DYD_OK;
 }
 
@@ -584,52 +533,32 @@ int dyd_eval_match_boxes(const double *gt_box4, const int32_t *gt_row_off, const
                          double *out_gt_best) {
     DYD_API_ENTER();
     DYD_REQUIRE(n_rows >= 0 && n_classes >= 0, "n_rows < 0 or n_classes < 0");
-    DYD_REQUIRE(T >= 1 && T <= K24_MAX_T, "T outside 1..32");
-    DYD_REQUIRE(max_dets >= 1, "max_dets < 1");
-    DYD_REQUIRE(iou_thr, "null pointer");
+    EvalLimits L;
+    int rc = L.set(iou_thr, T, max_dets);
+    if (rc) return rc;
     if (n_rows == 0) return DYD_OK;
     int64_t na, nb;
-    int rc;
     if ((rc = k18_check_side(gt_box4, gt_row_off, gt_cls, n_rows, n_classes, &na)) ||
         (rc = k18_check_side(dt_box4, dt_row_off, dt_cls, n_rows, n_classes, &nb)))
         return rc;
     DYD_REQUIRE(na == 0 || (out_gt_hit && out_gt_best), "null pointer");
     DYD_REQUIRE(nb == 0 || (dt_score && out_dt_state && out_dt_tp && out_dt_gt && out_dt_iou && out_dt_best), "null pointer");
-    double lim[K24_MAX_T], minlim = HUGE_VAL;
-    for (int t = 0; t < T; ++t) {
-        const double cap = 1.0 - 1e-10;
-        lim[t] = (cap < iou_thr[t]) ? cap : iou_thr[t];   // min(iou_thr[t], 1 - 1e-10); NaN stays and matches nothing
-        if (lim[t] < minlim) minlim = lim[t];
-    }
     K18Side A, B;
     if ((rc = A.upload(gt_box4, gt_row_off, gt_cls, n_rows, na)) || (rc = B.upload(dt_box4, dt_row_off, dt_cls, n_rows, nb))) return rc;
-    DevBuf d_sc, d_lim, d_st, d_tp, d_gt, d_iou, d_best, d_hit, d_gbest;
-    if ((rc = d_sc.alloc(8 * (size_t)nb)) || (rc = d_lim.alloc(8 * (size_t)T)) || (rc = d_st.alloc(4 * (size_t)nb)) ||
-        (rc = d_tp.alloc(4 * (size_t)nb)) || (rc = d_gt.alloc(4 * (size_t)nb)) || (rc = d_iou.alloc(8 * (size_t)nb)) ||
-        (rc = d_best.alloc(8 * (size_t)nb)) || (rc = d_hit.alloc(4 * (size_t)na)) || (rc = d_gbest.alloc(8 * (size_t)na)))
-        return rc;
+    DevBuf d_sc, d_lim;
+    EvalOutDev res;
+    if ((rc = d_sc.alloc(8 * (size_t)nb)) || (rc = d_lim.alloc(8 * (size_t)T)) || (rc = res.alloc(na, nb))) return rc;
     hipStream_t st = ctx().stream;
     if (nb) DYD_HIP(hipMemcpyAsync(d_sc.p, dt_score, 8 * (size_t)nb, hipMemcpyHostToDevice, st));
-    DYD_HIP(hipMemcpyAsync(d_lim.p, lim, 8 * (size_t)T, hipMemcpyHostToDevice, st));
-    DYD_HIP(hipStreamSynchronize(st));   // lim lives on this frame
-    const K24Out out = {d_st.as<int32_t>(), d_tp.as<uint32_t>(), d_gt.as<int32_t>(), d_iou.as<double>(), d_best.as<double>(),
-                        d_hit.as<uint32_t>(), d_gbest.as<double>()};
+    DYD_HIP(hipMemcpyAsync(d_lim.p, L.lim, 8 * (size_t)T, hipMemcpyHostToDevice, st));
+    DYD_HIP(hipStreamSynchronize(st));   // L lives on this frame
     KernelTimer timer(st);
     rc = launch_k24_match(A.box.as<double>(), A.off.as<int32_t>(), A.cls.as<int32_t>(), B.box.as<double>(), B.off.as<int32_t>(),
-                          B.cls.as<int32_t>(), d_sc.as<double>(), n_rows, na, nb, d_lim.as<double>(), T, minlim, max_dets, out, st);
+                          B.cls.as<int32_t>(), d_sc.as<double>(), n_rows, na, nb, d_lim.as<double>(), T, L.minlim, max_dets, res.out(),
+                          st);
     if (rc) return rc;
     timer.finish();
-    if (na) {
-        DYD_HIP(hipMemcpyAsync(out_gt_hit, d_hit.p, 4 * (size_t)na, hipMemcpyDeviceToHost, st));
-        DYD_HIP(hipMemcpyAsync(out_gt_best, d_gbest.p, 8 * (size_t)na, hipMemcpyDeviceToHost, st));
-    }
-    if (nb) {
-        DYD_HIP(hipMemcpyAsync(out_dt_state, d_st.p, 4 * (size_t)nb, hipMemcpyDeviceToHost, st));
-        DYD_HIP(hipMemcpyAsync(out_dt_tp, d_tp.p, 4 * (size_t)nb, hipMemcpyDeviceToHost, st));
-        DYD_HIP(hipMemcpyAsync(out_dt_gt, d_gt.p, 4 * (size_t)nb, hipMemcpyDeviceToHost, st));
-        DYD_HIP(hipMemcpyAsync(out_dt_iou, d_iou.p, 8 * (size_t)nb, hipMemcpyDeviceToHost, st));
-        DYD_HIP(hipMemcpyAsync(out_dt_best, d_best.p, 8 * (size_t)nb, hipMemcpyDeviceToHost, st));
-    }
+    if ((rc = res.copy_back({out_dt_state, out_dt_tp, out_dt_gt, out_dt_iou, out_dt_best, out_gt_hit, out_gt_best}, st))) return rc;
     DYD_HIP(hipStreamSynchronize(st));
     return DYD_OK;
 }
@@ -641,7 +570,7 @@ int dyd_eval_accumulate(const int32_t *cls, const double *score, const uint32_t 
     DYD_API_ENTER();
     DYD_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "n outside 0..2^31-1");
     DYD_REQUIRE(n_classes >= 0 && R >= 1, "n_classes < 0 or R < 1");
-    DYD_REQUIRE(T >= 1 && T <= K24_MAX_T, "T outside 1..32");
+    DYD_REQUIRE(T >= 1 && T <= EVAL_MAX_T, "T outside 1..32");
     DYD_REQUIRE((int64_t)n_classes * T < ((int64_t)1 << 31), "n_classes * T out of range");
     if (n_classes == 0) return DYD_OK;
     DYD_REQUIRE(npig && out_recall && out_ap && out_best_f1 && out_best_score && out_best_tp && out_best_dets, "null pointer");

@@ -12,44 +12,20 @@
 // from the pair cell and one division, the same as in k22_match_kernel, and the rows are those of K22: a few polygons each in
 // most tables, at most max_pairs_per_row pairs.  So K22's scheme is kept: lanes stride over the GT polygons, the detections are
 // taken in score order, and every reduction is a wave's own (shuffles and ballots), never a workgroup barrier between waves.
-// What K24's big-row kernel contributes is the part K22 lacks: the state and the rank of every detection counted by the lanes
-// over the row's scores, and the row's score order in a scratch column (ord, one i32 per detection).  The GT state is the T-bit
+// What K22 lacks is eval_match.h's, shared with k24_big_rows_kernel: the result columns and states, and eval_rank_row, the state
+// and rank of every detection counted by the lanes over the row's scores with the row's score order in a scratch column (ord,
+// one i32 per detection).  The arg-max is the big-row kernel's too, written out in both.  The GT state is the T-bit
 // mask in out_gt_hit, read and written by the owning lane (index % 64) only, as out_gt_best is.  A row of at most 64 GT
 // polygons keeps the detection's IoU in a register across the thresholds; a longer one recomputes it from the cell.  The
 // arg-max is over k18_pick.h's keys: the largest key, then the highest index (the last of equal keys stays in a lane's
 // ascending walk, then the maximum over the holders).  A detection without a same-class pair at or above the lowest limit
 // skips the T loop.  Exact for any row length; no atomics, no result depends on the schedule.
-#include <cmath>
-
-#include "k18_pick.h"
+#include "eval_match.h"
 #include "k21_cover.h"
 #include "k22_pairs.h"
 #include "poly_table.h"
 
 namespace dyd {
-
-constexpr int K25_MAX_T = 32;
-constexpr int32_t K25_SKIPPED = 3;   // dt_state: the polygon's action is not 0
-
-struct K25Out {
-    int32_t *dt_state;
-    uint32_t *dt_tp;
-    int32_t *dt_gt;
-    double *dt_iou, *dt_best;
-    uint32_t *gt_hit;
-    double *gt_best;
-};
-
-__device__ __forceinline__ bool k25_finite(double s) { return (s - s) == 0.0; }
-
-__device__ __forceinline__ unsigned long long k25_wave_max(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d);
-        v = (o > v) ? o : v;
-    }
-    return v;
-}
 
 // inter > 0: one correctly rounded division of two exact integers
 __device__ __forceinline__ double k25_iou(uint32_t inter, unsigned long long pg, unsigned long long pd) {
@@ -61,9 +37,9 @@ __global__ __launch_bounds__(kWave) void k25_match_kernel(
     const unsigned long long *__restrict__ a_pixels, const int32_t *__restrict__ b_row_off, const int32_t *__restrict__ b_cls,
     const uint8_t *__restrict__ b_action, const unsigned long long *__restrict__ b_pixels, const double *__restrict__ b_score,
     int64_t n_rows, int64_t n_a, int64_t n_b, const double *__restrict__ lim, int T, double minlim, int32_t max_dets,
-    const uint8_t *__restrict__ row_status, const int64_t *__restrict__ pair_off, const uint32_t *__restrict__ pairs, K25Out out,
+    const uint8_t *__restrict__ row_status, const int64_t *__restrict__ pair_off, const uint32_t *__restrict__ pairs, EvalOut out,
     int32_t *ord) {
-    __shared__ double s_lim[K25_MAX_T];
+    __shared__ double s_lim[EVAL_MAX_T];
     const int lane = threadIdx.x;
     if (lane < T) s_lim[lane] = lim[lane];
     __syncthreads();
@@ -73,45 +49,14 @@ __global__ __launch_bounds__(kWave) void k25_match_kernel(
         k21_row_polys(b_row_off, r, n_b, &b0, &b1);
         const int64_t na = a1 - a0, nb = b1 - b0, cell0 = pair_off[r];
         const bool one = na <= kWave;   // every GT polygon of the row has a lane of its own
-        for (int64_t i = lane; i < na; i += kWave) {
-            out.gt_hit[a0 + i] = 0u;
-            out.gt_best[a0 + i] = 0.0;
-        }
-        for (int64_t k = lane; k < nb; k += kWave) ord[b0 + k] = -1;
-        __syncthreads();
-        // state and rank of every detection; the row's score order.  A row that is not evaluated has no polygon of action 0.
-        for (int64_t k = lane; k < nb; k += kWave) {
-            int32_t state = K25_SKIPPED;
-            if (b_action[b0 + k] == COVER_DONE) {
-                const double sk = b_score[b0 + k] + 0.0;   // -0.0 -> 0.0
-                state = 2;
-                if (k25_finite(sk)) {
-                    const int32_t ck = b_cls[b0 + k];
-                    int64_t rank = 0, o = 0;
-                    for (int64_t j = 0; j < nb; ++j) {
-                        if (b_action[b0 + j] != COVER_DONE) continue;
-                        const double sj = b_score[b0 + j] + 0.0;
-                        if (k25_finite(sj) && (sj > sk || (sj == sk && j < k))) {
-                            ++o;
-                            rank += (b_cls[b0 + j] == ck) ? 1 : 0;
-                        }
-                    }
-                    state = (rank >= max_dets) ? 1 : 0;
-                    ord[b0 + o] = (int32_t)k;
-                }
-            }
-            out.dt_state[b0 + k] = state;
-            out.dt_tp[b0 + k] = 0u;
-            out.dt_gt[b0 + k] = -1;
-            out.dt_iou[b0 + k] = 0.0;
-            out.dt_best[b0 + k] = 0.0;
-        }
-        __syncthreads();
+        // a row that is not evaluated has no polygon of action 0
+        eval_rank_row<kWave>(lane, a0, na, b0, nb, b_score, b_cls, max_dets, [=](int64_t p) { return b_action[p] == COVER_DONE; },
+                             out, ord);
 
         for (int64_t s = 0; s < nb; ++s) {   // wave-uniform
             const int32_t k = ord[b0 + s];
             if (k < 0) break;                                   // the ranked ones come first
-            if (out.dt_state[b0 + k] != 0) continue;
+            if (out.dt_state[b0 + k] != EVAL_EVALUATED) continue;
             const int32_t cd = b_cls[b0 + k];
             const unsigned long long pd = b_pixels[b0 + k];
             // the detection's best IoU, the GT polygons' best IoU, and whether any pair comes near the lowest limit
@@ -129,7 +74,7 @@ __global__ __launch_bounds__(kWave) void k25_match_kernel(
                 near |= iou >= minlim;
                 iou1 = iou;
             }
-            bk = k25_wave_max(bk);
+            bk = eval_group_max<64>(bk);
             uint32_t tp = 0u;
             int64_t g0 = -1;
             unsigned long long k0 = 0ull;
@@ -158,7 +103,7 @@ __global__ __launch_bounds__(kWave) void k25_match_kernel(
                             }
                         }
                     }
-                    const unsigned long long wk = k25_wave_max(key);
+                    const unsigned long long wk = eval_group_max<64>(key);
                     if (wk == 0ull) continue;                   // wave-uniform
                     int64_t wi = (key == wk) ? idx : -1;
                     for (int d = 32; d >= 1; d >>= 1) {
@@ -201,11 +146,9 @@ int dyd_eval_match_polygons(const double *gt_xy, const int32_t *gt_pt_off, const
                             uint32_t *out_dt_tp, int32_t *out_dt_gt, double *out_dt_iou, double *out_dt_best, uint32_t *out_gt_hit,
                             double *out_gt_best) {
     DYD_API_ENTER();
+    EvalLimits L;
     int rc = compare_params(n_classes, max_pixels_per_row, max_pairs_per_row);
-    if (rc) return rc;
-    DYD_REQUIRE(T >= 1 && T <= K25_MAX_T, "T outside 1..32");
-    DYD_REQUIRE(max_dets >= 1, "max_dets < 1");
-    DYD_REQUIRE(iou_thr, "null pointer");
+    if (rc || (rc = L.set(iou_thr, T, max_dets))) return rc;
     DYD_REQUIRE(n_rows >= 0, "negative size");
     DYD_REQUIRE(n_rows < (1LL << 31), "size too large");
     if (n_rows == 0) return DYD_OK;
@@ -220,35 +163,26 @@ int dyd_eval_match_polygons(const double *gt_xy, const int32_t *gt_pt_off, const
         return rc;
     for (int64_t p = 0; p < na; ++p) DYD_REQUIRE(gt_cls[p] < n_classes, "class id outside the list");
     for (int64_t p = 0; p < nb; ++p) DYD_REQUIRE(dt_cls[p] < n_classes, "class id outside the list");
-    double lim[K25_MAX_T], minlim = HUGE_VAL;
-    for (int t = 0; t < T; ++t) {
-        const double cap = 1.0 - 1e-10;
-        lim[t] = (cap < iou_thr[t]) ? cap : iou_thr[t];   // min(iou_thr[t], 1 - 1e-10); NaN stays and matches nothing
-        if (lim[t] < minlim) minlim = lim[t];
-    }
     hipStream_t st = ctx().stream;
     PolyTableDev ta;
-    DevBuf b_xyd, b_pt, b_row, d_ca, d_cb, d_sc, d_lim, d_status, d_poff, d_aact, d_bact, d_apix, d_bpix, d_st, d_tp, d_gt, d_iou,
-        d_best, d_hit, d_gbest;
+    DevBuf b_xyd, b_pt, b_row, d_ca, d_cb, d_sc, d_lim, d_status, d_poff, d_aact, d_bact, d_apix, d_bpix;
+    EvalOutDev res;
     if ((rc = ta.upload(gt_xy, gt_pt_off, gt_row_off, width, height, n_rows, na, npa)) ||
         (rc = poly_column(b_xyd, npb ? dt_xy : nullptr, 16 * (size_t)npb)) ||
         (rc = poly_column(b_pt, nb ? dt_pt_off : nullptr, nb ? 4 * (size_t)(nb + 1) : 0)) ||
         (rc = poly_column(b_row, dt_row_off, 4 * (size_t)(n_rows + 1))) || (rc = poly_column(d_ca, gt_cls, 4 * (size_t)na)) ||
         (rc = poly_column(d_cb, dt_cls, 4 * (size_t)nb)) || (rc = poly_column(d_sc, dt_score, 8 * (size_t)nb)) ||
-        (rc = poly_column(d_lim, lim, 8 * (size_t)T)) || (rc = d_status.alloc((size_t)n_rows)) ||
+        (rc = poly_column(d_lim, L.lim, 8 * (size_t)T)) || (rc = d_status.alloc((size_t)n_rows)) ||
         (rc = d_poff.alloc(8 * (size_t)(n_rows + 1))) || (rc = d_aact.alloc((size_t)na)) || (rc = d_bact.alloc((size_t)nb)) ||
-        (rc = d_apix.alloc(8 * (size_t)na)) || (rc = d_bpix.alloc(8 * (size_t)nb)) || (rc = d_st.alloc(4 * (size_t)nb)) ||
-        (rc = d_tp.alloc(4 * (size_t)nb)) || (rc = d_gt.alloc(4 * (size_t)nb)) || (rc = d_iou.alloc(8 * (size_t)nb)) ||
-        (rc = d_best.alloc(8 * (size_t)nb)) || (rc = d_hit.alloc(4 * (size_t)na)) || (rc = d_gbest.alloc(8 * (size_t)na)))
+        (rc = d_apix.alloc(8 * (size_t)na)) || (rc = d_bpix.alloc(8 * (size_t)nb)) ||
+        (rc = res.alloc(na, nb)))
         return rc;
-    DYD_HIP(hipStreamSynchronize(st));   // lim lives on this frame
+    DYD_HIP(hipStreamSynchronize(st));   // L lives on this frame
     const K22Table a{ta.xy.as<double>(), ta.pt.as<int32_t>(), ta.row.as<int32_t>(), d_ca.as<int32_t>(), na, npa,
                      d_aact.as<uint8_t>(), d_apix.as<int64_t>(), nullptr, nullptr};
     const K22Table b{b_xyd.as<double>(), b_pt.as<int32_t>(), b_row.as<int32_t>(), d_cb.as<int32_t>(), nb, npb,
                      d_bact.as<uint8_t>(), d_bpix.as<int64_t>(), nullptr, nullptr};
     const K22Out o{d_status.as<uint8_t>(), d_poff.as<int64_t>(), nullptr, nullptr, nullptr, nullptr, nullptr};
-    const K25Out out = {d_st.as<int32_t>(), d_tp.as<uint32_t>(), d_gt.as<int32_t>(), d_iou.as<double>(), d_best.as<double>(),
-                        d_hit.as<uint32_t>(), d_gbest.as<double>()};
     SizedOut pairs(K25_PAIRS, st);
     KernelTimer timer(st);
     rc = compare_pairs_launch(a, b, ta.w.as<double>(), ta.h.as<double>(), n_rows, n_classes, max_pixels_per_row, max_pairs_per_row,
@@ -262,20 +196,17 @@ int dyd_eval_match_polygons(const double *gt_xy, const int32_t *gt_pt_off, const
         hipLaunchKernelGGL(k25_match_kernel, dim3((unsigned)(n_rows < want ? n_rows : want)), dim3(kWave), 0, st, a.row_off, a.cls,
                            a.action, reinterpret_cast<const unsigned long long *>(a.pixels), b.row_off, b.cls, b.action,
                            reinterpret_cast<const unsigned long long *>(b.pixels), d_sc.as<double>(), n_rows, na, nb,
-                           d_lim.as<double>(), (int)T, minlim, max_dets, o.row_status, o.pair_off, pairs.as<uint32_t>(), out,
+                           d_lim.as<double>(), (int)T, L.minlim, max_dets, o.row_status, o.pair_off, pairs.as<uint32_t>(), res.out(),
                            static_cast<int32_t *>(scr));
         DYD_HIP(hipGetLastError());
     }
     timer.finish();
     const CopyBack back[] = {{out_row_status, d_status.p, (size_t)n_rows}, {out_pair_off, d_poff.p, 8 * (size_t)(n_rows + 1)},
                              {out_gt_action, d_aact.p, (size_t)na}, {out_dt_action, d_bact.p, (size_t)nb},
-                             {out_gt_pixels, d_apix.p, 8 * (size_t)na}, {out_dt_pixels, d_bpix.p, 8 * (size_t)nb},
-                             {out_dt_state, d_st.p, 4 * (size_t)nb}, {out_dt_tp, d_tp.p, 4 * (size_t)nb},
-                             {out_dt_gt, d_gt.p, 4 * (size_t)nb}, {out_dt_iou, d_iou.p, 8 * (size_t)nb},
-                             {out_dt_best, d_best.p, 8 * (size_t)nb}, {out_gt_hit, d_hit.p, 4 * (size_t)na},
-                             {out_gt_best, d_gbest.p, 8 * (size_t)na}};
+                             {out_gt_pixels, d_apix.p, 8 * (size_t)na}, {out_dt_pixels, d_bpix.p, 8 * (size_t)nb}};
     for (const CopyBack &c : back)
         if (c.bytes) DYD_HIP(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, st));
+    if ((rc = res.copy_back({out_dt_state, out_dt_tp, out_dt_gt, out_dt_iou, out_dt_best, out_gt_hit, out_gt_best}, st))) return rc;
     DYD_HIP(hipStreamSynchronize(st));
     return DYD_OK;
 }

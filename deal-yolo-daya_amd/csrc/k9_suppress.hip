@@ -20,6 +20,7 @@
 //   of the earlier blocks, whose decisions are final, spread over the workgroup's waves; (2) the block resolves itself with the
 //   same ballot walk.  Exact for any row length, O(1) extra memory per row, never an n x n matrix.
 #include "k2_wave.h"
+#include "sized_out.h"
 
 namespace dyd {
 
@@ -218,8 +219,9 @@ int launch_k9(const double *box4, const int32_t *row_off, int64_t n_rows, int64_
     // rows above 64 boxes: at most n_boxes / 65 of them
     int64_t cap = n_boxes / (kWave + 1);
     cap = (cap < n_rows) ? cap : n_rows;
+    ScratchLease lease(st);   // the list of big rows
     void *scratch = nullptr;
-    int rc = get_scratch(4 * (size_t)(cap + 1), &scratch, st);
+    int rc = lease.get(4 * (size_t)(cap + 1), &scratch);
     if (rc) return rc;
     int32_t *bigl = static_cast<int32_t *>(scratch);
     DYD_HIP(hipMemsetAsync(bigl, 0, 4, st));
@@ -232,7 +234,6 @@ int launch_k9(const double *box4, const int32_t *row_off, int64_t n_rows, int64_
                            thr, out_keep, out_partner, bigl, (int32_t)cap);
         DYD_HIP(hipGetLastError());
     }
-    release_scratch(st);
     return DYD_OK;
 }
 

@@ -14,6 +14,7 @@ import pytest
 from box_eval_ref import MATCH_NAMES, REC, THR, check_evaluation, same_arrays
 from polygon_compare_tables import RANDOM, blob, box, random_rows, table
 from polygon_eval_ref import NAMES, expected_polygon_evaluation, match_polygon_rows
+from test_gpu_box_eval import _check_match as k24_check_match
 
 from deal_yolo_daya_amd.core import processor as P
 
@@ -186,6 +187,36 @@ def test_k25_equals_k24_on_integer_boxes(native):
                                   t[6], t[7], score, 2, thr)
     same_arrays(got[STATE:], k24, MATCH_NAMES, "K25 against K24")
     assert k24[1].astype(bool).sum() > 15 and (got[D_PIX] == 0).sum() > 3
+
+
+def tie_boxes(n, shift=0):
+    """n boxes of 2 x 1 pixels as corners, 16 to a scanline, classes in pairs (0 0 1 1 ..): moved right by a pixel a box has IoU
+    1/3 with the box at its own place and with the next one, which for an even k is of its class"""
+    return [((k // 2) % 2, [2 * (k % 16) + shift, k // 16, 2 * (k % 16) + 2 + shift, k // 16 + 1]) for k in range(n)]
+
+
+@pytest.mark.parametrize("max_dets", [100, 1])
+def test_k25_strided_row_equals_k24_big_row(native, max_dets):
+    """One row of 65 GT boxes and 129 detections in 2 classes, the smallest that leaves K24's 64-lane tile on both sides
+    (k24_big_rows_kernel), makes K25's lanes stride and sends the score order through the scratch column: the two kernels run one
+    rank pass (eval_match.h) and the same arg-max.  Integer two-point boxes inside a 34 x 8 image, so mask IoU and box IoU are
+    equal bit for bit; the detections are the GT boxes and 64 of them moved by a pixel (IoU 1/3, for an even k with two GT boxes
+    of its class: the highest index wins); scores of one decimal, so equal scores are settled by position."""
+    gts, dets = tie_boxes(65), tie_boxes(65) + tie_boxes(64, shift=1)
+    t = table([(34, 8, [(c, box(*b)) for c, b in gts], [(c, box(*b)) for c, b in dets])])
+    score = np.round(np.random.default_rng(75).random(129), 1)
+    thr = [0.25, 0.5, 1.0]
+    as_boxes = (np.asarray([b for _, b in gts], np.float64), t[2], t[3], np.asarray([b for _, b in dets], np.float64), t[6], t[7], score, 2)
+    want = both(native, t, score, 2, thr, max_dets=max_dets)
+    k24_check_match(native, "tie_boxes", as_boxes, thr, max_dets)
+    same_arrays(direct(native, t, score, 2, thr, max_dets=max_dets)[STATE:], native.eval_match_boxes(*as_boxes, thr, max_dets),
+                MATCH_NAMES, "K25 against K24")
+    assert all(((want[TP] >> k) & 1).any() for k in range(3)), "a true positive at every threshold"
+    if max_dets == 1:
+        assert (want[STATE] == 1).sum() == 127
+    else:
+        taken = want[GT][65::2]                                                           # the moved copies of the even boxes
+        assert (taken == np.arange(1, 65, 2)).any() and (taken == np.arange(0, 64, 2)).any(), "ties to the highest free index"
 
 
 # ----------------------------------------------------------------------------------------------- 6. against K22
